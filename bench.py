@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — frames/sec of the yolo3_darknet53 hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 608] [--batch 64] [--classes 20]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 608] [--batch 64] [--classes 20] [--dump-outputs DIR]
 
 One "step" = one inference pass of the whole path (stem + 74 fused conv launches + decode + NMS)
 over one batch of synthetic frames that is already resident in HBM.  Default workload is
@@ -289,6 +289,24 @@ def _emit(result):
         os.write(_JSON_FD, line)
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=233):
+    """--dump-outputs: {name: array, frames on axis 0} -> out_dir/<name>.npy in float32.  Above DUMP_CAP_BYTES in all, the
+    same seeded sample of frames is kept from every array, so the dumps of two builds still compare row for row."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        n = len(next(iter(arrays.values())))
+        rows = np.sort(np.random.default_rng(seed).choice(n, max(1, n * DUMP_CAP_BYTES // total), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def launch_table(net, x):
     """Median-of-3 per-launch table of one forward: [(name, ms, flops, algorithmic bytes)] (HIP events around every
     launch, on the launch stream) and the same aggregated per kernel instance {key: [launches, ms, flops, bytes]}."""
@@ -354,13 +372,14 @@ def _max_over_ranks(dt, dist, torch, dev):
 
 
 def train_leg(vy, dev, dist, rank, world, size, batch, classes, steps, warmup, syncbn=False, overlap=True,
-              split=True, allreduce_alone=False, conv_mode="exact"):
+              split=True, allreduce_alone=False, conv_mode="exact", keep_losses=False):
     """One training workload, timed like the headline: `warmup` un-timed steps, then exactly `steps` steps between
     barrier + synchronize, max over ranks.  One step = recorded forward (batch-statistics BatchNorm, targets, loss)
     + backward + gradient all-reduce (bucketed, overlapped with backward) + SGD: the call pattern of
     train_yolov3.py:623-634.  syncbn: the net is built the way train_yolov3.py:350-354 builds it
     (norm_layer=SyncBatchNorm, norm_kwargs={'num_devices': world}); with one rank that is plain BatchNorm.
-    EVERY rank runs this (it contains collectives); the returned dict is rank 0's view."""
+    EVERY rank runs this (it contains collectives); the returned dict is rank 0's view.  keep_losses: it also holds
+    "losses", the four (B,) loss vectors of the last timed step as numpy."""
     import torch
     from videoyolo_amd import autograd, targets
     cls_names = ["c%d" % i for i in range(classes)]
@@ -396,6 +415,8 @@ def train_leg(vy, dev, dist, rank, world, size, batch, classes, steps, warmup, s
         losses = step()
     _barrier(dist, torch)
     dt = _max_over_ranks(time.perf_counter() - t0, dist, torch, dev)
+    last = {k: l.detach().cpu().numpy() for k, l in zip(("obj_loss", "center_loss", "scale_loss", "cls_loss"), losses)} \
+        if keep_losses else None
     fps = global_batch * steps / dt
     fwd_gflop = FWD_GFLOP_PER_FRAME.get((size, classes))
     out = {"frames_per_s": fps, "ms_per_step": 1e3 * dt / steps, "n_gpus": world, "per_gpu_batch": batch,
@@ -404,6 +425,8 @@ def train_leg(vy, dev, dist, rank, world, size, batch, classes, steps, warmup, s
            "allreduce": ("bucketed, overlapped with backward" if overlap else "one all-reduce after backward") if multi else "none (1 rank)",
            "backend": dist.get_backend() if dist is not None else None,
            "loss_rank0": float(sum(l.sum() for l in losses).item() / batch)}
+    if last is not None:
+        out["losses"] = last
     if fwd_gflop:
         # whole timed step (forward + backward + exposed all-reduce + SGD) against the roof, per GPU
         out["whole_step_tflops_per_gpu"] = fps / world * 3 * fwd_gflop / 1e3
@@ -729,7 +752,12 @@ def main():
     ap.add_argument("--train-batch", type=int, default=16, help="frames per GPU of also_train416")
     ap.add_argument("--syncbn-size", type=int, default=608)
     ap.add_argument("--syncbn-batch", type=int, default=8, help="frames per GPU of also_syncbn608")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned as DIR/<name>.npy "
+                         "(rank 0; infer: ids, scores, bboxes; train: the four loss vectors), float32, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     # `python bench.py --gpus N` (no rank environment): this process only starts the N ranks and waits —
     # it never touches a GPU and never execs (videoyolo_amd/launch.py).  Under torch.distributed.run the
     # rank environment is already there and this is skipped.
@@ -841,6 +869,8 @@ def main():
     dt = _max_over_ranks(time.perf_counter() - t0, dist, torch, dev)
     frames = args.batch * world * args.steps
     fps = frames / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: t.cpu().numpy() for k, t in zip(("ids", "scores", "bboxes"), out)})
 
     result.update({
         "metric": "frames/sec, yolo3_darknet53 inference %dx%d" % (args.size, args.size),
@@ -1152,7 +1182,9 @@ def bench_train(args, vy, dev, dist, rank, world, traffic=None, traffic_note=Non
     dog.arm("headline")
     leg = train_leg(vy, dev, dist, rank, world, args.size, args.batch, args.classes, args.steps, args.warmup,
                     syncbn=args.syncbn, overlap=not args.no_overlap, split=not args.no_roofline,
-                    allreduce_alone=not args.no_roofline, conv_mode=args.conv_mode)
+                    allreduce_alone=not args.no_roofline, conv_mode=args.conv_mode, keep_losses=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, leg["losses"])
     result = {
         "metric": "frames/sec, yolo3_darknet53 training %dx%d" % (args.size, args.size),
         "value": leg["frames_per_s"], "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

@@ -213,3 +213,31 @@ def test_device_under_load_samples_while_the_step_runs():
     assert r["samples"] >= 5 and 2300 <= r["sclk_mhz_median"] <= 2302 and r["power_median"] == 900 and r["temperature_c_max"] == 60
     r = bench.device_under_load(types.SimpleNamespace(cuda=Cuda(ok=False)), dev, lambda: None)
     assert "amdsmi is not available" in r["error"]
+
+
+def test_dump_outputs_writes_float32_and_samples_the_same_frames(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per returned array; above the size cap every array keeps the same seeded frames."""
+    import numpy as np
+    import bench
+    ids = np.arange(8 * 3, dtype=np.float32).reshape(8, 3, 1)
+    boxes = np.arange(8 * 3 * 4, dtype=np.float64).reshape(8, 3, 4)
+    bench.dump_outputs(str(tmp_path / "all"), {"ids": ids, "bboxes": boxes})
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in ("ids", "bboxes")}
+    assert got["ids"].dtype == np.float32 and np.array_equal(got["ids"], ids)
+    assert got["bboxes"].dtype == np.float32 and np.array_equal(got["bboxes"], boxes)
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", (ids.nbytes + boxes.nbytes // 2) // 2)   # (bytes as float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"ids": ids, "bboxes": boxes})
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("ids", "bboxes")}
+    b = {k: np.load(str(tmp_path / "b" / (k + ".npy"))) for k in ("ids", "bboxes")}
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_CAP_BYTES and len(a["ids"]) == 4
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    frames = (a["ids"][:, 0, 0] // 3).astype(int)
+    assert np.array_equal(a["bboxes"], boxes[frames]) and len(set(frames.tolist())) == 4
+
+
+def test_steps_must_be_positive():
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 2 and "--steps" in p.stderr
