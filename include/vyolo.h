@@ -328,6 +328,28 @@ int vy_net_grad_get(vy_net* net, int32_t i, float* host_dst, void* stream);
  * resolution the output is stored (x2 for the transition cells). */
 int vy_net_read_grad_activation(vy_net* net, const char* name, float* dst_dev, void* stream);
 
+/* Test-only taps of the training step (per-cell parity checks; off the step's path).  Cell `name` (as in
+ * vy_net_conv_info), one of:
+ *   VY_TAP_Z             the cell's raw conv-output plane with its border, NCHW (B, Cout, H+2, W+2): z after
+ *                        vy_net_train_forward, dz after vy_net_train_backward (BatchNorm cells only)
+ *   VY_TAP_BN            [4][Cout]: the saved batch mean, the saved invstd, and the scale / shift the forward apply
+ *                        and the backward kernels used (BatchNorm cells only)
+ *   VY_TAP_GRAD_PADDED   the gradient of the cell's output channels with the border of their plane, NCHW
+ *                        (B, Cout, Ho+2, Wo+2) at the resolution the output is stored (x2 for the transitions)
+ *   VY_TAP_INPUT_PADDED  the input view the cell's conv reads, border included, NCHW (B, Cin, Hi+2, Wi+2) (not the stem)
+ * dims (int32[4], may be NULL) receives the tensor's shape; dst_dev NULL: shape only. */
+#define VY_TAP_Z 0
+#define VY_TAP_BN 1
+#define VY_TAP_GRAD_PADDED 2
+#define VY_TAP_INPUT_PADDED 3
+int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* dst_dev, int32_t* dims, void* stream);
+
+/* Host-only: the accumulation plan of conv i in the bound training plan — the weight gradient's split-K (pixel splits,
+ * pixels per split; the stem: the fp32 accumulators a block adds, the pixels one of them sums) and the BatchNorm backward's image rows per
+ * partial chunk (0: no BatchNorm).  Any pointer may be NULL. */
+int vy_net_train_conv_plan(const vy_net* net, int32_t i, int32_t* wgrad_splits, int32_t* wgrad_k_per_split,
+                           int32_t* bn_bwd_rows_per_chunk);
+
 /* SyncBatchNorm(num_devices) (train_yolov3.py:352-354).  With world > 1 the BatchNorm layers that
  * the reference builds with the passed norm_layer — the stem and the five stride-2 convs of
  * Darknet-53 (three_darknet.py:163-181; the residual blocks hard-code BatchNorm, :193-194, and

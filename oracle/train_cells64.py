@@ -1,0 +1,360 @@
+"""Per-cell float64 reference of the training step, fed the tensors the HIP step itself
+used.
+
+TEST INFRASTRUCTURE ONLY.  End-to-end gradient comparisons cannot be tight: a last-bit change in the forward moves
+gradients by up to 2e-2 through the LeakyReLU kinks.  Here every kernel of the step is checked on its own: it gets
+the exact inputs the device gave it (tapped z / dz planes, BatchNorm statistics, input views, output gradients), the
+same operation is recomputed in float64, and each element must lie within a worst-case rounding bound
+
+    |got - want| <= gamma_n * sum|terms|,   gamma_n = n u / (1 - n u),  u = 2^-24,
+
+where n is the fp32 accumulation depth the device's plan uses (any summation order of that depth satisfies it, so
+the bound never fails a correct kernel).  Forward convolutions (pinned summation order, include/vy_math.h) and the
+BatchNorm forward apply are bit-exact; the batch statistics are within 1 ulp of their float64 value rounded the way
+the finalize rounds it.
+
+The graph walked here mirrors OracleYolo3Train.forward_raw / backward: routes, concat order (the upsampled
+transition first), x2 transition gradients summed over 2x2, residual skips, planes with several consumers.
+
+Every check returns a Result; `ratio` is the worst error / bound (a pass is <= 1), `headroom` the worst
+error / (u sqrt(n) sum|terms|), the size of the error against a typical (random-walk) rounding error.
+"""
+import numpy as np
+import torch
+
+from . import yolo3_oracle as O
+
+U = 2.0 ** -24
+F32 = np.float32
+
+
+def gamma(n):
+    n = np.asarray(n, np.float64)
+    return n * U / (1.0 - n * U)
+
+
+class Result:
+    def __init__(self, kind, name, ratio, headroom, err_max=0.0, want_max=0.0, detail=""):
+        self.kind, self.name, self.ratio, self.headroom = kind, name, float(ratio), float(headroom)
+        self.err_max, self.want_max = float(err_max), float(want_max)
+        self.detail = detail
+
+    @property
+    def ok(self):
+        return self.ratio <= 1.0
+
+    @property
+    def old_bar_ok(self):
+        """would the end-to-end bar, max|got - want| < 2e-3 max|want| over the tensor, have passed?"""
+        return self.err_max < 2e-3 * self.want_max or self.err_max == 0.0
+
+    @staticmethod
+    def merge(parts):
+        """one Result of a tensor checked in pieces (channel blocks)"""
+        w = max(parts, key=lambda r: r.ratio)
+        r = Result(w.kind, w.name, w.ratio, max(p.headroom for p in parts), max(p.err_max for p in parts),
+                   max(p.want_max for p in parts), "; ".join(sorted(set(p.detail for p in parts if p.detail))))
+        return r
+
+    def __repr__(self):
+        return "%s %s: err/bound %.3g, err/(u sqrt(n) S) %.3g%s" % (self.kind, self.name, self.ratio, self.headroom,
+                                                                  (" " + self.detail) if self.detail else "")
+
+
+def _bounded(kind, name, got, want, absum, n, detail=""):
+    """got (fp32) vs want (float64) elementwise, bar gamma_n * absum (n scalar or per element)."""
+    got = np.asarray(got, np.float64)
+    err = np.abs(got - want)
+    bound = gamma(n) * absum
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(err == 0, 0.0, err / bound)
+        h = np.where(err == 0, 0.0, err / (U * np.sqrt(n) * absum))
+    return Result(kind, name, r.max(initial=0.0), h.max(initial=0.0), err.max(initial=0.0),
+                  np.abs(want).max(initial=0.0), detail)
+
+
+def _exact(kind, name, got, want):
+    bad = got != want
+    if got.dtype.kind == "f":
+        bad &= ~(np.isnan(got) & np.isnan(want))
+    nbad = int(np.count_nonzero(bad))
+    scale = np.abs(want.astype(np.float64)).max(initial=0.0)
+    err = np.abs(got.astype(np.float64) - want.astype(np.float64)).max(initial=0.0) if nbad else 0.0
+    return Result(kind, name, np.inf if nbad else 0.0, 0.0, err, scale, "%d elements differ" % nbad if nbad else "")
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a, np.float64))
+
+
+def fmaf(a, b, c):
+    """fp32 fmaf(a, b, c) exactly: a*b is exact in float64; s = fl64(a*b + c) plus its TwoSum error is the exact sum,
+    and rounding s to fp32 is only wrong when s sits exactly on an fp32 rounding midpoint (then the error's sign
+    decides)."""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = np.broadcast_to(c, p.shape).astype(np.float64)
+    s = p + c
+    bb = s - p
+    e = (p - (s - bb)) + (c - bb)
+    r = s.astype(F32)
+    rd = r.astype(np.float64)
+    # the fp32 neighbour on the other side of s, and whether s is their midpoint
+    other = np.where(s > rd, np.nextafter(r, F32(np.inf)), np.nextafter(r, F32(-np.inf))).astype(np.float64)
+    mid = (s != rd) & ((rd + other) * 0.5 == s)
+    fix = mid & (e != 0)
+    if np.any(fix):
+        up = e > 0
+        r = np.where(fix, np.where(up, np.maximum(r, other.astype(F32)), np.minimum(r, other.astype(F32))), r)
+    return r.astype(F32)
+
+
+def leaky(v):
+    return np.maximum(v, F32(0.1) * v)  # vy_leaky
+
+
+def upsample2(a):
+    return a.repeat(2, axis=-1).repeat(2, axis=-2)
+
+
+def interior(p):
+    return p[:, :, 1:-1, 1:-1]
+
+
+def border_zero(kind, name, p):
+    m = np.ones(p.shape[2:], bool)
+    m[1:-1, 1:-1] = False
+    nz = int(np.count_nonzero(p[:, :, m]))
+    return Result(kind, name, np.inf if nz else 0.0, 0.0, 0.0, 0.0, "%d nonzero border values" % nz if nz else "")
+
+
+# ---------------------------------------------------------------- the graph
+def graph(num_class):
+    """Cells in forward order: dict(name, k, s, cin, cout, bn, ups, src, skip).  `src`: the producers whose outputs,
+    concatenated in this order, are the cell's input ("image" for the stem); `skip`: the producer whose output is
+    added to this cell's (residual blocks)."""
+    cells = []
+
+    def add(name, k, s, cin, cout, src, bn=True, ups=1, skip=None):
+        cells.append(dict(name=name, k=k, s=s, cin=cin, cout=cout, bn=bn, ups=ups, src=list(src), skip=skip))
+
+    feats = O.darknet_feature_cells()
+    prev, routes = "image", []
+    for si, (lo, hi) in enumerate(O.STAGE_SLICES):
+        for j, f in enumerate(feats[lo:hi]):
+            pre = "stages.%d.%d" % (si, j)
+            if f[0] == "conv":
+                add(pre, f[3], f[4], f[1], f[2], [prev])
+                prev = pre
+            else:
+                c = f[1]
+                add(pre + ".body.0", 1, 1, c, c // 2, [prev])
+                add(pre + ".body.1", 3, 1, c // 2, c, [pre + ".body.0"], skip=prev)
+                prev = pre + ".body.1"
+        routes.append(prev)
+    chans = {c["name"]: c["cout"] for c in cells}
+    x = [routes[2]]
+    for i, ch in enumerate(O.HEAD_CHANNELS):
+        cin = sum(chans[p] for p in x)
+        for j in range(5):
+            oc, k = (ch, 1) if j % 2 == 0 else (2 * ch, 3)
+            name = "yolo_blocks.%d.body.%d" % (i, j)
+            add(name, k, 1, cin, oc, x)
+            x, cin = [name], oc
+        route = x[0]
+        add("yolo_blocks.%d.tip" % i, 3, 1, ch, 2 * ch, [route])
+        add("yolo_outputs.%d.prediction" % i, 1, 1, 2 * ch, 3 * (5 + num_class), ["yolo_blocks.%d.tip" % i], bn=False)
+        if i == 2:
+            break
+        add("transitions.%d" % i, 1, 1, ch, ch // 2, [route], ups=2)
+        chans["transitions.%d" % i] = ch // 2
+        x = ["transitions.%d" % i, routes[1 - i]]
+        chans.update({c["name"]: c["cout"] for c in cells})
+    return cells
+
+
+def consumers(cells):
+    """producer name -> [(consumer cell, channel offset of the producer inside the consumer's input)] and
+    producer name -> [cells whose skip it is]"""
+    cons, skips = {}, {}
+    for c in cells:
+        off = 0
+        for p in c["src"]:
+            cons.setdefault(p, []).append((c, off))
+            off += next((q["cout"] for q in cells if q["name"] == p), 3)
+        if c["skip"]:
+            skips.setdefault(c["skip"], []).append(c)
+    return cons, skips
+
+
+# ---------------------------------------------------------------- per-kernel checks
+def check_forward_conv(name, a, w, stride, z_got):
+    """raw conv output (no BN) on HIP's own input: bit-equal to the pinned-order oracle conv"""
+    k = w.shape[2]
+    return _exact("forward conv", name, z_got, O.conv2d(a, w, stride, k // 2))
+
+
+def check_stats(name, z, mean_got, invstd_got, gamma_p, beta_p, scale_got, shift_got, eps=1e-5):
+    """saved mean / invstd within 1 ulp of the float64 statistics rounded in the finalize's form; scale / shift as the
+    finalize forms them from those"""
+    z64 = z.astype(np.float64)
+    n = z.shape[0] * z.shape[2] * z.shape[3]
+    mean = z64.sum(axis=(0, 2, 3)) / n
+    var = np.maximum((z64 * z64).sum(axis=(0, 2, 3)) / n - mean * mean, 0.0)
+    mf, vf = mean.astype(F32), var.astype(F32)
+    inv = (F32(1.0) / np.sqrt(vf + F32(eps))).astype(F32)
+    e_m = np.abs(mean_got.astype(np.float64) - mf) / np.spacing(np.abs(mf)).astype(np.float64)
+    e_i = np.abs(invstd_got.astype(np.float64) - inv) / np.spacing(np.abs(inv)).astype(np.float64)
+    ulps = float(max(e_m.max(), e_i.max()))
+    r = Result("forward stats", name, ulps, ulps, np.abs(mean_got - mf).max(), np.abs(mf).max(), "%.2g ulp" % ulps)
+    sc = (gamma_p * invstd_got).astype(F32)
+    sh = fmaf(-mean_got, sc, beta_p)
+    if not (np.array_equal(sc, scale_got) and np.array_equal(sh, shift_got)):
+        r.ratio, r.detail = np.inf, r.detail + ", scale/shift differ from the finalize's form"
+    return r
+
+
+def check_apply(name, z, scale, shift, out_got, res=None, ups=1):
+    """forward apply: leaky(fmaf(z, scale, shift)) (+ skip) (x2 replicated), fp32, bit-equal"""
+    v = leaky(fmaf(z, scale.reshape(1, -1, 1, 1), shift.reshape(1, -1, 1, 1)))
+    if res is not None:
+        v = (v + res).astype(F32)
+    if ups == 2:
+        v = upsample2(v)
+    return _exact("forward apply", name, out_got, v)
+
+
+def bn_backward64(z, g_out, bn, gamma_p, ups):
+    """float64 BN + leaky backward from the tapped z, output gradient (interior, at the stored resolution) and
+    [mean, invstd, scale, shift]: dict of the references and their absolute-value sums"""
+    mean, inv, sc, sh = [bn[i].astype(np.float64).reshape(1, -1, 1, 1) for i in range(4)]
+    z64 = z.astype(np.float64)
+    g = g_out.astype(np.float64)
+    if ups == 2:
+        B, C, H2, W2 = g.shape
+        g4 = g.reshape(B, C, H2 // 2, 2, W2 // 2, 2)
+        da, da_abs = g4.sum(axis=(3, 5)), np.abs(g4).sum(axis=(3, 5))
+    else:
+        da, da_abs = g, np.abs(g)
+    # the mask: sign of fmaf(z, scale, shift) — z*scale is exact in float64 and one rounding keeps the sign
+    slope = np.where(z64 * sc + sh > 0, 1.0, 0.1)
+    dy, dy_abs = da * slope, da_abs * slope
+    xh = (z64 - mean) * inv
+    n = z.shape[0] * z.shape[2] * z.shape[3]
+    dbeta, s1 = dy.sum(axis=(0, 2, 3)), dy_abs.sum(axis=(0, 2, 3))
+    dgamma, s2 = (dy * xh).sum(axis=(0, 2, 3)), (dy_abs * np.abs(xh)).sum(axis=(0, 2, 3))
+    c1 = gamma_p.astype(np.float64).reshape(1, -1, 1, 1) * inv
+    c2, c3 = (dbeta / n).reshape(1, -1, 1, 1), (dgamma / n).reshape(1, -1, 1, 1)
+    dz = c1 * (dy - c2 - xh * c3)
+    return dict(dbeta=dbeta, s1=s1, dgamma=dgamma, s2=s2, dz=dz, c1=c1, c2=c2, c3=c3, dy_abs=dy_abs, xh=xh, n=n)
+
+
+def check_bn_backward(name, z, g_out, bn, gamma_p, ups, rows_per_chunk, dgamma_got, dbeta_got, dz_got):
+    """dgamma / dbeta: fp32 partial sums over one chunk of rows_per_chunk image rows (then float64), each term rounded
+    a few times on the way (2x2 sum, slope, xhat); dz = c1 ((dy - c2) - xhat c3) from the fp32 coefficients"""
+    r = bn_backward64(z, g_out, bn, gamma_p, ups)
+    d = rows_per_chunk * z.shape[3] + 8
+    out = [_bounded("bn backward dbeta", name, dbeta_got, r["dbeta"], r["s1"], d),
+           _bounded("bn backward dgamma", name, dgamma_got, r["dgamma"], r["s2"], d)]
+    e2 = gamma(d) * r["s1"].reshape(1, -1, 1, 1) / r["n"] + U * np.abs(r["c2"])
+    e3 = gamma(d) * r["s2"].reshape(1, -1, 1, 1) / r["n"] + U * np.abs(r["c3"])
+    absum = r["dy_abs"] + np.abs(r["c2"]) + np.abs(r["xh"] * r["c3"])
+    # bar = |c1| (e2 + |xhat| e3 + gamma_10 absum), written as gamma_10 * S_eff for _bounded
+    s_eff = np.abs(r["c1"]) * ((e2 + np.abs(r["xh"]) * e3) / gamma(10) + absum)
+    out.append(_bounded("bn backward dz", name, dz_got, r["dz"], s_eff, 10))
+    return out
+
+
+def wgrad64(dz, a, k, stride, sel):
+    """sum_p dz[p, o] a[p*stride + tap, c] for the output channels `sel`, and the same over |dz| |a|"""
+    shape = (len(sel), a.shape[1], k, k)
+    dzs = _t(dz[:, sel])
+    at = _t(a)
+    want = torch.nn.grad.conv2d_weight(at, shape, dzs, stride=stride, padding=k // 2).numpy()
+    absum = torch.nn.grad.conv2d_weight(at.abs(), shape, dzs.abs(), stride=stride, padding=k // 2).numpy()
+    return want, absum
+
+
+def check_wgrad(name, dz, a, k, stride, sel, got, splits, k_per_split, kind="weight gradient"):
+    """split-K over the pixels: fp32 within a split of k_per_split pixels, the slabs added in fp32"""
+    want, absum = wgrad64(dz, a, k, stride, sel)
+    return _bounded(kind, name, got, want, absum, k_per_split + splits + 2,
+                    "(%d splits x %d px)" % (splits, k_per_split))
+
+
+def check_bias_grad(name, dpred, got, chunk=64):
+    d = dpred.astype(np.float64)
+    return _bounded("bias gradient", name, got, d.sum(axis=(0, 2, 3)), np.abs(d).sum(axis=(0, 2, 3)), chunk + 2)
+
+
+def dgrad64(dz, w, stride, in_hw):
+    k = w.shape[2]
+    shape = (dz.shape[0], w.shape[1], in_hw[0], in_hw[1])
+    want = torch.nn.grad.conv2d_input(shape, _t(w), _t(dz), stride=stride, padding=k // 2).numpy()
+    absum = torch.nn.grad.conv2d_input(shape, _t(np.abs(w)), _t(np.abs(dz)), stride=stride, padding=k // 2).numpy()
+    return want, absum
+
+
+def check_dgrad(name, got, terms, addends=()):
+    """gradient plane of a producer: sum over its consumers of convT(dz, W) restricted to the producer's channels
+    [lo, lo + C), plus the skip addends.  terms: [(dz, w, stride, lo)]"""
+    C, hw = got.shape[1], got.shape[2:]
+    want = np.zeros(got.shape, np.float64)
+    absum = np.zeros(got.shape, np.float64)
+    n = 2
+    for dz, w, stride, lo in terms:
+        wv, av = dgrad64(dz, w[:, lo:lo + C], stride, hw)
+        want += wv
+        absum += av
+        n += w.shape[0] * w.shape[2] * w.shape[3]
+    for a in addends:
+        want += a.astype(np.float64)
+        absum += np.abs(a.astype(np.float64))
+        n += 1
+    return _bounded("data gradient", name, got, want, absum, n)
+
+
+# ---------------------------------------------------------------- loss gradient
+def head_grads(num_class, preds, gt_boxes, targets, ignore_iou_thresh=0.7, label_smooth=False, near=1e-6):
+    """d(loss)/d(pred) by the oracle's merge_targets + loss on the device's own raw predictions (fp32 oracle math,
+    float64 where it sums).  Returns (dpreds in the (B, A*P, H, W) head layout, exempt masks of the same shapes: the
+    positions whose ignore-IoU decision lies within `near` of the threshold)."""
+    from .yolo3_train_oracle import OracleYolo3Train
+    orc = OracleYolo3Train(num_class, {}, ignore_iou_thresh=ignore_iou_thresh, label_smooth=label_smooth)
+    pr = orc.split_preds(preds)
+    tg = orc.merge_targets(pr["box"], gt_boxes, *targets)
+    _, g = orc.loss(pr, tg)
+    ious_max = O.batch_iou(pr["box"], gt_boxes).max(axis=-1, keepdims=True)
+    close = (np.abs(ious_max.astype(np.float64) - ignore_iou_thresh) < near) & ~(targets[0] > 0)  # (B, N, 1)
+    A, P = 3, 5 + num_class
+    out, ex, n0 = [], [], 0
+    for pred in preds:
+        B, _, H, W = pred.shape
+        n1 = n0 + H * W * A
+        d = np.concatenate([g["xy"][:, n0:n1], g["wh"][:, n0:n1], g["obj"][:, n0:n1], g["cls"][:, n0:n1]], -1)
+        out.append(np.ascontiguousarray(d.reshape(B, H * W, A * P).transpose(0, 2, 1).reshape(B, A * P, H, W)))
+        m = np.broadcast_to(close[:, n0:n1].reshape(B, H * W, A, 1), (B, H * W, A, P)).reshape(B, H * W, A * P)
+        ex.append(np.ascontiguousarray(m.transpose(0, 2, 1).reshape(B, A * P, H, W)))
+        n0 = n1
+    return out, ex
+
+
+def check_head_grad(name, got, want, exempt, ulps=4):
+    """d(loss)/d(pred): a few ulp of the terms it is formed from (sigmoid(x) - t, weighted; sign(x - t), weighted)"""
+    got64, want64 = got.astype(np.float64), want.astype(np.float64)
+    err = np.where(exempt, 0.0, np.abs(got64 - want64))
+    bound = ulps * U * (np.abs(want64) + 2.0)  # sigmoid and targets are O(1), the box weights <= 2
+    r = (err / bound).max(initial=0.0)
+    return Result("loss gradient", name, r, r, err.max(initial=0.0), np.abs(want64).max(initial=0.0),
+                  "%d exempt (IoU within 1e-6 of the threshold)" % int(np.count_nonzero(exempt)))
+
+
+def summarize(results):
+    """per kernel class: the worst err/bound and err/(u sqrt(n) S)"""
+    by = {}
+    for r in results:
+        w = by.setdefault(r.kind, [-1.0, 0.0, "", 0])
+        w[3] += 1
+        if r.ratio > w[0]:
+            w[0], w[2] = r.ratio, r.name
+        w[1] = max(w[1], r.headroom)
+    return {k: dict(worst_ratio=v[0], worst_cell=v[2], worst_headroom=v[1], checks=v[3]) for k, v in sorted(by.items())}

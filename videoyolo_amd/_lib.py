@@ -8,6 +8,7 @@ LIB_PATH = os.path.join(_HERE, "libvyolo.so")
 
 VY_MAX_TOPK = 1024
 VY_CONV_EXACT_FP32, VY_CONV_SPLIT_BF16X3, VY_CONV_SPLIT_BF16X3_TRAIN = 0, 1, 2
+VY_TAP_Z, VY_TAP_BN, VY_TAP_GRAD_PADDED, VY_TAP_INPUT_PADDED = 0, 1, 2, 3
 
 
 class VyError(RuntimeError):
@@ -89,6 +90,8 @@ SIGNATURES.update({
     "vy_net_sgd_step": (ctypes.c_int, [_vp, _f32, _f32, _f32, _f32, _vp]),
     "vy_net_grad_get": (ctypes.c_int, [_vp, _i32, _vp, _vp]),
     "vy_net_read_grad_activation": (ctypes.c_int, [_vp, ctypes.c_char_p, _vp, _vp]),
+    "vy_net_read_train_tap": (ctypes.c_int, [_vp, ctypes.c_char_p, _i32, _vp, ctypes.POINTER(_i32), _vp]),
+    "vy_net_train_conv_plan": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "vy_net_set_sync_bn": (ctypes.c_int, [_vp, _i32, ALLREDUCE_CB, _vp]),
     "vy_net_set_grad_bucket_cb": (ctypes.c_int, [_vp, GRAD_BUCKET_CB, _vp]),
 })

@@ -165,6 +165,9 @@ hipError_t vy_launch_bn_fold(float* params, const FoldDesc* descs_dev, int n_lay
 // plane view -> dense NCHW copy (parity taps)
 hipError_t vy_launch_plane_to_nchw(const float* plane, int B, int H, int W, int cs, int co, int C,
                                    float* dst, hipStream_t s);
+// ... border included: (B, C, Hp, Wp) (training parity taps)
+hipError_t vy_launch_padded_plane_to_nchw(const float* plane, int B, int Hp, int Wp, int cs, int co, int C, float* dst,
+                                          hipStream_t s);
 hipError_t vy_launch_nchw_to_plane(const float* src, int B, int H, int W, int cs, int co, int C, float* plane,
                                    hipStream_t s);
 

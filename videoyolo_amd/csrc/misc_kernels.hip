@@ -252,6 +252,21 @@ __global__ void plane_to_nchw_kernel(const float* plane, int B, int H, int W, in
   }
 }
 
+// the whole padded plane view, border included -> dense NCHW (B, C, Hp, Wp) (training parity taps only)
+__global__ void padded_plane_to_nchw_kernel(const float* plane, int B, int Hp, int Wp, int cs, int co, int C, float* dst) {
+  const long long n = (long long)B * C * Hp * Wp;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(i % Wp);
+    long long t = i / Wp;
+    const int y = (int)(t % Hp);
+    t /= Hp;
+    const int c = (int)(t % C);
+    const int b = (int)(t / C);
+    dst[i] = plane[((long long)(b * Hp + y) * Wp + x) * cs + co + c];
+  }
+}
+
 // dense NCHW -> plane view (vy_net_detect_heads: caller-supplied prediction tensors into the head planes)
 __global__ void nchw_to_plane_kernel(const float* src, int B, int H, int W, int cs, int co, int C, float* plane) {
   const long long n = (long long)B * C * H * W;
@@ -283,5 +298,15 @@ hipError_t vy_launch_plane_to_nchw(const float* plane, int B, int H, int W, int 
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL(plane_to_nchw_kernel, dim3((unsigned)blocks), dim3(256), 0, s, plane, B, H, W, cs, co,
                      C, dst);
+  return hipGetLastError();
+}
+
+hipError_t vy_launch_padded_plane_to_nchw(const float* plane, int B, int Hp, int Wp, int cs, int co, int C, float* dst,
+                                          hipStream_t s) {
+  const long long n = (long long)B * C * Hp * Wp;
+  long long blocks = (n + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(padded_plane_to_nchw_kernel, dim3((unsigned)blocks), dim3(256), 0, s, plane, B, Hp, Wp, cs, co, C,
+                     dst);
   return hipGetLastError();
 }

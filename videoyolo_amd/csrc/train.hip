@@ -1129,6 +1129,88 @@ int vy_net_read_grad_activation(vy_net* net, const char* name, float* dst_dev, v
   return fail(VY_ERR_INVALID, "no cell named '%s'", name);
 }
 
+int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* dst_dev, int32_t* dims, void* stream) {
+  if (!net || !name) return fail(VY_ERR_INVALID, "bad argument");
+  if (int rc = net->check_ready()) return rc;
+  VyTrain* t = net->train;
+  if (!t || !t->grads) return fail(VY_ERR_STATE, "training workspace not bound");
+  TrainCtx c{net, t, static_cast<hipStream_t>(stream)};
+  for (size_t ci = 0; ci < net->convs.size(); ++ci) {
+    const ConvT& cv = net->convs[ci];
+    if (cv.name != name) continue;
+    const bool bn = cv.p_gamma >= 0;
+    int32_t d[4] = {net->B, cv.cout, 0, 0};
+    const float* src = nullptr;
+    int cs = 0, co = 0;
+    switch (which) {
+      case VY_TAP_Z:
+        if (!bn) return fail(VY_ERR_INVALID, "'%s' has no z plane", name);
+        src = c.zplane((int)ci);
+        d[2] = t->z[ci].H + 2;
+        d[3] = t->z[ci].W + 2;
+        cs = t->z[ci].C;
+        break;
+      case VY_TAP_BN:
+        if (!bn) return fail(VY_ERR_INVALID, "'%s' has no BatchNorm", name);
+        d[0] = 4;
+        d[2] = d[3] = 1;
+        break;
+      case VY_TAP_GRAD_PADDED: {
+        const PlaneT& p = net->planes[cv.out_plane];
+        src = c.gplane(cv.out_plane);
+        d[2] = p.H + 2;
+        d[3] = p.W + 2;
+        cs = p.C;
+        co = cv.out_co;
+        break;
+      }
+      case VY_TAP_INPUT_PADDED: {
+        if (cv.is_stem) return fail(VY_ERR_INVALID, "the stem reads the image, not a plane");
+        const PlaneT& p = net->planes[cv.in_plane];
+        src = net->plane_ptr(cv.in_plane);
+        d[1] = cv.cin;
+        d[2] = p.H + 2;
+        d[3] = p.W + 2;
+        cs = p.C;
+        co = cv.in_co;
+        break;
+      }
+      default:
+        return fail(VY_ERR_INVALID, "unknown tap %d", which);
+    }
+    if (dims) memcpy(dims, d, sizeof d);
+    if (!dst_dev) return 0;
+    if (which == VY_TAP_BN) {
+      const int C = cv.cout;
+      const float* rows[4] = {c.save((int)ci), c.save((int)ci) + ((C + 63) & ~63), net->dev_params + cv.scale_off,
+                              net->dev_params + cv.shift_off};
+      for (int r = 0; r < 4; ++r)
+        HIP_TRY(hipMemcpyAsync(dst_dev + (size_t)r * C, rows[r], sizeof(float) * C, hipMemcpyDeviceToDevice, c.s));
+      return 0;
+    }
+    HIP_TRY(vy_launch_padded_plane_to_nchw(src, d[0], d[2], d[3], cs, co, d[1], dst_dev, c.s));
+    return 0;
+  }
+  return fail(VY_ERR_INVALID, "no cell named '%s'", name);
+}
+
+int vy_net_train_conv_plan(const vy_net* net, int32_t i, int32_t* wgrad_splits, int32_t* wgrad_k_per_split,
+                           int32_t* bn_bwd_rows_per_chunk) {
+  if (!net || i < 0 || i >= (int32_t)net->convs.size()) return fail(VY_ERR_INVALID, "bad argument");
+  const VyTrain* t = net->train;
+  if (!t || t->splits.size() != net->convs.size()) return fail(VY_ERR_STATE, "no training plan");
+  const ConvT& cv = net->convs[i];
+  int sp = t->splits[i], kps = t->kps[i];
+  if (cv.is_stem) {  // stem_wgrad_kernel: one fp32 accumulator per wave over 512 pixels, the four waves of a block added
+    sp = 4;            // in fp32, the blocks in double
+    kps = 512;
+  }
+  if (wgrad_splits) *wgrad_splits = sp;
+  if (wgrad_k_per_split) *wgrad_k_per_split = kps;
+  if (bn_bwd_rows_per_chunk) *bn_bwd_rows_per_chunk = cv.p_gamma >= 0 ? vy_bn_bwd_rows_per_chunk(t->B, t->z[i].H, cv.cout) : 0;
+  return 0;
+}
+
 int vy_net_set_sync_bn(vy_net* net, int32_t world, vy_allreduce_cb cb, void* user) {
   if (!net || world < 1) return fail(VY_ERR_INVALID, "bad argument");
   if (world > 1 && !cb) return fail(VY_ERR_INVALID, "world > 1 needs an all-reduce callback");

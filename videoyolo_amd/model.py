@@ -720,6 +720,34 @@ class YOLOV3(object):
                                                              ctypes.c_void_p(out.data_ptr()), self._stream()))
         return out
 
+    def read_train_tap(self, name, which):
+        """Test-only tap of the training step (vy_net_read_train_tap): which = 'z' (z after forward_train, dz after
+        backward; border included), 'bn' ([4][Cout]: saved mean, saved invstd, scale, shift), 'grad' (output gradient,
+        border included) or 'input' (the input view the conv reads, border included).  Device tensor."""
+        torch = _torch()
+        w = {"z": _lib.VY_TAP_Z, "bn": _lib.VY_TAP_BN, "grad": _lib.VY_TAP_GRAD_PADDED,
+             "input": _lib.VY_TAP_INPUT_PADDED}[which]
+        dims = (ctypes.c_int32 * 4)()
+        _lib.check(self._lib.vy_net_read_train_tap(self._h, name.encode(), w, None, dims, None))
+        shape = tuple(dims)[:2] if which == "bn" else tuple(dims)
+        out = torch.empty(shape, dtype=torch.float32, device=self._device)
+        with torch.cuda.device(self._device):
+            _lib.check(self._lib.vy_net_read_train_tap(self._h, name.encode(), w, ctypes.c_void_p(out.data_ptr()), None,
+                                                       self._stream()))
+        return out
+
+    def train_conv_plan(self, name):
+        """(wgrad splits, wgrad pixels per split, BatchNorm-backward rows per chunk) of cell `name` in the bound
+        training plan (vy_net_train_conv_plan)."""
+        for i in range(self._lib.vy_net_num_convs(self._h)):
+            info = _lib.ConvInfo()
+            _lib.check(self._lib.vy_net_conv_info(self._h, i, ctypes.byref(info)))
+            if info.name.decode() == name:
+                v = [ctypes.c_int32() for _ in range(3)]
+                _lib.check(self._lib.vy_net_train_conv_plan(self._h, i, *[ctypes.byref(x) for x in v]))
+                return tuple(x.value for x in v)
+        raise KeyError(name)
+
     def _sync_opts(self):
         """Parameter.lr_mult / wd_mult / grad_req -> the library's SGD segment table; only the rows that
         changed since the last call are sent (steady state: no calls, no table re-upload)."""
