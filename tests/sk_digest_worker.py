@@ -1,7 +1,7 @@
 """Subprocess body of test_gpu_fullsize.py::test_stream_k_launches_equal_plain_launches: one seeded network, one seeded
 batch; prints which inference launches ran as stream-K and SHA-256 digests of (a) the three raw heads + the detections
-and (b) the four losses + all gradients of one recorded training step.  VY_CONV_SK is read once per process by the
-library, so the two switch positions need two processes.
+and (b) the four losses + all gradients of one recorded training step.  VY_CONV_SK is read from the environment when
+the library creates a net, so the two switch positions run in two processes, each with its own environment.
 With a third argument "graph" the net is hybridized BEFORE its first forward — the capture is then the first time the
 library sees these launches (its once-per-instance occupancy queries run inside the capture) — and only the inference
 digest is produced, from two replays.

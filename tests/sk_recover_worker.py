@@ -1,6 +1,6 @@
 """Subprocess body of tests/test_gpu_streamk.py::test_stale_flags_are_cleared_after_an_error_return.  Started with
 VY_CONV_SK_SLOTS=13, which makes EVERY conv launch of more than 13 tiles a stream-K launch on 13 blocks (the switch is
-read once per process).  Sequence: a forward (reference) -> every hand-off flag of the workspace is raised by hand, as
+read when the net is created).  Sequence: a forward (reference) -> every hand-off flag of the workspace is raised by hand, as
 an aborted launch sequence could leave them -> an entry point of the handle returns an error -> the next forward must
 zero the flags first and reproduce the reference bit for bit."""
 import ctypes

@@ -39,6 +39,42 @@ def test_product_does_not_touch_the_oracle():
                 assert "oracle" not in text.replace("the oracle", "").replace("CPU checker", ""), (dp, f)
 
 
+def test_only_the_switch_reader_reads_the_environment():
+    """The launch switches are read in one place (csrc/knobs.h, once per net at vy_net_create): no other library source
+    calls getenv."""
+    csrc = os.path.join(ROOT, "videoyolo_amd", "csrc")
+    readers = []
+    for dp, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".hip", ".h", ".cpp")) and "getenv" in open(os.path.join(dp, f)).read():
+                readers.append(f)
+    assert readers == ["knobs.h"], readers
+
+
+def test_switches_are_per_net(monkeypatch):
+    """A net keeps the switches it was created with: VY_SPLIT_TRAIN=0 leaves the data-gradient weight images out of the
+    split training plan, =1 (the default) puts them in — for nets created side by side in one process, whatever the
+    environment holds when they are planned."""
+    lib = _lib.load()
+
+    def create(split_train):
+        monkeypatch.setenv("VY_SPLIT_TRAIN", split_train)
+        h = ctypes.c_void_p()
+        _lib.check(lib.vy_net_create(20, ctypes.byref(h)))
+        _lib.check(lib.vy_net_set_conv_mode(h, _lib.VY_CONV_SPLIT_BF16X3_TRAIN))
+        return h
+
+    a = create("0")
+    size_a = lib.vy_net_train_workspace_bytes(a, 1, 416, 416)
+    b = create("1")
+    size_b = lib.vy_net_train_workspace_bytes(b, 1, 416, 416)
+    assert 0 < size_a < size_b
+    monkeypatch.delenv("VY_SPLIT_TRAIN")
+    assert lib.vy_net_train_workspace_bytes(a, 1, 416, 416) == size_a
+    lib.vy_net_destroy(a)
+    lib.vy_net_destroy(b)
+
+
 @pytest.mark.parametrize("ncls,total", [(20, 61626049), (30, 61679899)])
 def test_param_table_matches_reference_structure(ncls, total):
     from oracle import yolo3_oracle as O

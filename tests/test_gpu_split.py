@@ -172,11 +172,12 @@ def test_kernel_computes_the_six_products(voc_classes, synth20, name, src, k, st
 
 
 @pytest.mark.parametrize("batch,h,w", [(2, 96, 96), (3, 160, 160), (1, 128, 224), (1, 416, 416)])
-def test_winograd_cells_forced_everywhere(voc_classes, synth20, batch, h, w, monkeypatch, capsys):
+def test_winograd_cells_forced_everywhere_per_net(voc_classes, synth20, batch, h, w, monkeypatch, capsys):
     """conv_wino.hip — the long-K 3x3 stride-1 cells as a 1-D Winograd F(2, 3) on the same split arithmetic — is chosen by
     the product only for launches of >= 1024 blocks; VY_SPLIT_WINO=2 sends EVERY supported cell through it (the 31 cells
     of 128 output channels and more, residual adds included, at widths 3 ... 52: odd widths exercise the pair without a
-    second pixel).  Heads and layer taps within the split mode's bars, kept rows up to near-ties; =0 switches it off."""
+    second pixel).  Heads and layer taps within the split mode's bars, kept rows up to near-ties; =0 switches it off.
+    A net reads the switch when it is created, so each position gets a net of its own."""
     monkeypatch.setenv("VY_SPLIT_WINO", "2")
     rng = np.random.default_rng(h * 1000 + w)
     x = rng.standard_normal((batch, 3, h, w)).astype(np.float32)
@@ -195,7 +196,8 @@ def test_winograd_cells_forced_everywhere(voc_classes, synth20, batch, h, w, mon
     assert len(exc) <= 4
     np.testing.assert_allclose(np.sort(scores, 1), np.sort(r[1], 1), rtol=0, atol=TOL)
     monkeypatch.setenv("VY_SPLIT_WINO", "0")
-    assert not any("|wino" in n for n in _split_launches(net, x))
+    assert sum("|wino" in n for n in _split_launches(net, x)) == 31  # the live net keeps the value it was created with
+    assert not any("|wino" in n for n in _split_launches(_net(voc_classes, synth20), x))
 
 
 @pytest.mark.parametrize("batch,size,obj_bias", [(2, 96, 0.0), (2, 128, -3.0), (1, 416, 0.0), (2, 160, -5.0)])
@@ -376,7 +378,7 @@ def test_split_training_step_within_the_steps_own_sensitivity(C, B, S, capsys):
 @pytest.mark.parametrize("which,env", [("data gradients", {"VY_SPLIT_TRAIN": "3", "VY_SPLIT_WGRAD": "0"}),
                                        ("weight gradients", {"VY_SPLIT_TRAIN": "0", "VY_SPLIT_WGRAD": "1"})])
 def test_split_gradients_alone_meet_the_exact_bars(which, env):
-    """Own process (the switches are read once): forward EXACT — bit-equal to the oracle, so no branch flips — and ONE
+    """Own process (the switches are set before its nets are created): forward EXACT — bit-equal to the oracle, so no branch flips — and ONE
     kind of gradient on its split kernel.  VY_SPLIT_TRAIN=3: the data gradients (conv_split.hip: [k = cout][n = cin] weight
     images, flipped taps, the four parity classes of the stride-2 convs, cout = 3 (5 + C) zero-padded to 32 for the
     prediction convs, accumulate into a skip gradient).  VY_SPLIT_WGRAD=1 with VY_SPLIT_TRAIN=0: the weight gradients

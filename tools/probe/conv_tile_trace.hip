@@ -82,6 +82,8 @@ int main(int argc, char** argv) {
   a.w_taps = k * k; a.w_cin = Cin; a.w_cout = Cout; a.N = Cout;
   a.o_Hp = Ho + 2; a.o_Wp = Ho + 2; a.o_cs = Cout; a.o_co = 0; a.o_s = 1; a.o_oy = a.o_ox = 1; a.ups = 1;
   a.r_cs = Cout; a.r_co = 0; a.leaky = 1; a.dgrad = 0;
+  const VyKnobs knobs = vy_knobs_read();  // VY_CONV_FORCE / VY_CONV_SK / VY_CONV_SK_GAIN (run_model_sweep.sh, pmc_sk_traffic.sh)
+  a.knobs = &knobs;
   {  // stream-K scratch, as a net's workspace provides it (zeroed: all flags down)
     void* skp;
     CK(hipMalloc(&skp, (size_t)VY_SK_PARTIAL_BYTES + (size_t)VY_SK_FLAGS * 4));

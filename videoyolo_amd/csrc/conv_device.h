@@ -1,11 +1,10 @@
-// conv_device.h — device-side helpers shared by the implicit-GEMM conv kernels (conv_igemm.hip: 32x32x2 MFMA tiles,
-// conv_small.hip: 16x16x4 MFMA tiles for launches that cannot fill the chip with 32x32 wave tiles).
+// conv_device.h — device-side helpers shared by the implicit-GEMM conv kernels (conv_igemm.hip, conv_split.hip,
+// conv_wino.hip) and the split-fp32 weight gradient (wgrad_split.hip).
 #pragma once
 #include "kernels.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 

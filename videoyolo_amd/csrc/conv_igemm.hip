@@ -806,11 +806,8 @@ static int resident_blocks(K kernel, int threads) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0) != hipSuccess || n < 1) n = 1;
   return n;
 }
-// CUs of the current device (per device, queried once each; VY_CU_COUNT=n overrides it: tests of the cost models'
-// behaviour on a chip they were not fitted on).  256 when there is no device to ask (host-only callers)
+// CUs of the current device (per device, queried once each).  256 when there is no device to ask (host-only callers)
 int vy_cu_count_of(int dev) {
-  static const int forced = getenv("VY_CU_COUNT") ? atoi(getenv("VY_CU_COUNT")) : 0;
-  if (forced > 0) return forced;
   static std::atomic<int> cache[64];  // (several host threads may drive their own nets: relaxed atomics, idempotent fill)
   if (dev < 0 || dev >= 64) return VY_MODEL_CUS;
   int c = cache[dev].load(std::memory_order_relaxed);
@@ -854,7 +851,6 @@ int vy_sk_verify_topology(unsigned* scratch_dev, hipStream_t s) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
   if (cache[dev]) return cache[dev] == 1;
-  if (getenv("VY_CONV_SK_NO_TOPOLOGY_CHECK") && atoi(getenv("VY_CONV_SK_NO_TOPOLOGY_CHECK"))) return (cache[dev] = 1) == 1;
   constexpr int NB = 512;
   unsigned host[NB];
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -872,28 +868,16 @@ int vy_sk_verify_topology(unsigned* scratch_dev, hipStream_t s) {
 }
 
 // ---- the launch cost model (conv_cost_model.h), shared by the tile choice (select_cfg) and the stream-K decision ----
-struct SkSwitches {
-  int on, dgrad, slots;
-  double min_gain, cost;
-};
-// VY_CONV_SK=0: plain launches only.  VY_CONV_SK_DGRAD=1: data gradients too (off: in the training step the weight-
-// gradient stream runs beside them and its blocks already fill the CUs a partly filled round leaves idle; measured,
-// stream-K there only moves the idle time).  VY_CONV_SK_SLOTS=n (tests): EVERY launch of more than n tiles on n blocks.
-// VY_CONV_SK_GAIN / VY_CONV_SK_COST: the criterion's threshold (3 % of the plain launch) and hand-off cost (7.5 us).
-static const SkSwitches& sk_switches() {
-  static const SkSwitches s = {getenv("VY_CONV_SK") ? atoi(getenv("VY_CONV_SK")) : 1,
-                               getenv("VY_CONV_SK_DGRAD") ? atoi(getenv("VY_CONV_SK_DGRAD")) : 0,
-                               getenv("VY_CONV_SK_SLOTS") ? atoi(getenv("VY_CONV_SK_SLOTS")) : 0,
-                               getenv("VY_CONV_SK_GAIN") ? atof(getenv("VY_CONV_SK_GAIN")) : 0.03,
-                               getenv("VY_CONV_SK_COST") ? atof(getenv("VY_CONV_SK_COST")) : 7.5};
-  return s;
-}
+// Data gradients are never stream-K by the model (in the training step the weight-gradient stream runs beside them and
+// its blocks already fill the CUs a partly filled round leaves idle; measured, stream-K there only moves the idle time);
+// VY_CONV_SK_SLOTS (tests) forces it on them too
 static bool sk_allowed(const ConvArgs& a) {
-  const SkSwitches& w = sk_switches();
-  return w.on && a.sk_partials && a.sk_flags && (!a.dgrad || w.dgrad || w.slots > 0);
+  const VyKnobs& k = vy_args_knobs(a);
+  return k.conv_sk && a.sk_partials && a.sk_flags && (!a.dgrad || k.conv_sk_slots > 0);
 }
 static VySkPolicy sk_policy(const ConvArgs& a) {
-  return VySkPolicy{sk_allowed(a), sk_switches().min_gain, sk_switches().cost};
+  const VyKnobs& k = vy_args_knobs(a);
+  return VySkPolicy{sk_allowed(a), k.conv_sk_gain, k.conv_sk_cost};
 }
 
 // `sk_query` != nullptr: nothing is launched, *sk_query tells whether the launch would be a stream-K one (the profile's label)
@@ -920,7 +904,7 @@ static hipError_t launch_cfg(const ConvArgs& a_in, hipStream_t s, bool* sk_query
   if (sk_allowed(a)) {
     static const int res_f = resident_blocks(conv_igemm_kernel<BM, BN, WM, WN, false, NS, true>, WM * WN * 64);
     static const int res_d = resident_blocks(conv_igemm_kernel<BM, BN, WM, WN, true, NS, true>, WM * WN * 64);
-    const int sk_slots = sk_switches().slots;
+    const int sk_slots = vy_args_knobs(a).conv_sk_slots;
     const int cus = vy_args_cus(a);
     // blocks per CU: as many as fit, but never so many that a share is shorter than one tile (a share is at most
     // [head][whole tiles][tail]).  344 tiles (the 13x13 maps at batch 16): ONE block per CU with 1.34 tiles each, where
@@ -933,9 +917,8 @@ static hipError_t launch_cfg(const ConvArgs& a_in, hipStream_t s, bool* sk_query
     // Measured (profiles/r06_ksplit_probe.txt, one frame): 13x13 / 19x19 3x3 cells on 512 channels 75 -> 33 / 47 us; a
     // launch of 184 tiles cut in two lost 4 %: hence tiles <= CUs / 2.  VY_CONV_KSPLIT=0: never.
     if (ksplit_S > 1) {
-      static const int ks_on = getenv("VY_CONV_KSPLIT") ? atoi(getenv("VY_CONV_KSPLIT")) : 1;
       const long long cap = (long long)cus * res_f;
-      if (ks_on && sk_slots == 0 && 2 * tiles <= cus && tiles * ksplit_S <= cap && tiles * ksplit_S * BM * BN * 4ll <= (long long)a.sk_bytes &&
+      if (vy_args_knobs(a).conv_ksplit && sk_slots == 0 && 2 * tiles <= cus && tiles * ksplit_S <= cap && tiles * ksplit_S * BM * BN * 4ll <= (long long)a.sk_bytes &&
           tiles * ksplit_S <= a.sk_nflags) {
         if (sk_query) {
           *sk_query = false;
@@ -991,42 +974,21 @@ static hipError_t launch_cfg(const ConvArgs& a_in, hipStream_t s, bool* sk_query
   return hipGetLastError();
 }
 
-// Tile choice: conv_cost_model.h, plus the experiment switches.
+// Tile choice: conv_cost_model.h, or the tile VY_CONV_FORCE names (tools/train_layers.sh, tools/probe/run_model_sweep.sh)
 static void select_cfg(const ConvArgs& a, int* bm, int* bn) {
-  auto blocks = [&](int m, int n) { return (long long)((a.M + m - 1) / m) * ((a.N + n - 1) / n); };
-  // experiment switch (tools/train_layers.sh): VY_CONV_FORCE=128x64 runs every launch on that tile
-  static const char* force = getenv("VY_CONV_FORCE");
-  if (force && sscanf(force, "%dx%d", bm, bn) == 2 && !(*bm == 32 && a.dgrad)) return;
+  const VyKnobs& k = vy_args_knobs(a);
+  if (k.conv_force_bm) {
+    *bm = k.conv_force_bm;
+    *bn = k.conv_force_bn;
+    return;
+  }
   if (a.N <= 32) {
     *bm = 128;
     *bn = 32;
     return;
   }
-  const double K = (double)a.ntaps * a.Kc;
   bool sk_unused;
-  double best = vy_select_tile(a.M, a.N, K, sk_policy(a), bm, bn, &sk_unused, vy_args_cus(a));
-  // 16x16 wave tiles (conv_small.hip; block tile 32 x {32, 64}): OFF by default.  Measured on the MI355X (round 3,
-  // profiles/r03_negative_results.txt): bit-exact, but 1.9 - 2.0x SLOWER than the 64x64 tile on the batch-1 3x3 layers it
-  // was built for (76x76: 78-85 vs 42 us, 38x38: 85-88 vs 43, 19x19: 98-128 vs 77) — a 32-channel sub-step of a 32x32
-  // block is 8 MFMAs per wave against 2 LDS-DMA instructions (~95 cycles of issue each), 8 fragment reads, 16 selects
-  // and a barrier; the matrix pipe waits for the instruction stream, not the other way round.  VY_CONV_SMALL=1 enables
-  // the choice by this model (kept for experiments; VY_CONV_FORCE=32x32 / 32x64 forces the kernel for parity runs).
-  static const int small_on = getenv("VY_CONV_SMALL") ? atoi(getenv("VY_CONV_SMALL")) : 0;
-  if (small_on && !a.dgrad && blocks(64, 64) <= 2048) {
-    const int bns[2] = {32, 64};
-    for (int bn_s : bns) {
-      if (bn_s == 64 && a.N <= 32) continue;
-      const long long nb = blocks(32, bn_s);
-      const long long per_cu = (nb + 255) / 256;
-      const double units = bn_s / 32.0;  // 16x16 accumulators per wave
-      double t = (per_cu * units > 1.0 ? per_cu * units * 0.00333 : 0.00417) * K + 2.5 * (double)((per_cu + 1) / 2);
-      if (t < best * 0.97) {
-        best = t;
-        *bm = 32;
-        *bn = bn_s;
-      }
-    }
-  }
+  vy_select_tile(a.M, a.N, (double)a.ntaps * a.Kc, sk_policy(a), bm, bn, &sk_unused, vy_args_cus(a));
 }
 
 void vy_conv_cfg(const ConvArgs& a, int* bm, int* bn) { select_cfg(a, bm, bn); }
@@ -1061,23 +1023,12 @@ static hipError_t run_cfg(const ConvArgs& a, hipStream_t s, bool* sk_query, int*
   select_cfg(a, &bm, &bn);
   if (sk_query) *sk_query = false;
   if (ks_query) *ks_query = 0;
-  // (the 16x16-wave-tile kernel computes ONE chain: launches whose K is summed in runs stay on the 32x32 tiles)
-  const bool runs = !a.dgrad && vy_conv_runs(a.ntaps, a.Kc >> 5) > 1;
-  if (bm == 32 && runs) bm = bn = 64;
-  if (bm == 32) return sk_query ? hipSuccess : vy_launch_conv_s16(a, bm, bn, s);
-  // experiment switch: VY_CONV_S16=1 sends a forced tile (VY_CONV_FORCE) through the 16x16x4 kernel where it has the instance
-  static const int s16_forced = getenv("VY_CONV_S16") ? atoi(getenv("VY_CONV_S16")) : 0;
-  if (s16_forced && !runs && !sk_query && !a.dgrad && (bm % 32 == 0) && (bn == 64 || bn == 96)) {
-    const hipError_t e = vy_launch_conv_s16(a, bm, bn, s);
-    if (e != hipErrorInvalidValue) return e;
-  }
   if (bn == 32) return launch_cfg<128, 32, 4, 1>(a, s, sk_query, ks_query);
   if (bm == 128 && bn == 64) return launch_cfg<128, 64, 2, 2>(a, s, sk_query, ks_query);
   if (bm == 64) {
     // few blocks (at most two per CU) and a k-loop long enough to fill it: the four-stage pipeline
-    static const int deep = getenv("VY_CONV_DEEP") ? atoi(getenv("VY_CONV_DEEP")) : 512;
     const long long nb = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-    if (nb <= deep && a.ntaps * (a.Kc >> 5) >= 8) return launch_cfg<64, 64, 2, 2, 4>(a, s, sk_query, ks_query);
+    if (nb <= 512 && a.ntaps * (a.Kc >> 5) >= 8) return launch_cfg<64, 64, 2, 2, 4>(a, s, sk_query, ks_query);
     return launch_cfg<64, 64, 2, 2>(a, s, sk_query, ks_query);
   }
   return launch_cfg<128, 128, 2, 2>(a, s, sk_query, ks_query);

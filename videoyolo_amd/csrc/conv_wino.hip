@@ -376,8 +376,7 @@ static long long wino_tiles(const ConvArgs& a, int bm) {
 // pairs per block of the launch (probe builds: VY_WINO_BM=128)
 static int wino_bm(const ConvArgs& a) {
 #ifdef VY_WINO_BM128
-  const char* f = getenv("VY_WINO_BM");
-  if (f && atoi(f) == 128) return 128;
+  if (vy_args_knobs(a).wino_bm == 128) return 128;
 #endif
   return 64;
 }
@@ -387,11 +386,7 @@ static int wino_bm(const ConvArgs& a) {
 // a single frame's (the split kernel's k-split covers those).  VY_SPLIT_WINO=0: never, =2: wherever supported (tests)
 bool vy_conv_wino_pays(const ConvArgs& a) {
   if (!vy_conv_wino_supported(a)) return false;
-  int mode = a.env_wino_mode_p1 - 1;  // read once per forward by the net; per call only for hand-made ConvArgs
-  if (mode < 0) {
-    const char* sw = getenv("VY_SPLIT_WINO");
-    mode = sw ? atoi(sw) : 1;
-  }
+  const int mode = vy_args_knobs(a).split_wino;
   if (mode == 0) return false;
   if (mode == 2) return true;
   const int cus = vy_args_cus(a);

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knobs.h"
+
 // One launch of the implicit-GEMM conv kernel.  Rows m = (b, y, x) over a logical LH x LW grid;
 // the A row of pixel m for tap t is Kc contiguous floats at the plane position
 // (y*a_s + a_oy + tap_dy[t], x*a_s + a_ox + tap_dx[t]) (padded coordinates).  The same kernel runs
@@ -59,9 +61,9 @@ struct ConvArgs {
   // conv_wino.hip only: this conv's weights as four Winograd-transformed, pre-split image sets (vy_launch_wino_weights);
   // nullable
   const void* w_wino;
-  // the test switches VY_SPLIT_ALWAYS / VY_SPLIT_WINO as the net read them ONCE at the start of this forward / step
-  // (value + 1; 0: not read — vy_conv_*_pays read the environment themselves, e.g. for a probe's hand-made ConvArgs)
-  int env_split_always_p1, env_wino_mode_p1;
+  // host only: the launch switches of the net this launch belongs to (knobs.h; nullptr: the compiled-in defaults, e.g. a
+  // probe's hand-made ConvArgs)
+  const VyKnobs* knobs;
   // The pinned summation order cuts long K into S = vy_conv_k_chunks(K) runs (include/vy_math.h).  A workgroup that computes
   // more than one run of a tile parks every finished chain in this scratch ([run][tile][BM x BN] floats: written and read
   // back by the same lanes, or handed from the block that starts a stream-K tile to the one that finishes it,
@@ -80,9 +82,6 @@ struct ConvArgs {
 
 // 3x3/1x1 implicit-GEMM convolution on v_mfma_f32_32x32x2_f32.
 hipError_t vy_launch_conv_igemm(const ConvArgs& a, hipStream_t s);
-// the same on 16x16 wave tiles (v_mfma_f32_16x16x4_f32; conv_small.hip): forward launches too small to fill the chip
-// with 32x32 wave tiles.  Block tile bm x bn = 32x32 or 32x64; called by vy_launch_conv_igemm.
-hipError_t vy_launch_conv_s16(const ConvArgs& a, int bm, int bn, hipStream_t s);
 int vy_conv_tiles_m(const ConvArgs& a);
 void vy_conv_cfg(const ConvArgs& a, int* bm, int* bn);  // block tile the launch will use
 double vy_conv_predict_us(const ConvArgs& a);             // the cost model's time for the launch (conv_cost_model.h)
@@ -90,6 +89,7 @@ int vy_cu_count();                                        // CUs of the CURRENT 
 int vy_cu_count_of(int device);                           // ... of a given device ordinal
 int vy_cu_count_of_ptr(const void* dev_ptr);              // ... of the device that owns an allocation (0: not a device pointer)
 static inline int vy_args_cus(const ConvArgs& a) { return a.cus > 0 ? a.cus : vy_cu_count(); }
+static inline const VyKnobs& vy_args_knobs(const ConvArgs& a) { return a.knobs ? *a.knobs : vy_knobs_default(); }
 bool vy_conv_streamk(const ConvArgs& a);                  // ... and whether it will be a stream-K launch (label "<BM>x<BN>sk")
 int vy_conv_ksplit(const ConvArgs& a);                    // ... or a split-K one: the S workgroups per tile (label "<BM>x<BN>ks<S>"), else 0
 size_t vy_conv_chunk_scratch_bytes(long long M, int N, int runs);   // ck_scratch bytes a conv of M x N outputs summed in `runs` runs may need (any tile)
@@ -154,9 +154,10 @@ struct StemArgs {
   const FoldDesc* fold_descs = nullptr;
   int fold_n = 0, fold_stem = 0;
   float fold_eps = 0.0f;
+  int cus = 0;  // host only: CUs of the net's device (vy_net::cus): the inference launch's rows per block
 };
 hipError_t vy_launch_stem(const StemArgs& a, hipStream_t s);
-bool vy_stem_can_fold(int B, int H, int W, int n_layers);   // the inference stem launch of this shape has >= n_layers blocks
+bool vy_stem_can_fold(int B, int H, int W, int n_layers, int cus);   // the inference stem launch of this shape has >= n_layers blocks
 
 // (FoldDesc: above StemArgs)
 hipError_t vy_launch_bn_fold(float* params, const FoldDesc* descs_dev, int n_layers, int max_c,
@@ -261,7 +262,6 @@ struct BnBwdArgs {
 int vy_bn_bwd_rows_per_chunk(int B, int H, int C);
 int vy_bn_bwd_chunks(const BnBwdArgs& a);
 hipError_t vy_launch_bn_bwd_reduce(const BnBwdArgs& a, hipStream_t s);
-void vy_bn_prio_init();   // reads VY_BN_PRIO once (train_kernels.hip: issue priority of the BatchNorm passes)
 struct BnBwdFinalizeArgs {
   const double* sums;     // [2][C]: sum dy, sum dy*xhat (all ranks when SyncBN)
   double count;
@@ -295,7 +295,6 @@ struct WgradArgs {
   int a_Hp, a_Wp, a_cs, a_co, stride;
   int k, Cin;             // kernel size, input channels (multiple of 32)
   int splits, k_per_split;  // k_per_split pixels (multiple of 32) per split
-  int xcd_order;          // filled by the launcher: XCD-contiguous (split, tile) order (wgrad.hip)
 };
 hipError_t vy_launch_wgrad(const WgradArgs& a, hipStream_t s);
 // opt-in split-fp32 weight gradient (wgrad_split.hip: bf16 x 3, six products; same WgradArgs, table and slabs):

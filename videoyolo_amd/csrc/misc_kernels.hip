@@ -166,26 +166,26 @@ static hipError_t stem_check(const StemArgs& a) {
 }
 
 // rows per block of the inference launch
-static int stem_rows_infer(int B, int H, int W) {
+static int stem_rows_infer(int B, int H, int W, int cus) {
   int rows = stem_rows(W);
-  const int want = 2 * vy_cu_count();
+  const int want = 2 * cus;
   while (rows > 1 && B * ((H + rows - 1) / rows) < want) rows >>= 1;
   return rows;
 }
 
-bool vy_stem_can_fold(int B, int H, int W, int n_layers) {
-  const int rows = stem_rows_infer(B, H, W);
+bool vy_stem_can_fold(int B, int H, int W, int n_layers, int cus) {
+  const int rows = stem_rows_infer(B, H, W, cus);
   return B * ((H + rows - 1) / rows) >= n_layers;
 }
 
 hipError_t vy_launch_stem(const StemArgs& a, hipStream_t s) {
-  if (stem_check(a) != hipSuccess) return hipErrorInvalidValue;
+  if (stem_check(a) != hipSuccess || a.cus < 1) return hipErrorInvalidValue;
   // A few frames: four rows per block leave most CUs without a block (one 608x608 frame: 152 blocks, 30 us for 47 MB);
   // fewer rows per block until the launch has two blocks per CU (one frame: 608 blocks of one row, the input rows are
   // then staged three times — 13 MB).  Every pixel's fma chain is the same whatever the strip height.  (The training
   // launch below keeps the rule by width alone: its rows are also the layout of the statistics partials.)
-  const int rows = stem_rows_infer(a.B, a.H, a.W);
-  if (a.fold_descs && (!a.fold_params || a.fold_stem < 0 || a.fold_stem >= a.fold_n || !vy_stem_can_fold(a.B, a.H, a.W, a.fold_n)))
+  const int rows = stem_rows_infer(a.B, a.H, a.W, a.cus);
+  if (a.fold_descs && (!a.fold_params || a.fold_stem < 0 || a.fold_stem >= a.fold_n || !vy_stem_can_fold(a.B, a.H, a.W, a.fold_n, a.cus)))
     return hipErrorInvalidValue;
   const size_t lds = (size_t)3 * (rows + 2) * (((a.W + 31) & ~31) + 8) * sizeof(float);
   if (lds > 48 * 1024) {

@@ -37,6 +37,7 @@ int vy_net_create(int32_t num_class, vy_net** out) {
   if (num_class < 1 || num_class > 1000) return fail(VY_ERR_INVALID, "num_class %d out of range", num_class);
   vy_net* n = new vy_net();
   n->num_class = num_class;
+  n->knobs = vy_knobs_read();
   n->build();
   *out = n;
   return 0;

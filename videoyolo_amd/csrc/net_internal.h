@@ -100,9 +100,9 @@ struct vy_net {
   // for inference at the same size) but train.hip's refresh_split_images rebuilds only the forward and data-gradient sets —
   // only forward() below, which does rebuild them, may clear it
   bool wino_dirty = true;
-  // VY_SPLIT_ALWAYS / VY_SPLIT_WINO (test switches of the per-launch choice), read once at the start of every forward /
-  // training step (refresh_env) instead of by every launch's vy_conv_*_pays; -1: not read yet
-  int env_split_always = -1, env_wino_mode = -1;
+  // the launch switches (knobs.h), read from the environment once, by vy_net_create: every launch of this net reads them
+  // here (ConvArgs::knobs), so a switch set or changed later affects only nets created after it
+  VyKnobs knobs;
   // CUs of THIS net's device: resolved once, by the first sizing / bind call, from the calling thread's current device —
   // and checked at every bind against the device that owns the workspace (bind_cus below), so that a C-ABI caller whose
   // current device differs between vy_net_*workspace_bytes and vy_net_bind_* gets an error instead of a plan sized for
@@ -120,12 +120,6 @@ struct vy_net {
                   "the workspace lives on a device with %d CUs but this net sized its plan for %d (the calling thread's current "
                   "device at the first vy_net_*workspace_bytes call): size and bind with the same current device", owner, sized);
     return 0;
-  }
-  void refresh_env() {
-    const char* a = getenv("VY_SPLIT_ALWAYS");
-    const char* w = getenv("VY_SPLIT_WINO");
-    env_split_always = a && atoi(a) ? 1 : 0;
-    env_wino_mode = w ? atoi(w) : 1;
   }
   size_t wsplit_off = 0;
   struct VyTrain* train = nullptr;  // training planner state, owned by train.hip
@@ -300,14 +294,11 @@ struct vy_net {
 
   // which inference launches the split-fp32 kernel takes in conv mode VY_CONV_SPLIT_BF16X3: every conv+BN+leaky cell
   // whose tile geometry it has (cout a multiple of 64, cin of 32) — the 3x3 cells (1.4-1.5x the exact kernel at
-  // 608x608 batch 64; the two 64-channel ones 1.15x) and the 1x1 cells (1.13x at K = 128 ... 1.5x at K = 1024;
-  // VY_SPLIT_1X1=0 keeps those exact).  The stem (Cin = 3), the 64 -> 32 bottleneck and the prediction convs
-  // (75 channels) stay on the exact kernel.
+  // 608x608 batch 64; the two 64-channel ones 1.15x) and the 1x1 cells (1.13x at K = 128 ... 1.5x at K = 1024).
+  // The stem (Cin = 3), the 64 -> 32 bottleneck and the prediction convs (75 channels) stay on the exact kernel.
   bool split_eligible(const ConvT& c) const {
-    static const int with_1x1 = getenv("VY_SPLIT_1X1") ? atoi(getenv("VY_SPLIT_1X1")) : 1;
     if (conv_mode == VY_CONV_EXACT_FP32 || c.is_stem || c.p_gamma < 0) return false;
-    if (c.cout % 64 != 0 || c.cin % 32 != 0) return false;
-    return c.k == 3 || with_1x1;
+    return c.cout % 64 == 0 && c.cin % 32 == 0;
   }
 
   // Plane -> storage slot.  keep_all (training, or vy_net_set_keep_activations): every plane has its own storage — the
@@ -491,8 +482,7 @@ struct vy_net {
     a.dgrad = 0;
     a.w_split = c.split_off >= 0 ? dev_ws + wsplit_off + c.split_off : nullptr;
     a.w_wino = c.wino_off >= 0 ? dev_ws + wsplit_off + c.wino_off : nullptr;
-    a.env_split_always_p1 = env_split_always + 1;
-    a.env_wino_mode_p1 = env_wino_mode + 1;
+    a.knobs = &knobs;
     a.cus = cus;
     a.ck_scratch = ck_bytes ? reinterpret_cast<float*>(dev_ws + ck_off) : nullptr;
     a.ck_bytes = ck_bytes;
@@ -561,7 +551,6 @@ struct vy_net {
   int forward(const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx, hipStream_t s,
               Hook&& hook) {
     if (int rc = check_ready()) return rc;
-    refresh_env();
     const bool nms_on = nms_thresh > 0.f && nms_thresh < 1.f;  // yolo3.py:1197
     FoldDesc* fd = reinterpret_cast<FoldDesc*>(dev_ws + fold_desc_off);
     if (!fold_uploaded) {
@@ -570,10 +559,9 @@ struct vy_net {
       fold_uploaded = true;
     }
     // The fold runs EVERY forward (the caller owns the parameter buffer and may have written to it) — inside the stem launch
-    // when that has a block per layer (StemArgs), in a launch of its own otherwise.  VY_FOLD_IN_STEM=0: always its own.
-    static const int fold_in_stem_on = getenv("VY_FOLD_IN_STEM") ? atoi(getenv("VY_FOLD_IN_STEM")) : 1;
-    const bool fold_in_stem = fold_in_stem_on && !convs.empty() && convs[0].is_stem && convs[0].scale_off == folds[0].scale &&
-                              vy_stem_can_fold(B, H, W, (int)folds.size());
+    // when that has a block per layer (StemArgs), in a launch of its own otherwise
+    const bool fold_in_stem = !convs.empty() && convs[0].is_stem && convs[0].scale_off == folds[0].scale &&
+                              vy_stem_can_fold(B, H, W, (int)folds.size(), cus);
     if (!fold_in_stem) {
       hook("bn_fold", 0.0, 0.0, true);
       HIP_TRY(vy_launch_bn_fold(dev_params, fd, (int)folds.size(), 1024, 1e-5f, s));
@@ -606,6 +594,7 @@ struct vy_net {
         a.Cout = c.cout;
         a.out_cs = planes[c.out_plane].C;
         a.out_co = c.out_co;
+        a.cus = cus;
         if (fold_in_stem) {
           a.fold_params = dev_params;
           a.fold_descs = fd;

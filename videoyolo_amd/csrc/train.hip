@@ -90,14 +90,13 @@ size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 // can be joined with the layers by launch order within each kernel class.
 struct LabelLog {
   FILE* f = nullptr;
-  bool open_once() {
-    static const char* path = getenv("VY_TRAIN_LABELS");
-    if (!path) return false;
-    if (!f) f = fopen(path, "w");
+  bool open_once(const vy_net* net) {
+    if (net->knobs.train_labels.empty()) return false;
+    if (!f) f = fopen(net->knobs.train_labels.c_str(), "w");
     return f != nullptr;
   }
-  void note(const char* kind, const std::string& name, double M, double N, double K) {
-    if (open_once()) fprintf(f, "%s %s %.0f %.0f %.0f %.0f\n", kind, name.c_str(), 2.0 * M * N * K, M, N, K);
+  void note(const vy_net* net, const char* kind, const std::string& name, double M, double N, double K) {
+    if (open_once(net)) fprintf(f, "%s %s %.0f %.0f %.0f %.0f\n", kind, name.c_str(), 2.0 * M * N * K, M, N, K);
   }
   // "# via split 128x128 k2" / "# via exact": which kernel the preceding fwd / dgrad line went to (tests assert that the
   // launches they mean to cover really ran; tools/train_layers.py skips '#' lines)
@@ -126,22 +125,12 @@ bool g_labels_done = false;
 // bits 64 / 128 (a finalize launch skipped: its outputs keep the previous step's values) only after VY_TRAIN_ABL_AFTER recorded
 // forwards (default 3), so that the planes never hold the all-zero data of a net whose statistics were never finalized
 static int g_abl_forwards = 0;
-static int train_abl_all();
-static int train_abl() {
-  static const int after = getenv("VY_TRAIN_ABL_AFTER") ? atoi(getenv("VY_TRAIN_ABL_AFTER")) : 3;
-  const int v = train_abl_all();
-  return g_abl_forwards > after ? v : (v & ~(64 | 128));
-}
-static int train_abl_all() {
-  static const int v = [] {
-    const int e = getenv("VY_TRAIN_ABL") ? atoi(getenv("VY_TRAIN_ABL")) : 0;
-    if (e) fprintf(stderr, "libvyolo (VY_TRAIN_ABL_BUILD): VY_TRAIN_ABL=%d — training launches are being SKIPPED, gradients are garbage\n", e);
-    return e;
-  }();
-  return v;
+static int train_abl(const vy_net* net) {
+  const int v = net->knobs.train_abl;
+  return g_abl_forwards > net->knobs.train_abl_after ? v : (v & ~(64 | 128));
 }
 #else
-static constexpr int train_abl() { return 0; }
+static constexpr int train_abl(const vy_net*) { return 0; }
 #endif
 
 constexpr int kBwdChunk = 64;  // pixels per partial-sum block of the bias-gradient reductions (and the scratch bound)
@@ -166,8 +155,7 @@ size_t train_plan(vy_net* net, int b, int h, int w, bool commit) {
   std::vector<long long> dsplit(net->convs.size(), -1);
   const size_t dsplit_off = off;
   if (net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN) {
-    static const int train_split = getenv("VY_SPLIT_TRAIN") ? atoi(getenv("VY_SPLIT_TRAIN")) : 1;
-    for (size_t i = 0; i < net->convs.size() && train_split; ++i) {
+    for (size_t i = 0; i < net->convs.size() && net->knobs.split_train; ++i) {
       const ConvT& c = net->convs[i];
       if (c.is_stem || c.cin % 64 != 0) continue;
       dsplit[i] = (long long)(off - dsplit_off);
@@ -198,7 +186,7 @@ size_t train_plan(vy_net* net, int b, int h, int w, bool commit) {
       save[i] = sfl;
       sfl += 2 * (size_t)((c.cout + 63) & ~63);
       // partials: forward stats, backward sums
-      const size_t tiles_m = (size_t)((M + 31) / 32);  // per-tile statistics rows: the smallest tile height (conv_small.hip)
+      const size_t tiles_m = (size_t)((M + 31) / 32);  // per-tile statistics rows, sized for 32-row tiles (every tile has more)
       size_t pf = 2 * (c.is_stem ? (size_t)vy_stem_blocks(b, h, w) * 64 : tiles_m * 2 * c.cout);  // doubles
       const size_t chunks = (size_t)((M + kBwdChunk - 1) / kBwdChunk);
       if (chunks * 2 * c.cout > pf) pf = chunks * 2 * c.cout;
@@ -440,13 +428,12 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
 int forward_train(const TrainCtx& c, const float* x) {
   vy_net* net = c.net;
   const int B = net->B;
-  net->refresh_env();
   if (int rc = refresh_split_images(c)) return rc;
   for (size_t ci = 0; ci < net->convs.size(); ++ci) {
     const ConvT& cv = net->convs[ci];
     if (cv.p_gamma < 0) {  // prediction conv: bias, no BN
       const ConvArgs a = net->conv_args(cv);
-      if (!g_labels_done) g_labels.note("fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
+      if (!g_labels_done) g_labels.note(net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
       HIP_TRY(vy_launch_conv_igemm(a, c.s));
       continue;
     }
@@ -478,9 +465,9 @@ int forward_train(const TrainCtx& c, const float* x) {
       a.o_s = 1;
       a.ups = 1;
       a.stats = reinterpret_cast<double*>(c.partials());
-      static const int train_split = getenv("VY_SPLIT_TRAIN") ? atoi(getenv("VY_SPLIT_TRAIN")) : 1;  // 0 none, 1 both, 2 forward only, 3 dgrad only
+      const int train_split = net->knobs.split_train;  // 0 none, 1 both, 2 forward only, 3 dgrad only
       if (net->conv_mode != VY_CONV_SPLIT_BF16X3_TRAIN || train_split == 0 || train_split == 3) a.w_split = nullptr;
-      if (!g_labels_done) g_labels.note("fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
+      if (!g_labels_done) g_labels.note(net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
       if (int rc = launch_conv(a, c.s)) return rc;
       if (a.w_split && vy_conv_split_pays(a)) {  // the per-tile statistics rows follow the tile that ran
         int sbm, sbn, sks;
@@ -517,7 +504,7 @@ int forward_train(const TrainCtx& c, const float* x) {
     f.momentum = 0.9f;  // layers.py:68
     if (exchange)
       HIP_TRY(vy_launch_bn_finalize(f, c.s));
-    else if (!(train_abl() & 128))  // (128: the same for the forward statistics)
+    else if (!(train_abl(net) & 128))  // (128: the same for the forward statistics)
       HIP_TRY(vy_launch_bn_reduce_finalize(reinterpret_cast<const double*>(c.partials()), n_part, f, c.slice_sums(), c.s));
     BnApplyArgs ap;
     memset(&ap, 0, sizeof ap);
@@ -540,7 +527,7 @@ int forward_train(const TrainCtx& c, const float* x) {
       ap.r_cs = net->planes[cv.res_plane].C;
       ap.r_co = cv.res_co;
     }
-    if (!(train_abl() & 2)) HIP_TRY(vy_launch_bn_apply(ap, c.s));
+    if (!(train_abl(net) & 2)) HIP_TRY(vy_launch_bn_apply(ap, c.s));
   }
   return 0;
 }
@@ -577,14 +564,12 @@ BwdDgrad make_dgrad(const TrainCtx& c, const ConvT& cv, const float* dzp, int dz
   a.o_co = cv.in_co;
   a.ups = 1;
   a.dgrad = 1;
-  a.env_split_always_p1 = net->env_split_always + 1;  // (as read by this step's forward)
-  a.env_wino_mode_p1 = net->env_wino_mode + 1;
+  a.knobs = &net->knobs;
   a.cus = net->cus;
   net->set_sk(a);
   {  // split-fp32 conv mode: this conv's data-gradient weight images and the split-K scratch (the stream-K region)
     const size_t ci = (size_t)(&cv - net->convs.data());
-    static const int train_split = getenv("VY_SPLIT_TRAIN") ? atoi(getenv("VY_SPLIT_TRAIN")) : 1;
-    if (train_split != 2 && net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && ci < c.t->dsplit.size() && c.t->dsplit[ci] >= 0) {
+    if (net->knobs.split_train != 2 && net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && ci < c.t->dsplit.size() && c.t->dsplit[ci] >= 0) {
       a.w_split = net->dev_ws + c.t->dsplit_off + c.t->dsplit[ci];
       a.splitk_slabs = reinterpret_cast<float*>(net->dev_ws + net->sk_off + vy_net::al((size_t)VY_SK_FLAGS * sizeof(unsigned)));
       a.splitk_bytes = VY_SK_PARTIAL_BYTES;
@@ -657,13 +642,12 @@ int launch_wgrad(const TrainCtx& c, size_t ci, const float* dzp, int dz_cs, int 
   w.splits = c.t->splits[ci];
   w.k_per_split = c.t->kps[ci];
   w.tab = reinterpret_cast<const uint2*>(net->dev_ws + c.t->tab_off[ci]);
-  if (!g_labels_done) g_labels.note("wgrad", cv.name, w.M, w.Cout, (double)cv.k * cv.k * cv.cin);
+  if (!g_labels_done) g_labels.note(net, "wgrad", cv.name, w.M, w.Cout, (double)cv.k * cv.k * cv.cin);
   // conv mode VY_CONV_SPLIT_BF16X3_TRAIN: the split-fp32 weight-gradient kernel where it has the tile (Cout % 128 == 0)
-  static const int wgrad_split = getenv("VY_SPLIT_WGRAD") ? atoi(getenv("VY_SPLIT_WGRAD")) : 1;
-  if ((train_abl() & 8) || ((train_abl() & 32) && (long long)cv.k * cv.k * cv.cin <= 576 && cv.cout <= 128)) {
+  if ((train_abl(net) & 8) || ((train_abl(net) & 32) && (long long)cv.k * cv.k * cv.cin <= 576 && cv.cout <= 128)) {
     // (bound measurements: no weight-gradient kernel at all / none for the early cells — N <= 128, K <= 576: stages.0.1 ... 0.5 —
     // whose output tile is mostly padding: what would a perfect kernel for them return to the step?)
-  } else if (wgrad_split && net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && vy_wgrad_split_supported(w)) {
+  } else if (net->knobs.split_wgrad && net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && vy_wgrad_split_supported(w)) {
     HIP_TRY(vy_launch_wgrad_split(w, ws));
   } else {
     HIP_TRY(vy_launch_wgrad(w, ws));
@@ -790,7 +774,7 @@ int backward_train(const TrainCtx& c, const float* x) {
       bb.g_co = cv.out_co;
       bb.ups = cv.ups;
       bb.chunk = vy_bn_bwd_rows_per_chunk(B, zp.H, cv.cout);
-      if (!(train_abl() & 1)) HIP_TRY(vy_launch_bn_bwd_reduce(bb, c.s));
+      if (!(train_abl(net) & 1)) HIP_TRY(vy_launch_bn_bwd_reduce(bb, c.s));
       const bool exchange = sync_exchange(c.t) && is_sync_layer(cv);
       double count = (double)B * zp.H * zp.W;
       const double* use_sums = nullptr;
@@ -811,9 +795,9 @@ int backward_train(const TrainCtx& c, const float* x) {
       f.C = cv.cout;
       if (exchange)
         HIP_TRY(vy_launch_bn_bwd_finalize(f, c.s));
-      else if (!(train_abl() & (1 | 64)))  // (64: the finalize launch alone skipped)
+      else if (!(train_abl(net) & (1 | 64)))  // (64: the finalize launch alone skipped)
         HIP_TRY(vy_launch_bn_bwd_reduce_finalize(c.partials(), vy_bn_bwd_chunks(bb), f, c.s));
-      if (!(train_abl() & 4)) HIP_TRY(vy_launch_bn_bwd_apply(bb, c.s));
+      if (!(train_abl(net) & 4)) HIP_TRY(vy_launch_bn_bwd_apply(bb, c.s));
       dzp = c.zplane(ci);
       dz_cs = zp.C;
       dzH = zp.H;
@@ -865,8 +849,8 @@ int backward_train(const TrainCtx& c, const float* x) {
     }
     const BwdDgrad dg = make_dgrad(c, cv, dzp, dz_cs, dzH, dzW, addend, add_cs, add_co);
     for (int k = 0; k < dg.n; ++k) {
-      if (!g_labels_done) g_labels.note("dgrad", cv.name, dg.a[k].M, dg.a[k].N, (double)dg.a[k].ntaps * dg.a[k].Kc);
-      if (train_abl() & 16) continue;  // (bound measurement: no data-gradient kernel)
+      if (!g_labels_done) g_labels.note(net, "dgrad", cv.name, dg.a[k].M, dg.a[k].N, (double)dg.a[k].ntaps * dg.a[k].Kc);
+      if (train_abl(net) & 16) continue;  // (bound measurement: no data-gradient kernel)
       if (int rc = launch_conv(dg.a[k], c.s)) return rc;
     }
     if (cov == 0) touched[cv.in_plane].push_back({lo, hi});
@@ -921,13 +905,11 @@ int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, in
   HIP_TRY(hipMemsetAsync(dev_ws, 0, need, s));
   net->sk_dirty = false;
   net->sk_ok = vy_sk_verify_topology(reinterpret_cast<unsigned*>(net->dev_ws + net->sk_off), s) != 0;
-  static const int use_side = getenv("VY_TRAIN_SIDE_STREAM") ? atoi(getenv("VY_TRAIN_SIDE_STREAM")) : 1;
-  if (use_side && !t->side) {
+  if (net->knobs.train_side_stream && !t->side) {
     // (The weight-gradient stream at the LOWEST queue priority was measured: +0.4 % on top of the raised issue priority of the
     // BatchNorm passes in a fresh process — and the whole training step 1.55x SLOWER, forward included, in a process that had
     // run the host-fed inference legs before (other streams alive: profiles/r06_ab_bn_prio.txt).  Default priority it stays.)
     HIP_TRY(hipStreamCreateWithFlags(&t->side, hipStreamNonBlocking));
-    vy_bn_prio_init();
     HIP_TRY(hipEventCreateWithFlags(&t->ev_main, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&t->ev_side, hipEventDisableTiming));
   }

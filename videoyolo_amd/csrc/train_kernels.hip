@@ -136,19 +136,11 @@ __device__ __forceinline__ void reduce2_finalize(const T* __restrict__ partials,
 // (train.hip).  Those hold two MFMA waves per SIMD, and fp32 MFMA shares the vector FMA hardware: a bandwidth-bound pass
 // whose waves get the pipe only between 64-cycle matrix instructions crawls (bn_bwd_reduce 17.6 us alone, 150 us beside
 // wgrad_kernel<32,128>).  s_setprio raises the issuing priority of these short waves: they take the few vector slots they
-// need and the matrix waves lose only those.  VY_BN_PRIO=0 (read once, copied to the device) turns it off for A/B.
-__device__ int g_bn_prio = 1;
+// need and the matrix waves lose only those (A/B: profiles/r06_ab_bn_prio.txt).
 __device__ __forceinline__ void bn_raise_prio() {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (g_bn_prio) __builtin_amdgcn_s_setprio(3);
+  __builtin_amdgcn_s_setprio(3);
 #endif
-}
-void vy_bn_prio_init() {
-  static bool done = false;
-  if (done) return;
-  done = true;
-  const int v = getenv("VY_BN_PRIO") ? atoi(getenv("VY_BN_PRIO")) : 1;
-  if (v != 1) (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bn_prio), &v, sizeof v);
 }
 
 __global__ __launch_bounds__(1024) void bn_reduce_finalize_kernel(const double* __restrict__ partials, int n_part,
@@ -195,8 +187,7 @@ hipError_t vy_launch_bn_reduce_finalize(const double* partials, int n_part, cons
                                         hipStream_t s) {
   // Long per-tile lists go through the slice pass first; up to 2048 rows the finalize kernel's own 64-group reduce is
   // faster than a second launch on the forward chain (threshold 128 -> 2048: forward 10.48 -> 10.30 ms per step)
-  static const int min_parts = getenv("VY_REDUCE_MIN") ? atoi(getenv("VY_REDUCE_MIN")) : 2048;
-  if (n_part > min_parts && scratch) {
+  if (n_part > 2048 && scratch) {
     const int S = VY_REDUCE_SLICES;
     const int rps = (n_part + S - 1) / S;
     const int slices = (n_part + rps - 1) / rps;

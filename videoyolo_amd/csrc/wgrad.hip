@@ -108,17 +108,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a, const 
   const int h = lane >> 5, lrow = lane & 31;
   // Block -> (split, tile).  All tiles of a split read the same pixel range: every n-tile its dz rows, every o-tile the
   // input taps.  Blocks are dealt round-robin over the 8 XCDs (each with its own L2), so in launch order every XCD saw
-  // every split and each re-read went out to the fabric (round 2: 22.6 GB per step against 5.2 GB algorithmic).  With
-  // a.xcd_order the linear block index is mapped so that an XCD works through a CONTIGUOUS run of (split, tile) pairs,
-  // tile fastest — whole splits per XCD, their re-reads served by that XCD's L2.
-  int tile_id = blockIdx.x, split = blockIdx.y;
-  if (a.xcd_order) {
-    const int gx = gridDim.x, nblk = gx * gridDim.y, L = blockIdx.y * gx + blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
-    const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    split = v / gx;
-    tile_id = v - split * gx;
-  }
+  // every split and each re-read went out to the fabric (round 2: 22.6 GB per step against 5.2 GB algorithmic).  So the
+  // linear block index is mapped so that an XCD works through a CONTIGUOUS run of (split, tile) pairs, tile fastest —
+  // whole splits per XCD, their re-reads served by that XCD's L2.
+  const int gx = gridDim.x, nblk = gx * gridDim.y, L = blockIdx.y * gx + blockIdx.x;
+  const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
+  const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  const int split = v / gx;
+  const int tile_id = v - split * gx;
   const int tile_m = tile_id / tiles_n, tile_n = tile_id - tile_m * tiles_n;
   const int o0 = tile_m * BM, n0 = tile_n * BN;
   const int Ntot = a.k * a.k * a.Cin;
@@ -289,19 +286,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a, const 
 
 // 64-row tiles for Cout <= 64 (no zero padding in the MFMA rows) and for weight tensors of so few 128-row tiles that
 // the planner would cut the pixel range into dozens of splits of 64 KB slabs: every 1x1 layer and tensors of at most
-// VY_WGRAD_BM64_TILES (8) 128-row tiles (measured in the step: +0.4 %; larger 3x3 tensors lose)
+// 8 128-row tiles (measured in the step: +0.4 %; larger 3x3 tensors lose)
 int vy_wgrad_tile_rows(int Cout, int k, int Cin) {
-  static const int max_tiles = getenv("VY_WGRAD_BM64_TILES") ? atoi(getenv("VY_WGRAD_BM64_TILES")) : 8;
   if (Cout <= 64) return 64;
-  if (max_tiles < 0) return 128;  // experiment switch: the round-1 rule
   const int tiles128 = ((Cout + 127) / 128) * ((k * k * Cin + 127) / 128);
-  return (k == 1 || tiles128 <= max_tiles) ? 64 : 128;
+  return (k == 1 || tiles128 <= 8) ? 64 : 128;
 }
 
-hipError_t vy_launch_wgrad(const WgradArgs& a_in, hipStream_t s) {
-  WgradArgs a = a_in;
-  static const int xcd_order = getenv("VY_WGRAD_XCD") ? atoi(getenv("VY_WGRAD_XCD")) : 1;
-  a.xcd_order = xcd_order;
+hipError_t vy_launch_wgrad(const WgradArgs& a, hipStream_t s) {
   if (a.Cin % 32 != 0 || a.k_per_split % 32 != 0 || a.splits < 1 || (a.z_cs & 3) || (a.a_cs & 3) || (a.a_co & 3) || !a.tab)
     return hipErrorInvalidValue;
   const int Ntot = a.k * a.k * a.Cin;

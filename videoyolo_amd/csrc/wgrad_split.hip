@@ -68,14 +68,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int h = lane >> 5, lrow = lane & 31;
-  int tile_id = blockIdx.x, split = blockIdx.y;
-  if (a.xcd_order) {  // an XCD works through a contiguous run of (split, tile) pairs (wgrad.hip)
-    const int gx = gridDim.x, nblk = gx * gridDim.y, L = blockIdx.y * gx + blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
-    const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    split = v / gx;
-    tile_id = v - split * gx;
-  }
+  // an XCD works through a contiguous run of (split, tile) pairs (wgrad.hip)
+  const int gx = gridDim.x, nblk = gx * gridDim.y, L = blockIdx.y * gx + blockIdx.x;
+  const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
+  const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  const int split = v / gx;
+  const int tile_id = v - split * gx;
   const int tile_m = tile_id / tiles_n, tile_n = tile_id - tile_m * tiles_n;
   const int o0 = tile_m * BM, n0 = tile_n * BN;
   const int Ntot = a.k * a.k * a.Cin;
@@ -208,11 +206,8 @@ bool vy_wgrad_split_supported(const WgradArgs& a) {
          (a.a_cs & 3) == 0 && (a.a_co & 3) == 0 && a.tab != nullptr;
 }
 
-hipError_t vy_launch_wgrad_split(const WgradArgs& a_in, hipStream_t s) {
-  WgradArgs a = a_in;
+hipError_t vy_launch_wgrad_split(const WgradArgs& a, hipStream_t s) {
   if (!vy_wgrad_split_supported(a)) return hipErrorInvalidValue;
-  static const int xcd_order = getenv("VY_WGRAD_XCD") ? atoi(getenv("VY_WGRAD_XCD")) : 1;
-  a.xcd_order = xcd_order;
   const int Ntot = a.k * a.k * a.Cin;
   const int tiles_n = (Ntot + 127) / 128;
   hipLaunchKernelGGL(wgrad_split_kernel, dim3(a.Cout / 128 * tiles_n, a.splits), dim3(256), 0, s, a, tiles_n);
