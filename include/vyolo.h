@@ -67,6 +67,14 @@ const char* vy_version(void);
 /* yolo3_darknet53(classes, ...) at k=1 — wrappers.py:9-12,54-58,80-84,101-103 and
  * YOLOV3T.__init__ yolo3.py:959-1054.  num_class = len(classes). */
 int vy_net_create(int32_t num_class, vy_net** out);
+/* yolo3_no_backbone(classes) — wrappers.py:133-161, YOLOV3_noback yolo3.py:1686-1920 (train_yolov3.py:335-343 with
+ * --features_dir): the same heads, entered at the three Darknet-53 route tensors.  Its parameter table is the full net's
+ * head rows (yolo_blocks.*, transitions.*, yolo_outputs.*) with the same names and shapes, in the same order.  Sizing,
+ * binding, parameters, gradients, SGD, NMS, training options, taps and vy_net_train_conv_plan work as on a full net;
+ * (batch, height, width) stay the size of the image the routes came from.  Its forward / training entries are the
+ * *_routes ones below: an entry that takes an image batch fails on it with VY_ERR_STATE (and a *_routes entry on a full
+ * net), doing nothing. */
+int vy_net_create_heads(int32_t num_class, vy_net** out);
 void vy_net_destroy(vy_net* net);
 
 /* net.set_nms(nms_thresh, nms_topk, post_nms) — yolo3.py:1208-1228.
@@ -190,6 +198,20 @@ int32_t vy_net_num_anchors(const vy_net* net);
 int vy_net_forward_infer(vy_net* net, const float* x, float* ids, float* scores, float* bboxes,
                          int32_t* keep_idx, void* stream);
 
+/* Route tensors.  The three outputs of Darknet-53 that the heads read — features[:15], [15:24], [24:] of
+ * extract_base_features.py:120-160 (saved there as <id>_F1/F2/F3.npy) — as device fp32 NCHW:
+ *   f0 (batch, 256, ceil(H/8), ceil(W/8))   f1 (batch, 512, ceil(H/16), ceil(W/16))   f2 (batch, 1024, ceil(H/32), ceil(W/32))
+ * for the (batch, H, W) the workspace is planned for.  No entry writes into a caller's route buffer that it reads. */
+/* Full nets: the backbone alone (stem and stages, on the ordinary plan — no vy_net_set_keep_activations needed), then
+ * the routes copied out: what extract_base_features.py:120-160 computes per batch.  No head conv, no detection tail.
+ * Asynchronous on `stream`. */
+int vy_net_forward_features(vy_net* net, const float* x, float* f0, float* f1, float* f2, void* stream);
+/* Heads-only nets: net(f1, f2, f3) outside autograd — YOLOV3_noback.hybrid_forward's inference branch
+ * (train_yolov3.py:444-460 validates this way).  Outputs and the NMS-disabled raw-tensor rule as
+ * vy_net_forward_infer.  Asynchronous on `stream`. */
+int vy_net_forward_infer_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* ids, float* scores,
+                                float* bboxes, int32_t* keep_idx, void* stream);
+
 /* The detection tail ALONE, on caller-supplied prediction-conv outputs: YOLOOutputV3.hybrid_forward's inference branch
  * (yolo3.py:158-197: decode, x C tile, class-major rows) for the three scales, their concat (yolo3.py:1195), box_nms and
  * the slice (yolo3.py:1197-1206) — what `net.yolo_outputs[i](pred)` + `F.contrib.box_nms` compute in the reference.
@@ -295,6 +317,10 @@ int vy_net_set_train_options(vy_net* net, float ignore_iou_thresh, int32_t label
 int vy_net_train_forward(vy_net* net, const float* x, const float* gt_boxes, int32_t M,
                          const float* obj_t, const float* centers_t, const float* scales_t,
                          const float* weights_t, const float* clas_t, float* losses, void* stream);
+/* ... of a heads-only net on the three route tensors (train_yolov3.py:595-606 with --features_dir). */
+int vy_net_train_forward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, const float* gt_boxes,
+                                int32_t M, const float* obj_t, const float* centers_t, const float* scales_t,
+                                const float* weights_t, const float* clas_t, float* losses, void* stream);
 
 /* net(x) under autograd.train_mode() without recording — yolo3.py:1189-1192, the branch the DataLoader
  * transform drives (transforms.py:190-193): the network runs with BatchNorm on batch statistics (running
@@ -306,11 +332,18 @@ int vy_net_train_forward(vy_net* net, const float* x, const float* gt_boxes, int
  * Needs the training workspace (vy_net_bind_train).  All outputs are device buffers. */
 int vy_net_train_mode_forward(vy_net* net, const float* x, float* box_preds, float* centers, float* scales,
                               float* objness, float* class_pred, void* stream);
+/* ... of a heads-only net on the three route tensors. */
+int vy_net_train_mode_forward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* box_preds,
+                                     float* centers, float* scales, float* objness, float* class_pred, void* stream);
 
 /* autograd.backward(sum_losses) (train_yolov3.py:631): fills the gradient buffer (every trainable
  * tensor, device layout) from the state left by the last vy_net_train_forward.  `x` is the same
  * image batch (needed by the stem's weight gradient). */
 int vy_net_train_backward(vy_net* net, const float* x, void* stream);
+/* ... of a heads-only net: the head cells' gradients only — no data gradient into the routes (yolo_blocks.0.body.0 gets
+ * none, yolo_blocks.1/2.body.0 only that of the upsampled-transition channels of their concat input).  The routes are the
+ * ones of the recorded forward; nothing is read from them here. */
+int vy_net_train_backward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, void* stream);
 
 /* Per-parameter optimizer attributes: Parameter.lr_mult / wd_mult (train_yolov3.py:496-497) and
  * grad_req = 'null' (enabled = 0; wrappers.py:55-57 freeze_base). */

@@ -94,6 +94,13 @@ SIGNATURES.update({
     "vy_net_train_conv_plan": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "vy_net_set_sync_bn": (ctypes.c_int, [_vp, _i32, ALLREDUCE_CB, _vp]),
     "vy_net_set_grad_bucket_cb": (ctypes.c_int, [_vp, GRAD_BUCKET_CB, _vp]),
+    # heads-only nets and route tensors (yolo3_no_backbone)
+    "vy_net_create_heads": (ctypes.c_int, [_i32, ctypes.POINTER(_vp)]),
+    "vy_net_forward_features": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "vy_net_forward_infer_routes": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vy_net_train_forward_routes": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vy_net_train_mode_forward_routes": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "vy_net_train_backward_routes": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
 })
 
 _lib = None

@@ -172,6 +172,22 @@ hipError_t vy_launch_padded_plane_to_nchw(const float* plane, int B, int Hp, int
 hipError_t vy_launch_nchw_to_plane(const float* src, int B, int H, int W, int cs, int co, int C, float* plane,
                                    hipStream_t s);
 
+// ---- route tensors (routes.hip): dense NCHW (B, C, H, W) <-> channels [co, co + C) of a plane's interior, all three
+// routes in one launch (LDS-tiled transpose, 16-B accesses on both sides).  C a multiple of 64, cs and co of 4.
+struct RouteXfer {
+  float* plane;        // the plane (border included), channel stride cs
+  float* nchw;         // the caller's dense tensor (read by import, written by export)
+  int H, W, C, cs, co;
+};
+struct RouteArgs {
+  RouteXfer r[3];
+  int n;               // routes in this launch (1..3)
+  int B;
+  int tile_end[3];     // filled by the launcher
+};
+hipError_t vy_launch_route_import(const RouteArgs& a, hipStream_t s);
+hipError_t vy_launch_route_export(const RouteArgs& a, hipStream_t s);
+
 // ---- detection tail -------------------------------------------------------------------------
 #define VY_NMS_MAX_TOPK 1024
 struct HeadView {

@@ -26,6 +26,14 @@ int vy_fail(int code, const char* fmt, ...) {
 }
 #define fail vy_fail
 
+int vy_check_kind(const vy_net* net, bool routes_entry, const char* entry) {
+  if (net && net->heads_only != routes_entry)
+    return fail(VY_ERR_STATE, net->heads_only ? "%s takes an image batch: this is a heads-only net (vy_net_create_heads), "
+                                                "use the *_routes entry points"
+                                              : "%s takes route tensors: this is a full net (vy_net_create)", entry);
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -38,6 +46,18 @@ int vy_net_create(int32_t num_class, vy_net** out) {
   vy_net* n = new vy_net();
   n->num_class = num_class;
   n->knobs = vy_knobs_read();
+  n->build();
+  *out = n;
+  return 0;
+}
+
+int vy_net_create_heads(int32_t num_class, vy_net** out) {
+  if (!out) return fail(VY_ERR_INVALID, "out is null");
+  if (num_class < 1 || num_class > 1000) return fail(VY_ERR_INVALID, "num_class %d out of range", num_class);
+  vy_net* n = new vy_net();
+  n->num_class = num_class;
+  n->knobs = vy_knobs_read();
+  n->heads_only = true;
   n->build();
   *out = n;
   return 0;
@@ -221,11 +241,39 @@ int32_t vy_net_num_anchors(const vy_net* net) {
 
 int vy_net_forward_infer(vy_net* net, const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
                          void* stream) {
+  if (int rc = vy_check_kind(net, false, "vy_net_forward_infer")) return rc;
   if (net && (!x || !ids || !scores || !bboxes)) net->sk_dirty = true;  // (any error return: see vy_net::sk_dirty)
   if (!net || !x || !ids || !scores || !bboxes) return fail(VY_ERR_INVALID, "null argument");
   if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
   return net->sk_end(net->forward<false>(x, ids, scores, bboxes, keep_idx, static_cast<hipStream_t>(stream),
                                          [](const char*, double, double, bool) {}));
+}
+
+int vy_net_forward_features(vy_net* net, const float* x, float* f0, float* f1, float* f2, void* stream) {
+  if (int rc = vy_check_kind(net, false, "vy_net_forward_features")) return rc;
+  if (!net || !x || !f0 || !f1 || !f2) {
+    if (net) net->sk_dirty = true;
+    return fail(VY_ERR_INVALID, "null argument");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = net->sk_begin(s)) return rc;
+  float* const out[3] = {f0, f1, f2};
+  return net->sk_end(net->forward<false>(x, nullptr, nullptr, nullptr, nullptr, s, [](const char*, double, double, bool) {},
+                                         nullptr, out));
+}
+
+int vy_net_forward_infer_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* ids, float* scores,
+                                float* bboxes, int32_t* keep_idx, void* stream) {
+  if (int rc = vy_check_kind(net, true, "vy_net_forward_infer_routes")) return rc;
+  if (!net || !f0 || !f1 || !f2 || !ids || !scores || !bboxes) {
+    if (net) net->sk_dirty = true;
+    return fail(VY_ERR_INVALID, "null argument");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = net->sk_begin(s)) return rc;
+  const float* const in[3] = {f0, f1, f2};
+  return net->sk_end(net->forward<false>(nullptr, ids, scores, bboxes, keep_idx, s, [](const char*, double, double, bool) {},
+                                         in, nullptr));
 }
 
 int vy_net_read_head(vy_net* net, int32_t i, float* dst_dev, void* stream) {
@@ -279,6 +327,7 @@ int vy_net_read_activation(vy_net* net, const char* name, float* dst_dev, int32_
 
 int vy_net_profile_infer(vy_net* net, const float* x, float* ids, float* scores, float* bboxes,
                          vy_launch_stat* stats, int32_t* n, void* stream) {
+  if (int rc = vy_check_kind(net, false, "vy_net_profile_infer")) return rc;
   if (!net || !stats || !n) return fail(VY_ERR_INVALID, "null argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int cap = *n;

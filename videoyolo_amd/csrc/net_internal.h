@@ -19,6 +19,10 @@
 int vy_fail(int code, const char* fmt, ...);
 #define fail vy_fail
 
+struct vy_net;
+// VY_ERR_STATE unless `net` is of the kind the entry point serves: heads-only (routes_entry) or full (defined in net.hip)
+int vy_check_kind(const vy_net* net, bool routes_entry, const char* entry);
+
 #define HIP_TRY(expr)                                                                  \
   do {                                                                                 \
     hipError_t e_ = (expr);                                                            \
@@ -123,6 +127,13 @@ struct vy_net {
   }
   size_t wsplit_off = 0;
   struct VyTrain* train = nullptr;  // training planner state, owned by train.hip
+  // vy_net_create_heads: the graph starts at the three route tensors (YOLOV3_noback, yolo3.py:1686-1920) — no stem, no
+  // stages; the routes are imported into the planes the backbone's last blocks write in a full net
+  bool heads_only = false;
+  // the route slices, order stride 8, 16, 32 (features[:15], [15:24], [24:]): plane, first channel, channels
+  struct RouteSlot {
+    int plane = -1, co = 0, C = 0;
+  } routes[3];
 
   int add_param(const std::string& name, int kind, int ndim, const int* shape, int trainable, int backbone) {
     ParamT p;
@@ -205,10 +216,12 @@ struct vy_net {
       snprintf(nm, sizeof nm, "stages.%d.%d", si, j);
       return std::string(nm);
     };
-    int cur = add_plane(32, 1), cur_co = 0;
-    add_conv(feat_name(feat++), -1, 0, 3, cur, 0, 32, 3, 1, true, 1);
+    routes[0] = {cat2, 128, 256};
+    routes[1] = {cat1, 256, 512};
+    int cur = add_plane(heads_only ? 1024 : 32, heads_only ? 32 : 1), cur_co = 0;
+    if (!heads_only) add_conv(feat_name(feat++), -1, 0, 3, cur, 0, 32, 3, 1, true, 1);
     int div = 1;
-    for (int st = 0; st < 5; ++st) {
+    for (int st = 0; st < 5 && !heads_only; ++st) {
       const int ch = chans[st + 1];
       div *= 2;
       int nxt = add_plane(ch, div);
@@ -236,6 +249,7 @@ struct vy_net {
         cur_co = outco;
       }
     }
+    routes[2] = {cur, cur_co, 1024};
     // ---- heads, deep -> shallow (yolo3.py:1013-1054, 1126-1177)
     const int hch[3] = {512, 256, 128};
     const int hdiv[3] = {32, 16, 8};
@@ -321,6 +335,8 @@ struct vy_net {
       if (c.res_plane >= 0 && ci > last[c.res_plane]) last[c.res_plane] = ci;
     }
     for (int i = 0; i < 3; ++i) last[head_plane[i]] = kLive;  // read by decode + NMS (and vy_net_read_head) afterwards
+    if (heads_only)  // the routes are imported before the first conv: those planes own their storage
+      for (int i = 0; i < 3; ++i) def[routes[i].plane] = -1;
     std::vector<int> order(np);
     for (int i = 0; i < np; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return def[a] < def[b]; });
@@ -514,6 +530,25 @@ struct vy_net {
     a.sk_nflags = VY_SK_FLAGS;
   }
 
+  // the three route slices of the bound plan and the caller's dense NCHW tensors (routes.hip)
+  RouteArgs route_args(const float* const* nchw) const {
+    RouteArgs r;
+    memset(&r, 0, sizeof r);
+    r.n = 3;
+    r.B = B;
+    for (int i = 0; i < 3; ++i) {
+      const PlaneT& p = planes[routes[i].plane];
+      r.r[i].plane = plane_ptr(routes[i].plane);
+      r.r[i].nchw = const_cast<float*>(nchw[i]);
+      r.r[i].H = p.H;
+      r.r[i].W = p.W;
+      r.r[i].C = routes[i].C;
+      r.r[i].cs = p.C;
+      r.r[i].co = routes[i].co;
+    }
+    return r;
+  }
+
   DetArgs det_args() const {
     DetArgs d;
     memset(&d, 0, sizeof d);
@@ -547,9 +582,11 @@ struct vy_net {
 
   // launches of one inference forward; `hook` (optional) is called around every launch
   // kLabels = false: the hook is a no-op (vy_net_forward_infer) and the per-launch labels are not built
+  // routes_in (heads-only nets): the three route tensors, imported in front of the first conv (x unused);
+  // routes_out (full nets): stop after the backbone and export the routes there — no head conv, no detection tail
   template <bool kLabels = true, typename Hook>
   int forward(const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx, hipStream_t s,
-              Hook&& hook) {
+              Hook&& hook, const float* const* routes_in = nullptr, float* const* routes_out = nullptr) {
     if (int rc = check_ready()) return rc;
     const bool nms_on = nms_thresh > 0.f && nms_thresh < 1.f;  // yolo3.py:1197
     FoldDesc* fd = reinterpret_cast<FoldDesc*>(dev_ws + fold_desc_off);
@@ -580,7 +617,13 @@ struct vy_net {
       hook("split_weights", 0.0, 0.0, false);
       split_dirty = wino_dirty = false;
     }
+    if (routes_in) {
+      hook("route_import", 0.0, 0.0, true);
+      HIP_TRY(vy_launch_route_import(route_args(routes_in), s));
+      hook("route_import", 0.0, 0.0, false);
+    }
     for (const ConvT& c : convs) {
+      if (routes_out && !params[c.p_weight].info.backbone) break;
       if (c.is_stem) {
         StemArgs a;
         a.x = x;
@@ -649,6 +692,13 @@ struct vy_net {
         HIP_TRY(vy_launch_conv_igemm(a, s));
         hook(nm, fl, by, false);
       }
+    }
+    if (routes_out) {
+      const float* const out[3] = {routes_out[0], routes_out[1], routes_out[2]};
+      hook("route_export", 0.0, 0.0, true);
+      HIP_TRY(vy_launch_route_export(route_args(out), s));
+      hook("route_export", 0.0, 0.0, false);
+      return 0;
     }
     const DetArgs d = det_args();
     double dby = 0;

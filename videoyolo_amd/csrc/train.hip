@@ -425,10 +425,12 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
   return 0;
 }
 
-int forward_train(const TrainCtx& c, const float* x) {
+// routes (heads-only nets): the three route tensors, imported into their planes in front of the first conv
+int forward_train(const TrainCtx& c, const float* x, const float* const* routes) {
   vy_net* net = c.net;
   const int B = net->B;
   if (int rc = refresh_split_images(c)) return rc;
+  if (routes) HIP_TRY(vy_launch_route_import(net->route_args(routes), c.s));
   for (size_t ci = 0; ci < net->convs.size(); ++ci) {
     const ConvT& cv = net->convs[ci];
     if (cv.p_gamma < 0) {  // prediction conv: bias, no BN
@@ -827,8 +829,16 @@ int backward_train(const TrainCtx& c, const float* x) {
       HIP_TRY(hipStreamWaitEvent(c.t->side, c.t->ev_main, 0));
     }
     if (int rc = launch_wgrad(c, (size_t)ci, dzp, dz_cs, dzH, dzW, ws)) return rc;
-    // data gradient into the input view
-    const int lo = cv.in_co, hi = cv.in_co + cv.cin;
+    // data gradient into the input view.  A heads-only net computes none into its imported routes: yolo_blocks.0.body.0
+    // (input: the stride-32 route) gets no data gradient at all, yolo_blocks.1/2.body.0 only the one of the upsampled
+    // transition channels [0, co) in front of the route in their concat plane (a narrower N: every output is the same
+    // fp32 chain whatever the tile, so these channels are bit-identical to the full net's)
+    const int lo = cv.in_co;
+    int hi = cv.in_co + cv.cin;
+    if (net->heads_only)
+      for (const auto& r : net->routes)
+        if (r.plane == cv.in_plane && r.co < hi) hi = std::max(lo, r.co);
+    if (hi == lo) continue;
     const int cov = covered(cv.in_plane, lo, hi);
     if (cov < 0) return fail(VY_ERR_STATE, "internal: partial gradient overlap at '%s'", cv.name.c_str());
     const float* addend = nullptr;
@@ -847,7 +857,12 @@ int backward_train(const TrainCtx& c, const float* x) {
       add_cs = net->planes[cv.in_plane].C;
       add_co = cv.in_co;
     }
-    const BwdDgrad dg = make_dgrad(c, cv, dzp, dz_cs, dzH, dzW, addend, add_cs, add_co);
+    BwdDgrad dg = make_dgrad(c, cv, dzp, dz_cs, dzH, dzW, addend, add_cs, add_co);
+    if (hi - lo != cv.cin)
+      for (int k = 0; k < dg.n; ++k) {
+        dg.a[k].N = hi - lo;
+        dg.a[k].w_split = nullptr;  // (the split kernel's data-gradient images are tiled for the whole cin)
+      }
     for (int k = 0; k < dg.n; ++k) {
       if (!g_labels_done) g_labels.note(net, "dgrad", cv.name, dg.a[k].M, dg.a[k].N, (double)dg.a[k].ntaps * dg.a[k].Kc);
       if (train_abl(net) & 16) continue;  // (bound measurement: no data-gradient kernel)
@@ -924,17 +939,17 @@ int vy_net_set_train_options(vy_net* net, float ignore_iou_thresh, int32_t label
   return 0;
 }
 
-static int train_forward_impl(vy_net* net, const float* x, const float* gt_boxes, int32_t M, const float* obj_t,
-                         const float* centers_t, const float* scales_t, const float* weights_t,
-                         const float* clas_t, float* losses, void* stream) {
-  if (!net || !x || !obj_t || !centers_t || !scales_t || !weights_t || !clas_t || !losses || (M > 0 && !gt_boxes))
+static int train_forward_impl(vy_net* net, const float* x, const float* const* routes, const float* gt_boxes, int32_t M,
+                              const float* obj_t, const float* centers_t, const float* scales_t, const float* weights_t,
+                              const float* clas_t, float* losses, void* stream) {
+  if (!net || !(routes ? routes[0] && routes[1] && routes[2] : x != nullptr) || !obj_t || !centers_t || !scales_t || !weights_t || !clas_t || !losses || (M > 0 && !gt_boxes))
     return fail(VY_ERR_INVALID, "null argument");
   if (int rc = net->check_ready()) return rc;
   VyTrain* t = net->train;
   if (!t || !t->grads || t->B != net->B || t->H != net->H || t->W != net->W)
     return fail(VY_ERR_STATE, "training workspace not bound (vy_net_bind_train)");
   TrainCtx c{net, t, static_cast<hipStream_t>(stream)};
-  if (int rc = forward_train(c, x)) return rc;
+  if (int rc = forward_train(c, x, routes)) return rc;
   const DetArgs d = net->det_args();
   LossArgs la;
   memset(&la, 0, sizeof la);
@@ -967,24 +982,37 @@ static int train_forward_impl(vy_net* net, const float* x, const float* gt_boxes
 int vy_net_train_forward(vy_net* net, const float* x, const float* gt_boxes, int32_t M, const float* obj_t,
                          const float* centers_t, const float* scales_t, const float* weights_t,
                          const float* clas_t, float* losses, void* stream) {
+  if (int rc = vy_check_kind(net, false, "vy_net_train_forward")) return rc;
 #ifdef VY_TRAIN_ABL_BUILD
   ++g_abl_forwards;
 #endif
   if (net)
     if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
-  const int rc = train_forward_impl(net, x, gt_boxes, M, obj_t, centers_t, scales_t, weights_t, clas_t, losses, stream);
+  const int rc = train_forward_impl(net, x, nullptr, gt_boxes, M, obj_t, centers_t, scales_t, weights_t, clas_t, losses, stream);
   return net ? net->sk_end(rc) : rc;
 }
 
-static int train_mode_forward_impl(vy_net* net, const float* x, float* box_preds, float* centers, float* scales,
-                              float* objness, float* class_pred, void* stream) {
-  if (!net || !x || !box_preds || !centers || !scales || !objness || !class_pred) return fail(VY_ERR_INVALID, "null argument");
+int vy_net_train_forward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, const float* gt_boxes,
+                                int32_t M, const float* obj_t, const float* centers_t, const float* scales_t,
+                                const float* weights_t, const float* clas_t, float* losses, void* stream) {
+  if (int rc = vy_check_kind(net, true, "vy_net_train_forward_routes")) return rc;
+  if (net)
+    if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
+  const float* const routes[3] = {f0, f1, f2};
+  const int rc = train_forward_impl(net, nullptr, routes, gt_boxes, M, obj_t, centers_t, scales_t, weights_t, clas_t, losses,
+                                    stream);
+  return net ? net->sk_end(rc) : rc;
+}
+
+static int train_mode_forward_impl(vy_net* net, const float* x, const float* const* routes, float* box_preds, float* centers,
+                                   float* scales, float* objness, float* class_pred, void* stream) {
+  if (!net || !(routes ? routes[0] && routes[1] && routes[2] : x != nullptr) || !box_preds || !centers || !scales || !objness || !class_pred) return fail(VY_ERR_INVALID, "null argument");
   if (int rc = net->check_ready()) return rc;
   VyTrain* t = net->train;
   if (!t || !t->grads || t->B != net->B || t->H != net->H || t->W != net->W)
     return fail(VY_ERR_STATE, "training workspace not bound (vy_net_bind_train)");
   TrainCtx c{net, t, static_cast<hipStream_t>(stream)};
-  if (int rc = forward_train(c, x)) return rc;
+  if (int rc = forward_train(c, x, routes)) return rc;
   t->forward_done = false;  // nothing was recorded: no backward may follow
   const DetArgs d = net->det_args();
   RawPredArgs ra;
@@ -1008,14 +1036,25 @@ static int train_mode_forward_impl(vy_net* net, const float* x, float* box_preds
 
 int vy_net_train_mode_forward(vy_net* net, const float* x, float* box_preds, float* centers, float* scales,
                               float* objness, float* class_pred, void* stream) {
+  if (int rc = vy_check_kind(net, false, "vy_net_train_mode_forward")) return rc;
   if (net)
     if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
-  const int rc = train_mode_forward_impl(net, x, box_preds, centers, scales, objness, class_pred, stream);
+  const int rc = train_mode_forward_impl(net, x, nullptr, box_preds, centers, scales, objness, class_pred, stream);
+  return net ? net->sk_end(rc) : rc;
+}
+
+int vy_net_train_mode_forward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* box_preds,
+                                     float* centers, float* scales, float* objness, float* class_pred, void* stream) {
+  if (int rc = vy_check_kind(net, true, "vy_net_train_mode_forward_routes")) return rc;
+  if (net)
+    if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
+  const float* const routes[3] = {f0, f1, f2};
+  const int rc = train_mode_forward_impl(net, nullptr, routes, box_preds, centers, scales, objness, class_pred, stream);
   return net ? net->sk_end(rc) : rc;
 }
 
 static int train_backward_impl(vy_net* net, const float* x, void* stream) {
-  if (!net || !x) return fail(VY_ERR_INVALID, "null argument");
+  if (!net || (!x && !net->heads_only)) return fail(VY_ERR_INVALID, "null argument");
   if (int rc = net->check_ready()) return rc;
   VyTrain* t = net->train;
   if (!t || !t->forward_done) return fail(VY_ERR_STATE, "vy_net_train_backward without a recorded forward");
@@ -1025,10 +1064,18 @@ static int train_backward_impl(vy_net* net, const float* x, void* stream) {
 }
 
 int vy_net_train_backward(vy_net* net, const float* x, void* stream) {
+  if (int rc = vy_check_kind(net, false, "vy_net_train_backward")) return rc;
   if (net)
     if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
   const int rc = train_backward_impl(net, x, stream);
   return net ? net->sk_end(rc) : rc;
+}
+
+int vy_net_train_backward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, void* stream) {
+  if (int rc = vy_check_kind(net, true, "vy_net_train_backward_routes")) return rc;
+  if (!net || !f0 || !f1 || !f2) return fail(VY_ERR_INVALID, "null argument");
+  if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
+  return net->sk_end(train_backward_impl(net, nullptr, stream));  // (nothing is read from the routes: see backward_train)
 }
 
 int vy_net_param_set_opt(vy_net* net, int32_t i, float lr_mult, float wd_mult, int32_t enabled) {

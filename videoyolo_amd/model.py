@@ -110,6 +110,8 @@ def _torch():
 class YOLOV3(object):
     """yolo3_darknet53 detector bound to one device / stream."""
 
+    _CREATE = "vy_net_create"  # the library constructor of this graph
+
     def __init__(self, classes, nms_thresh=0.45, nms_topk=400, post_nms=100, pos_iou_thresh=1.0,
                  ignore_iou_thresh=0.7, norm_layer=BatchNorm, norm_kwargs=None, alloc_size=(128, 128)):
         if pos_iou_thresh < 1:
@@ -118,7 +120,7 @@ class YOLOV3(object):
         self._classes = list(classes)
         self._lib = _lib.load()
         h = ctypes.c_void_p()
-        _lib.check(self._lib.vy_net_create(len(self._classes), ctypes.byref(h)))
+        _lib.check(getattr(self._lib, self._CREATE)(len(self._classes), ctypes.byref(h)))
         self._h = h
         self.nms_thresh, self.nms_topk, self.post_nms = nms_thresh, nms_topk, post_nms
         self._ignore_iou_thresh = ignore_iou_thresh
@@ -485,7 +487,7 @@ class YOLOV3(object):
             reuse_weights = {classes.index(n): old_classes.index(n) for n in both}
         old_vals = {p.name: self._get_param(p.index) for p in self._params.values()}
         device = self._device
-        fresh = YOLOV3(classes, self.nms_thresh, self.nms_topk, self.post_nms, self._pos_iou_thresh,
+        fresh = type(self)(classes, self.nms_thresh, self.nms_topk, self.post_nms, self._pos_iou_thresh,
                        self._ignore_iou_thresh, self._norm_layer, self._norm_kwargs, self._alloc_size)
         new_vals = _init.uniform_params(fresh.param_table())  # prediction.initialize(), yolo3.py:110
         old_np, new_np = 5 + len(old_classes), 5 + len(classes)
@@ -525,7 +527,7 @@ class YOLOV3(object):
 
     def __deepcopy__(self, memo):
         """``copy.deepcopy(net)`` (transforms.py:190): a host-side copy, not bound to a device."""
-        twin = YOLOV3(self._classes, self.nms_thresh, self.nms_topk, self.post_nms, self._pos_iou_thresh,
+        twin = type(self)(self._classes, self.nms_thresh, self.nms_topk, self.post_nms, self._pos_iou_thresh,
                       self._ignore_iou_thresh, self._norm_layer, copy.deepcopy(self._norm_kwargs, memo),
                       self._alloc_size)
         if self._all_set():
@@ -697,6 +699,22 @@ class YOLOV3(object):
                 self._h, ctypes.c_void_p(x.data_ptr()), *[ctypes.c_void_p(t.data_ptr()) for t in outs],
                 self._stream()))
         return (outs[0], anchors, offsets, fms, outs[1], outs[2], outs[3], outs[4])
+
+    def extract_features(self, x):
+        """The backbone alone (extract_base_features.py:120-160): ``(f1, f2, f3)`` = features[:15], [15:24], [24:] of the
+        Darknet-53 stages for the (B,3,H,W) batch ``x`` — device tensors, NCHW, (B, 256, H/8, W/8), (B, 512, H/16, W/16),
+        (B, 1024, H/32, W/32) (sizes rounded up).  One launch sequence of the stem and the stages and one transpose out; no
+        head runs.  What ``yolo3_no_backbone(...)(f1, f2, f3)`` takes."""
+        torch = _torch()
+        x = self._as_input(x)
+        b, _, h, w = x.shape
+        with torch.cuda.device(self._device):
+            self._ensure_plan(b, h, w)
+            outs = [torch.empty((b, c, -(-h // s), -(-w // s)), dtype=torch.float32, device=self._device)
+                    for c, s in ((256, 8), (512, 16), (1024, 32))]
+            _lib.check(self._lib.vy_net_forward_features(
+                self._h, ctypes.c_void_p(x.data_ptr()), *[ctypes.c_void_p(t.data_ptr()) for t in outs], self._stream()))
+        return tuple(outs)
 
     def grad(self, name):
         """Gradient of parameter `name` in the reference layout (numpy)."""
@@ -948,6 +966,139 @@ class YOLOV3(object):
 YOLOV3T = YOLOV3
 
 
+class YOLOV3NoBackbone(YOLOV3):
+    """``YOLOV3_noback`` (yolo3.py:1686-1920): YOLOV3's heads entered at the three Darknet-53 route tensors, for the
+    reference's --features_dir workflow (extract_base_features.py once, then train_yolov3.py on the saved features).
+    ``net(f1, f2, f3)`` takes the routes as ``YOLOV3.extract_features`` returns them (NCHW, (B, 256, H/8, W/8),
+    (B, 512, H/16, W/16), (B, 1024, H/32, W/32)); the mode follows ``autograd`` as in ``YOLOV3.__call__``.  The parameter
+    table is the full net's head rows, so a full model's file loads with ``ignore_extra=True``.  Nothing is
+    back-propagated into the routes."""
+
+    _CREATE = "vy_net_create_heads"
+
+    def _as_routes(self, f1, f2, f3):
+        """Check the three routes against each other (before anything launches) -> (device tensors, (B, H, W)) with H, W
+        the smallest image size they can come from (the plan only depends on the route sizes)."""
+        torch = _torch()
+        fs = []
+        for f in (f1, f2, f3):
+            shape = tuple(f.shape) if hasattr(f, "shape") else tuple(np.shape(f))
+            fs.append(shape)
+        b = fs[0][0] if fs[0] else None
+        h8, w8 = (fs[0][2], fs[0][3]) if len(fs[0]) == 4 else (0, 0)
+        want = [(b, 256, h8, w8), (b, 512, -(-h8 // 2), -(-w8 // 2)), (b, 1024, -(-h8 // 4), -(-w8 // 4))]
+        if any(len(s) != 4 for s in fs) or fs != want or b < 1 or min(h8, w8) < 4 or max(h8, w8) > 512:
+            raise ValueError("route shapes %s are not the three Darknet-53 routes of one (B, 3, H, W) batch: expected "
+                             "(B, 256, h, w), (B, 512, ceil(h/2), ceil(w/2)), (B, 1024, ceil(h/4), ceil(w/4)) with h, w in "
+                             "[4, 512]" % (fs,))
+        if self._device is None:
+            raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
+        out = []
+        for f in (f1, f2, f3):
+            if not isinstance(f, torch.Tensor):
+                f = torch.as_tensor(np.asarray(f, np.float32))
+            out.append(f.to(device=self._device, dtype=torch.float32).contiguous())
+        return out, (b, 8 * h8, 8 * w8)
+
+    def __call__(self, f1, f2, f3, *args, return_index=False):
+        """YOLOV3_noback.hybrid_forward(F, x1, x2, x3, *args): mode by the autograd state."""
+        if autograd.is_training():
+            if autograd.is_recording():
+                if len(args) != 6:
+                    raise ValueError("training call: net(f1, f2, f3, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)")
+                return self.forward_train(f1, f2, f3, *args)
+            return self.forward_train_mode(f1, f2, f3)
+        return self.detect(f1, f2, f3, return_index=return_index)
+
+    def detect(self, f1, f2, f3, return_index=False):
+        """Inference branch: (ids, scores, bboxes[, keep_idx]) exactly as ``YOLOV3.detect`` returns them."""
+        torch = _torch()
+        fs, (b, h, w) = self._as_routes(f1, f2, f3)
+        with torch.cuda.device(self._device):
+            self._ensure_plan(b, h, w)
+            rows = self._out_rows()
+            ids = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
+            scores = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
+            bboxes = torch.empty((b, rows, 4), dtype=torch.float32, device=self._device)
+            keep = torch.empty((b, rows), dtype=torch.int32, device=self._device) if return_index else None
+            _lib.check(self._lib.vy_net_forward_infer_routes(
+                self._h, *[ctypes.c_void_p(f.data_ptr()) for f in fs], ctypes.c_void_p(ids.data_ptr()),
+                ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(bboxes.data_ptr()),
+                ctypes.c_void_p(keep.data_ptr()) if keep is not None else None, self._stream()))
+        return (ids, scores, bboxes, keep) if return_index else (ids, scores, bboxes)
+
+    def _single_rank(self):
+        from . import parallel
+        if parallel.world_size() > 1:
+            raise NotImplementedError("multi-rank training of a heads-only net (yolo3_no_backbone) is not supported: "
+                                      "train it on one rank")
+
+    def forward_train(self, f1, f2, f3, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t):
+        """Recording branch: the four (B,) losses; ``autograd.backward`` walks the heads afterwards."""
+        torch = _torch()
+        self._single_rank()
+        fs, (b, h, w) = self._as_routes(f1, f2, f3)
+        tg = [self._dev(t) for t in (gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)]
+        m = int(tg[0].shape[1])
+        with torch.cuda.device(self._device):
+            self._ensure_plan(b, h, w, train=True)
+            n = self._lib.vy_net_num_anchors(self._h)
+            c = len(self._classes)
+            want = [(b, m, 4), (b, n, 1), (b, n, 2), (b, n, 2), (b, n, 2), (b, n, c)]
+            for t, shp in zip(tg, want):
+                if tuple(t.shape) != shp:
+                    raise ValueError("target shape %s, expected %s" % (tuple(t.shape), shp))
+            _lib.check(self._lib.vy_net_set_train_options(
+                self._h, self._ignore_iou_thresh, int(bool(self._target_generator._label_smooth))))
+            losses = torch.empty((4, b), dtype=torch.float32, device=self._device)
+            p = [ctypes.c_void_p(t.data_ptr()) for t in tg]
+            _lib.check(self._lib.vy_net_train_forward_routes(
+                self._h, *[ctypes.c_void_p(f.data_ptr()) for f in fs], p[0], m, p[1], p[2], p[3], p[4], p[5],
+                ctypes.c_void_p(losses.data_ptr()), self._stream()))
+        self._train_x = fs
+        autograd._register(self)
+        return tuple(autograd.loss_vector(losses[i], self, i) for i in range(4))
+
+    def backward(self):
+        torch = _torch()
+        if self._train_x is None:
+            raise RuntimeError("backward() without a recorded forward")
+        with torch.cuda.device(self._device):
+            _lib.check(self._lib.vy_net_train_backward_routes(
+                self._h, *[ctypes.c_void_p(f.data_ptr()) for f in self._train_x], self._stream()))
+        self._train_x = None
+
+    def forward_train_mode(self, f1, f2, f3):
+        """``autograd.train_mode()`` without recording: the 8-tuple of ``YOLOV3.forward_train_mode``."""
+        torch = _torch()
+        self._single_rank()
+        fs, (b, h, w) = self._as_routes(f1, f2, f3)
+        anchors, offsets, fms = [], [], []
+        for i, s in enumerate((32, 16, 8)):
+            hh, ww = h // s, w // s
+            anchors.append(np.array(self._ANCHORS[i], np.float32).reshape(1, 1, 3, 2))
+            gx, gy = np.meshgrid(np.arange(ww), np.arange(hh))
+            offsets.append(np.stack([gx, gy], -1).astype(np.float32).reshape(1, hh * ww, 1, 2))
+            fms.append(np.zeros((1, 1, hh, ww), np.float32))
+        with torch.cuda.device(self._device):
+            self._ensure_plan(b, h, w, train=True)
+            n = self._lib.vy_net_num_anchors(self._h)
+            c = len(self._classes)
+            outs = [torch.empty((b, n, k), dtype=torch.float32, device=self._device) for k in (4, 2, 2, 1, c)]
+            _lib.check(self._lib.vy_net_train_mode_forward_routes(
+                self._h, *[ctypes.c_void_p(f.data_ptr()) for f in fs], *[ctypes.c_void_p(t.data_ptr()) for t in outs],
+                self._stream()))
+        return (outs[0], anchors, offsets, fms, outs[1], outs[2], outs[3], outs[4])
+
+    def _no_image(self, *args, **kwargs):
+        raise NotImplementedError("a heads-only net (yolo3_no_backbone) takes route tensors, not images")
+
+    extract_features = detect_two_streams = profile = load_darknet53_backbone = _no_image
+
+
+YOLOV3_noback = YOLOV3NoBackbone
+
+
 def _darknet_roots(root=None):
     """Where ``get_model_file('darknet53', root=...)`` would look: the reference's default root
     (three_darknet.py:234 ``models/definitions/darknet/weights``), gluoncv's cache, VY_MODEL_ROOT."""
@@ -988,6 +1139,13 @@ def darknet53_to_stage_names(arrays):
         si, j = (0, f) if f < 15 else ((1, f - 15) if f < 24 else (2, f - 24))
         out["stages.%d.%d.%s" % (si, j, m.group(2))] = v
     return out
+
+
+def yolo3_no_backbone(classes, norm_layer=BatchNorm, norm_kwargs=None, **kwargs):
+    """Drop-in for models/definitions/yolo/wrappers.py:133-161: the yolo3_darknet53 heads without the backbone
+    (``YOLOV3_noback``), for training and validating on saved Darknet-53 features.  ``norm_layer`` may be
+    ``SyncBatchNorm``: the heads hold none of the cells it applies to, so nothing is exchanged."""
+    return YOLOV3NoBackbone(classes, norm_layer=norm_layer, norm_kwargs=norm_kwargs, **kwargs)
 
 
 def yolo3_darknet53(classes, pretrained_base=True, norm_layer=BatchNorm, norm_kwargs=None, freeze_base=False,
