@@ -75,6 +75,21 @@ int vy_net_create(int32_t num_class, vy_net** out);
  * *_routes ones below: an entry that takes an image batch fails on it with VY_ERR_STATE (and a *_routes entry on a full
  * net), doing nothing. */
 int vy_net_create_heads(int32_t num_class, vy_net** out);
+/* yolo3_darknet53(classes, k=k, k_join_type=..., k_join_pos='early') — YOLOV3T yolo3.py:1016-1121 with early join: a
+ * k-frame clip net.  The backbone runs on batch * k frames (TimeDistributed: frame t of clip b is frame b * k + t, so
+ * x is (batch, k, 3, h, w)); each of its three routes is pooled over the clip's k frames (TemporalPooling 'direct',
+ * layers.py:193-204) as soon as its stage ends, and the ordinary heads run on the batch clips.  k >= 2 (k = 1 is
+ * vy_net_create); join VY_JOIN_MAX or VY_JOIN_MEAN; anything else is VY_ERR_INVALID.  The parameter table is
+ * vy_net_create's, name for name and offset for offset.  `batch` counts clips in sizing, binding and every entry.
+ * vy_net_forward_infer and the training entries work on it; vy_net_forward_features, vy_net_profile_infer and the
+ * *_routes entries fail with VY_ERR_STATE, the split conv modes with VY_ERR_UNSUPPORTED.  Taps: vy_net_read_activation
+ * and vy_net_read_grad_activation take "pool.0" .. "pool.2" (strides 8, 16, 32: the pooled route, (batch, C, h, w)); a
+ * backbone cell's tap gives its batch * k frames. */
+#define VY_JOIN_MAX 0
+#define VY_JOIN_MEAN 1
+int vy_net_create_window(int32_t num_class, int32_t k, int32_t join, vy_net** out);
+/* k and join of a window net; k = 0 for any other net. */
+int vy_net_window(const vy_net* net, int32_t* k, int32_t* join);
 void vy_net_destroy(vy_net* net);
 
 /* net.set_nms(nms_thresh, nms_topk, post_nms) — yolo3.py:1208-1228.

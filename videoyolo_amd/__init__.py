@@ -10,12 +10,13 @@ import os as _os
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 from . import autograd  # noqa: F401,E402
-from .model import (YOLOV3, YOLOV3T, YOLOV3NoBackbone, YOLOV3_noback, BatchNorm, SyncBatchNorm, yolo3_darknet53,  # noqa: F401,E402
+from .model import (YOLOV3, YOLOV3T, YOLOV3NoBackbone, YOLOV3_noback, YOLOV3Window, BatchNorm, SyncBatchNorm, yolo3_darknet53,  # noqa: F401,E402
                     yolo3_no_backbone)
 from .trainer import Trainer  # noqa: F401,E402
 from . import parallel  # noqa: F401,E402
 from . import lr_scheduler  # noqa: F401,E402
 from .lr_scheduler import LRScheduler, LRSequential  # noqa: F401,E402
 
-__all__ = ["yolo3_darknet53", "yolo3_no_backbone", "YOLOV3", "YOLOV3T", "YOLOV3NoBackbone", "YOLOV3_noback", "BatchNorm", "SyncBatchNorm", "autograd", "Trainer", "parallel", "lr_scheduler",
+__all__ = ["yolo3_darknet53", "yolo3_no_backbone", "YOLOV3", "YOLOV3T", "YOLOV3NoBackbone", "YOLOV3_noback", "YOLOV3Window",
+           "BatchNorm", "SyncBatchNorm", "autograd", "Trainer", "parallel", "lr_scheduler",
            "LRScheduler", "LRSequential"]

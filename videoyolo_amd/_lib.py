@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(_HERE, "libvyolo.so")
 VY_MAX_TOPK = 1024
 VY_CONV_EXACT_FP32, VY_CONV_SPLIT_BF16X3, VY_CONV_SPLIT_BF16X3_TRAIN = 0, 1, 2
 VY_TAP_Z, VY_TAP_BN, VY_TAP_GRAD_PADDED, VY_TAP_INPUT_PADDED = 0, 1, 2, 3
+VY_JOIN_MAX, VY_JOIN_MEAN = 0, 1
 
 
 class VyError(RuntimeError):
@@ -101,6 +102,9 @@ SIGNATURES.update({
     "vy_net_train_forward_routes": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vy_net_train_mode_forward_routes": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vy_net_train_backward_routes": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    # k-frame clip nets (yolo3_darknet53 with k > 1, early join)
+    "vy_net_create_window": (ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(_vp)]),
+    "vy_net_window": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
 })
 
 _lib = None

@@ -188,6 +188,30 @@ struct RouteArgs {
 hipError_t vy_launch_route_import(const RouteArgs& a, hipStream_t s);
 hipError_t vy_launch_route_export(const RouteArgs& a, hipStream_t s);
 
+// ---- temporal window pooling (temporal.hip): a window net's backbone runs on B*k frames (frame t of clip b is frame
+// b*k + t); its three per-frame route planes are pooled over each clip's k frames into the planes the heads read.
+// Interiors only, channels [co, co + C) of the destination: borders and other channels are never written.  C, cs and co
+// multiples of 4.
+struct PoolRoute {
+  const float* src;    // per-frame route plane (B*k frames, border included), channel stride s_cs, route at channel 0
+  float* dst;          // pooled plane (B clips), channel stride d_cs, route at channel d_co
+  float* gsrc;         // backward: gradient plane of src (written: overwrite, interior only)
+  const float* gdst;   // backward: gradient plane of dst (read)
+  int H, W, C, s_cs, d_cs, d_co;
+};
+struct WindowPoolArgs {
+  PoolRoute r[3];
+  int n;               // routes in this launch (1..3)
+  int B;               // clips
+  int k;               // frames per clip
+  int join;            // VY_JOIN_MAX / VY_JOIN_MEAN
+  long long item_end[3];  // filled by the launcher
+};
+// forward: dst = max / mean over the k frames of src
+hipError_t vy_launch_window_pool(const WindowPoolArgs& a, hipStream_t s);
+// backward: gsrc = gdst / k (mean), gdst where src == dst and 0 elsewhere (max)
+hipError_t vy_launch_window_pool_bwd(const WindowPoolArgs& a, hipStream_t s);
+
 // ---- detection tail -------------------------------------------------------------------------
 #define VY_NMS_MAX_TOPK 1024
 struct HeadView {

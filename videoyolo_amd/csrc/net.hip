@@ -34,6 +34,14 @@ int vy_check_kind(const vy_net* net, bool routes_entry, const char* entry) {
   return 0;
 }
 
+// VY_ERR_STATE for a window net (vy_net_create_window) at an entry point that does not serve one
+static int refuse_window(const vy_net* net, const char* entry) {
+  if (net && net->window_k)
+    return fail(VY_ERR_STATE, "%s does not take a window net (vy_net_create_window): use vy_net_create for single frames",
+                entry);
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -60,6 +68,29 @@ int vy_net_create_heads(int32_t num_class, vy_net** out) {
   n->heads_only = true;
   n->build();
   *out = n;
+  return 0;
+}
+
+int vy_net_create_window(int32_t num_class, int32_t k, int32_t join, vy_net** out) {
+  if (!out) return fail(VY_ERR_INVALID, "out is null");
+  if (num_class < 1 || num_class > 1000) return fail(VY_ERR_INVALID, "num_class %d out of range", num_class);
+  if (k < 2 || k > 64) return fail(VY_ERR_INVALID, "window k = %d: a window net has 2 ... 64 frames (k = 1: vy_net_create)", k);
+  if (join != VY_JOIN_MAX && join != VY_JOIN_MEAN)
+    return fail(VY_ERR_INVALID, "join %d: VY_JOIN_MAX (%d) or VY_JOIN_MEAN (%d)", join, VY_JOIN_MAX, VY_JOIN_MEAN);
+  vy_net* n = new vy_net();
+  n->num_class = num_class;
+  n->knobs = vy_knobs_read();
+  n->window_k = k;
+  n->window_join = join;
+  n->build();
+  *out = n;
+  return 0;
+}
+
+int vy_net_window(const vy_net* net, int32_t* k, int32_t* join) {
+  if (!net) return fail(VY_ERR_INVALID, "net is null");
+  if (k) *k = net->window_k;
+  if (join) *join = net->window_k ? net->window_join : 0;
   return 0;
 }
 
@@ -207,6 +238,8 @@ int vy_net_set_keep_activations(vy_net* net, int32_t keep) {
 int vy_net_set_conv_mode(vy_net* net, int32_t mode) {
   if (!net) return fail(VY_ERR_INVALID, "net is null");
   if (mode < VY_CONV_EXACT_FP32 || mode > VY_CONV_SPLIT_BF16X3_TRAIN) return fail(VY_ERR_INVALID, "conv mode %d", mode);
+  if (net->window_k && mode != VY_CONV_EXACT_FP32)
+    return fail(VY_ERR_UNSUPPORTED, "conv mode %d: a window net runs the exact fp32 kernels only", mode);
   if (mode != net->conv_mode) {
     net->conv_mode = mode;
     net->dev_ws = nullptr;  // the plan changed (the weight images live in the workspace): size and bind again
@@ -251,6 +284,7 @@ int vy_net_forward_infer(vy_net* net, const float* x, float* ids, float* scores,
 
 int vy_net_forward_features(vy_net* net, const float* x, float* f0, float* f1, float* f2, void* stream) {
   if (int rc = vy_check_kind(net, false, "vy_net_forward_features")) return rc;
+  if (int rc = refuse_window(net, "vy_net_forward_features")) return rc;
   if (!net || !x || !f0 || !f1 || !f2) {
     if (net) net->sk_dirty = true;
     return fail(VY_ERR_INVALID, "null argument");
@@ -311,6 +345,17 @@ int vy_net_read_activation(vy_net* net, const char* name, float* dst_dev, int32_
   if (dst_dev && net->planes_shared)
     return fail(VY_ERR_STATE, "activation planes are recycled in this plan: call vy_net_set_keep_activations(net, 1) "
                 "before sizing / binding the workspace to read intermediate activations");
+  if (const int i = vy_pool_tap(net, name); i >= 0) {
+    const vy_net::RouteSlot& r = net->routes[i];
+    const PlaneT& p = net->planes[r.plane];
+    if (c) *c = r.C;
+    if (h) *h = p.H;
+    if (w) *w = p.W;
+    if (dst_dev)
+      HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(r.plane), net->B, p.H, p.W, p.C, r.co, r.C, dst_dev,
+                                      static_cast<hipStream_t>(stream)));
+    return 0;
+  }
   for (const ConvT& cv : net->convs) {
     if (cv.name != name) continue;
     const PlaneT& p = net->planes[cv.out_plane];
@@ -318,8 +363,8 @@ int vy_net_read_activation(vy_net* net, const char* name, float* dst_dev, int32_
     if (h) *h = p.H;
     if (w) *w = p.W;
     if (dst_dev)
-      HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(cv.out_plane), net->B, p.H, p.W, p.C, cv.out_co, cv.cout,
-                                      dst_dev, static_cast<hipStream_t>(stream)));
+      HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(cv.out_plane), net->plane_batch(cv.out_plane), p.H, p.W, p.C, cv.out_co,
+                                      cv.cout, dst_dev, static_cast<hipStream_t>(stream)));
     return 0;
   }
   return fail(VY_ERR_INVALID, "no cell named '%s'", name);
@@ -328,6 +373,7 @@ int vy_net_read_activation(vy_net* net, const char* name, float* dst_dev, int32_
 int vy_net_profile_infer(vy_net* net, const float* x, float* ids, float* scores, float* bboxes,
                          vy_launch_stat* stats, int32_t* n, void* stream) {
   if (int rc = vy_check_kind(net, false, "vy_net_profile_infer")) return rc;
+  if (int rc = refuse_window(net, "vy_net_profile_infer")) return rc;
   if (!net || !stats || !n) return fail(VY_ERR_INVALID, "null argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int cap = *n;

@@ -38,6 +38,7 @@ struct PlaneT {
   int div = 1;       // spatial = input / div
   size_t off = 0;    // float offset in workspace (set by plan)
   int H = 0, W = 0;  // set by plan
+  int fm = 1;        // frames per batch entry: k for the stem and stage planes of a window net (B*k frames), 1 otherwise
 };
 
 struct ConvT {
@@ -134,6 +135,44 @@ struct vy_net {
   struct RouteSlot {
     int plane = -1, co = 0, C = 0;
   } routes[3];
+  // vy_net_create_window: a k-frame clip net (YOLOV3T, early join).  The stem and stages run on B*k frames; the three
+  // route cells write per-frame planes of their own (frame_routes, order stride 8, 16, 32), which window_pool
+  // (temporal.hip) pools over each clip into `routes` — the slices the heads read — once, after the last stage cell
+  int window_k = 0;  // 0: not a window net
+  int window_join = 0;
+  int frame_routes[3] = {-1, -1, -1};
+
+  // frames of the batch a plane holds / a conv runs on (its output plane's: a window net's backbone cells B*k)
+  int plane_batch(int p) const { return B * planes[p].fm; }
+  int conv_batch(const ConvT& c) const { return plane_batch(c.out_plane); }
+  // the pooling launch of a window net, forward (grads == nullptr) or backward (grads: the training gradient planes,
+  // same offsets as the activation planes)
+  WindowPoolArgs pool_args(float* grads) const {
+    WindowPoolArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = 3;
+    a.B = B;
+    a.k = window_k;
+    a.join = window_join;
+    for (int i = 0; i < 3; ++i) {
+      const PlaneT& fp = planes[frame_routes[i]];
+      const PlaneT& dp = planes[routes[i].plane];
+      PoolRoute& r = a.r[i];
+      r.src = plane_ptr(frame_routes[i]);
+      r.dst = plane_ptr(routes[i].plane);
+      if (grads) {
+        r.gsrc = grads + fp.off;
+        r.gdst = grads + dp.off;
+      }
+      r.H = dp.H;
+      r.W = dp.W;
+      r.C = routes[i].C;
+      r.s_cs = fp.C;
+      r.d_cs = dp.C;
+      r.d_co = routes[i].co;
+    }
+    return a;
+  }
 
   int add_param(const std::string& name, int kind, int ndim, const int* shape, int trainable, int backbone) {
     ParamT p;
@@ -155,10 +194,11 @@ struct vy_net {
     return (int)params.size() - 1;
   }
 
-  int add_plane(int C, int div) {
+  int add_plane(int C, int div, int fm = 1) {
     PlaneT p;
     p.C = C;
     p.div = div;
+    p.fm = fm;
     planes.push_back(p);
     return (int)planes.size() - 1;
   }
@@ -218,36 +258,45 @@ struct vy_net {
     };
     routes[0] = {cat2, 128, 256};
     routes[1] = {cat1, 256, 512};
-    int cur = add_plane(heads_only ? 1024 : 32, heads_only ? 32 : 1), cur_co = 0;
+    const int bfm = window_k ? window_k : 1;  // frames per batch entry of the backbone planes
+    int cur = add_plane(heads_only ? 1024 : 32, heads_only ? 32 : 1, bfm), cur_co = 0;
     if (!heads_only) add_conv(feat_name(feat++), -1, 0, 3, cur, 0, 32, 3, 1, true, 1);
     int div = 1;
     for (int st = 0; st < 5 && !heads_only; ++st) {
       const int ch = chans[st + 1];
       div *= 2;
-      int nxt = add_plane(ch, div);
+      int nxt = add_plane(ch, div, bfm);
       add_conv(feat_name(feat++), cur, cur_co, chans[st], nxt, 0, ch, 3, 2, true, 1);
       cur = nxt;
       cur_co = 0;
       for (int bi = 0; bi < layers[st]; ++bi) {
         const std::string pre = feat_name(feat++);
-        const int mid = add_plane(ch / 2, div);
+        const int mid = add_plane(ch / 2, div, bfm);
         add_conv(pre + ".body.0", cur, cur_co, ch, mid, 0, ch / 2, 1, 1, true, 1);
         // the last block of stages 0 and 1 (features[14], features[23]) writes the route straight
-        // into its concat plane
+        // into its concat plane (a window net: into a per-frame route plane, pooled into the concat plane later)
         int outp, outco = 0;
-        if (feat - 1 == 14) {
+        if (window_k && (feat - 1 == 14 || feat - 1 == 23)) {
+          outp = add_plane(ch, div, bfm);
+          frame_routes[feat - 1 == 14 ? 0 : 1] = outp;
+        } else if (feat - 1 == 14) {
           outp = cat2;
           outco = 128;
         } else if (feat - 1 == 23) {
           outp = cat1;
           outco = 256;
         } else {
-          outp = add_plane(ch, div);
+          outp = add_plane(ch, div, bfm);
         }
         add_conv(pre + ".body.1", mid, 0, ch / 2, outp, outco, ch, 3, 1, true, 1, cur, cur_co);
         cur = outp;
         cur_co = outco;
       }
+    }
+    if (window_k) {  // the heads read the pooled stride-32 route
+      frame_routes[2] = cur;
+      cur = add_plane(1024, 32);
+      cur_co = 0;
     }
     routes[2] = {cur, cur_co, 1024};
     // ---- heads, deep -> shallow (yolo3.py:1013-1054, 1126-1177)
@@ -335,8 +384,10 @@ struct vy_net {
       if (c.res_plane >= 0 && ci > last[c.res_plane]) last[c.res_plane] = ci;
     }
     for (int i = 0; i < 3; ++i) last[head_plane[i]] = kLive;  // read by decode + NMS (and vy_net_read_head) afterwards
-    if (heads_only)  // the routes are imported before the first conv: those planes own their storage
+    if (heads_only || window_k)  // the routes are imported / pooled outside the conv list: those planes own their storage
       for (int i = 0; i < 3; ++i) def[routes[i].plane] = -1;
+    if (window_k)  // ... and window_pool reads the per-frame routes after the last stage cell
+      for (int i = 0; i < 3; ++i) last[frame_routes[i]] = kLive;
     std::vector<int> order(np);
     for (int i = 0; i < np; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return def[a] < def[b]; });
@@ -349,7 +400,8 @@ struct vy_net {
       // stage-1 bottleneck planes)
       const bool is_head = p == head_plane[0] || p == head_plane[1] || p == head_plane[2];
       for (int o : owners)
-        if (!is_head && planes[o].C == planes[p].C && planes[o].div == planes[p].div && free_at[o] < def[p]) {
+        if (!is_head && planes[o].C == planes[p].C && planes[o].div == planes[p].div && planes[o].fm == planes[p].fm &&
+            free_at[o] < def[p]) {
           take = o;
           break;
         }
@@ -385,7 +437,7 @@ struct vy_net {
       const int runs = c.is_stem ? 1 : vy_conv_runs(c.k * c.k, (c.cin + 31) >> 5);
       if (runs < 2) continue;
       const PlaneT& op = planes[c.out_plane];
-      const long long Mo = (long long)b * cdiv(h, op.div) * cdiv(w, op.div);
+      const long long Mo = (long long)b * op.fm * cdiv(h, op.div) * cdiv(w, op.div);
       ck_b = std::max(ck_b, vy_conv_chunk_scratch_bytes(Mo, c.cout, runs));
     }
     off += al(ck_b);
@@ -407,7 +459,7 @@ struct vy_net {
       const int ph = cdiv(h, p.div), pw = cdiv(w, p.div);
       if ((size_t)slot[i] == i) {  // owns its storage (owners come first in definition order: see plane_slots)
         slot_off[i] = fl;
-        fl += ((size_t)b * (ph + 2) * (pw + 2) * p.C + 63) & ~(size_t)63;
+        fl += ((size_t)b * p.fm * (ph + 2) * (pw + 2) * p.C + 63) & ~(size_t)63;
       }
     }
     for (size_t i = 0; i < planes.size() && commit; ++i) {
@@ -462,10 +514,11 @@ struct vy_net {
     a.out = plane_ptr(c.out_plane);
     a.stats = nullptr;
     const int Ho = (ip.H + c.stride - 1) / c.stride, Wo = (ip.W + c.stride - 1) / c.stride;
-    a.B = B;
+    const int Bf = conv_batch(c);
+    a.B = Bf;
     a.LH = Ho;
     a.LW = Wo;
-    a.M = B * Ho * Wo;
+    a.M = Bf * Ho * Wo;
     a.a_Hp = ip.H + 2;
     a.a_Wp = ip.W + 2;
     a.a_cs = ip.C;
@@ -598,7 +651,7 @@ struct vy_net {
     // The fold runs EVERY forward (the caller owns the parameter buffer and may have written to it) — inside the stem launch
     // when that has a block per layer (StemArgs), in a launch of its own otherwise
     const bool fold_in_stem = !convs.empty() && convs[0].is_stem && convs[0].scale_off == folds[0].scale &&
-                              vy_stem_can_fold(B, H, W, (int)folds.size(), cus);
+                              vy_stem_can_fold(conv_batch(convs[0]), H, W, (int)folds.size(), cus);
     if (!fold_in_stem) {
       hook("bn_fold", 0.0, 0.0, true);
       HIP_TRY(vy_launch_bn_fold(dev_params, fd, (int)folds.size(), 1024, 1e-5f, s));
@@ -622,16 +675,25 @@ struct vy_net {
       HIP_TRY(vy_launch_route_import(route_args(routes_in), s));
       hook("route_import", 0.0, 0.0, false);
     }
+    bool pooled = false;
     for (const ConvT& c : convs) {
       if (routes_out && !params[c.p_weight].info.backbone) break;
+      if (window_k && !pooled && !params[c.p_weight].info.backbone) {  // the stages are done: pool the routes
+        const WindowPoolArgs pa = pool_args(nullptr);
+        hook("window_pool", 0.0, 0.0, true);
+        HIP_TRY(vy_launch_window_pool(pa, s));
+        hook("window_pool", 0.0, 0.0, false);
+        pooled = true;
+      }
       if (c.is_stem) {
+        const int Bs = conv_batch(c);
         StemArgs a;
         a.x = x;
         a.w = dev_params + params[c.p_weight].info.offset;
         a.scale = dev_params + c.scale_off;
         a.shift = dev_params + c.shift_off;
         a.out = plane_ptr(c.out_plane);
-        a.B = B;
+        a.B = Bs;
         a.H = H;
         a.W = W;
         a.Cout = c.cout;
@@ -645,8 +707,8 @@ struct vy_net {
           a.fold_stem = 0;
           a.fold_eps = 1e-5f;
         }
-        const double fl = 2.0 * B * H * W * 27.0 * c.cout;
-        const double by = 4.0 * B * H * W * (3.0 + c.cout);
+        const double fl = 2.0 * Bs * H * W * 27.0 * c.cout;
+        const double by = 4.0 * Bs * H * W * (3.0 + c.cout);
         hook(c.name.c_str(), fl, by, true);
         HIP_TRY(vy_launch_stem(a, s));
         hook(c.name.c_str(), fl, by, false);
@@ -662,7 +724,7 @@ struct vy_net {
           continue;
         }
         const double fl = 2.0 * a.M * (double)a.N * a.ntaps * a.Kc;
-        const double by = 4.0 * ((double)B * (a.a_Hp - 2) * (a.a_Wp - 2) * a.Kc + (double)a.M * a.N * a.ups * a.ups +
+        const double by = 4.0 * ((double)a.B * (a.a_Hp - 2) * (a.a_Wp - 2) * a.Kc + (double)a.M * a.N * a.ups * a.ups +
                                  (double)a.N * a.ntaps * a.Kc + (a.res ? (double)a.M * a.N : 0.0));
         char nm[96];
         if (a.w_wino && vy_conv_wino_pays(a)) {
@@ -713,3 +775,8 @@ struct vy_net {
   }
 };
 
+// the pooled route `name` = "pool.<i>" of a window net (the taps of vy_net_read_activation / read_grad_activation): 0..2, or -1
+inline int vy_pool_tap(const vy_net* net, const char* name) {
+  if (!net->window_k || strncmp(name, "pool.", 5) != 0 || name[5] < '0' || name[5] > '2' || name[6]) return -1;
+  return name[5] - '0';
+}

@@ -164,7 +164,7 @@ size_t train_plan(vy_net* net, int b, int h, int w, bool commit) {
   }
   // gradient planes mirror the activation planes
   size_t gfl = 0;
-  for (auto& p : net->planes) gfl += ((size_t)b * (h / p.div + 2) * (w / p.div + 2) * p.C + 63) & ~(size_t)63;
+  for (auto& p : net->planes) gfl += ((size_t)b * p.fm * (h / p.div + 2) * (w / p.div + 2) * p.C + 63) & ~(size_t)63;
   const size_t g_off = off;
   off += al256(gfl * sizeof(float));
   // z planes: one per BN conv
@@ -176,29 +176,30 @@ size_t train_plan(vy_net* net, int b, int h, int w, bool commit) {
     const ConvT& c = net->convs[i];
     const int div_in = c.is_stem ? 1 : net->planes[c.in_plane].div;
     const int Ho = h / div_in / c.stride, Wo = w / div_in / c.stride;
-    const long long M = (long long)b * Ho * Wo;
+    const int bc = b * net->planes[c.out_plane].fm;  // frames the conv runs on (a window net's backbone: b * k)
+    const long long M = (long long)bc * Ho * Wo;
     if (c.p_gamma >= 0) {
       z[i].C = c.cout;
       z[i].H = Ho;
       z[i].W = Wo;
       z[i].off = zfl;
-      zfl += ((size_t)b * (Ho + 2) * (Wo + 2) * c.cout + 63) & ~(size_t)63;
+      zfl += ((size_t)bc * (Ho + 2) * (Wo + 2) * c.cout + 63) & ~(size_t)63;
       save[i] = sfl;
       sfl += 2 * (size_t)((c.cout + 63) & ~63);
       // partials: forward stats, backward sums
       const size_t tiles_m = (size_t)((M + 31) / 32);  // per-tile statistics rows, sized for 32-row tiles (every tile has more)
-      size_t pf = 2 * (c.is_stem ? (size_t)vy_stem_blocks(b, h, w) * 64 : tiles_m * 2 * c.cout);  // doubles
+      size_t pf = 2 * (c.is_stem ? (size_t)vy_stem_blocks(bc, h, w) * 64 : tiles_m * 2 * c.cout);  // doubles
       const size_t chunks = (size_t)((M + kBwdChunk - 1) / kBwdChunk);
       if (chunks * 2 * c.cout > pf) pf = chunks * 2 * c.cout;
       // bn_bwd_reduce chunks by image rows, not by 64 pixels: ceil(B*Ho / rows_per_chunk) partial rows of 2*C
       // floats — more than the pixel-chunk bound on maps narrower than 64 pixels (W = 32 training shapes)
       {
-        const int rpc = vy_bn_bwd_rows_per_chunk(b, Ho, c.cout);
-        const size_t bwd_rows = (size_t)(((long long)b * Ho + rpc - 1) / rpc);
+        const int rpc = vy_bn_bwd_rows_per_chunk(bc, Ho, c.cout);
+        const size_t bwd_rows = (size_t)(((long long)bc * Ho + rpc - 1) / rpc);
         if (bwd_rows * 2 * c.cout > pf) pf = bwd_rows * 2 * c.cout;
       }
       if (c.is_stem) {
-        const size_t sw = (size_t)vy_stem_wgrad_blocks(b, h, w) * 864;
+        const size_t sw = (size_t)vy_stem_wgrad_blocks(bc, h, w) * 864;
         if (sw > pf) pf = sw;
       }
       if (pf > part) part = pf;
@@ -292,7 +293,7 @@ size_t train_plan(vy_net* net, int b, int h, int w, bool commit) {
     const ConvT& c = net->convs[i];
     if (c.is_stem) continue;
     const int div_in = net->planes[c.in_plane].div;
-    const long long M = (long long)b * (h / div_in / c.stride) * (w / div_in / c.stride);
+    const long long M = (long long)b * net->planes[c.out_plane].fm * (h / div_in / c.stride) * (w / div_in / c.stride);
     tab_off[i] = off;
     off += al256(vy_wgrad_table_entries(M) * 8);
   }
@@ -428,11 +429,16 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
 // routes (heads-only nets): the three route tensors, imported into their planes in front of the first conv
 int forward_train(const TrainCtx& c, const float* x, const float* const* routes) {
   vy_net* net = c.net;
-  const int B = net->B;
   if (int rc = refresh_split_images(c)) return rc;
   if (routes) HIP_TRY(vy_launch_route_import(net->route_args(routes), c.s));
+  bool pooled = false;
   for (size_t ci = 0; ci < net->convs.size(); ++ci) {
     const ConvT& cv = net->convs[ci];
+    const int B = net->conv_batch(cv);  // (a window net's backbone cells: B * k frames)
+    if (net->window_k && !pooled && !net->params[cv.p_weight].info.backbone) {  // the stages are done: pool the routes
+      HIP_TRY(vy_launch_window_pool(net->pool_args(nullptr), c.s));
+      pooled = true;
+    }
     if (cv.p_gamma < 0) {  // prediction conv: bias, no BN
       const ConvArgs a = net->conv_args(cv);
       if (!g_labels_done) g_labels.note(net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
@@ -548,7 +554,7 @@ BwdDgrad make_dgrad(const TrainCtx& c, const ConvT& cv, const float* dzp, int dz
   a.res = addend;
   a.r_cs = add_cs;
   a.r_co = add_co;
-  a.B = net->B;
+  a.B = net->conv_batch(cv);
   a.a_Hp = dz_H + 2;
   a.a_Wp = dz_W + 2;
   a.a_cs = dz_cs;
@@ -580,7 +586,7 @@ BwdDgrad make_dgrad(const TrainCtx& c, const ConvT& cv, const float* dzp, int dz
   if (cv.stride == 1) {
     a.LH = ip.H;
     a.LW = ip.W;
-    a.M = net->B * ip.H * ip.W;
+    a.M = a.B * ip.H * ip.W;
     a.o_s = 1;
     a.o_oy = a.o_ox = 1;
     a.ntaps = cv.k * cv.k;
@@ -597,7 +603,7 @@ BwdDgrad make_dgrad(const TrainCtx& c, const ConvT& cv, const float* dzp, int dz
         ConvArgs q = a;
         q.LH = ip.H / 2;
         q.LW = ip.W / 2;
-        q.M = net->B * q.LH * q.LW;
+        q.M = a.B * q.LH * q.LW;
         q.o_s = 2;
         q.o_oy = 1 + py;
         q.o_ox = 1 + px;
@@ -628,10 +634,10 @@ int launch_wgrad(const TrainCtx& c, size_t ci, const float* dzp, int dz_cs, int 
   w.a = net->plane_ptr(cv.in_plane);
   w.slabs = c.slabs();
   w.zero = c.zero();
-  w.B = net->B;
+  w.B = net->conv_batch(cv);
   w.Ho = Ho;
   w.Wo = Wo;
-  w.M = net->B * Ho * Wo;
+  w.M = w.B * Ho * Wo;
   w.z_cs = dz_cs;
   w.Cout = cv.cout;
   w.a_Hp = ip.H + 2;
@@ -667,12 +673,13 @@ int build_wgrad_tables(const TrainCtx& c) {
     if (cv.is_stem) continue;
     const PlaneT& ip = net->planes[cv.in_plane];
     const int Ho = ip.H / cv.stride, Wo = ip.W / cv.stride;
-    const long long M = (long long)net->B * Ho * Wo;
+    const int Bc = net->conv_batch(cv);
+    const long long M = (long long)Bc * Ho * Wo;
     const int z_cs = cv.p_gamma >= 0 ? c.t->z[ci].C : net->planes[cv.out_plane].C;
     if (M >= (1ll << 31) - 64) return fail(VY_ERR_UNSUPPORTED, "'%s': 2^31 output pixels or more in one batch", cv.name.c_str());
     // (offsets are relative to each split's first pixel: planes of 4 GiB and more are fine — 608x608 past batch 84)
     HIP_TRY(vy_launch_wgrad_table(net->dev_ws + c.t->tab_off[ci], (int)M, (int)vy_wgrad_table_entries(M), Ho, Wo, z_cs,
-                                  ip.H + 2, ip.W + 2, ip.C, cv.stride, net->B, c.t->kps[ci], c.s));
+                                  ip.H + 2, ip.W + 2, ip.C, cv.stride, Bc, c.t->kps[ci], c.s));
   }
   c.t->tabs_built = true;
   return 0;
@@ -680,7 +687,6 @@ int build_wgrad_tables(const TrainCtx& c) {
 
 int backward_train(const TrainCtx& c, const float* x) {
   vy_net* net = c.net;
-  const int B = net->B;
   if (!c.t->tabs_built)
     if (int rc = build_wgrad_tables(c)) return rc;
   // which channel ranges of each gradient plane already hold a contribution
@@ -731,12 +737,21 @@ int backward_train(const TrainCtx& c, const float* x) {
     return 0;
   };
   int cur_bucket = 0;
+  bool unpooled = false;
   for (int ci = (int)net->convs.size() - 1; ci >= 0; --ci) {
     const ConvT& cv = net->convs[ci];
+    const int B = net->conv_batch(cv);  // (a window net's backbone cells: B * k frames)
     const int bk = bucket_of(cv);
     if (bk != cur_bucket) {
       if (int rc = emit_bucket(cur_bucket)) return rc;
       cur_bucket = bk;
+    }
+    if (net->window_k && !unpooled && net->params[cv.p_weight].info.backbone) {
+      // the heads are done: the pooled routes' gradients (cat2 / cat1 route channels, the pooled stride-32 plane) are
+      // final.  window_pool_bwd writes the per-frame route planes' gradients; stages.1.0 / stages.2.0 accumulate onto them
+      HIP_TRY(vy_launch_window_pool_bwd(net->pool_args(reinterpret_cast<float*>(net->dev_ws + c.t->g_off)), c.s));
+      for (int i = 0; i < 3; ++i) touched[net->frame_routes[i]].push_back({0, net->planes[net->frame_routes[i]].C});
+      unpooled = true;
     }
     const float* dzp;
     int dz_cs, dzH, dzW;
@@ -1149,10 +1164,17 @@ int vy_net_read_grad_activation(vy_net* net, const char* name, float* dst_dev, v
   VyTrain* t = net->train;
   if (!t || !t->grads) return fail(VY_ERR_STATE, "training workspace not bound");
   TrainCtx c{net, t, static_cast<hipStream_t>(stream)};
+  if (const int i = vy_pool_tap(net, name); i >= 0) {
+    const vy_net::RouteSlot& r = net->routes[i];
+    const PlaneT& p = net->planes[r.plane];
+    HIP_TRY(vy_launch_plane_to_nchw(c.gplane(r.plane), net->B, p.H, p.W, p.C, r.co, r.C, dst_dev, c.s));
+    return 0;
+  }
   for (const ConvT& cv : net->convs) {
     if (cv.name != name) continue;
     const PlaneT& p = net->planes[cv.out_plane];
-    HIP_TRY(vy_launch_plane_to_nchw(c.gplane(cv.out_plane), net->B, p.H, p.W, p.C, cv.out_co, cv.cout, dst_dev, c.s));
+    HIP_TRY(vy_launch_plane_to_nchw(c.gplane(cv.out_plane), net->plane_batch(cv.out_plane), p.H, p.W, p.C, cv.out_co,
+                                    cv.cout, dst_dev, c.s));
     return 0;
   }
   return fail(VY_ERR_INVALID, "no cell named '%s'", name);
@@ -1168,7 +1190,7 @@ int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* d
     const ConvT& cv = net->convs[ci];
     if (cv.name != name) continue;
     const bool bn = cv.p_gamma >= 0;
-    int32_t d[4] = {net->B, cv.cout, 0, 0};
+    int32_t d[4] = {net->conv_batch(cv), cv.cout, 0, 0};
     const float* src = nullptr;
     int cs = 0, co = 0;
     switch (which) {
@@ -1236,7 +1258,7 @@ int vy_net_train_conv_plan(const vy_net* net, int32_t i, int32_t* wgrad_splits, 
   }
   if (wgrad_splits) *wgrad_splits = sp;
   if (wgrad_k_per_split) *wgrad_k_per_split = kps;
-  if (bn_bwd_rows_per_chunk) *bn_bwd_rows_per_chunk = cv.p_gamma >= 0 ? vy_bn_bwd_rows_per_chunk(t->B, t->z[i].H, cv.cout) : 0;
+  if (bn_bwd_rows_per_chunk) *bn_bwd_rows_per_chunk = cv.p_gamma >= 0 ? vy_bn_bwd_rows_per_chunk(t->B * net->planes[cv.out_plane].fm, t->z[i].H, cv.cout) : 0;
   return 0;
 }
 

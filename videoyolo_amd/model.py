@@ -120,7 +120,7 @@ class YOLOV3(object):
         self._classes = list(classes)
         self._lib = _lib.load()
         h = ctypes.c_void_p()
-        _lib.check(getattr(self._lib, self._CREATE)(len(self._classes), ctypes.byref(h)))
+        _lib.check(self._create_handle(len(self._classes), ctypes.byref(h)))
         self._h = h
         self.nms_thresh, self.nms_topk, self.post_nms = nms_thresh, nms_topk, post_nms
         self._ignore_iou_thresh = ignore_iou_thresh
@@ -158,6 +158,26 @@ class YOLOV3(object):
         self.two_stream_batch = int(os.environ.get("VY_TWO_STREAM_BATCH", "0"))
         self._twin = None
         _lib.check(self._lib.vy_net_set_nms(self._h, nms_thresh, nms_topk, post_nms))
+
+    def _create_handle(self, num_class, out):
+        return getattr(self._lib, self._CREATE)(num_class, out)
+
+    def _ctor_kwargs(self):
+        """Constructor arguments beyond the common ones that a copy of this net needs (reset_class, deepcopy)."""
+        return {}
+
+    def _bhw(self, x):
+        """(batch, height, width) of an input checked by ``_as_input``."""
+        return x.shape[0], x.shape[2], x.shape[3]
+
+    def _tap_batch(self, name):
+        """Leading dimension of the tap of cell `name` in the bound plan."""
+        return self._plan[0]
+
+    @staticmethod
+    def _key(name):
+        """Structural library name -> this model's parameter key (the same, for every net but the window net)."""
+        return name
 
     def __del__(self):
         try:
@@ -346,7 +366,7 @@ class YOLOV3(object):
         else:
             from . import mxparams
             loaded = mxparams.load(filename)
-        mapped = darknet53_to_stage_names(loaded)
+        mapped = {self._key(k): v for k, v in darknet53_to_stage_names(loaded).items()}
         want = [k for k, p in self._params.items() if p.backbone]
         missing = [k for k in want if k not in mapped]
         if missing:
@@ -488,7 +508,7 @@ class YOLOV3(object):
         old_vals = {p.name: self._get_param(p.index) for p in self._params.values()}
         device = self._device
         fresh = type(self)(classes, self.nms_thresh, self.nms_topk, self.post_nms, self._pos_iou_thresh,
-                       self._ignore_iou_thresh, self._norm_layer, self._norm_kwargs, self._alloc_size)
+                       self._ignore_iou_thresh, self._norm_layer, self._norm_kwargs, self._alloc_size, **self._ctor_kwargs())
         new_vals = _init.uniform_params(fresh.param_table())  # prediction.initialize(), yolo3.py:110
         old_np, new_np = 5 + len(old_classes), 5 + len(classes)
         for name in new_vals:
@@ -529,7 +549,7 @@ class YOLOV3(object):
         """``copy.deepcopy(net)`` (transforms.py:190): a host-side copy, not bound to a device."""
         twin = type(self)(self._classes, self.nms_thresh, self.nms_topk, self.post_nms, self._pos_iou_thresh,
                       self._ignore_iou_thresh, self._norm_layer, copy.deepcopy(self._norm_kwargs, memo),
-                      self._alloc_size)
+                      self._alloc_size, **self._ctor_kwargs())
         if self._all_set():
             for p in self._params.values():
                 twin._params[p.name].set_data(self._get_param(p.index))
@@ -607,7 +627,7 @@ class YOLOV3(object):
         produced by ``autograd.backward(...)`` / ``net.backward()`` afterwards."""
         torch = _torch()
         x = self._as_input(x)
-        b, _, h, w = x.shape
+        b, h, w = self._bhw(x)
         tg = [self._dev(t) for t in (gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)]
         m = int(tg[0].shape[1])
         from . import parallel
@@ -680,7 +700,7 @@ class YOLOV3(object):
         shape (numpy), which is all the reference's consumer reads."""
         torch = _torch()
         x = self._as_input(x)
-        b, _, h, w = x.shape
+        b, h, w = self._bhw(x)
         anchors, offsets, fms = [], [], []
         table = [[116, 90, 156, 198, 373, 326], [30, 61, 62, 45, 59, 119], [10, 13, 16, 30, 33, 23]]
         for i, s in enumerate((32, 16, 8)):
@@ -732,7 +752,7 @@ class YOLOV3(object):
         c, h, w = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         _lib.check(self._lib.vy_net_read_activation(self._h, name.encode(), None, ctypes.byref(c),
                                                     ctypes.byref(h), ctypes.byref(w), None))
-        out = torch.empty((self._plan[0], c.value, h.value, w.value), dtype=torch.float32, device=self._device)
+        out = torch.empty((self._tap_batch(name), c.value, h.value, w.value), dtype=torch.float32, device=self._device)
         with torch.cuda.device(self._device):
             _lib.check(self._lib.vy_net_read_grad_activation(self._h, name.encode(),
                                                              ctypes.c_void_p(out.data_ptr()), self._stream()))
@@ -786,7 +806,7 @@ class YOLOV3(object):
         (ids (B,R,1), scores (B,R,1), bboxes (B,R,4)) fp32 device tensors, R = post_nms."""
         torch = _torch()
         x = self._as_input(x)
-        b, _, h, w = x.shape
+        b, h, w = self._bhw(x)
         with torch.cuda.device(self._device):
             replanned = self._plan is None or self._plan[:3] != (b, h, w)
             self._ensure_plan(b, h, w)
@@ -922,7 +942,7 @@ class YOLOV3(object):
         c, h, w = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         _lib.check(self._lib.vy_net_read_activation(self._h, name.encode(), None, ctypes.byref(c),
                                                     ctypes.byref(h), ctypes.byref(w), None))
-        out = torch.empty((self._plan[0], c.value, h.value, w.value), dtype=torch.float32, device=self._device)
+        out = torch.empty((self._tap_batch(name), c.value, h.value, w.value), dtype=torch.float32, device=self._device)
         with torch.cuda.device(self._device):
             _lib.check(self._lib.vy_net_read_activation(self._h, name.encode(), ctypes.c_void_p(out.data_ptr()),
                                                         None, None, None, self._stream()))
@@ -1099,6 +1119,93 @@ class YOLOV3NoBackbone(YOLOV3):
 YOLOV3_noback = YOLOV3NoBackbone
 
 
+class YOLOV3Window(YOLOV3):
+    """``YOLOV3T`` with ``k > 1`` and ``k_join_pos='early'`` (yolo3.py:1016-1121): a detector over k-frame clips.  Input
+    is ``(B, k, 3, H, W)``; the Darknet-53 stages run on the ``B * k`` frames (``TimeDistributed``, frame t of clip b is
+    frame ``b * k + t``), each route is pooled over the clip's k frames (``TemporalPooling`` 'direct': max or mean) and
+    the ordinary heads run on the B clips.  Targets, losses and detections are per clip.  BatchNorm normalises over the
+    ``B * k`` frames in the stages and over the B clips in the heads.  The parameters are the single-frame net's tensors;
+    stage keys carry ``TimeDistributed``'s child, ``stages.N.model.<rest>``, as in the reference's files."""
+
+    _CREATE = "vy_net_create_window"
+    _JOINS = {"max": _lib.VY_JOIN_MAX, "mean": _lib.VY_JOIN_MEAN}
+    _STAGE_RE = re.compile(r"^(stages\.\d+)\.(?!model\.)")
+
+    def __init__(self, classes, *args, k=2, k_join_type="max", **kwargs):
+        if int(k) < 2 or k_join_type not in self._JOINS:
+            raise ValueError("window net: k >= 2 and k_join_type in %s (got k=%r, %r)" % (sorted(self._JOINS), k, k_join_type))
+        self._k, self._join_type = int(k), k_join_type
+        super().__init__(classes, *args, **kwargs)
+        renamed = ParameterDict(self)
+        for p in self._params.values():
+            p.name = self._key(p.name)
+            renamed[p.name] = p
+        self._params = renamed
+        self.two_stream_batch = 0
+
+    @property
+    def k(self):
+        return self._k
+
+    @property
+    def k_join_type(self):
+        return self._join_type
+
+    def _create_handle(self, num_class, out):
+        return self._lib.vy_net_create_window(num_class, self._k, self._JOINS[self._join_type], out)
+
+    def _ctor_kwargs(self):
+        return dict(k=self._k, k_join_type=self._join_type)
+
+    @classmethod
+    def _key(cls, name):
+        return cls._STAGE_RE.sub(r"\1.model.", name)
+
+    def _bhw(self, x):
+        return x.shape[0], x.shape[3], x.shape[4]
+
+    def _tap_batch(self, name):
+        return self._plan[0] * (self._k if name.startswith("stages.") else 1)
+
+    def set_parameters(self, arrays, allow_missing=False, ignore_extra=False):
+        """As ``YOLOV3.set_parameters``; stage keys may also come in the single-frame form (``stages.N.<rest>``)."""
+        super().set_parameters(OrderedDict((self._key(k), v) for k, v in arrays.items()), allow_missing=allow_missing,
+                               ignore_extra=ignore_extra)
+
+    def load_parameters(self, filename, ctx=None, allow_missing=False, ignore_extra=False):
+        """Both containers, as ``YOLOV3.load_parameters``.  Also accepts a single-frame (k = 1) file: its stage keys
+        lack ``.model.`` but name the same tensors, so a window model starts from a trained single-frame one this way."""
+        super().load_parameters(filename, ctx=ctx, allow_missing=allow_missing, ignore_extra=ignore_extra)
+
+    def _as_input(self, x):
+        shape = tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
+        if len(shape) != 5 or shape[1] != self._k or shape[2] != 3:
+            raise ValueError("a window net takes (B, k, 3, H, W) clips with k = %d, got %s" % (self._k, shape))
+        torch = _torch()
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x, np.float32))
+        return super()._as_input(x.reshape((-1,) + shape[2:])).view(shape)
+
+    def _single_rank(self):
+        from . import parallel
+        if parallel.world_size() > 1:
+            raise NotImplementedError("multi-rank training of a window net (yolo3_darknet53 with k > 1) is not supported: "
+                                      "train it on one rank")
+
+    def forward_train(self, x, *args):
+        self._single_rank()
+        return super().forward_train(x, *args)
+
+    def forward_train_mode(self, x):
+        self._single_rank()
+        return super().forward_train_mode(x)
+
+    def _not_windowed(self, *args, **kwargs):
+        raise NotImplementedError("not available on a window net (yolo3_darknet53 with k > 1): use a single-frame net")
+
+    extract_features = detect_two_streams = profile = _not_windowed
+
+
 def _darknet_roots(root=None):
     """Where ``get_model_file('darknet53', root=...)`` would look: the reference's default root
     (three_darknet.py:234 ``models/definitions/darknet/weights``), gluoncv's cache, VY_MODEL_ROOT."""
@@ -1153,15 +1260,18 @@ def yolo3_darknet53(classes, pretrained_base=True, norm_layer=BatchNorm, norm_kw
                     corr_pos=None, corr_d=None, motion_stream=None, add_type=None, agnostic=False,
                     new_model=False, hierarchical=(1, 1, 1, 1, 1), h_join_type=None, temporal=False,
                     t_out=False, **kwargs):
-    """Drop-in for models/definitions/yolo/wrappers.py:9-110 on the default (k=1) branch.
+    """Drop-in for models/definitions/yolo/wrappers.py:9-110 on the default (k=1) branch and on the early-join window
+    branch: ``k >= 2`` with ``k_join_type`` 'max' or 'mean' and ``k_join_pos='early'`` returns a ``YOLOV3Window``.
 
-    Only the arguments that select the hot path are honoured; a non-default value for any
-    temporal / two-stream / hierarchical option raises NotImplementedError (out of scope).
+    Only the arguments that select those paths are honoured; any other temporal / two-stream / hierarchical option
+    raises NotImplementedError (out of scope).
     ``pretrained_base=True`` cannot be honoured offline (gluoncv model zoo download,
     three_darknet.py:262): it warns and leaves the backbone to ``initialize()`` / ``load_parameters``.
     """
+    window = k not in (None, 1) and int(k) >= 2 and k_join_type in YOLOV3Window._JOINS and k_join_pos == 'early'
     unsupported = {
-        "k": k not in (None, 1), "k_join_type": k_join_type is not None, "k_join_pos": k_join_pos is not None,
+        "k": k not in (None, 1) and not window, "k_join_type": k_join_type is not None and not window,
+        "k_join_pos": k_join_pos is not None and not window,
         "block_conv_type": str(block_conv_type) != '2', "rnn_pos": rnn_pos is not None,
         "corr_pos": corr_pos is not None, "corr_d": corr_d is not None, "motion_stream": motion_stream is not None,
         "add_type": add_type is not None, "agnostic": bool(agnostic), "new_model": bool(new_model),
@@ -1173,7 +1283,11 @@ def yolo3_darknet53(classes, pretrained_base=True, norm_layer=BatchNorm, norm_kw
             "yolo3_darknet53: option(s) %s select a temporal/two-stream research variant outside the "
             "MI355X hot path" % ", ".join(bad))
     root = kwargs.pop("root", None)
-    net = YOLOV3(classes, norm_layer=norm_layer, norm_kwargs=norm_kwargs, **kwargs)
+    if window:
+        net = YOLOV3Window(classes, norm_layer=norm_layer, norm_kwargs=norm_kwargs, k=int(k), k_join_type=k_join_type,
+                           **kwargs)
+    else:
+        net = YOLOV3(classes, norm_layer=norm_layer, norm_kwargs=norm_kwargs, **kwargs)
     if pretrained_base:
         # three_darknet.py:262-264: net.load_parameters(get_model_file('darknet53', tag=pretrained, root=root)).  There is
         # no model-zoo download here: the file must already be where gluoncv would have cached it.
