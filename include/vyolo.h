@@ -227,6 +227,38 @@ int vy_net_forward_features(vy_net* net, const float* x, float* f0, float* f1, f
 int vy_net_forward_infer_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* ids, float* scores,
                                 float* bboxes, int32_t* keep_idx, void* stream);
 
+/* Video plans: a window net (vy_net_create_window) run over a video, the backbone once per frame.
+ * detect_yolo3.py with --window k,step builds one k-frame clip per frame of a video (datasets/imgnetvid.py:480-506: centred
+ * on the frame, frames `step` apart, clamped at the ends), so consecutive clips share frames and the clip entries above run
+ * Darknet-53 on each frame up to k times.  With the early join a frame's three routes do not depend on its clip, so a video
+ * plan keeps them in a ring of `ring` slots in the workspace: vy_net_video_push runs the backbone on `frames` single
+ * frames and stores their routes in the slots the caller names, vy_net_video_detect pools `clips` windows out of the slots
+ * the caller names and runs the heads on them — bit for bit what vy_net_forward_infer gives for the materialised clips.
+ * The library does not track which frame sits in which slot: that is the caller's bookkeeping.  frames, clips, ring >= 1;
+ * frames <= VY_VIDEO_TABLE_MAX and clips * k <= VY_VIDEO_TABLE_MAX (the tables travel in the kernel arguments: no copy,
+ * no synchronisation inside a call).  Every entry: VY_ERR_STATE on a net that is not a window net, doing nothing. */
+#define VY_VIDEO_TABLE_MAX 512
+/* Bytes of the workspace of a video plan (the ring included); 0 plus vy_last_error on a bad request. */
+size_t vy_net_video_workspace_bytes(const vy_net* net, int32_t frames, int32_t clips, int32_t ring, int32_t height,
+                                    int32_t width);
+/* Binds (and zeroes, borders included, as vy_net_bind_workspace) a video plan.  The net then serves the video entries and
+ * the taps only: vy_net_forward_infer and the training entries return VY_ERR_STATE until vy_net_bind_workspace /
+ * vy_net_bind_train bind a clip plan again — which in turn ends the video plan; the ring's contents do not survive. */
+int vy_net_bind_video(vy_net* net, void* dev_ws, size_t bytes, int32_t frames, int32_t clips, int32_t ring, int32_t height,
+                      int32_t width, void* stream);
+/* The per-frame half of detect_yolo3.py's loop: stem and stages on x (frames, 3, height, width), then the three routes of
+ * frame f go to ring slot slots[f] (host array of `frames` entries in [-1, ring); -1: the frame is padding and is not
+ * stored).  No head conv, no detection tail.  Asynchronous on `stream`; `slots` is consumed before the call returns. */
+int vy_net_video_push(vy_net* net, const float* x, const int32_t* slots, void* stream);
+/* The per-clip half: for clip b the routes of slots table[b * k + t], t < k (host array, entries in [0, ring); a slot may
+ * repeat: clamped ends of a video), are pooled in that order (TemporalPooling 'direct', layers.py:193-204) and the heads
+ * and the detection tail run on the `clips` clips.  Outputs as vy_net_forward_infer at batch = clips.  Asynchronous. */
+int vy_net_video_detect(vy_net* net, const int32_t* table, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
+                        void* stream);
+/* Test tap: the three routes held in `slot` as NCHW (1, 256, ..), (1, 512, ..), (1, 1024, ..) — what
+ * vy_net_forward_features exports for that frame (extract_base_features.py:120-160). */
+int vy_net_video_read_slot(vy_net* net, int32_t slot, float* f0, float* f1, float* f2, void* stream);
+
 /* The detection tail ALONE, on caller-supplied prediction-conv outputs: YOLOOutputV3.hybrid_forward's inference branch
  * (yolo3.py:158-197: decode, x C tile, class-major rows) for the three scales, their concat (yolo3.py:1195), box_nms and
  * the slice (yolo3.py:1197-1206) — what `net.yolo_outputs[i](pred)` + `F.contrib.box_nms` compute in the reference.

@@ -1,0 +1,21 @@
+"""-m gpu: examples/detect_video.py runs end to end — the reference's windowed detect loop (detect_yolo3.py --window k,step)
+on a synthetic video through the public surface only; the script itself asserts that the video path and the clip path
+return the same bits."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
+
+
+def test_detect_video_example():
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    p = subprocess.run([sys.executable, "examples/detect_video.py", "--frames", "8", "--k", "3", "--size", "416",
+                        "--frames-per-step", "4"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       timeout=600, universal_newlines=True)
+    assert p.returncode == 0, p.stdout[-3000:]
+    assert "8 frames, k = 3" in p.stdout and "bit for bit" in p.stdout
+    assert "video path" in p.stdout and "clip path" in p.stdout and "frames/s" in p.stdout

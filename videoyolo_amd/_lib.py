@@ -10,6 +10,7 @@ VY_MAX_TOPK = 1024
 VY_CONV_EXACT_FP32, VY_CONV_SPLIT_BF16X3, VY_CONV_SPLIT_BF16X3_TRAIN = 0, 1, 2
 VY_TAP_Z, VY_TAP_BN, VY_TAP_GRAD_PADDED, VY_TAP_INPUT_PADDED = 0, 1, 2, 3
 VY_JOIN_MAX, VY_JOIN_MEAN = 0, 1
+VY_VIDEO_TABLE_MAX = 512
 
 
 class VyError(RuntimeError):
@@ -105,6 +106,12 @@ SIGNATURES.update({
     # k-frame clip nets (yolo3_darknet53 with k > 1, early join)
     "vy_net_create_window": (ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(_vp)]),
     "vy_net_window": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    # video plans of a window net: the backbone once per frame, routes in a ring (videoyolo_amd/video.py)
+    "vy_net_video_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
+    "vy_net_bind_video": (ctypes.c_int, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vy_net_video_push": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i32), _vp]),
+    "vy_net_video_detect": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), _vp, _vp, _vp, _vp, _vp]),
+    "vy_net_video_read_slot": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
 })
 
 _lib = None

@@ -212,6 +212,40 @@ hipError_t vy_launch_window_pool(const WindowPoolArgs& a, hipStream_t s);
 // backward: gsrc = gdst / k (mean), gdst where src == dst and 0 elsewhere (max)
 hipError_t vy_launch_window_pool_bwd(const WindowPoolArgs& a, hipStream_t s);
 
+// ---- per-frame route ring of a video plan (video.hip): the three routes of single frames, kept in R slots and pooled by
+// window.  A slot is the three routes back to back, tight NHWC without borders (only ring_pool and the test tap read it):
+// route i of slot s starts at ring + s * slot_stride (+ the sizes of the routes before it).  Frame -> slot and clip -> slots
+// tables travel in the kernel arguments: at most VY_RING_TABLE_MAX entries per launch.
+#define VY_RING_TABLE_MAX 512
+struct RingRoute {
+  float* plane;        // push: per-frame route plane (F frames, border included), channel stride s_cs, route at channel 0 (read)
+  float* ring;         // route i of slot 0
+  float* dst;          // pool: pooled plane (B clips, border included), channel stride d_cs, route at channel d_co (written)
+  int H, W, C, s_cs, d_cs, d_co;
+};
+struct RingPushArgs {
+  RingRoute r[3];
+  int n;                   // routes in this launch (1..3)
+  int F;                   // frames the backbone ran
+  int R;                   // slots of the ring
+  long long slot_stride;   // floats per slot
+  long long item_end[3];   // filled by the launcher
+  int slot[VY_RING_TABLE_MAX];  // frame f -> slot, -1: not stored
+};
+struct RingPoolArgs {
+  RingRoute r[3];
+  int n, B, k, join, R;    // routes, clips, frames per clip, VY_JOIN_*, slots of the ring
+  long long slot_stride;
+  long long item_end[3];
+  int table[VY_RING_TABLE_MAX];  // clip b, position t -> slot table[b * k + t]
+};
+// interiors of the per-frame route planes -> ring slots
+hipError_t vy_launch_ring_push(const RingPushArgs& a, hipStream_t s);
+// window_pool's arithmetic over the slots the table names, into the planes the heads read (interior, route channels only)
+hipError_t vy_launch_ring_pool(const RingPoolArgs& a, hipStream_t s);
+// test tap: route i of one slot (tight NHWC, H x W x C) as dense CHW
+hipError_t vy_launch_ring_read(const float* slot_route, int H, int W, int C, float* chw, hipStream_t s);
+
 // ---- detection tail -------------------------------------------------------------------------
 #define VY_NMS_MAX_TOPK 1024
 struct HeadView {

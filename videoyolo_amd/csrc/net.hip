@@ -310,9 +310,100 @@ int vy_net_forward_infer_routes(vy_net* net, const float* f0, const float* f1, c
                                          in, nullptr));
 }
 
+// ---- video plans
+// VY_ERR_STATE unless `net` is a window net: the video entries serve nothing else
+static int need_window(const vy_net* net, const char* entry) {
+  if (!net) return fail(VY_ERR_INVALID, "net is null");
+  if (!net->window_k)
+    return fail(VY_ERR_STATE, "%s takes a window net (vy_net_create_window): this net has no temporal window", entry);
+  return 0;
+}
+
+static int check_video_shape(const vy_net* net, int32_t frames, int32_t clips, int32_t ring, int32_t h, int32_t w) {
+  if (frames < 1 || clips < 1 || ring < 1)
+    return fail(VY_ERR_INVALID, "video plan: frames %d, clips %d, ring %d must all be >= 1", frames, clips, ring);
+  if (frames > VY_VIDEO_TABLE_MAX || (long long)clips * net->window_k > VY_VIDEO_TABLE_MAX)
+    return fail(VY_ERR_INVALID, "video plan: frames %d and clips * k = %d x %d must not exceed %d table entries (they travel "
+                "in the kernel arguments)", frames, clips, net->window_k, VY_VIDEO_TABLE_MAX);
+  if (net->conv_mode != VY_CONV_EXACT_FP32) return fail(VY_ERR_UNSUPPORTED, "a video plan runs the exact fp32 kernels only");
+  return check_shape(clips, h, w);
+}
+
+size_t vy_net_video_workspace_bytes(const vy_net* net, int32_t frames, int32_t clips, int32_t ring, int32_t height,
+                                    int32_t width) {
+  if (need_window(net, "vy_net_video_workspace_bytes") || check_video_shape(net, frames, clips, ring, height, width)) return 0;
+  const_cast<vy_net*>(net)->resolve_cus();
+  return const_cast<vy_net*>(net)->plan(clips, height, width, false, net->keep_activations, frames, ring);
+}
+
+int vy_net_bind_video(vy_net* net, void* dev_ws, size_t bytes, int32_t frames, int32_t clips, int32_t ring, int32_t height,
+                      int32_t width, void* stream) {
+  if (int rc = need_window(net, "vy_net_bind_video")) return rc;
+  if (!dev_ws) return fail(VY_ERR_INVALID, "null argument");
+  if (int rc = check_video_shape(net, frames, clips, ring, height, width)) return rc;
+  if (int rc = net->bind_cus(dev_ws)) return rc;
+  const size_t need = net->plan(clips, height, width, false, net->keep_activations, frames, ring);
+  if (bytes < need) return fail(VY_ERR_INVALID, "video workspace too small: %zu < %zu bytes", bytes, need);
+  net->plan(clips, height, width, true, net->keep_activations, frames, ring);
+  net->dev_ws = static_cast<unsigned char*>(dev_ws);
+  net->ws_bytes = bytes;
+  net->fold_uploaded = false;
+  HIP_TRY(hipMemsetAsync(dev_ws, 0, need, static_cast<hipStream_t>(stream)));
+  net->sk_dirty = false;
+  net->sk_ok = vy_sk_verify_topology(reinterpret_cast<unsigned*>(net->dev_ws + net->sk_off), static_cast<hipStream_t>(stream)) != 0;
+  return 0;
+}
+
+// a video entry's common checks, before anything is launched: window net, pointers, bound for video, table entries in [lo, R)
+static int video_checks(vy_net* net, const char* entry, bool ptrs_ok, const int32_t* table, int n_of_k, int lo) {
+  if (!ptrs_ok) return fail(VY_ERR_INVALID, "null argument");
+  if (int rc = net->check_ready(true)) return rc;
+  if (!net->video_F) return fail(VY_ERR_STATE, "%s: the net is not bound for video (vy_net_bind_video)", entry);
+  const int n = n_of_k < 0 ? net->video_F : n_of_k * net->B * net->window_k;
+  for (int i = 0; i < n; ++i)
+    if (table[i] < lo || table[i] >= net->video_R)
+      return fail(VY_ERR_INVALID, "%s: entry %d of the slot table is %d, outside [%d, %d)", entry, i, table[i], lo, net->video_R);
+  return 0;
+}
+static int video_ready(vy_net* net, const char* entry, bool ptrs_ok, const int32_t* table, int n_of_k, int lo) {
+  if (int rc = need_window(net, entry)) return rc;
+  const int rc = video_checks(net, entry, ptrs_ok, table, n_of_k, lo);
+  if (rc) net->sk_dirty = true;  // (any error return: see vy_net::sk_dirty)
+  return rc;
+}
+
+int vy_net_video_push(vy_net* net, const float* x, const int32_t* slots, void* stream) {
+  if (int rc = video_ready(net, "vy_net_video_push", x && slots, slots, -1, -1)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = net->sk_begin(s)) return rc;
+  return net->sk_end(net->forward<false>(x, nullptr, nullptr, nullptr, nullptr, s, [](const char*, double, double, bool) {},
+                                         nullptr, nullptr, slots, nullptr));
+}
+
+int vy_net_video_detect(vy_net* net, const int32_t* table, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
+                        void* stream) {
+  if (int rc = video_ready(net, "vy_net_video_detect", table && ids && scores && bboxes, table, 1, 0)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = net->sk_begin(s)) return rc;
+  return net->sk_end(net->forward<false>(nullptr, ids, scores, bboxes, keep_idx, s, [](const char*, double, double, bool) {},
+                                         nullptr, nullptr, nullptr, table));
+}
+
+int vy_net_video_read_slot(vy_net* net, int32_t slot, float* f0, float* f1, float* f2, void* stream) {
+  if (int rc = video_ready(net, "vy_net_video_read_slot", f0 && f1 && f2, &slot, 0, 0)) return rc;
+  if (slot < 0 || slot >= net->video_R) return fail(VY_ERR_INVALID, "slot %d outside [0, %d)", slot, net->video_R);
+  RingRoute rr[3];
+  net->ring_routes(rr);
+  float* const out[3] = {f0, f1, f2};
+  for (int i = 0; i < 3; ++i)
+    HIP_TRY(vy_launch_ring_read(rr[i].ring + slot * net->ring_slot_floats, rr[i].H, rr[i].W, rr[i].C, out[i],
+                                static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
 int vy_net_read_head(vy_net* net, int32_t i, float* dst_dev, void* stream) {
   if (!net || !dst_dev || i < 0 || i > 2) return fail(VY_ERR_INVALID, "bad argument");
-  if (int rc = net->check_ready()) return rc;
+  if (int rc = net->check_ready(true)) return rc;
   const PlaneT& p = net->planes[net->head_plane[i]];
   HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(net->head_plane[i]), net->B, p.H, p.W, p.C, 0,
                                   3 * (5 + net->num_class), dst_dev, static_cast<hipStream_t>(stream)));
@@ -341,7 +432,7 @@ int vy_net_detect_heads(vy_net* net, const float* head0, const float* head1, con
 int vy_net_read_activation(vy_net* net, const char* name, float* dst_dev, int32_t* c, int32_t* h, int32_t* w,
                            void* stream) {
   if (!net || !name) return fail(VY_ERR_INVALID, "bad argument");
-  if (int rc = net->check_ready()) return rc;
+  if (int rc = net->check_ready(true)) return rc;
   if (dst_dev && net->planes_shared)
     return fail(VY_ERR_STATE, "activation planes are recycled in this plan: call vy_net_set_keep_activations(net, 1) "
                 "before sizing / binding the workspace to read intermediate activations");

@@ -142,8 +142,17 @@ struct vy_net {
   int window_join = 0;
   int frame_routes[3] = {-1, -1, -1};
 
+  // video plan of a window net (vy_net_bind_video): the stem and stage planes hold video_F single frames, the
+  // planes from the pooled routes on hold B clips, and behind the planes lies a ring of video_R slots of per-frame routes
+  // (video.hip).  0: the clip plan (or no plan); every plan(commit) sets them, so binding either way switches the net over
+  int video_F = 0, video_R = 0;
+  size_t ring_off = 0;            // byte offset of the ring in the workspace
+  long long ring_slot_floats = 0;  // floats per slot
+
+  // frames a stem / stage plane of a window net holds for `b` clips: b*k of the clip plan, `frames` of a video plan
+  static int backbone_frames(const PlaneT& p, int b, int frames) { return frames && p.fm > 1 ? frames : b * p.fm; }
   // frames of the batch a plane holds / a conv runs on (its output plane's: a window net's backbone cells B*k)
-  int plane_batch(int p) const { return B * planes[p].fm; }
+  int plane_batch(int p) const { return backbone_frames(planes[p], B, video_F); }
   int conv_batch(const ConvT& c) const { return plane_batch(c.out_plane); }
   // the pooling launch of a window net, forward (grads == nullptr) or backward (grads: the training gradient planes,
   // same offsets as the activation planes)
@@ -172,6 +181,35 @@ struct vy_net {
       r.d_co = routes[i].co;
     }
     return a;
+  }
+
+  // floats of one ring slot at input size (h, w): the three routes, tight, rounded to 256 B
+  long long slot_floats(int h, int w) const {
+    long long fl = 0;
+    for (int i = 0; i < 3; ++i) {
+      const int d = planes[routes[i].plane].div;
+      fl += (long long)((h + d - 1) / d) * ((w + d - 1) / d) * routes[i].C;
+    }
+    return (fl + 63) & ~63ll;
+  }
+  // the three routes of a video plan's launches (video.hip): per-frame planes, ring, pooled planes
+  void ring_routes(RingRoute* rr) const {
+    float* ring = reinterpret_cast<float*>(dev_ws + ring_off);
+    for (int i = 0; i < 3; ++i) {
+      const PlaneT& fp = planes[frame_routes[i]];
+      const PlaneT& dp = planes[routes[i].plane];
+      RingRoute& r = rr[i];
+      r.plane = plane_ptr(frame_routes[i]);
+      r.ring = ring;
+      r.dst = plane_ptr(routes[i].plane);
+      r.H = dp.H;
+      r.W = dp.W;
+      r.C = routes[i].C;
+      r.s_cs = fp.C;
+      r.d_cs = dp.C;
+      r.d_co = routes[i].co;
+      ring += (long long)r.H * r.W * r.C;
+    }
   }
 
   int add_param(const std::string& name, int kind, int ndim, const int* shape, int trainable, int backbone) {
@@ -415,7 +453,9 @@ struct vy_net {
     return slot;
   }
 
-  size_t plan(int b, int h, int w, bool commit, bool keep_all) {
+  // frames / ring: a video plan (vy_net_bind_video) — `frames` single frames in the stem and stage planes instead of b*k,
+  // b clips from the pooled routes on, and `ring` route slots behind the planes; 0, 0: the clip plan
+  size_t plan(int b, int h, int w, bool commit, bool keep_all, int frames = 0, int ring = 0) {
     size_t off = 0;
     const size_t fold_off = off;
     off += al(sizeof(FoldDesc) * folds.size());
@@ -437,7 +477,7 @@ struct vy_net {
       const int runs = c.is_stem ? 1 : vy_conv_runs(c.k * c.k, (c.cin + 31) >> 5);
       if (runs < 2) continue;
       const PlaneT& op = planes[c.out_plane];
-      const long long Mo = (long long)b * op.fm * cdiv(h, op.div) * cdiv(w, op.div);
+      const long long Mo = (long long)backbone_frames(op, b, frames) * cdiv(h, op.div) * cdiv(w, op.div);
       ck_b = std::max(ck_b, vy_conv_chunk_scratch_bytes(Mo, c.cout, runs));
     }
     off += al(ck_b);
@@ -459,7 +499,7 @@ struct vy_net {
       const int ph = cdiv(h, p.div), pw = cdiv(w, p.div);
       if ((size_t)slot[i] == i) {  // owns its storage (owners come first in definition order: see plane_slots)
         slot_off[i] = fl;
-        fl += ((size_t)b * p.fm * (ph + 2) * (pw + 2) * p.C + 63) & ~(size_t)63;
+        fl += ((size_t)backbone_frames(p, b, frames) * (ph + 2) * (pw + 2) * p.C + 63) & ~(size_t)63;
       }
     }
     for (size_t i = 0; i < planes.size() && commit; ++i) {
@@ -469,7 +509,13 @@ struct vy_net {
       p.off = slot_off[slot[i]];
     }
     off += fl * sizeof(float);
+    const size_t ring_o = al(off);
+    if (ring > 0) off = ring_o + (size_t)ring * slot_floats(h, w) * sizeof(float);
     if (commit) {
+      video_F = ring > 0 ? frames : 0;
+      video_R = ring > 0 ? ring : 0;
+      ring_off = ring_o;
+      ring_slot_floats = ring > 0 ? slot_floats(h, w) : 0;
       planes_shared = !keep_all;
       fold_desc_off = fold_off;
       det_scratch_off = det_off;
@@ -488,9 +534,13 @@ struct vy_net {
 
   float* plane_ptr(int i) const { return reinterpret_cast<float*>(dev_ws + planes_off) + planes[i].off; }
 
-  int check_ready() const {
+  // video_ok: the entry also serves a net bound for video (the video entries, the taps); every other entry runs the clip plan
+  int check_ready(bool video_ok = false) const {
     if (!dev_params) return fail(VY_ERR_STATE, "parameters not bound (vy_net_bind_params)");
     if (!dev_ws) return fail(VY_ERR_STATE, "workspace not bound (vy_net_bind_workspace)");
+    if (video_F && !video_ok)
+      return fail(VY_ERR_STATE, "the net is bound for video (vy_net_bind_video): bind a clip plan again with "
+                  "vy_net_bind_workspace / vy_net_bind_train");
     return 0;
   }
 
@@ -637,10 +687,15 @@ struct vy_net {
   // kLabels = false: the hook is a no-op (vy_net_forward_infer) and the per-launch labels are not built
   // routes_in (heads-only nets): the three route tensors, imported in front of the first conv (x unused);
   // routes_out (full nets): stop after the backbone and export the routes there — no head conv, no detection tail
+  // video plans (the caller has checked the tables): push_slots = stop after the backbone and ring_push its video_F frames'
+  // routes there; pool_table = skip the backbone, ring_pool the B clips out of the ring, then heads and detection tail
   template <bool kLabels = true, typename Hook>
   int forward(const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx, hipStream_t s,
-              Hook&& hook, const float* const* routes_in = nullptr, float* const* routes_out = nullptr) {
-    if (int rc = check_ready()) return rc;
+              Hook&& hook, const float* const* routes_in = nullptr, float* const* routes_out = nullptr,
+              const int32_t* push_slots = nullptr, const int32_t* pool_table = nullptr) {
+    const bool video = push_slots || pool_table;
+    if (int rc = check_ready(video)) return rc;
+    if (video && !video_F) return fail(VY_ERR_STATE, "the net is not bound for video (vy_net_bind_video)");
     const bool nms_on = nms_thresh > 0.f && nms_thresh < 1.f;  // yolo3.py:1197
     FoldDesc* fd = reinterpret_cast<FoldDesc*>(dev_ws + fold_desc_off);
     if (!fold_uploaded) {
@@ -650,7 +705,7 @@ struct vy_net {
     }
     // The fold runs EVERY forward (the caller owns the parameter buffer and may have written to it) — inside the stem launch
     // when that has a block per layer (StemArgs), in a launch of its own otherwise
-    const bool fold_in_stem = !convs.empty() && convs[0].is_stem && convs[0].scale_off == folds[0].scale &&
+    const bool fold_in_stem = !pool_table && !convs.empty() && convs[0].is_stem && convs[0].scale_off == folds[0].scale &&
                               vy_stem_can_fold(conv_batch(convs[0]), H, W, (int)folds.size(), cus);
     if (!fold_in_stem) {
       hook("bn_fold", 0.0, 0.0, true);
@@ -677,12 +732,29 @@ struct vy_net {
     }
     bool pooled = false;
     for (const ConvT& c : convs) {
-      if (routes_out && !params[c.p_weight].info.backbone) break;
+      if ((routes_out || push_slots) && !params[c.p_weight].info.backbone) break;
+      if (pool_table && params[c.p_weight].info.backbone) continue;
       if (window_k && !pooled && !params[c.p_weight].info.backbone) {  // the stages are done: pool the routes
-        const WindowPoolArgs pa = pool_args(nullptr);
-        hook("window_pool", 0.0, 0.0, true);
-        HIP_TRY(vy_launch_window_pool(pa, s));
-        hook("window_pool", 0.0, 0.0, false);
+        if (pool_table) {
+          RingPoolArgs ra;
+          memset(&ra, 0, sizeof ra);
+          ring_routes(ra.r);
+          ra.n = 3;
+          ra.B = B;
+          ra.k = window_k;
+          ra.join = window_join;
+          ra.R = video_R;
+          ra.slot_stride = ring_slot_floats;
+          memcpy(ra.table, pool_table, sizeof(int32_t) * B * window_k);
+          hook("ring_pool", 0.0, 4.0 * (window_k + 1) * B * ring_slot_floats, true);
+          HIP_TRY(vy_launch_ring_pool(ra, s));
+          hook("ring_pool", 0.0, 4.0 * (window_k + 1) * B * ring_slot_floats, false);
+        } else {
+          const WindowPoolArgs pa = pool_args(nullptr);
+          hook("window_pool", 0.0, 0.0, true);
+          HIP_TRY(vy_launch_window_pool(pa, s));
+          hook("window_pool", 0.0, 0.0, false);
+        }
         pooled = true;
       }
       if (c.is_stem) {
@@ -754,6 +826,20 @@ struct vy_net {
         HIP_TRY(vy_launch_conv_igemm(a, s));
         hook(nm, fl, by, false);
       }
+    }
+    if (push_slots) {
+      RingPushArgs ra;
+      memset(&ra, 0, sizeof ra);
+      ring_routes(ra.r);
+      ra.n = 3;
+      ra.F = video_F;
+      ra.R = video_R;
+      ra.slot_stride = ring_slot_floats;
+      memcpy(ra.slot, push_slots, sizeof(int32_t) * video_F);
+      hook("ring_push", 0.0, 8.0 * video_F * ring_slot_floats, true);
+      HIP_TRY(vy_launch_ring_push(ra, s));
+      hook("ring_push", 0.0, 8.0 * video_F * ring_slot_floats, false);
+      return 0;
     }
     if (routes_out) {
       const float* const out[3] = {routes_out[0], routes_out[1], routes_out[2]};

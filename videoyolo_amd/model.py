@@ -1200,6 +1200,36 @@ class YOLOV3Window(YOLOV3):
         self._single_rank()
         return super().forward_train_mode(x)
 
+    # ---- over a whole video: the backbone once per frame (videoyolo_amd/video.py)
+    _video = None  # the VideoSession that holds the workspace binding, if one does
+
+    def _ensure_plan(self, b, h, w, train=False):
+        if self._video is not None:  # a session took the binding: this call binds its own plan again
+            self._video, self._plan = None, None
+        super()._ensure_plan(b, h, w, train=train)
+
+    def keep_activations(self, keep=True):
+        self._video = None  # the library dropped the binding: a session opened earlier binds again (or raises)
+        super().keep_activations(keep)
+
+    def video(self, frames_per_step=16, step=1, ring=None):
+        """A ``VideoSession`` on this net: ``session.push(frames)`` / ``session.flush()`` detect a video frame by frame, with
+        the clips of the reference's windowed detect loop (``detect_yolo3.py --window k,step``; the table is
+        ``video.window_indices``) but Darknet-53 run once per frame.  ``frames_per_step``: frames per backbone call (and
+        clips per heads call); ``ring``: slots of the route ring, default ``video.min_ring(k, step, frames_per_step)``; a
+        smaller one raises ``ValueError``.  The session takes the workspace binding: see ``VideoSession``."""
+        from .video import VideoSession
+        return VideoSession(self, frames_per_step=frames_per_step, step=step, ring=ring)
+
+    def detect_video(self, frames, step=1, frames_per_step=16, return_index=False):
+        """``(ids, scores, bboxes)`` for the ``(T, 3, H, W)`` video ``frames``, one row-block per frame: bit for bit
+        ``net(frames[window_indices(T, k, step)])``, any T >= 1."""
+        import torch
+        session = self.video(frames_per_step=frames_per_step, step=step)
+        head = session.push(frames, return_index=return_index)
+        tail = session.flush(return_index=return_index)
+        return tuple(torch.cat([a, b], 0) for a, b in zip(head, tail))
+
     def _not_windowed(self, *args, **kwargs):
         raise NotImplementedError("not available on a window net (yolo3_darknet53 with k > 1): use a single-frame net")
 
