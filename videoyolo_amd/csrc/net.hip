@@ -42,6 +42,56 @@ static int refuse_window(const vy_net* net, const char* entry) {
   return 0;
 }
 
+// the three constructors: the checks they share, and the net itself (k = 0: not a window net)
+static int check_create(int32_t num_class, vy_net** out) {
+  if (!out) return fail(VY_ERR_INVALID, "out is null");
+  if (num_class < 1 || num_class > 1000) return fail(VY_ERR_INVALID, "num_class %d out of range", num_class);
+  return 0;
+}
+static vy_net* create(int32_t num_class, bool heads_only, int32_t k, int32_t join) {
+  vy_net* n = new vy_net();
+  n->num_class = num_class;
+  n->knobs = vy_knobs_read();
+  n->heads_only = heads_only;
+  n->window_k = k;
+  n->window_join = join;
+  n->build();
+  return n;
+}
+
+// ---- the inference entries: each is the sequence of vy_net steps it documents in vyolo.h, inside one shared frame
+static NoHook plain;  // of every entry but vy_net_profile_infer, which has its own
+// The frame's checks, before anything is launched: arguments, bound, and for a video entry (named) bound for video
+static int entry_ready(vy_net* net, bool args_ok, const char* video_entry) {
+  int rc = 0;
+  if (!net || !args_ok) rc = fail(VY_ERR_INVALID, "null argument");
+  if (rc == 0) rc = net->check_ready(video_entry != nullptr);
+  if (rc == 0 && video_entry && !net->video_F)
+    rc = fail(VY_ERR_STATE, "%s: the net is not bound for video (vy_net_bind_video)", video_entry);
+  if (rc && net) net->sk_dirty = true;  // (any error return: see vy_net::sk_dirty)
+  return rc;
+}
+// ... then the stream-K flags zeroed if an earlier call left them dirty, and `run(stream)`: the launches
+template <typename Run>
+static int run_entry(vy_net* net, bool args_ok, const char* video_entry, void* stream, Run&& run) {
+  VY_TRY(entry_ready(net, args_ok, video_entry));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int rc = net->sk_begin(s);
+  if (rc == 0) rc = run(s);
+  return net->sk_end(rc);
+}
+
+// vy_net_forward_infer and vy_net_profile_infer: stem and stages, the pooling of a window net, heads, detection tail
+template <typename Hook>
+static int infer_sequence(vy_net* net, const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
+                          hipStream_t s, Hook& hook) {
+  VY_TRY(net->prepare(s, hook, true));
+  VY_TRY(net->run_cells(0, net->n_backbone, x, s, hook));
+  if (net->window_k) VY_TRY(net->window_pool(s, hook));
+  VY_TRY(net->run_cells(net->n_backbone, (int)net->convs.size(), nullptr, s, hook));
+  return net->detect_tail(ids, scores, bboxes, keep_idx, s, hook);
+}
+
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -49,41 +99,23 @@ const char* vy_last_error(void) { return g_err.c_str(); }
 const char* vy_version(void) { return "vyolo 1 gfx950"; }
 
 int vy_net_create(int32_t num_class, vy_net** out) {
-  if (!out) return fail(VY_ERR_INVALID, "out is null");
-  if (num_class < 1 || num_class > 1000) return fail(VY_ERR_INVALID, "num_class %d out of range", num_class);
-  vy_net* n = new vy_net();
-  n->num_class = num_class;
-  n->knobs = vy_knobs_read();
-  n->build();
-  *out = n;
+  VY_TRY(check_create(num_class, out));
+  *out = create(num_class, false, 0, 0);
   return 0;
 }
 
 int vy_net_create_heads(int32_t num_class, vy_net** out) {
-  if (!out) return fail(VY_ERR_INVALID, "out is null");
-  if (num_class < 1 || num_class > 1000) return fail(VY_ERR_INVALID, "num_class %d out of range", num_class);
-  vy_net* n = new vy_net();
-  n->num_class = num_class;
-  n->knobs = vy_knobs_read();
-  n->heads_only = true;
-  n->build();
-  *out = n;
+  VY_TRY(check_create(num_class, out));
+  *out = create(num_class, true, 0, 0);
   return 0;
 }
 
 int vy_net_create_window(int32_t num_class, int32_t k, int32_t join, vy_net** out) {
-  if (!out) return fail(VY_ERR_INVALID, "out is null");
-  if (num_class < 1 || num_class > 1000) return fail(VY_ERR_INVALID, "num_class %d out of range", num_class);
+  VY_TRY(check_create(num_class, out));
   if (k < 2 || k > 64) return fail(VY_ERR_INVALID, "window k = %d: a window net has 2 ... 64 frames (k = 1: vy_net_create)", k);
   if (join != VY_JOIN_MAX && join != VY_JOIN_MEAN)
     return fail(VY_ERR_INVALID, "join %d: VY_JOIN_MAX (%d) or VY_JOIN_MEAN (%d)", join, VY_JOIN_MAX, VY_JOIN_MEAN);
-  vy_net* n = new vy_net();
-  n->num_class = num_class;
-  n->knobs = vy_knobs_read();
-  n->window_k = k;
-  n->window_join = join;
-  n->build();
-  *out = n;
+  *out = create(num_class, false, k, join);
   return 0;
 }
 
@@ -208,21 +240,21 @@ size_t vy_net_workspace_bytes(const vy_net* net, int32_t batch, int32_t height, 
   return const_cast<vy_net*>(net)->plan(batch, height, width, false, net->keep_activations);
 }
 
+// size the plan, check the caller's workspace against it, commit it and take the workspace.  frames, ring: vy_net::plan
+static int bind_plan(vy_net* net, void* dev_ws, size_t bytes, int b, int h, int w, int frames, int ring, const char* what,
+                     void* stream) {
+  VY_TRY(net->bind_cus(dev_ws));
+  const size_t need = net->plan(b, h, w, false, net->keep_activations, frames, ring);
+  if (bytes < need) return fail(VY_ERR_INVALID, "%sworkspace too small: %zu < %zu bytes", what, bytes, need);
+  net->plan(b, h, w, true, net->keep_activations, frames, ring);
+  return net->commit_bind(dev_ws, bytes, need, static_cast<hipStream_t>(stream));
+}
+
 int vy_net_bind_workspace(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, int32_t height, int32_t width,
                           void* stream) {
   if (!net || !dev_ws) return fail(VY_ERR_INVALID, "null argument");
-  if (int rc = check_shape(batch, height, width)) return rc;
-  if (int rc = net->bind_cus(dev_ws)) return rc;
-  const size_t need = net->plan(batch, height, width, false, net->keep_activations);
-  if (bytes < need) return fail(VY_ERR_INVALID, "workspace too small: %zu < %zu bytes", bytes, need);
-  net->plan(batch, height, width, true, net->keep_activations);
-  net->dev_ws = static_cast<unsigned char*>(dev_ws);
-  net->ws_bytes = bytes;
-  net->fold_uploaded = false;
-  HIP_TRY(hipMemsetAsync(dev_ws, 0, need, static_cast<hipStream_t>(stream)));
-  net->sk_dirty = false;
-  net->sk_ok = vy_sk_verify_topology(reinterpret_cast<unsigned*>(net->dev_ws + net->sk_off), static_cast<hipStream_t>(stream)) != 0;
-  return 0;
+  VY_TRY(check_shape(batch, height, width));
+  return bind_plan(net, dev_ws, bytes, batch, height, width, 0, 0, "", stream);
 }
 
 int vy_net_set_keep_activations(vy_net* net, int32_t keep) {
@@ -274,40 +306,33 @@ int32_t vy_net_num_anchors(const vy_net* net) {
 
 int vy_net_forward_infer(vy_net* net, const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
                          void* stream) {
-  if (int rc = vy_check_kind(net, false, "vy_net_forward_infer")) return rc;
-  if (net && (!x || !ids || !scores || !bboxes)) net->sk_dirty = true;  // (any error return: see vy_net::sk_dirty)
-  if (!net || !x || !ids || !scores || !bboxes) return fail(VY_ERR_INVALID, "null argument");
-  if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
-  return net->sk_end(net->forward<false>(x, ids, scores, bboxes, keep_idx, static_cast<hipStream_t>(stream),
-                                         [](const char*, double, double, bool) {}));
+  VY_TRY(vy_check_kind(net, false, "vy_net_forward_infer"));
+  return run_entry(net, x && ids && scores && bboxes, nullptr, stream, [&](hipStream_t s) {
+    return infer_sequence(net, x, ids, scores, bboxes, keep_idx, s, plain);
+  });
 }
 
 int vy_net_forward_features(vy_net* net, const float* x, float* f0, float* f1, float* f2, void* stream) {
-  if (int rc = vy_check_kind(net, false, "vy_net_forward_features")) return rc;
-  if (int rc = refuse_window(net, "vy_net_forward_features")) return rc;
-  if (!net || !x || !f0 || !f1 || !f2) {
-    if (net) net->sk_dirty = true;
-    return fail(VY_ERR_INVALID, "null argument");
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = net->sk_begin(s)) return rc;
-  float* const out[3] = {f0, f1, f2};
-  return net->sk_end(net->forward<false>(x, nullptr, nullptr, nullptr, nullptr, s, [](const char*, double, double, bool) {},
-                                         nullptr, out));
+  VY_TRY(vy_check_kind(net, false, "vy_net_forward_features"));
+  VY_TRY(refuse_window(net, "vy_net_forward_features"));
+  return run_entry(net, x && f0 && f1 && f2, nullptr, stream, [&](hipStream_t s) {
+    const float* const out[3] = {f0, f1, f2};
+    VY_TRY(net->prepare(s, plain, true));
+    VY_TRY(net->run_cells(0, net->n_backbone, x, s, plain));
+    return net->route_export(out, s, plain);
+  });
 }
 
 int vy_net_forward_infer_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* ids, float* scores,
                                 float* bboxes, int32_t* keep_idx, void* stream) {
-  if (int rc = vy_check_kind(net, true, "vy_net_forward_infer_routes")) return rc;
-  if (!net || !f0 || !f1 || !f2 || !ids || !scores || !bboxes) {
-    if (net) net->sk_dirty = true;
-    return fail(VY_ERR_INVALID, "null argument");
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = net->sk_begin(s)) return rc;
-  const float* const in[3] = {f0, f1, f2};
-  return net->sk_end(net->forward<false>(nullptr, ids, scores, bboxes, keep_idx, s, [](const char*, double, double, bool) {},
-                                         in, nullptr));
+  VY_TRY(vy_check_kind(net, true, "vy_net_forward_infer_routes"));
+  return run_entry(net, f0 && f1 && f2 && ids && scores && bboxes, nullptr, stream, [&](hipStream_t s) {
+    const float* const in[3] = {f0, f1, f2};
+    VY_TRY(net->prepare(s, plain, false));
+    VY_TRY(net->route_import(in, s, plain));
+    VY_TRY(net->run_cells(0, (int)net->convs.size(), nullptr, s, plain));
+    return net->detect_tail(ids, scores, bboxes, keep_idx, s, plain);
+  });
 }
 
 // ---- video plans
@@ -338,59 +363,45 @@ size_t vy_net_video_workspace_bytes(const vy_net* net, int32_t frames, int32_t c
 
 int vy_net_bind_video(vy_net* net, void* dev_ws, size_t bytes, int32_t frames, int32_t clips, int32_t ring, int32_t height,
                       int32_t width, void* stream) {
-  if (int rc = need_window(net, "vy_net_bind_video")) return rc;
+  VY_TRY(need_window(net, "vy_net_bind_video"));
   if (!dev_ws) return fail(VY_ERR_INVALID, "null argument");
-  if (int rc = check_video_shape(net, frames, clips, ring, height, width)) return rc;
-  if (int rc = net->bind_cus(dev_ws)) return rc;
-  const size_t need = net->plan(clips, height, width, false, net->keep_activations, frames, ring);
-  if (bytes < need) return fail(VY_ERR_INVALID, "video workspace too small: %zu < %zu bytes", bytes, need);
-  net->plan(clips, height, width, true, net->keep_activations, frames, ring);
-  net->dev_ws = static_cast<unsigned char*>(dev_ws);
-  net->ws_bytes = bytes;
-  net->fold_uploaded = false;
-  HIP_TRY(hipMemsetAsync(dev_ws, 0, need, static_cast<hipStream_t>(stream)));
-  net->sk_dirty = false;
-  net->sk_ok = vy_sk_verify_topology(reinterpret_cast<unsigned*>(net->dev_ws + net->sk_off), static_cast<hipStream_t>(stream)) != 0;
-  return 0;
+  VY_TRY(check_video_shape(net, frames, clips, ring, height, width));
+  return bind_plan(net, dev_ws, bytes, clips, height, width, frames, ring, "video ", stream);
 }
 
-// a video entry's common checks, before anything is launched: window net, pointers, bound for video, table entries in [lo, R)
-static int video_checks(vy_net* net, const char* entry, bool ptrs_ok, const int32_t* table, int n_of_k, int lo) {
-  if (!ptrs_ok) return fail(VY_ERR_INVALID, "null argument");
-  if (int rc = net->check_ready(true)) return rc;
-  if (!net->video_F) return fail(VY_ERR_STATE, "%s: the net is not bound for video (vy_net_bind_video)", entry);
-  const int n = n_of_k < 0 ? net->video_F : n_of_k * net->B * net->window_k;
+// VY_ERR_INVALID unless the `n` entries of a video entry's slot table lie in [lo, ring)
+static int check_slots(const vy_net* net, const char* entry, const int32_t* table, int n, int lo) {
   for (int i = 0; i < n; ++i)
     if (table[i] < lo || table[i] >= net->video_R)
       return fail(VY_ERR_INVALID, "%s: entry %d of the slot table is %d, outside [%d, %d)", entry, i, table[i], lo, net->video_R);
   return 0;
 }
-static int video_ready(vy_net* net, const char* entry, bool ptrs_ok, const int32_t* table, int n_of_k, int lo) {
-  if (int rc = need_window(net, entry)) return rc;
-  const int rc = video_checks(net, entry, ptrs_ok, table, n_of_k, lo);
-  if (rc) net->sk_dirty = true;  // (any error return: see vy_net::sk_dirty)
-  return rc;
-}
 
 int vy_net_video_push(vy_net* net, const float* x, const int32_t* slots, void* stream) {
-  if (int rc = video_ready(net, "vy_net_video_push", x && slots, slots, -1, -1)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = net->sk_begin(s)) return rc;
-  return net->sk_end(net->forward<false>(x, nullptr, nullptr, nullptr, nullptr, s, [](const char*, double, double, bool) {},
-                                         nullptr, nullptr, slots, nullptr));
+  VY_TRY(need_window(net, "vy_net_video_push"));
+  return run_entry(net, x && slots, "vy_net_video_push", stream, [&](hipStream_t s) {
+    VY_TRY(check_slots(net, "vy_net_video_push", slots, net->video_F, -1));
+    VY_TRY(net->prepare(s, plain, true));
+    VY_TRY(net->run_cells(0, net->n_backbone, x, s, plain));
+    return net->ring_push(slots, s, plain);
+  });
 }
 
 int vy_net_video_detect(vy_net* net, const int32_t* table, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
                         void* stream) {
-  if (int rc = video_ready(net, "vy_net_video_detect", table && ids && scores && bboxes, table, 1, 0)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = net->sk_begin(s)) return rc;
-  return net->sk_end(net->forward<false>(nullptr, ids, scores, bboxes, keep_idx, s, [](const char*, double, double, bool) {},
-                                         nullptr, nullptr, nullptr, table));
+  VY_TRY(need_window(net, "vy_net_video_detect"));
+  return run_entry(net, table && ids && scores && bboxes, "vy_net_video_detect", stream, [&](hipStream_t s) {
+    VY_TRY(check_slots(net, "vy_net_video_detect", table, net->B * net->window_k, 0));
+    VY_TRY(net->prepare(s, plain, false));
+    VY_TRY(net->ring_pool(table, s, plain));
+    VY_TRY(net->run_cells(net->n_backbone, (int)net->convs.size(), nullptr, s, plain));
+    return net->detect_tail(ids, scores, bboxes, keep_idx, s, plain);
+  });
 }
 
 int vy_net_video_read_slot(vy_net* net, int32_t slot, float* f0, float* f1, float* f2, void* stream) {
-  if (int rc = video_ready(net, "vy_net_video_read_slot", f0 && f1 && f2, &slot, 0, 0)) return rc;
+  VY_TRY(need_window(net, "vy_net_video_read_slot"));
+  VY_TRY(entry_ready(net, f0 && f1 && f2, "vy_net_video_read_slot"));
   if (slot < 0 || slot >= net->video_R) return fail(VY_ERR_INVALID, "slot %d outside [0, %d)", slot, net->video_R);
   RingRoute rr[3];
   net->ring_routes(rr);
@@ -421,12 +432,7 @@ int vy_net_detect_heads(vy_net* net, const float* head0, const float* head1, con
     HIP_TRY(vy_launch_nchw_to_plane(src[i], net->B, p.H, p.W, p.C, 0, 3 * (5 + net->num_class),
                                     net->plane_ptr(net->head_plane[i]), s));
   }
-  const DetArgs d = net->det_args();
-  if (net->nms_thresh > 0.f && net->nms_thresh < 1.f)  // yolo3.py:1197
-    HIP_TRY(vy_launch_detect(d, net->dev_ws + net->det_scratch_off, ids, scores, bboxes, keep_idx, s));
-  else
-    HIP_TRY(vy_launch_raw_detections(d, ids, scores, bboxes, keep_idx, s));
-  return 0;
+  return net->detect_tail(ids, scores, bboxes, keep_idx, s, plain);
 }
 
 int vy_net_read_activation(vy_net* net, const char* name, float* dst_dev, int32_t* c, int32_t* h, int32_t* w,
@@ -490,8 +496,8 @@ int vy_net_profile_infer(vy_net* net, const float* x, float* ids, float* scores,
       ev1.push_back(e);
     }
   };
-  int rc = net->sk_begin(s);
-  if (rc == 0) rc = net->sk_end(net->forward(x, ids, scores, bboxes, nullptr, s, hook));
+  int rc = run_entry(net, true, nullptr, stream,
+                     [&](hipStream_t) { return infer_sequence(net, x, ids, scores, bboxes, nullptr, s, hook); });
   if (rc == 0) {
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) rc = fail(VY_ERR_HIP, "sync: %s", hipGetErrorString(e));

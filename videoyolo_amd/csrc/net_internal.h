@@ -8,6 +8,7 @@
 #include <cstring>
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -28,6 +29,25 @@ int vy_check_kind(const vy_net* net, bool routes_entry, const char* entry);
     hipError_t e_ = (expr);                                                            \
     if (e_ != hipSuccess) return fail(VY_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
+
+// a step's error ends the sequence it is part of
+#define VY_TRY(expr)                 \
+  do {                               \
+    if (int rc_ = (expr)) return rc_; \
+  } while (0)
+
+// hook before, launch, hook after
+#define HOOKED(hook, name, fl, by, launch) \
+  do {                                     \
+    hook(name, fl, by, true);              \
+    HIP_TRY(launch);                       \
+    hook(name, fl, by, false);             \
+  } while (0)
+
+// the hook of a plain forward (vy_net::kLabels)
+struct NoHook {
+  void operator()(const char*, double, double, bool) const {}
+};
 
 struct ParamT {
   vy_param_info info;
@@ -76,6 +96,7 @@ struct vy_net {
   std::vector<ParamT> params;
   std::vector<PlaneT> planes;
   std::vector<ConvT> convs;
+  int n_backbone = 0;  // convs [0, n_backbone) are the stem and the stages, [n_backbone, size) the heads (0: heads-only net)
   int head_plane[3] = {-1, -1, -1};  // prediction conv outputs, order stride 32,16,8
   int64_t param_elems = 0;           // tensors + scratch
   int64_t tensor_elems = 0;
@@ -88,6 +109,7 @@ struct vy_net {
   size_t fold_desc_off = 0, det_scratch_off = 0, planes_off = 0, sk_off = 0;  // byte offsets in workspace
   size_t ck_off = 0, ck_bytes = 0;  // running-sum scratch of the convs whose K is summed in runs (conv_igemm.hip)
   bool fold_uploaded = false;
+  bool fold_in_stem = false;  // set by prepare(): this sequence's stem launch carries the BatchNorm fold
   bool keep_activations = false;  // vy_net_set_keep_activations: inference planes are not recycled (parity taps)
   bool planes_shared = false;     // the committed plan recycles planes (read_activation is then meaningless)
   // vy_net_set_conv_mode: VY_CONV_SPLIT_BF16X3 sends the inference launches conv_split.hip can serve through the bf16
@@ -103,7 +125,7 @@ struct vy_net {
   bool dsplit_dirty = true;   // the data-gradient weight images (training plans; train.hip) are stale
   // the Winograd image sets (conv_wino.hip) are stale.  Their own flag: a training plan holds them too (model.py reuses it
   // for inference at the same size) but train.hip's refresh_split_images rebuilds only the forward and data-gradient sets —
-  // only forward() below, which does rebuild them, may clear it
+  // only prepare() below, which does rebuild them, may clear it
   bool wino_dirty = true;
   // the launch switches (knobs.h), read from the environment once, by vy_net_create: every launch of this net reads them
   // here (ConvArgs::knobs), so a switch set or changed later affects only nets created after it
@@ -369,6 +391,7 @@ struct vy_net {
       x_co = 0;
       x_c = planes[cat].C;
     }
+    while (n_backbone < (int)convs.size() && params[convs[n_backbone].p_weight].info.backbone) ++n_backbone;
     tensor_elems = param_elems;
     // folded-BN scratch behind the tensors
     for (auto& c : convs) {
@@ -611,6 +634,18 @@ struct vy_net {
     return a;
   }
 
+  // a plan was just committed for the workspace `ws`: take it, zero the `need` bytes the plan uses (all stream-K flags
+  // down) and probe the device's workgroup placement
+  int commit_bind(void* ws, size_t bytes, size_t need, hipStream_t s) {
+    dev_ws = static_cast<unsigned char*>(ws);
+    ws_bytes = bytes;
+    fold_uploaded = false;
+    HIP_TRY(hipMemsetAsync(ws, 0, need, s));
+    sk_dirty = false;
+    sk_ok = vy_sk_verify_topology(reinterpret_cast<unsigned*>(dev_ws + sk_off), s) != 0;
+    return 0;
+  }
+
   int sk_begin(hipStream_t s) {
     if (sk_dirty && dev_ws) {
       HIP_TRY(hipMemsetAsync(dev_ws + sk_off, 0, al((size_t)VY_SK_FLAGS * sizeof(unsigned)), s));
@@ -683,20 +718,15 @@ struct vy_net {
     return d;
   }
 
-  // launches of one inference forward; `hook` (optional) is called around every launch
-  // kLabels = false: the hook is a no-op (vy_net_forward_infer) and the per-launch labels are not built
-  // routes_in (heads-only nets): the three route tensors, imported in front of the first conv (x unused);
-  // routes_out (full nets): stop after the backbone and export the routes there — no head conv, no detection tail
-  // video plans (the caller has checked the tables): push_slots = stop after the backbone and ring_push its video_F frames'
-  // routes there; pool_table = skip the backbone, ring_pool the B clips out of the ring, then heads and detection tail
-  template <bool kLabels = true, typename Hook>
-  int forward(const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx, hipStream_t s,
-              Hook&& hook, const float* const* routes_in = nullptr, float* const* routes_out = nullptr,
-              const int32_t* push_slots = nullptr, const int32_t* pool_table = nullptr) {
-    const bool video = push_slots || pool_table;
-    if (int rc = check_ready(video)) return rc;
-    if (video && !video_F) return fail(VY_ERR_STATE, "the net is not bound for video (vy_net_bind_video)");
-    const bool nms_on = nms_thresh > 0.f && nms_thresh < 1.f;  // yolo3.py:1197
+  // ---- the steps of an inference launch sequence; the entry points of net.hip put them together.  `hook` is called around
+  // every launch (vy_net_profile_infer: an event on either side); NoHook = the plain path, which builds no label
+  template <typename Hook>
+  static constexpr bool kLabels = !std::is_same<Hook, NoHook>::value;
+
+  // In front of the first cell: the one-time fold-table upload, the BatchNorm fold, the weight images of the split modes.
+  // stem_runs: the sequence launches the stem, which then carries the fold if it can (run_cells reads fold_in_stem)
+  template <typename Hook>
+  int prepare(hipStream_t s, Hook& hook, bool stem_runs) {
     FoldDesc* fd = reinterpret_cast<FoldDesc*>(dev_ws + fold_desc_off);
     if (!fold_uploaded) {
       HIP_TRY(hipMemcpyAsync(fd, folds.data(), sizeof(FoldDesc) * folds.size(), hipMemcpyHostToDevice, s));
@@ -705,13 +735,9 @@ struct vy_net {
     }
     // The fold runs EVERY forward (the caller owns the parameter buffer and may have written to it) — inside the stem launch
     // when that has a block per layer (StemArgs), in a launch of its own otherwise
-    const bool fold_in_stem = !pool_table && !convs.empty() && convs[0].is_stem && convs[0].scale_off == folds[0].scale &&
-                              vy_stem_can_fold(conv_batch(convs[0]), H, W, (int)folds.size(), cus);
-    if (!fold_in_stem) {
-      hook("bn_fold", 0.0, 0.0, true);
-      HIP_TRY(vy_launch_bn_fold(dev_params, fd, (int)folds.size(), 1024, 1e-5f, s));
-      hook("bn_fold", 0.0, 0.0, false);
-    }
+    fold_in_stem = stem_runs && !convs.empty() && convs[0].is_stem && convs[0].scale_off == folds[0].scale &&
+                   vy_stem_can_fold(conv_batch(convs[0]), H, W, (int)folds.size(), cus);
+    if (!fold_in_stem) HOOKED(hook, "bn_fold", 0.0, 0.0, vy_launch_bn_fold(dev_params, fd, (int)folds.size(), 1024, 1e-5f, s));
     if (conv_mode != VY_CONV_EXACT_FP32 && (split_dirty || wino_dirty)) {  // once per parameter change, not per forward
       hook("split_weights", 0.0, 0.0, true);
       for (const ConvT& c : convs)
@@ -725,38 +751,19 @@ struct vy_net {
       hook("split_weights", 0.0, 0.0, false);
       split_dirty = wino_dirty = false;
     }
-    if (routes_in) {
-      hook("route_import", 0.0, 0.0, true);
-      HIP_TRY(vy_launch_route_import(route_args(routes_in), s));
-      hook("route_import", 0.0, 0.0, false);
-    }
-    bool pooled = false;
-    for (const ConvT& c : convs) {
-      if ((routes_out || push_slots) && !params[c.p_weight].info.backbone) break;
-      if (pool_table && params[c.p_weight].info.backbone) continue;
-      if (window_k && !pooled && !params[c.p_weight].info.backbone) {  // the stages are done: pool the routes
-        if (pool_table) {
-          RingPoolArgs ra;
-          memset(&ra, 0, sizeof ra);
-          ring_routes(ra.r);
-          ra.n = 3;
-          ra.B = B;
-          ra.k = window_k;
-          ra.join = window_join;
-          ra.R = video_R;
-          ra.slot_stride = ring_slot_floats;
-          memcpy(ra.table, pool_table, sizeof(int32_t) * B * window_k);
-          hook("ring_pool", 0.0, 4.0 * (window_k + 1) * B * ring_slot_floats, true);
-          HIP_TRY(vy_launch_ring_pool(ra, s));
-          hook("ring_pool", 0.0, 4.0 * (window_k + 1) * B * ring_slot_floats, false);
-        } else {
-          const WindowPoolArgs pa = pool_args(nullptr);
-          hook("window_pool", 0.0, 0.0, true);
-          HIP_TRY(vy_launch_window_pool(pa, s));
-          hook("window_pool", 0.0, 0.0, false);
-        }
-        pooled = true;
-      }
+    return 0;
+  }
+
+  enum ConvKernel { kExact, kSplit, kWino };
+  static hipError_t launch_conv(ConvKernel kernel, const ConvArgs& a, hipStream_t s) {
+    return kernel == kWino ? vy_launch_conv_wino(a, s) : kernel == kSplit ? vy_launch_conv_split(a, s) : vy_launch_conv_igemm(a, s);
+  }
+
+  // the cells [first, last) of the conv list; x: the image batch the stem reads (unused unless the span holds it)
+  template <typename Hook>
+  int run_cells(int first, int last, const float* x, hipStream_t s, Hook& hook) {
+    for (int ci = first; ci < last; ++ci) {
+      const ConvT& c = convs[ci];
       if (c.is_stem) {
         const int Bs = conv_batch(c);
         StemArgs a;
@@ -774,89 +781,104 @@ struct vy_net {
         a.cus = cus;
         if (fold_in_stem) {
           a.fold_params = dev_params;
-          a.fold_descs = fd;
+          a.fold_descs = reinterpret_cast<FoldDesc*>(dev_ws + fold_desc_off);
           a.fold_n = (int)folds.size();
           a.fold_stem = 0;
           a.fold_eps = 1e-5f;
         }
-        const double fl = 2.0 * Bs * H * W * 27.0 * c.cout;
-        const double by = 4.0 * Bs * H * W * (3.0 + c.cout);
-        hook(c.name.c_str(), fl, by, true);
-        HIP_TRY(vy_launch_stem(a, s));
-        hook(c.name.c_str(), fl, by, false);
+        const double fl = kLabels<Hook> ? 2.0 * Bs * H * W * 27.0 * c.cout : 0.0;
+        const double by = kLabels<Hook> ? 4.0 * Bs * H * W * (3.0 + c.cout) : 0.0;
+        HOOKED(hook, c.name.c_str(), fl, by, vy_launch_stem(a, s));
+        continue;
+      }
+      const ConvArgs a = conv_args(c);
+      const ConvKernel kernel = a.w_wino && vy_conv_wino_pays(a) ? kWino : a.w_split && vy_conv_split_pays(a) ? kSplit : kExact;
+      if (!kLabels<Hook>) {  // plain forward: no label, no second tile / stream-K query per launch (batch-1 latency path)
+        HIP_TRY(launch_conv(kernel, a, s));
+        continue;
+      }
+      const double fl = 2.0 * a.M * (double)a.N * a.ntaps * a.Kc;
+      const double by = 4.0 * ((double)a.B * (a.a_Hp - 2) * (a.a_Wp - 2) * a.Kc + (double)a.M * a.N * a.ups * a.ups +
+                               (double)a.N * a.ntaps * a.Kc + (a.res ? (double)a.M * a.N : 0.0));
+      char nm[96];
+      int bm, bn, ks;
+      if (kernel == kWino) {
+        snprintf(nm, sizeof nm, "%s|wino64x128", c.name.c_str());
+      } else if (kernel == kSplit) {
+        vy_conv_split_cfg(a, &bm, &bn, &ks);
+        if (ks > 1) snprintf(nm, sizeof nm, "%s|split%dx%dk%d", c.name.c_str(), bm, bn, ks);
+        else snprintf(nm, sizeof nm, "%s|split%dx%d", c.name.c_str(), bm, bn);
       } else {
-        const ConvArgs a = conv_args(c);
-        if (!kLabels) {  // plain forward: no label, no second tile / stream-K query per launch (batch-1 latency path)
-          if (a.w_wino && vy_conv_wino_pays(a))
-            HIP_TRY(vy_launch_conv_wino(a, s));
-          else if (a.w_split && vy_conv_split_pays(a))
-            HIP_TRY(vy_launch_conv_split(a, s));
-          else
-            HIP_TRY(vy_launch_conv_igemm(a, s));
-          continue;
-        }
-        const double fl = 2.0 * a.M * (double)a.N * a.ntaps * a.Kc;
-        const double by = 4.0 * ((double)a.B * (a.a_Hp - 2) * (a.a_Wp - 2) * a.Kc + (double)a.M * a.N * a.ups * a.ups +
-                                 (double)a.N * a.ntaps * a.Kc + (a.res ? (double)a.M * a.N : 0.0));
-        char nm[96];
-        if (a.w_wino && vy_conv_wino_pays(a)) {
-          snprintf(nm, sizeof nm, "%s|wino64x128", c.name.c_str());
-          hook(nm, fl, by, true);
-          HIP_TRY(vy_launch_conv_wino(a, s));
-          hook(nm, fl, by, false);
-          continue;
-        }
-        if (a.w_split && vy_conv_split_pays(a)) {
-          int sbm, sbn, sks;
-          vy_conv_split_cfg(a, &sbm, &sbn, &sks);
-          if (sks > 1) snprintf(nm, sizeof nm, "%s|split%dx%dk%d", c.name.c_str(), sbm, sbn, sks);
-          else snprintf(nm, sizeof nm, "%s|split%dx%d", c.name.c_str(), sbm, sbn);
-          hook(nm, fl, by, true);
-          HIP_TRY(vy_launch_conv_split(a, s));
-          hook(nm, fl, by, false);
-          continue;
-        }
-        int bm, bn;
         vy_conv_cfg(a, &bm, &bn);
-        if (const int ks = vy_conv_ksplit(a))
+        if ((ks = vy_conv_ksplit(a)))
           snprintf(nm, sizeof nm, "%s|%dx%dks%d", c.name.c_str(), bm, bn, ks);
         else
           snprintf(nm, sizeof nm, "%s|%dx%d%s", c.name.c_str(), bm, bn, vy_conv_streamk(a) ? "sk" : "");
-        hook(nm, fl, by, true);
-        HIP_TRY(vy_launch_conv_igemm(a, s));
-        hook(nm, fl, by, false);
       }
+      HOOKED(hook, nm, fl, by, launch_conv(kernel, a, s));
     }
-    if (push_slots) {
-      RingPushArgs ra;
-      memset(&ra, 0, sizeof ra);
-      ring_routes(ra.r);
-      ra.n = 3;
-      ra.F = video_F;
-      ra.R = video_R;
-      ra.slot_stride = ring_slot_floats;
-      memcpy(ra.slot, push_slots, sizeof(int32_t) * video_F);
-      hook("ring_push", 0.0, 8.0 * video_F * ring_slot_floats, true);
-      HIP_TRY(vy_launch_ring_push(ra, s));
-      hook("ring_push", 0.0, 8.0 * video_F * ring_slot_floats, false);
-      return 0;
-    }
-    if (routes_out) {
-      const float* const out[3] = {routes_out[0], routes_out[1], routes_out[2]};
-      hook("route_export", 0.0, 0.0, true);
-      HIP_TRY(vy_launch_route_export(route_args(out), s));
-      hook("route_export", 0.0, 0.0, false);
-      return 0;
-    }
+    return 0;
+  }
+
+  // heads-only nets: the caller's three route tensors into the planes the first head cells read
+  template <typename Hook>
+  int route_import(const float* const* nchw, hipStream_t s, Hook& hook) {
+    HOOKED(hook, "route_import", 0.0, 0.0, vy_launch_route_import(route_args(nchw), s));
+    return 0;
+  }
+  // full nets, after the last stage cell: the three routes out to the caller's tensors
+  template <typename Hook>
+  int route_export(const float* const* nchw, hipStream_t s, Hook& hook) {
+    HOOKED(hook, "route_export", 0.0, 0.0, vy_launch_route_export(route_args(nchw), s));
+    return 0;
+  }
+  // window nets, clip plan: the stages are done, pool the per-frame routes of each clip
+  template <typename Hook>
+  int window_pool(hipStream_t s, Hook& hook) {
+    HOOKED(hook, "window_pool", 0.0, 0.0, vy_launch_window_pool(pool_args(nullptr), s));
+    return 0;
+  }
+  // video plans (the caller has checked the tables): pool the B clips of `table` out of the ring ...
+  template <typename Hook>
+  int ring_pool(const int32_t* table, hipStream_t s, Hook& hook) {
+    RingPoolArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ring_routes(ra.r);
+    ra.n = 3;
+    ra.B = B;
+    ra.k = window_k;
+    ra.join = window_join;
+    ra.R = video_R;
+    ra.slot_stride = ring_slot_floats;
+    memcpy(ra.table, table, sizeof(int32_t) * B * window_k);
+    HOOKED(hook, "ring_pool", 0.0, 4.0 * (window_k + 1) * B * ring_slot_floats, vy_launch_ring_pool(ra, s));
+    return 0;
+  }
+  // ... and store the routes of the video_F frames the stages just ran on in the slots `slots`
+  template <typename Hook>
+  int ring_push(const int32_t* slots, hipStream_t s, Hook& hook) {
+    RingPushArgs ra;
+    memset(&ra, 0, sizeof ra);
+    ring_routes(ra.r);
+    ra.n = 3;
+    ra.F = video_F;
+    ra.R = video_R;
+    ra.slot_stride = ring_slot_floats;
+    memcpy(ra.slot, slots, sizeof(int32_t) * video_F);
+    HOOKED(hook, "ring_push", 0.0, 8.0 * video_F * ring_slot_floats, vy_launch_ring_push(ra, s));
+    return 0;
+  }
+
+  // decode + NMS of the three prediction planes into the caller's outputs
+  template <typename Hook>
+  int detect_tail(float* ids, float* scores, float* bboxes, int32_t* keep_idx, hipStream_t s, Hook& hook) {
     const DetArgs d = det_args();
     double dby = 0;
     for (int i = 0; i < 3; ++i) dby += 4.0 * B * d.head[i].H * d.head[i].W * d.head[i].cs;
-    hook("decode_nms", 0.0, dby, true);
-    if (nms_on)
-      HIP_TRY(vy_launch_detect(d, dev_ws + det_scratch_off, ids, scores, bboxes, keep_idx, s));
-    else  // outputs are (B, N*C, .): the detection tensor itself
-      HIP_TRY(vy_launch_raw_detections(d, ids, scores, bboxes, keep_idx, s));
-    hook("decode_nms", 0.0, dby, false);
+    const bool nms_on = nms_thresh > 0.f && nms_thresh < 1.f;  // yolo3.py:1197; off: the outputs are (B, N*C, .), the detection tensor itself
+    HOOKED(hook, "decode_nms", 0.0, dby,
+           nms_on ? vy_launch_detect(d, dev_ws + det_scratch_off, ids, scores, bboxes, keep_idx, s)
+                  : vy_launch_raw_detections(d, ids, scores, bboxes, keep_idx, s));
     return 0;
   }
 };

@@ -924,17 +924,11 @@ int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, in
   if (bytes < need) return fail(VY_ERR_INVALID, "training workspace too small: %zu < %zu bytes", bytes, need);
   train_plan(net, batch, height, width, true);
   VyTrain* t = net->train;
-  net->dev_ws = static_cast<unsigned char*>(dev_ws);
-  net->ws_bytes = bytes;
-  net->fold_uploaded = false;
   t->grads = static_cast<float*>(dev_grads);
   t->mom = static_cast<float*>(dev_momentum);
   t->forward_done = false;
   t->sdesc_uploaded = false;  // (the workspace is zeroed below)
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(hipMemsetAsync(dev_ws, 0, need, s));
-  net->sk_dirty = false;
-  net->sk_ok = vy_sk_verify_topology(reinterpret_cast<unsigned*>(net->dev_ws + net->sk_off), s) != 0;
+  VY_TRY(net->commit_bind(dev_ws, bytes, need, static_cast<hipStream_t>(stream)));
   if (net->knobs.train_side_stream && !t->side) {
     // (The weight-gradient stream at the LOWEST queue priority was measured: +0.4 % on top of the raised issue priority of the
     // BatchNorm passes in a fresh process — and the whole training step 1.55x SLOWER, forward included, in a process that had

@@ -107,10 +107,30 @@ def _torch():
     return torch
 
 
+def _ptrs(tensors):
+    """Device tensors as pointer arguments of the library; None (an output the caller did not ask for) stays None."""
+    return [None if t is None else ctypes.c_void_p(t.data_ptr()) for t in tensors]
+
+
+def _read_param_file(filename):
+    """{name: array} of a parameter file in either container (sniffed from the first bytes: zip = .npz, else mxnet's
+    NDArray-dict layout, 0x112)."""
+    with open(filename, "rb") as f:
+        head = f.read(2)
+    if head == b"PK":
+        with np.load(filename) as z:
+            return {k: z[k] for k in z.files}
+    from . import mxparams
+    return mxparams.load(filename)
+
+
 class YOLOV3(object):
     """yolo3_darknet53 detector bound to one device / stream."""
 
     _CREATE = "vy_net_create"  # the library constructor of this graph
+    _TRAIN_ENTRY = ""          # suffix of the library's training entries ("_routes": they take the three route tensors)
+    _ONE_RANK = None           # a kind of net that trains on one rank only names itself here (_single_rank)
+    _EXCHANGES = True          # train-mode forwards keep the replicas and the SyncBatchNorm statistics of the ranks in step
 
     def __init__(self, classes, nms_thresh=0.45, nms_topk=400, post_nms=100, pos_iou_thresh=1.0,
                  ignore_iou_thresh=0.7, norm_layer=BatchNorm, norm_kwargs=None, alloc_size=(128, 128)):
@@ -141,7 +161,7 @@ class YOLOV3(object):
         self._plan = None        # (B, H, W, train?) the workspace is planned for
         self._grads = None       # torch float32 flat gradient buffer (device layout, training only)
         self._mom = None         # torch float32 flat SGD momentum buffer
-        self._train_x = None     # image batch of the recorded forward (stem weight gradient)
+        self._train_x = None     # inputs of the recorded forward, device tensors (stem weight gradient)
         self._cb_keep = []       # ctypes callbacks kept alive
         self._sync_hook = None   # parallel.SyncBatchNormHook once installed (norm_layer=SyncBatchNorm or by hand)
         self._sync_bn_checked = False
@@ -320,6 +340,19 @@ class YOLOV3(object):
             out["yolo_outputs.%d.offsets" % i] = offsets.copy()
         return out
 
+    @classmethod
+    def _train_mode_constants(cls, h, w):
+        """Items 1-3 of the train-mode 8-tuple (yolo3.py:1189-1192) for an (h, w) input: [anchors (1,1,3,2)]*3,
+        [offsets (1,HW,1,2)]*3 and [zero feature maps (1,1,H,W)]*3, scales in the order stride 32, 16, 8."""
+        anchors, offsets, fms = [], [], []
+        for i, s in enumerate((32, 16, 8)):
+            hh, ww = h // s, w // s
+            anchors.append(np.array(cls._ANCHORS[i], np.float32).reshape(1, 1, 3, 2))
+            gx, gy = np.meshgrid(np.arange(ww), np.arange(hh))
+            offsets.append(np.stack([gx, gy], -1).astype(np.float32).reshape(1, hh * ww, 1, 2))
+            fms.append(np.zeros((1, 1, hh, ww), np.float32))
+        return anchors, offsets, fms
+
     def save_parameters(self, filename, format=None):
         """Gluon structural names, reference layouts, including the anchors / offsets Constants — the key set
         of the reference's own ``net.save_parameters`` file.  Container: numpy .npz by default; mxnet's
@@ -341,16 +374,8 @@ class YOLOV3(object):
             np.savez(f, **arrays)
 
     def load_parameters(self, filename, ctx=None, allow_missing=False, ignore_extra=False):
-        """Accepts both containers (sniffed from the first bytes: zip = .npz, 0x112 = mxnet list)."""
-        with open(filename, "rb") as f:
-            head = f.read(8)
-        if head[:2] == b"PK":
-            with np.load(filename) as z:
-                loaded = {k: z[k] for k in z.files}
-        else:
-            from . import mxparams
-            loaded = mxparams.load(filename)
-        self.set_parameters(loaded, allow_missing=allow_missing, ignore_extra=ignore_extra)
+        """Accepts both containers (``_read_param_file``)."""
+        self.set_parameters(_read_param_file(filename), allow_missing=allow_missing, ignore_extra=ignore_extra)
         if ctx is not None:
             self.reset_ctx(ctx)
 
@@ -358,15 +383,7 @@ class YOLOV3(object):
         """``pretrained_base=True`` (three_darknet.py:262-264): load an ImageNet darknet53 checkpoint (gluoncv's
         ``darknet53-<hash>.params``, mxnet NDArray-dict layout, or an .npz with the same names) into the 52 backbone
         cells; the heads keep whatever ``initialize()`` gives them (wrappers.py builds them fresh)."""
-        with open(filename, "rb") as f:
-            head = f.read(2)
-        if head == b"PK":
-            with np.load(filename) as z:
-                loaded = {k: z[k] for k in z.files}
-        else:
-            from . import mxparams
-            loaded = mxparams.load(filename)
-        mapped = {self._key(k): v for k, v in darknet53_to_stage_names(loaded).items()}
+        mapped = {self._key(k): v for k, v in darknet53_to_stage_names(_read_param_file(filename)).items()}
         want = [k for k, p in self._params.items() if p.backbone]
         missing = [k for k in want if k not in mapped]
         if missing:
@@ -418,30 +435,22 @@ class YOLOV3(object):
         key = (tuple(x.shape), rows, self.nms_thresh, self.nms_topk, self.post_nms)
         g = self._graphs.get(key)
         if g is None:
-            b = x.shape[0]
-            st = dict(x=torch.empty_like(x),
-                      ids=torch.empty((b, rows, 1), dtype=torch.float32, device=self._device),
-                      scores=torch.empty((b, rows, 1), dtype=torch.float32, device=self._device),
-                      bboxes=torch.empty((b, rows, 4), dtype=torch.float32, device=self._device),
-                      keep=torch.empty((b, rows), dtype=torch.int32, device=self._device))
+            xin, outs = torch.empty_like(x), self._detect_outputs(x.shape[0], rows, keep=True)
 
             def launch():
-                _lib.check(self._lib.vy_net_forward_infer(
-                    self._h, ctypes.c_void_p(st["x"].data_ptr()), ctypes.c_void_p(st["ids"].data_ptr()),
-                    ctypes.c_void_p(st["scores"].data_ptr()), ctypes.c_void_p(st["bboxes"].data_ptr()),
-                    ctypes.c_void_p(st["keep"].data_ptr()), self._stream()))
-            st["x"].copy_(x)
+                _lib.check(self._lib.vy_net_forward_infer(self._h, *_ptrs((xin,) + outs), self._stream()))
+            xin.copy_(x)
             launch()  # eager warm-up: one-time uploads happen outside the capture
             torch.cuda.synchronize(self._device)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 launch()
-            g = (graph, st)
+            g = (graph, xin, outs)
             self._graphs = {key: g}  # one shape at a time (the workspace is planned for one shape)
-        graph, st = g
-        st["x"].copy_(x)
+        graph, xin, outs = g
+        xin.copy_(x)
         graph.replay()
-        return st["ids"].clone(), st["scores"].clone(), st["bboxes"].clone(), st["keep"].clone()
+        return tuple(t.clone() for t in outs)
 
     def keep_activations(self, keep=True):
         """Parity taps: give every cell its own activation plane so that ``read_activation`` works after an inference
@@ -593,6 +602,14 @@ class YOLOV3(object):
                 return rows  # both "disabled": box_nms's un-sliced output, all N*C rows (yolo3.py:1198-1202)
         return int(self._lib.vy_net_num_anchors(self._h)) * len(self._classes)
 
+    def _detect_outputs(self, b, rows, keep):
+        """The outputs of a detect call at batch b: (ids (b,rows,1), scores (b,rows,1), bboxes (b,rows,4), keep), keep the
+        (b,rows) int32 indices if asked for, else None — the four pointers every detect entry of the library takes."""
+        torch = _torch()
+        f32 = dict(dtype=torch.float32, device=self._device)
+        return (torch.empty((b, rows, 1), **f32), torch.empty((b, rows, 1), **f32), torch.empty((b, rows, 4), **f32),
+                torch.empty((b, rows), dtype=torch.int32, device=self._device) if keep else None)
+
     def _as_input(self, x):
         torch = _torch()
         if not isinstance(x, torch.Tensor):
@@ -622,23 +639,40 @@ class YOLOV3(object):
             a = torch.as_tensor(np.asarray(a, np.float32))
         return a.to(device=self._device, dtype=torch.float32).contiguous()
 
-    def forward_train(self, x, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t):
-        """Recording branch (yolo3.py:1181-1187): the four (B,) losses.  The network gradient is
+    def _train_inputs(self, x):
+        """The network inputs of a train-mode call, checked -> (device tensors, (B, H, W) of the plan)."""
+        x = self._as_input(x)
+        return [x], self._bhw(x)
+
+    def _single_rank(self):
+        if self._ONE_RANK:
+            from . import parallel
+            if parallel.world_size() > 1:
+                raise NotImplementedError("multi-rank training of %s is not supported: train it on one rank" % self._ONE_RANK)
+
+    def _train_entry(self, name):
+        return getattr(self._lib, name + self._TRAIN_ENTRY)
+
+    def forward_train(self, *args):
+        """Recording branch (yolo3.py:1181-1187), ``net.forward_train(x, gt_boxes, obj_t, centers_t, scales_t, weights_t,
+        clas_t)`` (a heads-only net: its three routes in place of x): the four (B,) losses.  The network gradient is
         produced by ``autograd.backward(...)`` / ``net.backward()`` afterwards."""
         torch = _torch()
-        x = self._as_input(x)
-        b, h, w = self._bhw(x)
-        tg = [self._dev(t) for t in (gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)]
+        self._single_rank()
+        xs, (b, h, w) = self._train_inputs(*args[:-6])
+        tg = [self._dev(t) for t in args[-6:]]
         m = int(tg[0].shape[1])
-        from . import parallel
-        # data parallel: all ranks train the same model.  Collective-safe: the ranks first agree (all-reduce MAX of
-        # their dirty flags) whether anybody wrote parameters since the last broadcast (no-op single process).
-        parallel.sync_replicas_if_any_dirty(self)
+        if self._EXCHANGES:
+            from . import parallel
+            # data parallel: all ranks train the same model.  Collective-safe: the ranks first agree (all-reduce MAX of
+            # their dirty flags) whether anybody wrote parameters since the last broadcast (no-op single process).
+            parallel.sync_replicas_if_any_dirty(self)
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w, train=True)
-            self._ensure_sync_bn()
-            if self._sync_hook is not None:
-                self._sync_hook.begin_step()
+            if self._EXCHANGES:
+                self._ensure_sync_bn()
+                if self._sync_hook is not None:
+                    self._sync_hook.begin_step()
             n = self._lib.vy_net_num_anchors(self._h)
             c = len(self._classes)
             want = [(b, m, 4), (b, n, 1), (b, n, 2), (b, n, 2), (b, n, 2), (b, n, c)]
@@ -648,11 +682,11 @@ class YOLOV3(object):
             _lib.check(self._lib.vy_net_set_train_options(
                 self._h, self._ignore_iou_thresh, int(bool(self._target_generator._label_smooth))))
             losses = torch.empty((4, b), dtype=torch.float32, device=self._device)
-            p = [ctypes.c_void_p(t.data_ptr()) for t in tg]
-            _lib.check(self._lib.vy_net_train_forward(
-                self._h, ctypes.c_void_p(x.data_ptr()), p[0], m, p[1], p[2], p[3], p[4], p[5],
-                ctypes.c_void_p(losses.data_ptr()), self._stream()))
-        self._train_x = x
+            p = _ptrs(tg)
+            _lib.check(self._train_entry("vy_net_train_forward")(
+                self._h, *_ptrs(xs), p[0], m, p[1], p[2], p[3], p[4], p[5], ctypes.c_void_p(losses.data_ptr()),
+                self._stream()))
+        self._train_x = xs
         autograd._register(self)
         return tuple(autograd.loss_vector(losses[i], self, i) for i in range(4))
 
@@ -687,11 +721,10 @@ class YOLOV3(object):
         if self._train_x is None:
             raise RuntimeError("backward() without a recorded forward")
         with torch.cuda.device(self._device):
-            _lib.check(self._lib.vy_net_train_backward(self._h, ctypes.c_void_p(self._train_x.data_ptr()),
-                                                       self._stream()))
+            _lib.check(self._train_entry("vy_net_train_backward")(self._h, *_ptrs(self._train_x), self._stream()))
         self._train_x = None
 
-    def forward_train_mode(self, x):
+    def forward_train_mode(self, *inputs):
         """``autograd.train_mode()`` without recording (transforms.py:190-193): the 8-tuple of
         yolo3.py:1189-1192 — (box_preds (B,N,4), [anchors (1,1,3,2)]*3, [offsets (1,HW,1,2)]*3,
         [fake feature maps (1,1,H,W)]*3, centers (B,N,2), scales (B,N,2), objness (B,N,1),
@@ -699,25 +732,17 @@ class YOLOV3(object):
         from one train-mode forward (BatchNorm on batch statistics); items 1-3 are constants of the input
         shape (numpy), which is all the reference's consumer reads."""
         torch = _torch()
-        x = self._as_input(x)
-        b, h, w = self._bhw(x)
-        anchors, offsets, fms = [], [], []
-        table = [[116, 90, 156, 198, 373, 326], [30, 61, 62, 45, 59, 119], [10, 13, 16, 30, 33, 23]]
-        for i, s in enumerate((32, 16, 8)):
-            hh, ww = h // s, w // s
-            anchors.append(np.array(table[i], np.float32).reshape(1, 1, 3, 2))
-            gx, gy = np.meshgrid(np.arange(ww), np.arange(hh))
-            offsets.append(np.stack([gx, gy], -1).astype(np.float32).reshape(1, hh * ww, 1, 2))
-            fms.append(np.zeros((1, 1, hh, ww), np.float32))
+        self._single_rank()
+        xs, (b, h, w) = self._train_inputs(*inputs)
+        anchors, offsets, fms = self._train_mode_constants(h, w)
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w, train=True)
-            self._ensure_sync_bn()
+            if self._EXCHANGES:
+                self._ensure_sync_bn()
             n = self._lib.vy_net_num_anchors(self._h)
             c = len(self._classes)
             outs = [torch.empty((b, n, k), dtype=torch.float32, device=self._device) for k in (4, 2, 2, 1, c)]
-            _lib.check(self._lib.vy_net_train_mode_forward(
-                self._h, ctypes.c_void_p(x.data_ptr()), *[ctypes.c_void_p(t.data_ptr()) for t in outs],
-                self._stream()))
+            _lib.check(self._train_entry("vy_net_train_mode_forward")(self._h, *_ptrs(xs + outs), self._stream()))
         return (outs[0], anchors, offsets, fms, outs[1], outs[2], outs[3], outs[4])
 
     def extract_features(self, x):
@@ -732,8 +757,7 @@ class YOLOV3(object):
             self._ensure_plan(b, h, w)
             outs = [torch.empty((b, c, -(-h // s), -(-w // s)), dtype=torch.float32, device=self._device)
                     for c, s in ((256, 8), (512, 16), (1024, 32))]
-            _lib.check(self._lib.vy_net_forward_features(
-                self._h, ctypes.c_void_p(x.data_ptr()), *[ctypes.c_void_p(t.data_ptr()) for t in outs], self._stream()))
+            _lib.check(self._lib.vy_net_forward_features(self._h, *_ptrs([x] + outs), self._stream()))
         return tuple(outs)
 
     def grad(self, name):
@@ -748,15 +772,7 @@ class YOLOV3(object):
 
     def read_grad_activation(self, name):
         """d(loss)/d(output of cell `name`) after backward(), NCHW (parity tap)."""
-        torch = _torch()
-        c, h, w = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(self._lib.vy_net_read_activation(self._h, name.encode(), None, ctypes.byref(c),
-                                                    ctypes.byref(h), ctypes.byref(w), None))
-        out = torch.empty((self._tap_batch(name), c.value, h.value, w.value), dtype=torch.float32, device=self._device)
-        with torch.cuda.device(self._device):
-            _lib.check(self._lib.vy_net_read_grad_activation(self._h, name.encode(),
-                                                             ctypes.c_void_p(out.data_ptr()), self._stream()))
-        return out
+        return self._read_tap(name, self._tap_batch(name), grad=True)
 
     def read_train_tap(self, name, which):
         """Test-only tap of the training step (vy_net_read_train_tap): which = 'z' (z after forward_train, dz after
@@ -814,19 +830,11 @@ class YOLOV3(object):
             if getattr(self, "_hybrid", False) and self._use_graphs:
                 if replanned:
                     self._graphs = {}
-                ids, scores, bboxes, keep = self._graph_forward(x, rows)
-                return (ids, scores, bboxes, keep) if return_index else (ids, scores, bboxes)
-            ids = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
-            scores = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
-            bboxes = torch.empty((b, rows, 4), dtype=torch.float32, device=self._device)
-            keep = torch.empty((b, rows), dtype=torch.int32, device=self._device) if return_index else None
-            _lib.check(self._lib.vy_net_forward_infer(
-                self._h, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(ids.data_ptr()),
-                ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(bboxes.data_ptr()),
-                ctypes.c_void_p(keep.data_ptr()) if keep is not None else None, self._stream()))
-        if return_index:
-            return ids, scores, bboxes, keep
-        return ids, scores, bboxes
+                outs = self._graph_forward(x, rows)
+            else:
+                outs = self._detect_outputs(b, rows, return_index)
+                _lib.check(self._lib.vy_net_forward_infer(self._h, *_ptrs((x,) + outs), self._stream()))
+        return outs if return_index else outs[:3]
 
     def detect_heads(self, heads, size, return_index=False):
         """The detection tail alone (``vy_net_detect_heads``): ``heads`` = the three prediction-conv outputs
@@ -848,16 +856,9 @@ class YOLOV3(object):
                 raise ValueError("head of stride %d: shape %s, expected %s" % (div, tuple(t.shape), want))
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w)
-            rows = self._out_rows()
-            ids = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
-            scores = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
-            bboxes = torch.empty((b, rows, 4), dtype=torch.float32, device=self._device)
-            keep = torch.empty((b, rows), dtype=torch.int32, device=self._device) if return_index else None
-            _lib.check(self._lib.vy_net_detect_heads(
-                self._h, *[ctypes.c_void_p(t.data_ptr()) for t in hs], ctypes.c_void_p(ids.data_ptr()),
-                ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(bboxes.data_ptr()),
-                ctypes.c_void_p(keep.data_ptr()) if keep is not None else None, self._stream()))
-        return (ids, scores, bboxes, keep) if return_index else (ids, scores, bboxes)
+            outs = self._detect_outputs(b, self._out_rows(), return_index)
+            _lib.check(self._lib.vy_net_detect_heads(self._h, *_ptrs(tuple(hs) + outs), self._stream()))
+        return outs if return_index else outs[:3]
 
     def detect_two_streams(self, x, return_index=False):
         """Frames are independent, so a large batch is run as two half-batches on two HIP streams (a twin
@@ -895,26 +896,18 @@ class YOLOV3(object):
                 _lib.check(self._lib.vy_net_bind_workspace(tw["h"], ctypes.c_void_p(tw["ws"].data_ptr()),
                                                            tw["ws"].numel(), hb, h, w, ctypes.c_void_p(cur.cuda_stream)))
                 tw["plan"] = (hb, h, w)
-            rows = self._out_rows()
-            ids = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
-            scores = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
-            bboxes = torch.empty((b, rows, 4), dtype=torch.float32, device=self._device)
-            keep = torch.empty((b, rows), dtype=torch.int32, device=self._device) if return_index else None
+            outs = self._detect_outputs(b, self._out_rows(), return_index)
             side = tw["stream"]
             side.wait_stream(cur)  # inputs, workspace zeroing and the output allocations are ordered before it
             for half, (hnd, st) in enumerate(((self._h, cur), (tw["h"], side))):
                 lo = half * hb
                 _lib.check(self._lib.vy_net_forward_infer(
-                    hnd, ctypes.c_void_p(x[lo:].data_ptr()), ctypes.c_void_p(ids[lo:].data_ptr()),
-                    ctypes.c_void_p(scores[lo:].data_ptr()), ctypes.c_void_p(bboxes[lo:].data_ptr()),
-                    ctypes.c_void_p(keep[lo:].data_ptr()) if keep is not None else None,
-                    ctypes.c_void_p(st.cuda_stream)))
+                    hnd, *_ptrs([None if t is None else t[lo:] for t in (x,) + outs]), ctypes.c_void_p(st.cuda_stream)))
             cur.wait_stream(side)
-            for t in (x, ids, scores, bboxes) + ((keep,) if keep is not None else ()):
-                t.record_stream(side)
-        if return_index:
-            return ids, scores, bboxes, keep
-        return ids, scores, bboxes
+            for t in (x,) + outs:
+                if t is not None:
+                    t.record_stream(side)
+        return outs if return_index else outs[:3]
 
     def streamk_enabled(self):
         """Did the bind-time placement probe (8 XCDs, workgroups dealt round-robin: csrc/conv_igemm.hip
@@ -938,14 +931,22 @@ class YOLOV3(object):
 
     def read_activation(self, name):
         """Output of cell `name` (e.g. 'stages.0.14.body.1') of the last forward, NCHW."""
+        return self._read_tap(name, self._tap_batch(name))
+
+    def _read_tap(self, name, batch, grad=False):
+        """Ask the library for the (C, H, W) of tap `name`, then read it (its gradient plane: grad) into a fresh
+        (batch, C, H, W) device tensor; `batch` is the caller's: the leading dimension of that tap in the bound plan."""
         torch = _torch()
         c, h, w = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         _lib.check(self._lib.vy_net_read_activation(self._h, name.encode(), None, ctypes.byref(c),
                                                     ctypes.byref(h), ctypes.byref(w), None))
-        out = torch.empty((self._tap_batch(name), c.value, h.value, w.value), dtype=torch.float32, device=self._device)
+        out = torch.empty((batch, c.value, h.value, w.value), dtype=torch.float32, device=self._device)
+        dst = ctypes.c_void_p(out.data_ptr())
         with torch.cuda.device(self._device):
-            _lib.check(self._lib.vy_net_read_activation(self._h, name.encode(), ctypes.c_void_p(out.data_ptr()),
-                                                        None, None, None, self._stream()))
+            if grad:
+                _lib.check(self._lib.vy_net_read_grad_activation(self._h, name.encode(), dst, self._stream()))
+            else:
+                _lib.check(self._lib.vy_net_read_activation(self._h, name.encode(), dst, None, None, None, self._stream()))
         return out
 
     def profile(self, x):
@@ -956,17 +957,12 @@ class YOLOV3(object):
         b, _, h, w = x.shape
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w)
-            rows = self._out_rows()
-            ids = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
-            scores = torch.empty_like(ids)
-            bboxes = torch.empty((b, rows, 4), dtype=torch.float32, device=self._device)
+            outs = self._detect_outputs(b, self._out_rows(), keep=False)
             cap = 256
             stats = (_lib.LaunchStat * cap)()
             n = ctypes.c_int32(cap)
-            _lib.check(self._lib.vy_net_profile_infer(
-                self._h, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(ids.data_ptr()),
-                ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(bboxes.data_ptr()), stats,
-                ctypes.byref(n), self._stream()))
+            _lib.check(self._lib.vy_net_profile_infer(self._h, *_ptrs((x,) + outs[:3]), stats, ctypes.byref(n),
+                                                      self._stream()))
         return [(stats[i].name.decode(), float(stats[i].ms), float(stats[i].flops), float(stats[i].bytes))
                 for i in range(n.value)]
 
@@ -995,11 +991,13 @@ class YOLOV3NoBackbone(YOLOV3):
     back-propagated into the routes."""
 
     _CREATE = "vy_net_create_heads"
+    _TRAIN_ENTRY = "_routes"
+    _ONE_RANK = "a heads-only net (yolo3_no_backbone)"
+    _EXCHANGES = False  # no SyncBatchNorm cell among the heads (a SyncBatchNorm norm_layer is accepted: DESIGN §10)
 
     def _as_routes(self, f1, f2, f3):
         """Check the three routes against each other (before anything launches) -> (device tensors, (B, H, W)) with H, W
         the smallest image size they can come from (the plan only depends on the route sizes)."""
-        torch = _torch()
         fs = []
         for f in (f1, f2, f3):
             shape = tuple(f.shape) if hasattr(f, "shape") else tuple(np.shape(f))
@@ -1013,12 +1011,9 @@ class YOLOV3NoBackbone(YOLOV3):
                              "[4, 512]" % (fs,))
         if self._device is None:
             raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
-        out = []
-        for f in (f1, f2, f3):
-            if not isinstance(f, torch.Tensor):
-                f = torch.as_tensor(np.asarray(f, np.float32))
-            out.append(f.to(device=self._device, dtype=torch.float32).contiguous())
-        return out, (b, 8 * h8, 8 * w8)
+        return [self._dev(f) for f in (f1, f2, f3)], (b, 8 * h8, 8 * w8)
+
+    _train_inputs = _as_routes
 
     def __call__(self, f1, f2, f3, *args, return_index=False):
         """YOLOV3_noback.hybrid_forward(F, x1, x2, x3, *args): mode by the autograd state."""
@@ -1036,79 +1031,9 @@ class YOLOV3NoBackbone(YOLOV3):
         fs, (b, h, w) = self._as_routes(f1, f2, f3)
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w)
-            rows = self._out_rows()
-            ids = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
-            scores = torch.empty((b, rows, 1), dtype=torch.float32, device=self._device)
-            bboxes = torch.empty((b, rows, 4), dtype=torch.float32, device=self._device)
-            keep = torch.empty((b, rows), dtype=torch.int32, device=self._device) if return_index else None
-            _lib.check(self._lib.vy_net_forward_infer_routes(
-                self._h, *[ctypes.c_void_p(f.data_ptr()) for f in fs], ctypes.c_void_p(ids.data_ptr()),
-                ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(bboxes.data_ptr()),
-                ctypes.c_void_p(keep.data_ptr()) if keep is not None else None, self._stream()))
-        return (ids, scores, bboxes, keep) if return_index else (ids, scores, bboxes)
-
-    def _single_rank(self):
-        from . import parallel
-        if parallel.world_size() > 1:
-            raise NotImplementedError("multi-rank training of a heads-only net (yolo3_no_backbone) is not supported: "
-                                      "train it on one rank")
-
-    def forward_train(self, f1, f2, f3, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t):
-        """Recording branch: the four (B,) losses; ``autograd.backward`` walks the heads afterwards."""
-        torch = _torch()
-        self._single_rank()
-        fs, (b, h, w) = self._as_routes(f1, f2, f3)
-        tg = [self._dev(t) for t in (gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)]
-        m = int(tg[0].shape[1])
-        with torch.cuda.device(self._device):
-            self._ensure_plan(b, h, w, train=True)
-            n = self._lib.vy_net_num_anchors(self._h)
-            c = len(self._classes)
-            want = [(b, m, 4), (b, n, 1), (b, n, 2), (b, n, 2), (b, n, 2), (b, n, c)]
-            for t, shp in zip(tg, want):
-                if tuple(t.shape) != shp:
-                    raise ValueError("target shape %s, expected %s" % (tuple(t.shape), shp))
-            _lib.check(self._lib.vy_net_set_train_options(
-                self._h, self._ignore_iou_thresh, int(bool(self._target_generator._label_smooth))))
-            losses = torch.empty((4, b), dtype=torch.float32, device=self._device)
-            p = [ctypes.c_void_p(t.data_ptr()) for t in tg]
-            _lib.check(self._lib.vy_net_train_forward_routes(
-                self._h, *[ctypes.c_void_p(f.data_ptr()) for f in fs], p[0], m, p[1], p[2], p[3], p[4], p[5],
-                ctypes.c_void_p(losses.data_ptr()), self._stream()))
-        self._train_x = fs
-        autograd._register(self)
-        return tuple(autograd.loss_vector(losses[i], self, i) for i in range(4))
-
-    def backward(self):
-        torch = _torch()
-        if self._train_x is None:
-            raise RuntimeError("backward() without a recorded forward")
-        with torch.cuda.device(self._device):
-            _lib.check(self._lib.vy_net_train_backward_routes(
-                self._h, *[ctypes.c_void_p(f.data_ptr()) for f in self._train_x], self._stream()))
-        self._train_x = None
-
-    def forward_train_mode(self, f1, f2, f3):
-        """``autograd.train_mode()`` without recording: the 8-tuple of ``YOLOV3.forward_train_mode``."""
-        torch = _torch()
-        self._single_rank()
-        fs, (b, h, w) = self._as_routes(f1, f2, f3)
-        anchors, offsets, fms = [], [], []
-        for i, s in enumerate((32, 16, 8)):
-            hh, ww = h // s, w // s
-            anchors.append(np.array(self._ANCHORS[i], np.float32).reshape(1, 1, 3, 2))
-            gx, gy = np.meshgrid(np.arange(ww), np.arange(hh))
-            offsets.append(np.stack([gx, gy], -1).astype(np.float32).reshape(1, hh * ww, 1, 2))
-            fms.append(np.zeros((1, 1, hh, ww), np.float32))
-        with torch.cuda.device(self._device):
-            self._ensure_plan(b, h, w, train=True)
-            n = self._lib.vy_net_num_anchors(self._h)
-            c = len(self._classes)
-            outs = [torch.empty((b, n, k), dtype=torch.float32, device=self._device) for k in (4, 2, 2, 1, c)]
-            _lib.check(self._lib.vy_net_train_mode_forward_routes(
-                self._h, *[ctypes.c_void_p(f.data_ptr()) for f in fs], *[ctypes.c_void_p(t.data_ptr()) for t in outs],
-                self._stream()))
-        return (outs[0], anchors, offsets, fms, outs[1], outs[2], outs[3], outs[4])
+            outs = self._detect_outputs(b, self._out_rows(), return_index)
+            _lib.check(self._lib.vy_net_forward_infer_routes(self._h, *_ptrs(tuple(fs) + outs), self._stream()))
+        return outs if return_index else outs[:3]
 
     def _no_image(self, *args, **kwargs):
         raise NotImplementedError("a heads-only net (yolo3_no_backbone) takes route tensors, not images")
@@ -1125,9 +1050,12 @@ class YOLOV3Window(YOLOV3):
     frame ``b * k + t``), each route is pooled over the clip's k frames (``TemporalPooling`` 'direct': max or mean) and
     the ordinary heads run on the B clips.  Targets, losses and detections are per clip.  BatchNorm normalises over the
     ``B * k`` frames in the stages and over the B clips in the heads.  The parameters are the single-frame net's tensors;
-    stage keys carry ``TimeDistributed``'s child, ``stages.N.model.<rest>``, as in the reference's files."""
+    stage keys carry ``TimeDistributed``'s child, ``stages.N.model.<rest>``, as in the reference's files.
+    ``load_parameters`` / ``set_parameters`` also accept a single-frame (k = 1) file: its stage keys lack ``.model.`` but
+    name the same tensors, so a window model starts from a trained single-frame one this way."""
 
     _CREATE = "vy_net_create_window"
+    _ONE_RANK = "a window net (yolo3_darknet53 with k > 1)"
     _JOINS = {"max": _lib.VY_JOIN_MAX, "mean": _lib.VY_JOIN_MEAN}
     _STAGE_RE = re.compile(r"^(stages\.\d+)\.(?!model\.)")
 
@@ -1172,11 +1100,6 @@ class YOLOV3Window(YOLOV3):
         super().set_parameters(OrderedDict((self._key(k), v) for k, v in arrays.items()), allow_missing=allow_missing,
                                ignore_extra=ignore_extra)
 
-    def load_parameters(self, filename, ctx=None, allow_missing=False, ignore_extra=False):
-        """Both containers, as ``YOLOV3.load_parameters``.  Also accepts a single-frame (k = 1) file: its stage keys
-        lack ``.model.`` but name the same tensors, so a window model starts from a trained single-frame one this way."""
-        super().load_parameters(filename, ctx=ctx, allow_missing=allow_missing, ignore_extra=ignore_extra)
-
     def _as_input(self, x):
         shape = tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
         if len(shape) != 5 or shape[1] != self._k or shape[2] != 3:
@@ -1185,20 +1108,6 @@ class YOLOV3Window(YOLOV3):
         if not isinstance(x, torch.Tensor):
             x = torch.as_tensor(np.asarray(x, np.float32))
         return super()._as_input(x.reshape((-1,) + shape[2:])).view(shape)
-
-    def _single_rank(self):
-        from . import parallel
-        if parallel.world_size() > 1:
-            raise NotImplementedError("multi-rank training of a window net (yolo3_darknet53 with k > 1) is not supported: "
-                                      "train it on one rank")
-
-    def forward_train(self, x, *args):
-        self._single_rank()
-        return super().forward_train(x, *args)
-
-    def forward_train_mode(self, x):
-        self._single_rank()
-        return super().forward_train_mode(x)
 
     # ---- over a whole video: the backbone once per frame (videoyolo_amd/video.py)
     _video = None  # the VideoSession that holds the workspace binding, if one does

@@ -15,6 +15,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .model import _ptrs
 
 
 def window_indices(n_frames, k, step=1):
@@ -168,21 +169,13 @@ class VideoSession:
 
     def raw_detect(self, table, return_index=False):
         """``vy_net_video_detect``: table (B, k) slots; outputs at batch B."""
-        import torch
         net, b = self._net, self._sched.B
         flat = [int(v) for row in table for v in row]
         if len(flat) != b * net.k:
             raise ValueError("slot table of %d entries, expected %d x %d" % (len(flat), b, net.k))
-        rows = net._out_rows()
-        ids = torch.empty((b, rows, 1), dtype=torch.float32, device=net._device)
-        scores = torch.empty((b, rows, 1), dtype=torch.float32, device=net._device)
-        bboxes = torch.empty((b, rows, 4), dtype=torch.float32, device=net._device)
-        keep = torch.empty((b, rows), dtype=torch.int32, device=net._device) if return_index else None
-        _lib.check(net._lib.vy_net_video_detect(
-            net._h, (ctypes.c_int32 * len(flat))(*flat), ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
-            ctypes.c_void_p(bboxes.data_ptr()), ctypes.c_void_p(keep.data_ptr()) if keep is not None else None,
-            net._stream()))
-        return (ids, scores, bboxes, keep) if return_index else (ids, scores, bboxes)
+        outs = net._detect_outputs(b, net._out_rows(), return_index)
+        _lib.check(net._lib.vy_net_video_detect(net._h, (ctypes.c_int32 * len(flat))(*flat), *_ptrs(outs), net._stream()))
+        return outs if return_index else outs[:3]
 
     def slot_of(self, frame):
         """Ring slot that holds (or held) frame `frame` of the current video."""
@@ -197,24 +190,13 @@ class VideoSession:
         outs = [torch.empty((1, c, -(-h // s), -(-w // s)), dtype=torch.float32, device=net._device)
                 for c, s in ((256, 8), (512, 16), (1024, 32))]
         with torch.cuda.device(net._device):
-            _lib.check(net._lib.vy_net_video_read_slot(net._h, int(slot), *[ctypes.c_void_p(t.data_ptr()) for t in outs],
-                                                       net._stream()))
+            _lib.check(net._lib.vy_net_video_read_slot(net._h, int(slot), *_ptrs(outs), net._stream()))
         return tuple(outs)
 
     def read_activation(self, name):
         """``net.read_activation`` on the video plan (needs ``net.keep_activations()`` before the session is opened): a
         stage cell's tap has the F frames of the last push, ``pool.i`` and the head cells the B clips of the last detect."""
-        import torch
-        net = self._net
-        c, h, w = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(net._lib.vy_net_read_activation(net._h, name.encode(), None, ctypes.byref(c), ctypes.byref(h),
-                                                   ctypes.byref(w), None))
-        n = self._sched.F if name.startswith("stages.") else self._sched.B
-        out = torch.empty((n, c.value, h.value, w.value), dtype=torch.float32, device=net._device)
-        with torch.cuda.device(net._device):
-            _lib.check(net._lib.vy_net_read_activation(net._h, name.encode(), ctypes.c_void_p(out.data_ptr()), None, None,
-                                                       None, net._stream()))
-        return out
+        return self._net._read_tap(name, self._sched.F if name.startswith("stages.") else self._sched.B)
 
     # ------------------------------------------------------------------ the session
     def _as_frames(self, frames):
@@ -250,13 +232,8 @@ class VideoSession:
         net = self._net
         if outs:
             return tuple(torch.cat(ts, 0) for ts in zip(*outs))
-        rows = net._out_rows() if self._bound else 0
-        empty = [torch.empty((0, rows, 1), dtype=torch.float32, device=net._device),
-                 torch.empty((0, rows, 1), dtype=torch.float32, device=net._device),
-                 torch.empty((0, rows, 4), dtype=torch.float32, device=net._device)]
-        if return_index:
-            empty.append(torch.empty((0, rows), dtype=torch.int32, device=net._device))
-        return tuple(empty)
+        outs = net._detect_outputs(0, net._out_rows() if self._bound else 0, return_index)
+        return outs if return_index else outs[:3]
 
     def push(self, frames, return_index=False):
         """Store ``frames`` ((n, 3, H, W), host or device, n >= 1) and return ``(ids, scores, bboxes)`` of every frame whose
