@@ -61,25 +61,7 @@ static vy_net* create(int32_t num_class, bool heads_only, int32_t k, int32_t joi
 
 // ---- the inference entries: each is the sequence of vy_net steps it documents in vyolo.h, inside one shared frame
 static NoHook plain;  // of every entry but vy_net_profile_infer, which has its own
-// The frame's checks, before anything is launched: arguments, bound, and for a video entry (named) bound for video
-static int entry_ready(vy_net* net, bool args_ok, const char* video_entry) {
-  int rc = 0;
-  if (!net || !args_ok) rc = fail(VY_ERR_INVALID, "null argument");
-  if (rc == 0) rc = net->check_ready(video_entry != nullptr);
-  if (rc == 0 && video_entry && !net->video_F)
-    rc = fail(VY_ERR_STATE, "%s: the net is not bound for video (vy_net_bind_video)", video_entry);
-  if (rc && net) net->sk_dirty = true;  // (any error return: see vy_net::sk_dirty)
-  return rc;
-}
-// ... then the stream-K flags zeroed if an earlier call left them dirty, and `run(stream)`: the launches
-template <typename Run>
-static int run_entry(vy_net* net, bool args_ok, const char* video_entry, void* stream, Run&& run) {
-  VY_TRY(entry_ready(net, args_ok, video_entry));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc = net->sk_begin(s);
-  if (rc == 0) rc = run(s);
-  return net->sk_end(rc);
-}
+// (run_entry / entry_ready: net_internal.h, shared with the training entries)
 
 // vy_net_forward_infer and vy_net_profile_infer: stem and stages, the pooling of a window net, heads, detection tail
 template <typename Hook>

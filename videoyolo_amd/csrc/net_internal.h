@@ -624,13 +624,26 @@ struct vy_net {
     a.dgrad = 0;
     a.w_split = c.split_off >= 0 ? dev_ws + wsplit_off + c.split_off : nullptr;
     a.w_wino = c.wino_off >= 0 ? dev_ws + wsplit_off + c.wino_off : nullptr;
-    a.knobs = &knobs;
+    launch_env(a, /*k_runs=*/true, /*splitk=*/true);
+    return a;
+  }
+
+  // the stem launch of conv `c` on the image batch `x`: the folded BatchNorm affine into the activation plane (run_cells adds
+  // the fold that may ride in it; the training forward turns it into the raw launch that writes z)
+  StemArgs stem_args(const ConvT& c, const float* x) const {
+    StemArgs a;
+    a.x = x;
+    a.w = dev_params + params[c.p_weight].info.offset;
+    a.scale = dev_params + c.scale_off;
+    a.shift = dev_params + c.shift_off;
+    a.out = plane_ptr(c.out_plane);
+    a.B = conv_batch(c);
+    a.H = H;
+    a.W = W;
+    a.Cout = c.cout;
+    a.out_cs = planes[c.out_plane].C;
+    a.out_co = c.out_co;
     a.cus = cus;
-    a.ck_scratch = ck_bytes ? reinterpret_cast<float*>(dev_ws + ck_off) : nullptr;
-    a.ck_bytes = ck_bytes;
-    a.splitk_slabs = reinterpret_cast<float*>(dev_ws + sk_off + al((size_t)VY_SK_FLAGS * sizeof(unsigned)));
-    a.splitk_bytes = VY_SK_PARTIAL_BYTES;
-    set_sk(a);
     return a;
   }
 
@@ -658,12 +671,25 @@ struct vy_net {
     return rc;
   }
 
-  // the stream-K scratch of this net's workspace (zeroed with the workspace at bind time: all flags down); left null —
-  // plain launches only — unless the device's workgroup placement was verified
-  void set_sk(ConvArgs& a) const {
+  // The launch environment of a conv launch, forward or data gradient: the net's switches and CU count (the cost models read
+  // them) and the scratch it may use — k_runs: the parked chains of a K summed in runs; splitk: the split-fp32 kernel's
+  // split-K slabs (in the stream-K region); and the stream-K scratch of this net's workspace (zeroed at bind time: all flags
+  // down), left null — plain launches only — unless the device's workgroup placement was verified
+  void launch_env(ConvArgs& a, bool k_runs, bool splitk) const {
+    a.knobs = &knobs;
+    a.cus = cus;
+    float* const sk_slabs = reinterpret_cast<float*>(dev_ws + sk_off + al((size_t)VY_SK_FLAGS * sizeof(unsigned)));
+    if (k_runs) {
+      a.ck_scratch = ck_bytes ? reinterpret_cast<float*>(dev_ws + ck_off) : nullptr;
+      a.ck_bytes = ck_bytes;
+    }
+    if (splitk) {
+      a.splitk_slabs = sk_slabs;
+      a.splitk_bytes = VY_SK_PARTIAL_BYTES;
+    }
     if (!sk_ok) return;
     a.sk_flags = reinterpret_cast<unsigned*>(dev_ws + sk_off);
-    a.sk_partials = reinterpret_cast<float*>(dev_ws + sk_off + al((size_t)VY_SK_FLAGS * sizeof(unsigned)));
+    a.sk_partials = sk_slabs;
     a.sk_bytes = VY_SK_PARTIAL_BYTES;
     a.sk_nflags = VY_SK_FLAGS;
   }
@@ -765,20 +791,8 @@ struct vy_net {
     for (int ci = first; ci < last; ++ci) {
       const ConvT& c = convs[ci];
       if (c.is_stem) {
-        const int Bs = conv_batch(c);
-        StemArgs a;
-        a.x = x;
-        a.w = dev_params + params[c.p_weight].info.offset;
-        a.scale = dev_params + c.scale_off;
-        a.shift = dev_params + c.shift_off;
-        a.out = plane_ptr(c.out_plane);
-        a.B = Bs;
-        a.H = H;
-        a.W = W;
-        a.Cout = c.cout;
-        a.out_cs = planes[c.out_plane].C;
-        a.out_co = c.out_co;
-        a.cus = cus;
+        StemArgs a = stem_args(c, x);
+        const int Bs = a.B;
         if (fold_in_stem) {
           a.fold_params = dev_params;
           a.fold_descs = reinterpret_cast<FoldDesc*>(dev_ws + fold_desc_off);
@@ -882,6 +896,27 @@ struct vy_net {
     return 0;
   }
 };
+
+// ---- the frame of every entry point that launches a sequence of steps, inference (net.hip) and training (train.hip)
+// The frame's checks, before anything is launched: arguments, bound, and for a video entry (named) bound for video
+inline int entry_ready(vy_net* net, bool args_ok, const char* video_entry) {
+  int rc = 0;
+  if (!net || !args_ok) rc = fail(VY_ERR_INVALID, "null argument");
+  if (rc == 0) rc = net->check_ready(video_entry != nullptr);
+  if (rc == 0 && video_entry && !net->video_F)
+    rc = fail(VY_ERR_STATE, "%s: the net is not bound for video (vy_net_bind_video)", video_entry);
+  if (rc && net) net->sk_dirty = true;  // (any error return: see vy_net::sk_dirty)
+  return rc;
+}
+// ... then the stream-K flags zeroed if an earlier call left them dirty, and `run(stream)`: the launches
+template <typename Run>
+int run_entry(vy_net* net, bool args_ok, const char* video_entry, void* stream, Run&& run) {
+  VY_TRY(entry_ready(net, args_ok, video_entry));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int rc = net->sk_begin(s);
+  if (rc == 0) rc = run(s);
+  return net->sk_end(rc);
+}
 
 // the pooled route `name` = "pool.<i>" of a window net (the taps of vy_net_read_activation / read_grad_activation): 0..2, or -1
 inline int vy_pool_tap(const vy_net* net, const char* name) {

@@ -11,16 +11,46 @@
 //   overwrites z) -> wgrad (split-K slabs + ordered reduce) -> dgrad into the input's gradient plane
 //   (overwrite, or accumulate when the plane already holds another consumer's contribution, plus
 //   the skip connection's gradient as an addend).
+// plan_train computes one TrainPlan (regions, a TrainCell per conv, tables); the passes are sequences of per-cell steps that
+// read it; the six step entries share the run_entry frame of the inference entries.
 #include <cstdlib>
 
 #include "net_internal.h"
 
 namespace {
 
-struct ZPlane {
-  int C = 0;        // channel stride (Cout padded to 4; 0 = none)
-  size_t off = 0;   // float offset in the z region
-  int H = 0, W = 0;
+// One conv at the planned shape.  Its geometry is derived in plan_train and nowhere else: the pixel tables, both passes, the
+// taps and vy_net_train_conv_plan read it (training sizes are multiples of 32: it agrees with the planes' ceil(input / div))
+struct TrainCell {
+  int B = 0, Ho = 0, Wo = 0;  // frames the conv runs on (a window net's backbone: b * k) and its output size
+  long long M = 0;            // B * Ho * Wo output pixels
+  int z_cs = 0;               // BatchNorm cells: channel stride of the raw-output plane z (0: none) ...
+  size_t z_off = 0;           // ... its float offset in the z region
+  size_t save_off = 0;        // ... and the float offset of the saved [mean | invstd] rows in the save region
+  int splits = 1, k_per_split = 32;  // weight-gradient split-K
+  size_t tab_off = 0;         // byte offset of its weight-gradient pixel table in the workspace
+  // conv mode VY_CONV_SPLIT_BF16X3_TRAIN: byte offset of its weights' DATA-GRADIENT tile images ([k = cout][n = cin]
+  // operand; conv_split.hip) in the region at TrainPlan::dsplit_off, -1: none.  The forward images are the net's.
+  long long dsplit = -1;
+  // the split-fp32 routing, decided once from (conv mode, VY_SPLIT_TRAIN): does the forward launch of this cell carry its
+  // split images, does its data gradient (the cost model has the last word)
+  bool fwd_split = false, dgrad_split = false;
+  int bucket = 0;             // gradient bucket: 0 heads, 1 stages.2, 2 stages.1, 3 stages.0
+};
+
+struct TrainPlan {
+  int B = 0, H = 0, W = 0;
+  // regions: byte offsets in the workspace, behind the inference plan
+  size_t dsplit_off = 0, g_off = 0, z_off = 0, save_off = 0, coef_off = 0, sums_off = 0, slice_off = 0, part_off = 0;
+  size_t slab_off = 0, loss_part_off = 0, loss_off = 0, zero_off = 0, sdesc_off = 0, seg_off = 0, chunk_off = 0, total = 0;
+  std::vector<TrainCell> cells;  // per conv
+  // all image sets (forward + data gradient) for the one-launch rebuild (the forward ones are the net's: committed plans only)
+  std::vector<SplitDesc> sdesc;
+  long long sdesc_total = 0;
+  std::vector<SgdSeg> segs;
+  std::vector<int32_t> chunk_seg;
+  // gradient buckets (contiguous parameter ranges, by TrainCell::bucket): first element, length (0: no such bucket)
+  int64_t bucket_lo[4] = {0, 0, 0, 0}, bucket_len[4] = {0, 0, 0, 0};
 };
 
 struct BwdDgrad {
@@ -30,32 +60,14 @@ struct BwdDgrad {
 
 }  // namespace
 
+// what outlives a plan: buffers, options, callbacks, the side stream — and the committed plan with its upload flags
 struct VyTrain {
-  int B = 0, H = 0, W = 0;
+  TrainPlan plan;
+  bool sdesc_uploaded = false, tabs_built = false, seg_uploaded = false;
   float* grads = nullptr;
   float* mom = nullptr;
   float ignore_iou = 0.7f;
   int label_smooth = 0;
-  // regions (byte offsets in the workspace)
-  size_t g_off = 0, z_off = 0, save_off = 0, coef_off = 0, sums_off = 0, slice_off = 0, part_off = 0, slab_off = 0;
-  size_t loss_part_off = 0, loss_off = 0, zero_off = 0, seg_off = 0, chunk_off = 0, total = 0;
-  size_t part_floats = 0, slab_floats = 0;
-  std::vector<ZPlane> z;               // per conv
-  std::vector<size_t> save_idx;        // per conv: float offset of [2][C] saved mean/invstd
-  std::vector<int> splits, kps;        // per conv wgrad split-K
-  // conv mode VY_CONV_SPLIT_BF16X3: per conv, byte offset of its weights' DATA-GRADIENT tile images ([k = cout][n = cin]
-  // operand; conv_split.hip) inside the region at dsplit_off, -1: exact kernel.  The forward images are the net's.
-  std::vector<long long> dsplit;
-  size_t dsplit_off = 0;
-  std::vector<SplitDesc> sdesc;        // all image sets (forward + data gradient) for the one-launch rebuild
-  size_t sdesc_off = 0;
-  long long sdesc_total = 0;
-  bool sdesc_uploaded = false;
-  std::vector<size_t> tab_off;         // per conv: byte offset of its weight-gradient pixel table in the workspace
-  bool tabs_built = false;
-  std::vector<SgdSeg> segs;
-  std::vector<int32_t> chunk_seg;
-  bool seg_uploaded = false;
   std::vector<float> lr_mult, wd_mult;
   std::vector<int> enabled;
   // SyncBN
@@ -83,20 +95,16 @@ void vy_train_free(vy_net* net) {
 
 namespace {
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Profiling aid (tools/train_layers.py): with VY_TRAIN_LABELS=<path> the first training step appends one line per
 // matrix-core launch — kind (fwd / wgrad / dgrad), cell name, FLOPs, GEMM dims — so that a rocprofv3 kernel trace
-// can be joined with the layers by launch order within each kernel class.
+// can be joined with the layers by launch order within each kernel class.  Once per process: `done`.
 struct LabelLog {
   FILE* f = nullptr;
-  bool open_once(const vy_net* net) {
-    if (net->knobs.train_labels.empty()) return false;
-    if (!f) f = fopen(net->knobs.train_labels.c_str(), "w");
-    return f != nullptr;
-  }
+  bool done = false;
   void note(const vy_net* net, const char* kind, const std::string& name, double M, double N, double K) {
-    if (open_once(net)) fprintf(f, "%s %s %.0f %.0f %.0f %.0f\n", kind, name.c_str(), 2.0 * M * N * K, M, N, K);
+    if (done || net->knobs.train_labels.empty()) return;
+    if (!f) f = fopen(net->knobs.train_labels.c_str(), "w");
+    if (f) fprintf(f, "%s %s %.0f %.0f %.0f %.0f\n", kind, name.c_str(), 2.0 * M * N * K, M, N, K);
   }
   // "# via split 128x128 k2" / "# via exact": which kernel the preceding fwd / dgrad line went to (tests assert that the
   // launches they mean to cover really ran; tools/train_layers.py skips '#' lines)
@@ -104,14 +112,13 @@ struct LabelLog {
     if (f) fprintf(f, "# via %s\n", text);
   }
   void close_step() {
-    if (f) {
-      fclose(f);
-      f = nullptr;
-    }
+    if (!f) return;
+    fclose(f);
+    f = nullptr;
+    done = true;
   }
 };
 LabelLog g_labels;
-bool g_labels_done = false;
 
 // Measurement aid (tools/ab_bn_bounds.sh): VY_TRAIN_ABL skips BatchNorm launches of the training step to BOUND what
 // fusing them into the neighbouring conv launches could return — bit 1: bn_bwd_reduce (+ its finalize), 2: the forward
@@ -147,246 +154,219 @@ VyTrain* get_train(vy_net* net) {
   return net->train;
 }
 
-// plan the training regions behind the inference workspace
-size_t train_plan(vy_net* net, int b, int h, int w, bool commit) {
-  VyTrain* t = get_train(net);
-  size_t off = al256(net->plan(b, h, w, commit, /*keep_all=*/true));  // backward reads every activation plane
-  // split-fp32 conv mode: the data gradients whose N (= cin) the split kernel has a tile for get their own weight images
-  std::vector<long long> dsplit(net->convs.size(), -1);
-  const size_t dsplit_off = off;
-  if (net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN) {
-    for (size_t i = 0; i < net->convs.size() && net->knobs.split_train; ++i) {
-      const ConvT& c = net->convs[i];
-      if (c.is_stem || c.cin % 64 != 0) continue;
-      dsplit[i] = (long long)(off - dsplit_off);
-      off += al256(vy_split_weight_dgrad_bytes(c.cout, c.k * c.k, c.cin));
+// Split-K of a weight gradient over its M pixels.  A block runs k_per_split / 32 k-steps (+ ~3 k-steps worth of prologue
+// and slab store); the chip holds `held` blocks at a time (2 per CU: 512 on the MI355X), so the launch costs about
+// ceil(tiles * splits / held) * (k_per_split / 32 + 3).  Round 1 took the smallest split count with >= 1024
+// blocks, which for the three big 3x3 groups lands just past a multiple of 512 (18 x 57 = 1026,
+// 72 x 15 = 1080, 288 x 4 = 1152 blocks): a last round of a few blocks with the chip idle around them.  Now the
+// cheapest (splits, k_per_split) under that model is taken; a split is >= 256 pixels.
+void wgrad_split_k(long long M, long long tiles, long long held, int* splits, int* k_per_split) {
+  const long long whole = ((M + 31) / 32) * 32;
+  long long best_k = whole, best_sp = 1;
+  double best_cost = 1e300;
+  for (long long k = 256; k <= whole && M >= 256; k += 32) {
+    const long long sp_k = (M + k - 1) / k;
+    const long long rounds = (tiles * sp_k + held - 1) / held;
+    const double cost = (double)rounds * ((double)k / 32.0 + 3.0);
+    if (cost < best_cost) {
+      best_cost = cost;
+      best_k = k;
+      best_sp = sp_k;
+    }
+  }
+  *splits = (int)best_sp;
+  *k_per_split = (int)best_k;
+}
+
+// The training regions behind the inference workspace, and everything the step derives from the shape.  Reads the
+// per-parameter options of `opt`, writes nothing but the net's own plan (vy_net::plan, when commit).
+TrainPlan plan_train(vy_net* net, const VyTrain& opt, int b, int h, int w, bool commit) {
+  TrainPlan p;
+  p.B = b;
+  p.H = h;
+  p.W = w;
+  struct {  // carves 256-byte aligned regions off the workspace, in call order
+    size_t off;
+    size_t take(size_t bytes) { return std::exchange(off, off + vy_net::al(bytes)); }
+  } ws{vy_net::al(net->plan(b, h, w, commit, /*keep_all=*/true))};  // backward reads every activation plane
+  const size_t n = net->convs.size();
+  p.cells.resize(n);
+  // split-fp32 training mode: the data gradients whose N (= cin) the split kernel has a tile for get their own weight
+  // images — whenever VY_SPLIT_TRAIN != 0, the forward-only mode 2 included, which does not launch with them
+  const int st = net->knobs.split_train;  // 0 none, 1 both, 2 forward only, 3 dgrad only
+  const bool images = net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && st != 0;
+  p.dsplit_off = ws.off;
+  for (size_t i = 0; i < n; ++i) {
+    const ConvT& c = net->convs[i];
+    TrainCell& cell = p.cells[i];
+    const int div_in = c.is_stem ? 1 : net->planes[c.in_plane].div;
+    cell.B = b * net->planes[c.out_plane].fm;
+    cell.Ho = h / div_in / c.stride;
+    cell.Wo = w / div_in / c.stride;
+    cell.M = (long long)cell.B * cell.Ho * cell.Wo;
+    cell.bucket = c.name.rfind("stages.2", 0) == 0 ? 1 : c.name.rfind("stages.1", 0) == 0 ? 2 : c.name.rfind("stages.0", 0) == 0 ? 3 : 0;
+    cell.fwd_split = images && st != 3 && net->split_eligible(c);
+    if (images && !c.is_stem && c.cin % 64 == 0) {
+      cell.dsplit = (long long)(ws.take(vy_split_weight_dgrad_bytes(c.cout, c.k * c.k, c.cin)) - p.dsplit_off);
+      cell.dgrad_split = st != 2;
     }
   }
   // gradient planes mirror the activation planes
   size_t gfl = 0;
-  for (auto& p : net->planes) gfl += ((size_t)b * p.fm * (h / p.div + 2) * (w / p.div + 2) * p.C + 63) & ~(size_t)63;
-  const size_t g_off = off;
-  off += al256(gfl * sizeof(float));
-  // z planes: one per BN conv
-  std::vector<ZPlane> z(net->convs.size());
-  std::vector<size_t> save(net->convs.size(), 0);
-  std::vector<int> splits(net->convs.size(), 1), kps(net->convs.size(), 32);
+  for (auto& pl : net->planes) gfl += ((size_t)b * pl.fm * (h / pl.div + 2) * (w / pl.div + 2) * pl.C + 63) & ~(size_t)63;
+  p.g_off = ws.take(gfl * sizeof(float));
+  // z planes and saved statistics: one per BN conv; the partial-sum and slab scratch: the largest any conv needs
   size_t zfl = 0, sfl = 0, part = 0, slab = 0;
-  for (size_t i = 0; i < net->convs.size(); ++i) {
+  for (size_t i = 0; i < n; ++i) {
     const ConvT& c = net->convs[i];
-    const int div_in = c.is_stem ? 1 : net->planes[c.in_plane].div;
-    const int Ho = h / div_in / c.stride, Wo = w / div_in / c.stride;
-    const int bc = b * net->planes[c.out_plane].fm;  // frames the conv runs on (a window net's backbone: b * k)
-    const long long M = (long long)bc * Ho * Wo;
+    TrainCell& cell = p.cells[i];
+    const long long M = cell.M;
+    const size_t chunks = (size_t)((M + kBwdChunk - 1) / kBwdChunk);
     if (c.p_gamma >= 0) {
-      z[i].C = c.cout;
-      z[i].H = Ho;
-      z[i].W = Wo;
-      z[i].off = zfl;
-      zfl += ((size_t)bc * (Ho + 2) * (Wo + 2) * c.cout + 63) & ~(size_t)63;
-      save[i] = sfl;
+      cell.z_cs = c.cout;
+      cell.z_off = zfl;
+      zfl += ((size_t)cell.B * (cell.Ho + 2) * (cell.Wo + 2) * c.cout + 63) & ~(size_t)63;
+      cell.save_off = sfl;
       sfl += 2 * (size_t)((c.cout + 63) & ~63);
       // partials: forward stats, backward sums
       const size_t tiles_m = (size_t)((M + 31) / 32);  // per-tile statistics rows, sized for 32-row tiles (every tile has more)
-      size_t pf = 2 * (c.is_stem ? (size_t)vy_stem_blocks(bc, h, w) * 64 : tiles_m * 2 * c.cout);  // doubles
-      const size_t chunks = (size_t)((M + kBwdChunk - 1) / kBwdChunk);
-      if (chunks * 2 * c.cout > pf) pf = chunks * 2 * c.cout;
+      size_t pf = 2 * (c.is_stem ? (size_t)vy_stem_blocks(cell.B, h, w) * 64 : tiles_m * 2 * c.cout);  // doubles
+      pf = std::max(pf, chunks * 2 * c.cout);
       // bn_bwd_reduce chunks by image rows, not by 64 pixels: ceil(B*Ho / rows_per_chunk) partial rows of 2*C
       // floats — more than the pixel-chunk bound on maps narrower than 64 pixels (W = 32 training shapes)
-      {
-        const int rpc = vy_bn_bwd_rows_per_chunk(bc, Ho, c.cout);
-        const size_t bwd_rows = (size_t)(((long long)bc * Ho + rpc - 1) / rpc);
-        if (bwd_rows * 2 * c.cout > pf) pf = bwd_rows * 2 * c.cout;
-      }
-      if (c.is_stem) {
-        const size_t sw = (size_t)vy_stem_wgrad_blocks(bc, h, w) * 864;
-        if (sw > pf) pf = sw;
-      }
-      if (pf > part) part = pf;
+      const int rpc = vy_bn_bwd_rows_per_chunk(cell.B, cell.Ho, c.cout);
+      pf = std::max(pf, (size_t)(((long long)cell.B * cell.Ho + rpc - 1) / rpc) * 2 * c.cout);
+      if (c.is_stem) pf = std::max(pf, (size_t)vy_stem_wgrad_blocks(cell.B, h, w) * 864);
+      part = std::max(part, pf);
     } else {
-      const size_t chunks = (size_t)((M + kBwdChunk - 1) / kBwdChunk);
-      if (chunks * c.cout > part) part = chunks * c.cout;
+      part = std::max(part, chunks * c.cout);
     }
     if (!c.is_stem) {
       const int Ntot = c.k * c.k * c.cin;
       const int rows = vy_wgrad_tile_rows(c.cout, c.k, c.cin);
       const int tiles = ((c.cout + rows - 1) / rows) * ((Ntot + 127) / 128);
-      // Split-K over the pixels.  A block runs k_per_split / 32 k-steps (+ ~3 k-steps worth of prologue and slab
-      // store); the chip holds 512 blocks at a time (2 per CU), so the launch costs about
-      // ceil(tiles * splits / 512) * (k_per_split / 32 + 3).  Round 1 took the smallest split count with >= 1024
-      // blocks, which for the three big 3x3 groups lands just past a multiple of 512 (18 x 57 = 1026,
-      // 72 x 15 = 1080, 288 x 4 = 1152 blocks): a last round of a few blocks with the chip idle around them.  Now the
-      // cheapest (splits, k_per_split) under that model is taken; a split is >= 256 pixels.
-      long long best_k = ((M + 31) / 32) * 32, best_sp = 1;
-      double best_cost = 1e300;
-      const long long held = 2ll * net->resolve_cus();  // blocks the net's device holds at a time (512 on the MI355X)
-      for (long long k = 256; k <= ((M + 31) / 32) * 32; k += 32) {
-        const long long sp_k = (M + k - 1) / k;
-        const long long rounds = (tiles * sp_k + held - 1) / held;
-        const double cost = (double)rounds * ((double)k / 32.0 + 3.0);
-        if (cost < best_cost) {
-          best_cost = cost;
-          best_k = k;
-          best_sp = sp_k;
-        }
-      }
-      if (M < 256) {
-        best_k = ((M + 31) / 32) * 32;
-        best_sp = 1;
-      }
-      const long long sp = best_sp;
-      splits[i] = (int)sp;
-      kps[i] = (int)best_k;
-      const size_t sl = (size_t)sp * c.cout * Ntot;
-      if (sl > slab) slab = sl;
+      wgrad_split_k(M, tiles, 2ll * net->resolve_cus(), &cell.splits, &cell.k_per_split);
+      slab = std::max(slab, (size_t)cell.splits * c.cout * Ntot);
     }
   }
-  const size_t z_off = off;
-  off += al256(zfl * sizeof(float));
-  const size_t save_off = off;
-  off += al256(sfl * sizeof(float));
-  const size_t coef_off = off;
-  off += al256(3 * 1024 * sizeof(float));
-  const size_t sums_off = off;
-  off += al256(2 * 2 * 1024 * sizeof(double));  // [global | local] x [2][C]
-  const size_t slice_off = off;
-  off += al256((size_t)VY_REDUCE_SLICES * 2 * 1024 * sizeof(double));  // slice sums of long per-tile statistics lists
-  const size_t part_off = off;
-  off += al256(part * sizeof(float));
-  const size_t slab_off = off;
-  off += al256(slab * sizeof(float));
+  p.z_off = ws.take(zfl * sizeof(float));
+  p.save_off = ws.take(sfl * sizeof(float));
+  p.coef_off = ws.take(3 * 1024 * sizeof(float));
+  p.sums_off = ws.take(2 * 2 * 1024 * sizeof(double));  // [global | local] x [2][C]
+  p.slice_off = ws.take((size_t)VY_REDUCE_SLICES * 2 * 1024 * sizeof(double));  // slice sums of long per-tile statistics lists
+  p.part_off = ws.take(part * sizeof(float));
+  p.slab_off = ws.take(slab * sizeof(float));
   int N = 0;
   for (int i = 0; i < 3; ++i) {
     const int dv = net->planes[net->head_plane[i]].div;
     N += 3 * (h / dv) * (w / dv);
   }
-  const size_t loss_part_off = off;
-  off += al256((size_t)vy_loss_blocks_per_image(N) * b * 4 * sizeof(float));
-  const size_t loss_off = off;
-  off += al256((size_t)4 * b * sizeof(float));
-  const size_t zero_off = off;
-  off += 1024;
+  p.loss_part_off = ws.take((size_t)vy_loss_blocks_per_image(N) * b * 4 * sizeof(float));
+  p.loss_off = ws.take((size_t)4 * b * sizeof(float));
+  p.zero_off = ws.take(1024);
   // SGD segment tables
-  std::vector<SgdSeg> segs;
-  std::vector<int32_t> chunk_seg;
   for (size_t i = 0; i < net->params.size(); ++i) {
     const vy_param_info& pi = net->params[i].info;
-    SgdSeg sg;
-    sg.off = pi.offset;
-    sg.size = pi.size;
-    sg.lr_mult = t->lr_mult[i];
-    sg.wd_mult = t->wd_mult[i];
-    sg.enabled = (pi.trainable && t->enabled[i]) ? 1 : 0;
-    sg.pad = 0;
     if (!pi.trainable) continue;
-    const int32_t si = (int32_t)segs.size();
-    segs.push_back(sg);
+    const int32_t si = (int32_t)p.segs.size();
+    p.segs.push_back(SgdSeg{pi.offset, pi.size, opt.lr_mult[i], opt.wd_mult[i], opt.enabled[i] ? 1 : 0, 0});
     const int nch = (int)((pi.size + VY_SGD_CHUNK - 1) / VY_SGD_CHUNK);
     for (int c = 0; c < nch; ++c) {
-      chunk_seg.push_back(si);
-      chunk_seg.push_back(c);
+      p.chunk_seg.push_back(si);
+      p.chunk_seg.push_back(c);
     }
   }
   // weight-gradient pixel tables (wgrad.hip): 8 bytes per output pixel of every conv but the stem
-  std::vector<size_t> tab_off(net->convs.size(), 0);
-  for (size_t i = 0; i < net->convs.size(); ++i) {
+  for (size_t i = 0; i < n; ++i)
+    if (!net->convs[i].is_stem) p.cells[i].tab_off = ws.take(vy_wgrad_table_entries(p.cells[i].M) * 8);
+  p.sdesc_off = ws.take(sizeof(SplitDesc) * 2 * n);
+  p.seg_off = ws.take(p.segs.size() * sizeof(SgdSeg));
+  p.chunk_off = ws.take(p.chunk_seg.size() * sizeof(int32_t));
+  p.total = ws.off;
+  // the image sets and the gradient buckets' parameter ranges
+  int64_t lo[4] = {INT64_MAX, INT64_MAX, INT64_MAX, INT64_MAX}, hi[4] = {0, 0, 0, 0};
+  for (size_t i = 0; i < n; ++i) {
     const ConvT& c = net->convs[i];
-    if (c.is_stem) continue;
-    const int div_in = net->planes[c.in_plane].div;
-    const long long M = (long long)b * net->planes[c.out_plane].fm * (h / div_in / c.stride) * (w / div_in / c.stride);
-    tab_off[i] = off;
-    off += al256(vy_wgrad_table_entries(M) * 8);
-  }
-  const size_t sdesc_off = off;
-  off += al256(sizeof(SplitDesc) * 2 * net->convs.size());
-  const size_t seg_off = off;
-  off += al256(segs.size() * sizeof(SgdSeg));
-  const size_t chunk_off = off;
-  off += al256(chunk_seg.size() * sizeof(int32_t));
-  if (commit) {
-    t->B = b;
-    t->H = h;
-    t->W = w;
-    t->g_off = g_off;
-    t->z_off = z_off;
-    t->save_off = save_off;
-    t->coef_off = coef_off;
-    t->sums_off = sums_off;
-    t->slice_off = slice_off;
-    t->part_off = part_off;
-    t->slab_off = slab_off;
-    t->loss_part_off = loss_part_off;
-    t->loss_off = loss_off;
-    t->zero_off = zero_off;
-    t->seg_off = seg_off;
-    t->chunk_off = chunk_off;
-    t->part_floats = part;
-    t->slab_floats = slab;
-    t->z = z;
-    t->save_idx = save;
-    t->splits = splits;
-    t->kps = kps;
-    t->dsplit = dsplit;
-    t->dsplit_off = dsplit_off;
-    t->sdesc.clear();
-    t->sdesc_total = 0;
-    for (size_t i = 0; i < net->convs.size(); ++i) {
-      const ConvT& c = net->convs[i];
-      const long long w_off = net->params[c.p_weight].info.offset;
-      if (c.split_off >= 0) {
-        t->sdesc.push_back(SplitDesc{t->sdesc_total, w_off, (long long)(net->wsplit_off + c.split_off), c.cout, c.k * c.k, c.cin, 0});
-        t->sdesc_total += (long long)c.cout * c.k * c.k * c.cin / 8;
-      }
-      if (dsplit[i] >= 0) {
-        t->sdesc.push_back(SplitDesc{t->sdesc_total, w_off, (long long)(dsplit_off + dsplit[i]), c.cout, c.k * c.k, c.cin, 1});
-        t->sdesc_total += (long long)((c.cout + 31) & ~31) * c.k * c.k * c.cin / 8;
-      }
+    const TrainCell& cell = p.cells[i];
+    const long long w_off = net->params[c.p_weight].info.offset;
+    if (c.split_off >= 0) {
+      p.sdesc.push_back(SplitDesc{p.sdesc_total, w_off, (long long)(net->wsplit_off + c.split_off), c.cout, c.k * c.k, c.cin, 0});
+      p.sdesc_total += (long long)c.cout * c.k * c.k * c.cin / 8;
     }
-    t->sdesc_off = sdesc_off;
-    t->sdesc_uploaded = false;
-    t->tab_off = tab_off;
-    t->tabs_built = false;
-    t->segs = segs;
-    t->chunk_seg = chunk_seg;
-    t->seg_uploaded = false;
-    t->total = off;
+    if (cell.dsplit >= 0) {
+      p.sdesc.push_back(SplitDesc{p.sdesc_total, w_off, (long long)(p.dsplit_off + cell.dsplit), c.cout, c.k * c.k, c.cin, 1});
+      p.sdesc_total += (long long)((c.cout + 31) & ~31) * c.k * c.k * c.cin / 8;
+    }
+    for (int pidx : {c.p_weight, c.p_gamma, c.p_beta, c.p_bias}) {
+      if (pidx < 0) continue;
+      const vy_param_info& pi = net->params[pidx].info;
+      lo[cell.bucket] = std::min(lo[cell.bucket], pi.offset);
+      hi[cell.bucket] = std::max(hi[cell.bucket], pi.offset + ((pi.size + 63) & ~(int64_t)63));
+    }
   }
-  return off;
+  for (int k = 0; k < 4; ++k)
+    if (hi[k] > lo[k]) {
+      p.bucket_lo[k] = lo[k];
+      p.bucket_len[k] = hi[k] - lo[k];
+    }
+  return p;
 }
+
+// BatchNorm state of one cell: parameters, folded affine, the statistics saved for backward
+struct BnViews {
+  float *gamma, *beta, *running_mean, *running_var, *scale, *shift, *save_mean, *save_invstd;
+};
 
 struct TrainCtx {
   vy_net* net;
   VyTrain* t;
+  const TrainPlan& p;
   hipStream_t s;
-  float* gplane(int i) const { return reinterpret_cast<float*>(net->dev_ws + t->g_off) + net->planes[i].off; }
-  float* zplane(int ci) const { return reinterpret_cast<float*>(net->dev_ws + t->z_off) + t->z[ci].off; }
-  float* save(int ci) const { return reinterpret_cast<float*>(net->dev_ws + t->save_off) + t->save_idx[ci]; }
-  float* coef() const { return reinterpret_cast<float*>(net->dev_ws + t->coef_off); }
-  double* sums_global() const { return reinterpret_cast<double*>(net->dev_ws + t->sums_off); }
+  TrainCtx(vy_net* n, void* stream) : net(n), t(n->train), p(n->train->plan), s(static_cast<hipStream_t>(stream)) {}
+  template <typename T>
+  T* at(size_t off) const { return reinterpret_cast<T*>(net->dev_ws + off); }
+  const TrainCell& cell(int ci) const { return p.cells[ci]; }
+  float* gplanes() const { return at<float>(p.g_off); }
+  float* gplane(int i) const { return gplanes() + net->planes[i].off; }
+  float* zplane(int ci) const { return at<float>(p.z_off) + p.cells[ci].z_off; }
+  float* coef() const { return at<float>(p.coef_off); }
+  double* sums_global() const { return at<double>(p.sums_off); }
   double* sums_local() const { return sums_global() + 2 * 1024; }
-  double* slice_sums() const { return reinterpret_cast<double*>(net->dev_ws + t->slice_off); }
-  float* partials() const { return reinterpret_cast<float*>(net->dev_ws + t->part_off); }
-  float* slabs() const { return reinterpret_cast<float*>(net->dev_ws + t->slab_off); }
-  const float* zero() const { return reinterpret_cast<const float*>(net->dev_ws + t->zero_off); }
+  double* slice_sums() const { return at<double>(p.slice_off); }
+  float* partials() const { return at<float>(p.part_off); }
+  float* slabs() const { return at<float>(p.slab_off); }
+  float* param(int pidx) const { return net->dev_params + net->params[pidx].info.offset; }
   float* grad_of(int pidx) const { return t->grads + net->params[pidx].info.offset; }
+  BnViews bn_views(int ci) const {
+    const ConvT& cv = net->convs[ci];
+    float* save = at<float>(p.save_off) + p.cells[ci].save_off;
+    return {param(cv.p_gamma), param(cv.p_beta), param(cv.p_mean), param(cv.p_var), net->dev_params + cv.scale_off,
+            net->dev_params + cv.shift_off, save, save + ((cv.cout + 63) & ~63)};
+  }
 };
+
+NoHook plain;  // the shared vy_net steps of the forward run without a hook
 
 // SyncBatchNorm statistics are exchanged when there is more than one rank — or when a callback was installed for ONE rank
 // (videoyolo_amd.parallel with VY_FORCE_COLLECTIVES=1: the all-reduce over one rank is the identity; it exists so that the
 // whole exchange path, RCCL included, can be executed on a one-GPU box)
 static bool sync_exchange(const VyTrain* t) { return t->world > 1 || (t->world == 1 && t->ar_cb != nullptr); }
 
-// the sums the normalisation uses: the local ones, or (SyncBN layers, world > 1) their all-reduce
-int combine_sums(const TrainCtx& c, const ConvT& cv, int n_cols, double* count, const double** use) {
-  *use = c.sums_local();
-  if (sync_exchange(c.t) && is_sync_layer(cv)) {
-    if (!c.t->ar_cb) return fail(VY_ERR_STATE, "SyncBN world > 1 without an all-reduce callback");
-    HIP_TRY(hipMemcpyAsync(c.sums_global(), c.sums_local(), sizeof(double) * n_cols, hipMemcpyDeviceToDevice, c.s));
-    if (int rc = c.t->ar_cb(c.t->ar_user, c.sums_global(), n_cols))
-      return fail(VY_ERR_STATE, "all-reduce callback failed (%d)", rc);
-    *count *= c.t->world;
-    *use = c.sums_global();
-  }
+// The statistics hand-off of a BatchNorm cell, forward and backward alike: from the partial rows a pass left to the sums the
+// normalisation uses.  Ranks exchange statistics only for the SyncBatchNorm layers: `reduce_to_local` launches the ordered
+// reduce of the partial rows into sums_local(), the all-reduce gives *use = the global sums and *count samples over all
+// ranks, and the caller finalizes from them.  Everywhere else *use stays null: the ordered reduce of the partial rows and
+// the finalize are ONE launch, the caller's.
+template <typename Reduce>
+int combine_sums(const TrainCtx& c, const ConvT& cv, int n_cols, Reduce&& reduce_to_local, double* count, const double** use) {
+  *use = nullptr;
+  if (!(sync_exchange(c.t) && is_sync_layer(cv))) return 0;
+  HIP_TRY(reduce_to_local());
+  if (!c.t->ar_cb) return fail(VY_ERR_STATE, "SyncBN world > 1 without an all-reduce callback");
+  HIP_TRY(hipMemcpyAsync(c.sums_global(), c.sums_local(), sizeof(double) * n_cols, hipMemcpyDeviceToDevice, c.s));
+  if (int rc = c.t->ar_cb(c.t->ar_user, c.sums_global(), n_cols)) return fail(VY_ERR_STATE, "all-reduce callback failed (%d)", rc);
+  *count *= c.t->world;
+  *use = c.sums_global();
   return 0;
 }
 
@@ -394,24 +374,24 @@ int combine_sums(const TrainCtx& c, const ConvT& cv, int n_cols, double* count, 
 // optimizer step: 0.6 GB of traffic, ~0.3 ms, beside a 26 ms step)
 int refresh_split_images(const TrainCtx& c) {
   vy_net* net = c.net;
-  if (net->conv_mode != VY_CONV_SPLIT_BF16X3_TRAIN || !(net->split_dirty || net->dsplit_dirty) || c.t->sdesc.empty()) return 0;
-  SplitDesc* d = reinterpret_cast<SplitDesc*>(net->dev_ws + c.t->sdesc_off);
+  if (net->conv_mode != VY_CONV_SPLIT_BF16X3_TRAIN || !(net->split_dirty || net->dsplit_dirty) || c.p.sdesc.empty()) return 0;
+  SplitDesc* d = c.at<SplitDesc>(c.p.sdesc_off);
   if (!c.t->sdesc_uploaded) {
-    HIP_TRY(hipMemcpyAsync(d, c.t->sdesc.data(), sizeof(SplitDesc) * c.t->sdesc.size(), hipMemcpyHostToDevice, c.s));
+    HIP_TRY(hipMemcpyAsync(d, c.p.sdesc.data(), sizeof(SplitDesc) * c.p.sdesc.size(), hipMemcpyHostToDevice, c.s));
     HIP_TRY(hipStreamSynchronize(c.s));  // pageable host vector; once per plan
     c.t->sdesc_uploaded = true;
   }
   // one launch for every image set of the net (per-conv launches: 140 kernel boundaries per step)
-  HIP_TRY(vy_launch_split_weights_batch(net->dev_params, net->dev_ws, d, (int)c.t->sdesc.size(), c.t->sdesc_total, c.s));
+  HIP_TRY(vy_launch_split_weights_batch(net->dev_params, net->dev_ws, d, (int)c.p.sdesc.size(), c.p.sdesc_total, c.s));
   net->split_dirty = net->dsplit_dirty = false;
   return 0;
 }
 
-// the conv launch of the training passes: the split-fp32 kernel where the net's mode allows it, the launch has its
-// weight images (a.w_split) and the cost model predicts a gain; the exact kernel otherwise
+// the conv launch of the training passes: the split-fp32 kernel where the launch has its weight images (a.w_split: see
+// TrainCell::fwd_split / dgrad_split) and the cost model predicts a gain; the exact kernel otherwise
 static int launch_conv(const ConvArgs& a, hipStream_t s) {
   if (a.w_split && vy_conv_split_pays(a)) {
-    if (!g_labels_done && g_labels.f) {
+    if (g_labels.f) {
       int bm, bn, ks;
       char t[64];
       vy_conv_split_cfg(a, &bm, &bn, &ks);
@@ -420,8 +400,123 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
     }
     HIP_TRY(vy_launch_conv_split(a, s));
   } else {
-    if (!g_labels_done && g_labels.f) g_labels.via("exact");
+    g_labels.via("exact");
     HIP_TRY(vy_launch_conv_igemm(a, s));
+  }
+  return 0;
+}
+
+// ---- forward: the steps of one cell
+// prediction conv: bias, no BatchNorm, straight into its plane
+int pred_conv(const TrainCtx& c, int ci) {
+  const ConvT& cv = c.net->convs[ci];
+  const ConvArgs a = c.net->conv_args(cv);
+  g_labels.note(c.net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
+  HIP_TRY(vy_launch_conv_igemm(a, c.s));
+  return 0;
+}
+
+// the raw conv of a BatchNorm cell (the stem: from the image batch x) into its z plane, with the per-tile channel sums
+// in partials(); *n_part: their rows
+int raw_conv(const TrainCtx& c, int ci, const float* x, int* n_part) {
+  vy_net* net = c.net;
+  const ConvT& cv = net->convs[ci];
+  const TrainCell& cell = c.cell(ci);
+  if (cv.is_stem) {
+    StemArgs a = net->stem_args(cv, x);
+    a.scale = a.shift = nullptr;
+    a.out = c.zplane(ci);
+    a.out_cs = cell.z_cs;
+    a.out_co = 0;
+    HIP_TRY(vy_launch_stem_raw(a, reinterpret_cast<double*>(c.partials()), c.s));
+    *n_part = vy_stem_blocks(a.B, a.H, a.W);
+    return 0;
+  }
+  ConvArgs a = net->conv_args(cv);
+  a.scale = a.shift = a.res = nullptr;
+  a.leaky = 0;
+  a.out = c.zplane(ci);
+  a.o_Hp = cell.Ho + 2;
+  a.o_Wp = cell.Wo + 2;
+  a.o_cs = cell.z_cs;
+  a.o_co = 0;
+  a.o_s = 1;
+  a.ups = 1;
+  a.stats = reinterpret_cast<double*>(c.partials());
+  if (!cell.fwd_split) a.w_split = nullptr;
+  g_labels.note(net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
+  VY_TRY(launch_conv(a, c.s));
+  if (a.w_split && vy_conv_split_pays(a)) {  // the per-tile statistics rows follow the tile that ran
+    int sbm, sbn, sks;
+    vy_conv_split_cfg(a, &sbm, &sbn, &sks);
+    *n_part = (a.M + sbm - 1) / sbm;
+  } else {
+    *n_part = vy_conv_tiles_m(a);
+  }
+  return 0;
+}
+
+// statistics -> scale / shift, running and saved statistics; then the apply pass from z into the cell's output view
+int bn_forward(const TrainCtx& c, int ci, int n_part) {
+  vy_net* net = c.net;
+  const ConvT& cv = net->convs[ci];
+  const TrainCell& cell = c.cell(ci);
+  const BnViews bn = c.bn_views(ci);
+  const int C = cv.cout;
+  const double* parts = reinterpret_cast<const double*>(c.partials());
+  BnFinalizeArgs f;
+  f.count = (double)cell.M;
+  VY_TRY(combine_sums(c, cv, 2 * C, [&] { return vy_launch_reduce_partials_f64(parts, n_part, 2 * C, c.sums_local(), c.s); },
+                      &f.count, &f.sums));
+  f.gamma = bn.gamma;
+  f.beta = bn.beta;
+  f.running_mean = bn.running_mean;
+  f.running_var = bn.running_var;
+  f.scale = bn.scale;
+  f.shift = bn.shift;
+  f.save_mean = bn.save_mean;
+  f.save_invstd = bn.save_invstd;
+  f.C = C;
+  f.eps = 1e-5f;
+  f.momentum = 0.9f;  // layers.py:68
+  if (f.sums)
+    HIP_TRY(vy_launch_bn_finalize(f, c.s));
+  else if (!(train_abl(net) & 128))  // (128: the finalize launch of the forward statistics skipped)
+    HIP_TRY(vy_launch_bn_reduce_finalize(parts, n_part, f, c.slice_sums(), c.s));
+  BnApplyArgs ap;
+  memset(&ap, 0, sizeof ap);
+  ap.z = c.zplane(ci);
+  ap.scale = bn.scale;
+  ap.shift = bn.shift;
+  ap.out = net->plane_ptr(cv.out_plane);
+  ap.B = cell.B;
+  ap.H = cell.Ho;
+  ap.W = cell.Wo;
+  ap.C = C;
+  ap.o_Hp = cell.Ho * cv.ups + 2;
+  ap.o_Wp = cell.Wo * cv.ups + 2;
+  ap.o_cs = net->planes[cv.out_plane].C;
+  ap.o_co = cv.out_co;
+  ap.ups = cv.ups;
+  if (cv.res_plane >= 0) {
+    ap.res = net->plane_ptr(cv.res_plane);
+    ap.r_cs = net->planes[cv.res_plane].C;
+    ap.r_co = cv.res_co;
+  }
+  if (!(train_abl(net) & 2)) HIP_TRY(vy_launch_bn_apply(ap, c.s));
+  return 0;
+}
+
+// the cells [first, last) in recording mode; x: the image batch the stem reads
+int train_cells(const TrainCtx& c, int first, int last, const float* x) {
+  for (int ci = first; ci < last; ++ci) {
+    if (c.net->convs[ci].p_gamma < 0) {
+      VY_TRY(pred_conv(c, ci));
+      continue;
+    }
+    int n_part = 0;
+    VY_TRY(raw_conv(c, ci, x, &n_part));
+    VY_TRY(bn_forward(c, ci, n_part));
   }
   return 0;
 }
@@ -429,135 +524,188 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
 // routes (heads-only nets): the three route tensors, imported into their planes in front of the first conv
 int forward_train(const TrainCtx& c, const float* x, const float* const* routes) {
   vy_net* net = c.net;
-  if (int rc = refresh_split_images(c)) return rc;
-  if (routes) HIP_TRY(vy_launch_route_import(net->route_args(routes), c.s));
-  bool pooled = false;
-  for (size_t ci = 0; ci < net->convs.size(); ++ci) {
-    const ConvT& cv = net->convs[ci];
-    const int B = net->conv_batch(cv);  // (a window net's backbone cells: B * k frames)
-    if (net->window_k && !pooled && !net->params[cv.p_weight].info.backbone) {  // the stages are done: pool the routes
-      HIP_TRY(vy_launch_window_pool(net->pool_args(nullptr), c.s));
-      pooled = true;
-    }
-    if (cv.p_gamma < 0) {  // prediction conv: bias, no BN
-      const ConvArgs a = net->conv_args(cv);
-      if (!g_labels_done) g_labels.note(net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
-      HIP_TRY(vy_launch_conv_igemm(a, c.s));
-      continue;
-    }
-    const ZPlane& zp = c.t->z[ci];
-    int n_part;
-    if (cv.is_stem) {
-      StemArgs a;
-      a.x = x;
-      a.w = net->dev_params + net->params[cv.p_weight].info.offset;
-      a.scale = a.shift = nullptr;
-      a.out = c.zplane((int)ci);
-      a.B = B;
-      a.H = net->H;
-      a.W = net->W;
-      a.Cout = cv.cout;
-      a.out_cs = zp.C;
-      a.out_co = 0;
-      HIP_TRY(vy_launch_stem_raw(a, reinterpret_cast<double*>(c.partials()), c.s));
-      n_part = vy_stem_blocks(B, net->H, net->W);
-    } else {
-      ConvArgs a = net->conv_args(cv);
-      a.scale = a.shift = a.res = nullptr;
-      a.leaky = 0;
-      a.out = c.zplane((int)ci);
-      a.o_Hp = zp.H + 2;
-      a.o_Wp = zp.W + 2;
-      a.o_cs = zp.C;
-      a.o_co = 0;
-      a.o_s = 1;
-      a.ups = 1;
-      a.stats = reinterpret_cast<double*>(c.partials());
-      const int train_split = net->knobs.split_train;  // 0 none, 1 both, 2 forward only, 3 dgrad only
-      if (net->conv_mode != VY_CONV_SPLIT_BF16X3_TRAIN || train_split == 0 || train_split == 3) a.w_split = nullptr;
-      if (!g_labels_done) g_labels.note(net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
-      if (int rc = launch_conv(a, c.s)) return rc;
-      if (a.w_split && vy_conv_split_pays(a)) {  // the per-tile statistics rows follow the tile that ran
-        int sbm, sbn, sks;
-        vy_conv_split_cfg(a, &sbm, &sbn, &sks);
-        n_part = (a.M + sbm - 1) / sbm;
-      } else {
-        n_part = vy_conv_tiles_m(a);
-      }
-    }
-    const int C = cv.cout;
-    // statistics exchange between ranks only for the SyncBatchNorm layers; everywhere else the ordered
-    // reduce of the per-tile sums and the finalize are one launch
-    const bool exchange = sync_exchange(c.t) && is_sync_layer(cv);
-    double count = (double)B * zp.H * zp.W;
-    const double* use_sums = nullptr;
-    if (exchange) {
-      HIP_TRY(vy_launch_reduce_partials_f64(reinterpret_cast<const double*>(c.partials()), n_part, 2 * C,
-                                            c.sums_local(), c.s));
-      if (int rc = combine_sums(c, cv, 2 * C, &count, &use_sums)) return rc;
-    }
-    BnFinalizeArgs f;
-    f.sums = use_sums;
-    f.count = count;
-    f.gamma = net->dev_params + net->params[cv.p_gamma].info.offset;
-    f.beta = net->dev_params + net->params[cv.p_beta].info.offset;
-    f.running_mean = net->dev_params + net->params[cv.p_mean].info.offset;
-    f.running_var = net->dev_params + net->params[cv.p_var].info.offset;
-    f.scale = net->dev_params + cv.scale_off;
-    f.shift = net->dev_params + cv.shift_off;
-    f.save_mean = c.save((int)ci);
-    f.save_invstd = c.save((int)ci) + ((C + 63) & ~63);
-    f.C = C;
-    f.eps = 1e-5f;
-    f.momentum = 0.9f;  // layers.py:68
-    if (exchange)
-      HIP_TRY(vy_launch_bn_finalize(f, c.s));
-    else if (!(train_abl(net) & 128))  // (128: the same for the forward statistics)
-      HIP_TRY(vy_launch_bn_reduce_finalize(reinterpret_cast<const double*>(c.partials()), n_part, f, c.slice_sums(), c.s));
-    BnApplyArgs ap;
-    memset(&ap, 0, sizeof ap);
-    ap.z = c.zplane((int)ci);
-    ap.scale = f.scale;
-    ap.shift = f.shift;
-    const PlaneT& op = net->planes[cv.out_plane];
-    ap.out = net->plane_ptr(cv.out_plane);
-    ap.B = B;
-    ap.H = zp.H;
-    ap.W = zp.W;
-    ap.C = C;
-    ap.o_Hp = zp.H * cv.ups + 2;
-    ap.o_Wp = zp.W * cv.ups + 2;
-    ap.o_cs = op.C;
-    ap.o_co = cv.out_co;
-    ap.ups = cv.ups;
-    if (cv.res_plane >= 0) {
-      ap.res = net->plane_ptr(cv.res_plane);
-      ap.r_cs = net->planes[cv.res_plane].C;
-      ap.r_co = cv.res_co;
-    }
-    if (!(train_abl(net) & 2)) HIP_TRY(vy_launch_bn_apply(ap, c.s));
+  VY_TRY(refresh_split_images(c));
+  if (routes) VY_TRY(net->route_import(routes, c.s, plain));
+  VY_TRY(train_cells(c, 0, net->n_backbone, x));
+  if (net->window_k) VY_TRY(net->window_pool(c.s, plain));  // the stages are done: pool the routes
+  return train_cells(c, net->n_backbone, (int)net->convs.size(), nullptr);
+}
+
+// ---- backward
+// dz of a cell, final on the main stream: a plane (B, Ho + 2, Wo + 2, cs) of the cell's geometry
+struct DzView {
+  const float* p;
+  int cs;
+};
+
+// what the cells of one backward pass share
+struct BwdState {
+  // which channel ranges of each gradient plane already hold a contribution
+  std::vector<std::vector<std::pair<int, int>>> touched;
+  // pending skip-connection gradients: block input plane view -> gradient view of the block output
+  struct Skip {
+    int plane, co;  // input view of the block (where the addend must land)
+    int src_plane, src_co;
+  };
+  std::vector<Skip> skips;
+  int covered(int plane, int lo, int hi) const {  // 1 accumulate, 0 overwrite, -1 partial overlap
+    for (auto& r : touched[plane])
+      if (lo < r.second && r.first < hi) return (r.first <= lo && hi <= r.second) ? 1 : -1;
+    return 0;
   }
+  void whole(const vy_net* net, int plane) { touched[plane].push_back({0, net->planes[plane].C}); }
+};
+
+// prediction conv: dz = d(loss)/d(pred) as written by the loss kernel; its column sums are the bias gradient
+int bias_grad(const TrainCtx& c, int ci, DzView* dz) {
+  const ConvT& cv = c.net->convs[ci];
+  const TrainCell& cell = c.cell(ci);
+  const int cs = c.net->planes[cv.out_plane].C;
+  *dz = {c.gplane(cv.out_plane), cs};
+  const int chunks = vy_colsum_chunks(cell.B, cell.Ho, cell.Wo, kBwdChunk);
+  HIP_TRY(vy_launch_colsum(dz->p, cell.B, cell.Ho, cell.Wo, cs, 0, cv.cout, kBwdChunk, c.partials(), c.s));
+  HIP_TRY(vy_launch_reduce_partials(c.partials(), chunks, cv.cout, c.sums_local(), c.s));
+  HIP_TRY(vy_launch_f64_to_f32(c.sums_local(), c.grad_of(cv.p_bias), cv.cout, c.s));
   return 0;
 }
 
-// dgrad launches of conv cv: gradient w.r.t. its input view, from dz stored in `dzp`
-BwdDgrad make_dgrad(const TrainCtx& c, const ConvT& cv, const float* dzp, int dz_cs, int dz_H, int dz_W,
-                    const float* addend, int add_cs, int add_co) {
+// BatchNorm + leaky backward: reduce -> dgamma, dbeta, coefficients -> apply (dz overwrites z)
+int bn_backward(const TrainCtx& c, int ci, BwdState& st, DzView* dz) {
   vy_net* net = c.net;
+  const ConvT& cv = net->convs[ci];
+  const TrainCell& cell = c.cell(ci);
+  const BnViews bn = c.bn_views(ci);
+  if (st.covered(cv.out_plane, cv.out_co, cv.out_co + cv.cout) != 1)
+    return fail(VY_ERR_STATE, "internal: gradient of '%s' output was never produced", cv.name.c_str());
+  BnBwdArgs bb;
+  memset(&bb, 0, sizeof bb);
+  bb.g = c.gplane(cv.out_plane);
+  bb.z = c.zplane(ci);
+  bb.scale = bn.scale;
+  bb.shift = bn.shift;
+  bb.save_mean = bn.save_mean;
+  bb.save_invstd = bn.save_invstd;
+  bb.coef = c.coef();
+  bb.partials = c.partials();
+  bb.B = cell.B;
+  bb.H = cell.Ho;
+  bb.W = cell.Wo;
+  bb.C = cv.cout;
+  bb.g_Hp = cell.Ho * cv.ups + 2;
+  bb.g_Wp = cell.Wo * cv.ups + 2;
+  bb.g_cs = net->planes[cv.out_plane].C;
+  bb.g_co = cv.out_co;
+  bb.ups = cv.ups;
+  bb.chunk = vy_bn_bwd_rows_per_chunk(cell.B, cell.Ho, cv.cout);
+  if (!(train_abl(net) & 1)) HIP_TRY(vy_launch_bn_bwd_reduce(bb, c.s));
+  BnBwdFinalizeArgs f;
+  memset(&f, 0, sizeof f);
+  f.count = (double)cell.M;
+  VY_TRY(combine_sums(c, cv, 2 * cv.cout,
+                      [&] { return vy_launch_reduce_partials(c.partials(), vy_bn_bwd_chunks(bb), 2 * cv.cout, c.sums_local(), c.s); },
+                      &f.count, &f.sums));
+  f.local_sums = c.sums_local();
+  f.gamma = bn.gamma;
+  f.save_invstd = bn.save_invstd;
+  f.dgamma = c.grad_of(cv.p_gamma);
+  f.dbeta = c.grad_of(cv.p_beta);
+  f.coef = c.coef();
+  f.C = cv.cout;
+  if (f.sums)
+    HIP_TRY(vy_launch_bn_bwd_finalize(f, c.s));
+  else if (!(train_abl(net) & (1 | 64)))  // (64: the finalize launch alone skipped)
+    HIP_TRY(vy_launch_bn_bwd_reduce_finalize(c.partials(), vy_bn_bwd_chunks(bb), f, c.s));
+  if (!(train_abl(net) & 4)) HIP_TRY(vy_launch_bn_bwd_apply(bb, c.s));
+  *dz = {c.zplane(ci), cell.z_cs};
+  if (cv.res_plane >= 0) st.skips.push_back({cv.res_plane, cv.res_co, cv.out_plane, cv.out_co});
+  return 0;
+}
+
+// split-K slabs + ordered slab reduce into the weight's gradient, on stream ws
+int launch_wgrad(const TrainCtx& c, int ci, DzView dz, hipStream_t ws) {
+  vy_net* net = c.net;
+  const ConvT& cv = net->convs[ci];
+  const TrainCell& cell = c.cell(ci);
+  const PlaneT& ip = net->planes[cv.in_plane];
+  WgradArgs w;
+  memset(&w, 0, sizeof w);
+  w.dz = dz.p;
+  w.a = net->plane_ptr(cv.in_plane);
+  w.slabs = c.slabs();
+  w.zero = c.at<const float>(c.p.zero_off);
+  w.B = cell.B;
+  w.Ho = cell.Ho;
+  w.Wo = cell.Wo;
+  w.M = (int)cell.M;
+  w.z_cs = dz.cs;
+  w.Cout = cv.cout;
+  w.a_Hp = ip.H + 2;
+  w.a_Wp = ip.W + 2;
+  w.a_cs = ip.C;
+  w.a_co = cv.in_co;
+  w.stride = cv.stride;
+  w.k = cv.k;
+  w.Cin = cv.cin;
+  w.splits = cell.splits;
+  w.k_per_split = cell.k_per_split;
+  w.tab = c.at<const uint2>(cell.tab_off);
+  g_labels.note(net, "wgrad", cv.name, w.M, w.Cout, (double)cv.k * cv.k * cv.cin);
+  // conv mode VY_CONV_SPLIT_BF16X3_TRAIN: the split-fp32 weight-gradient kernel where it has the tile (Cout % 128 == 0)
+  if ((train_abl(net) & 8) || ((train_abl(net) & 32) && (long long)cv.k * cv.k * cv.cin <= 576 && cv.cout <= 128)) {
+    // (bound measurements: no weight-gradient kernel at all / none for the early cells — N <= 128, K <= 576: stages.0.1 ... 0.5 —
+    // whose output tile is mostly padding: what would a perfect kernel for them return to the step?)
+  } else if (net->knobs.split_wgrad && net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && vy_wgrad_split_supported(w)) {
+    HIP_TRY(vy_launch_wgrad_split(w, ws));
+  } else {
+    HIP_TRY(vy_launch_wgrad(w, ws));
+  }
+  HIP_TRY(vy_launch_slab_reduce(c.slabs(), w.splits, (long long)cv.cout * cv.k * cv.k * cv.cin, c.grad_of(cv.p_weight), ws));
+  return 0;
+}
+
+// the weight gradient of a cell from its final dz: the stem's from the image batch x, every other conv's through the slabs
+int weight_grad(const TrainCtx& c, int ci, DzView dz, const float* x) {
+  const ConvT& cv = c.net->convs[ci];
+  if (cv.is_stem) {
+    StemWgradArgs sw;
+    sw.x = x;
+    sw.dz = dz.p;
+    sw.partials = c.partials();
+    sw.B = c.cell(ci).B;
+    sw.H = c.net->H;
+    sw.W = c.net->W;
+    HIP_TRY(vy_launch_stem_wgrad(sw, c.s));
+    HIP_TRY(vy_launch_reduce_partials(c.partials(), vy_stem_wgrad_blocks(sw.B, sw.H, sw.W), 864, c.sums_local(), c.s));
+    HIP_TRY(vy_launch_f64_to_f32(c.sums_local(), c.grad_of(cv.p_weight), 864, c.s));
+    return 0;
+  }
+  // dz is final on the main stream: the weight gradient (its own scratch: the slabs) goes to the side
+  // stream and overlaps with this layer's dgrad and the next layers' BatchNorm kernels
+  if (!c.t->side) return launch_wgrad(c, ci, dz, c.s);
+  HIP_TRY(hipEventRecord(c.t->ev_main, c.s));
+  HIP_TRY(hipStreamWaitEvent(c.t->side, c.t->ev_main, 0));
+  return launch_wgrad(c, ci, dz, c.t->side);
+}
+
+// dgrad launches of conv ci: gradient w.r.t. its input view, from the dz view
+BwdDgrad make_dgrad(const TrainCtx& c, int ci, DzView dz, const float* addend, int add_cs, int add_co) {
+  vy_net* net = c.net;
+  const ConvT& cv = net->convs[ci];
+  const TrainCell& cell = c.cell(ci);
   BwdDgrad out;
   const PlaneT& ip = net->planes[cv.in_plane];
   ConvArgs a;
-  memset(&a, 0, sizeof a);
-  a.in = dzp;
-  a.w = net->dev_params + net->params[cv.p_weight].info.offset;
+  memset(&a, 0, sizeof a);  // (ntaps = 0: counted below)
+  a.in = dz.p;
+  a.w = c.param(cv.p_weight);
   a.out = c.gplane(cv.in_plane);
   a.res = addend;
   a.r_cs = add_cs;
   a.r_co = add_co;
-  a.B = net->conv_batch(cv);
-  a.a_Hp = dz_H + 2;
-  a.a_Wp = dz_W + 2;
-  a.a_cs = dz_cs;
+  a.B = cell.B;
+  a.a_Hp = cell.Ho + 2;
+  a.a_Wp = cell.Wo + 2;
+  a.a_cs = dz.cs;
   a.a_co = 0;
   a.a_s = 1;
   a.a_oy = a.a_ox = 1;
@@ -572,96 +720,112 @@ BwdDgrad make_dgrad(const TrainCtx& c, const ConvT& cv, const float* dzp, int dz
   a.o_co = cv.in_co;
   a.ups = 1;
   a.dgrad = 1;
-  a.knobs = &net->knobs;
-  a.cus = net->cus;
-  net->set_sk(a);
-  {  // split-fp32 conv mode: this conv's data-gradient weight images and the split-K scratch (the stream-K region)
-    const size_t ci = (size_t)(&cv - net->convs.data());
-    if (net->knobs.split_train != 2 && net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && ci < c.t->dsplit.size() && c.t->dsplit[ci] >= 0) {
-      a.w_split = net->dev_ws + c.t->dsplit_off + c.t->dsplit[ci];
-      a.splitk_slabs = reinterpret_cast<float*>(net->dev_ws + net->sk_off + vy_net::al((size_t)VY_SK_FLAGS * sizeof(unsigned)));
-      a.splitk_bytes = VY_SK_PARTIAL_BYTES;
-    }
-  }
-  if (cv.stride == 1) {
-    a.LH = ip.H;
-    a.LW = ip.W;
-    a.M = a.B * ip.H * ip.W;
-    a.o_s = 1;
-    a.o_oy = a.o_ox = 1;
-    a.ntaps = cv.k * cv.k;
-    for (int t = 0; t < a.ntaps; ++t) {
-      a.tap_dy[t] = (signed char)(cv.k == 3 ? 1 - t / 3 : 0);
-      a.tap_dx[t] = (signed char)(cv.k == 3 ? 1 - t % 3 : 0);
-      a.tap_w[t] = (unsigned char)t;
-    }
-    out.a[out.n++] = a;
-  } else {
-    // stride 2, 3x3, pad 1: input pixel (2y'+py, 2x'+px) receives taps with (py+1-kh), (px+1-kw) even
-    for (int py = 0; py < 2; ++py)
-      for (int px = 0; px < 2; ++px) {
-        ConvArgs q = a;
-        q.LH = ip.H / 2;
-        q.LW = ip.W / 2;
-        q.M = a.B * q.LH * q.LW;
-        q.o_s = 2;
-        q.o_oy = 1 + py;
-        q.o_ox = 1 + px;
-        q.ntaps = 0;
-        for (int kh = 0; kh < 3; ++kh) {
-          if ((py + 1 - kh) & 1) continue;
-          for (int kw = 0; kw < 3; ++kw) {
-            if ((px + 1 - kw) & 1) continue;
-            q.tap_dy[q.ntaps] = (signed char)((py + 1 - kh) / 2);
-            q.tap_dx[q.ntaps] = (signed char)((px + 1 - kw) / 2);
-            q.tap_w[q.ntaps] = (unsigned char)(kh * 3 + kw);
-            ++q.ntaps;
-          }
+  // split-fp32 conv mode: this conv's data-gradient weight images and the split-K scratch (the stream-K region)
+  net->launch_env(a, /*k_runs=*/false, /*splitk=*/cell.dgrad_split);
+  if (cell.dgrad_split) a.w_split = net->dev_ws + c.p.dsplit_off + cell.dsplit;
+  // Input pixel (s y' + py, s x' + px) of a stride-s conv (pad k / 2) receives the taps with (py + pad - kh), (px + pad - kw)
+  // multiples of s: one launch at stride 1, one per parity class (py, px) at stride 2
+  const int sd = cv.stride, pad = cv.k / 2;
+  for (int py = 0; py < sd; ++py)
+    for (int px = 0; px < sd; ++px) {
+      ConvArgs& q = out.a[out.n++] = a;
+      q.LH = cell.Ho;
+      q.LW = cell.Wo;
+      q.M = (int)cell.M;
+      q.o_s = sd;
+      q.o_oy = 1 + py;
+      q.o_ox = 1 + px;
+      for (int kh = 0; kh < cv.k; ++kh) {
+        if ((py + pad - kh) % sd) continue;
+        for (int kw = 0; kw < cv.k; ++kw) {
+          if ((px + pad - kw) % sd) continue;
+          q.tap_dy[q.ntaps] = (signed char)((py + pad - kh) / sd);
+          q.tap_dx[q.ntaps] = (signed char)((px + pad - kw) / sd);
+          q.tap_w[q.ntaps] = (unsigned char)(kh * cv.k + kw);
+          ++q.ntaps;
         }
-        out.a[out.n++] = q;
       }
-  }
+    }
   return out;
 }
 
-int launch_wgrad(const TrainCtx& c, size_t ci, const float* dzp, int dz_cs, int Ho, int Wo, hipStream_t ws) {
+// Data gradient into the input view.  A heads-only net computes none into its imported routes: yolo_blocks.0.body.0
+// (input: the stride-32 route) gets no data gradient at all, yolo_blocks.1/2.body.0 only the one of the upsampled
+// transition channels [0, co) in front of the route in their concat plane (a narrower N: every output is the same
+// fp32 chain whatever the tile, so these channels are bit-identical to the full net's)
+int data_grad(const TrainCtx& c, int ci, DzView dz, BwdState& st) {
   vy_net* net = c.net;
   const ConvT& cv = net->convs[ci];
-  const PlaneT& ip = net->planes[cv.in_plane];
-  WgradArgs w;
-  memset(&w, 0, sizeof w);
-  w.dz = dzp;
-  w.a = net->plane_ptr(cv.in_plane);
-  w.slabs = c.slabs();
-  w.zero = c.zero();
-  w.B = net->conv_batch(cv);
-  w.Ho = Ho;
-  w.Wo = Wo;
-  w.M = w.B * Ho * Wo;
-  w.z_cs = dz_cs;
-  w.Cout = cv.cout;
-  w.a_Hp = ip.H + 2;
-  w.a_Wp = ip.W + 2;
-  w.a_cs = ip.C;
-  w.a_co = cv.in_co;
-  w.stride = cv.stride;
-  w.k = cv.k;
-  w.Cin = cv.cin;
-  w.splits = c.t->splits[ci];
-  w.k_per_split = c.t->kps[ci];
-  w.tab = reinterpret_cast<const uint2*>(net->dev_ws + c.t->tab_off[ci]);
-  if (!g_labels_done) g_labels.note(net, "wgrad", cv.name, w.M, w.Cout, (double)cv.k * cv.k * cv.cin);
-  // conv mode VY_CONV_SPLIT_BF16X3_TRAIN: the split-fp32 weight-gradient kernel where it has the tile (Cout % 128 == 0)
-  if ((train_abl(net) & 8) || ((train_abl(net) & 32) && (long long)cv.k * cv.k * cv.cin <= 576 && cv.cout <= 128)) {
-    // (bound measurements: no weight-gradient kernel at all / none for the early cells — N <= 128, K <= 576: stages.0.1 ... 0.5 —
-    // whose output tile is mostly padding: what would a perfect kernel for them return to the step?)
-  } else if (net->knobs.split_wgrad && net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && vy_wgrad_split_supported(w)) {
-    HIP_TRY(vy_launch_wgrad_split(w, ws));
-  } else {
-    HIP_TRY(vy_launch_wgrad(w, ws));
+  const int lo = cv.in_co;
+  int hi = cv.in_co + cv.cin;
+  if (net->heads_only)
+    for (const auto& r : net->routes)
+      if (r.plane == cv.in_plane && r.co < hi) hi = std::max(lo, r.co);
+  if (hi == lo) return 0;
+  const int cov = st.covered(cv.in_plane, lo, hi);
+  if (cov < 0) return fail(VY_ERR_STATE, "internal: partial gradient overlap at '%s'", cv.name.c_str());
+  const float* addend = nullptr;
+  int add_cs = 0, add_co = 0;
+  int skip_i = -1;
+  for (size_t k = 0; k < st.skips.size(); ++k)
+    if (st.skips[k].plane == cv.in_plane && st.skips[k].co == cv.in_co) skip_i = (int)k;
+  if (skip_i >= 0) {
+    if (cov == 1) return fail(VY_ERR_STATE, "internal: skip + accumulate at '%s'", cv.name.c_str());
+    addend = c.gplane(st.skips[skip_i].src_plane);
+    add_cs = net->planes[st.skips[skip_i].src_plane].C;
+    add_co = st.skips[skip_i].src_co;
+    st.skips.erase(st.skips.begin() + skip_i);
+  } else if (cov == 1) {
+    addend = c.gplane(cv.in_plane);
+    add_cs = net->planes[cv.in_plane].C;
+    add_co = cv.in_co;
   }
-  HIP_TRY(vy_launch_slab_reduce(c.slabs(), w.splits, (long long)cv.cout * cv.k * cv.k * cv.cin,
-                                c.grad_of(cv.p_weight), ws));
+  BwdDgrad dg = make_dgrad(c, ci, dz, addend, add_cs, add_co);
+  for (int k = 0; k < dg.n; ++k) {
+    ConvArgs& a = dg.a[k];
+    if (hi - lo != cv.cin) {
+      a.N = hi - lo;
+      a.w_split = nullptr;  // (the split kernel's data-gradient images are tiled for the whole cin)
+    }
+    g_labels.note(net, "dgrad", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
+    if (train_abl(net) & 16) continue;  // (bound measurement: no data-gradient kernel)
+    VY_TRY(launch_conv(a, c.s));
+  }
+  if (cov == 0) st.touched[cv.in_plane].push_back({lo, hi});
+  return 0;
+}
+
+// the main stream waits for the weight gradients launched so far
+int join_side(const TrainCtx& c) {
+  if (!c.t->side) return 0;
+  HIP_TRY(hipEventRecord(c.t->ev_side, c.t->side));
+  HIP_TRY(hipStreamWaitEvent(c.s, c.t->ev_side, 0));
+  return 0;
+}
+
+// gradient bucket bk is complete: heads | stages.2 | stages.1 | stages.0 (TrainPlan::bucket_lo / bucket_len)
+int emit_bucket(const TrainCtx& c, int bk) {
+  if (!c.t->gb_cb) return 0;
+  VY_TRY(join_side(c));  // the bucket's weight gradients must be final
+  if (c.p.bucket_len[bk] == 0) return 0;
+  if (int rc = c.t->gb_cb(c.t->gb_user, c.p.bucket_lo[bk], c.p.bucket_len[bk]))
+    return fail(VY_ERR_STATE, "gradient bucket callback failed (%d)", rc);
+  return 0;
+}
+
+// the cells [first, last) in reverse order; a bucket closes behind its first cell
+int backward_cells(const TrainCtx& c, BwdState& st, int first, int last, const float* x) {
+  for (int ci = last - 1; ci >= first; --ci) {
+    const ConvT& cv = c.net->convs[ci];
+    DzView dz;
+    if (cv.p_gamma < 0)
+      VY_TRY(bias_grad(c, ci, &dz));
+    else
+      VY_TRY(bn_backward(c, ci, st, &dz));
+    VY_TRY(weight_grad(c, ci, dz, x));
+    if (!cv.is_stem) VY_TRY(data_grad(c, ci, dz, st));  // (no gradient w.r.t. the image)
+    if (ci == 0 || c.cell(ci - 1).bucket != c.cell(ci).bucket) VY_TRY(emit_bucket(c, c.cell(ci).bucket));
+  }
   return 0;
 }
 
@@ -670,16 +834,14 @@ int build_wgrad_tables(const TrainCtx& c) {
   vy_net* net = c.net;
   for (size_t ci = 0; ci < net->convs.size(); ++ci) {
     const ConvT& cv = net->convs[ci];
+    const TrainCell& cell = c.cell((int)ci);
     if (cv.is_stem) continue;
     const PlaneT& ip = net->planes[cv.in_plane];
-    const int Ho = ip.H / cv.stride, Wo = ip.W / cv.stride;
-    const int Bc = net->conv_batch(cv);
-    const long long M = (long long)Bc * Ho * Wo;
-    const int z_cs = cv.p_gamma >= 0 ? c.t->z[ci].C : net->planes[cv.out_plane].C;
-    if (M >= (1ll << 31) - 64) return fail(VY_ERR_UNSUPPORTED, "'%s': 2^31 output pixels or more in one batch", cv.name.c_str());
+    const int z_cs = cv.p_gamma >= 0 ? cell.z_cs : net->planes[cv.out_plane].C;
+    if (cell.M >= (1ll << 31) - 64) return fail(VY_ERR_UNSUPPORTED, "'%s': 2^31 output pixels or more in one batch", cv.name.c_str());
     // (offsets are relative to each split's first pixel: planes of 4 GiB and more are fine — 608x608 past batch 84)
-    HIP_TRY(vy_launch_wgrad_table(net->dev_ws + c.t->tab_off[ci], (int)M, (int)vy_wgrad_table_entries(M), Ho, Wo, z_cs,
-                                  ip.H + 2, ip.W + 2, ip.C, cv.stride, Bc, c.t->kps[ci], c.s));
+    HIP_TRY(vy_launch_wgrad_table(net->dev_ws + cell.tab_off, (int)cell.M, (int)vy_wgrad_table_entries(cell.M), cell.Ho, cell.Wo,
+                                  z_cs, ip.H + 2, ip.W + 2, ip.C, cv.stride, cell.B, cell.k_per_split, c.s));
   }
   c.t->tabs_built = true;
   return 0;
@@ -687,212 +849,109 @@ int build_wgrad_tables(const TrainCtx& c) {
 
 int backward_train(const TrainCtx& c, const float* x) {
   vy_net* net = c.net;
-  if (!c.t->tabs_built)
-    if (int rc = build_wgrad_tables(c)) return rc;
-  // which channel ranges of each gradient plane already hold a contribution
-  std::vector<std::vector<std::pair<int, int>>> touched(net->planes.size());
-  auto covered = [&](int plane, int lo, int hi) -> int {  // 1 accumulate, 0 overwrite, -1 partial overlap
-    for (auto& r : touched[plane])
-      if (lo < r.second && r.first < hi) return (r.first <= lo && hi <= r.second) ? 1 : -1;
-    return 0;
-  };
+  if (!c.t->tabs_built) VY_TRY(build_wgrad_tables(c));
+  BwdState st;
+  st.touched.resize(net->planes.size());
   // the prediction planes' gradients were written by the loss kernel
-  for (int i = 0; i < 3; ++i) touched[net->head_plane[i]].push_back({0, net->planes[net->head_plane[i]].C});
-  // pending skip-connection gradients: block input plane view -> gradient view of the block output
-  struct Skip {
-    int plane, co;     // input view of the block (where the addend must land)
-    int src_plane, src_co;
-  };
-  std::vector<Skip> skips;
-  // gradient buckets: heads | stages.2 | stages.1 | stages.0 (contiguous parameter ranges)
-  auto bucket_of = [&](const ConvT& cv) {
-    if (cv.name.rfind("stages.2", 0) == 0) return 1;
-    if (cv.name.rfind("stages.1", 0) == 0) return 2;
-    if (cv.name.rfind("stages.0", 0) == 0) return 3;
-    return 0;
-  };
-  auto join_side = [&]() -> int {
-    if (!c.t->side) return 0;
-    HIP_TRY(hipEventRecord(c.t->ev_side, c.t->side));
-    HIP_TRY(hipStreamWaitEvent(c.s, c.t->ev_side, 0));
-    return 0;
-  };
-  auto emit_bucket = [&](int bk) -> int {
-    if (!c.t->gb_cb) return 0;
-    if (int rc = join_side()) return rc;  // the bucket's weight gradients must be final
-    int64_t lo = INT64_MAX, hi = 0;
-    for (const ConvT& cv : net->convs) {
-      if (bucket_of(cv) != bk) continue;
-      const int ps[6] = {cv.p_weight, cv.p_gamma, cv.p_beta, cv.p_bias, -1, -1};
-      for (int p : ps) {
-        if (p < 0) continue;
-        const vy_param_info& pi = net->params[p].info;
-        if (pi.offset < lo) lo = pi.offset;
-        const int64_t e = pi.offset + ((pi.size + 63) & ~(int64_t)63);
-        if (e > hi) hi = e;
-      }
-    }
-    if (hi <= lo) return 0;
-    if (int rc = c.t->gb_cb(c.t->gb_user, lo, hi - lo)) return fail(VY_ERR_STATE, "gradient bucket callback failed (%d)", rc);
-    return 0;
-  };
-  int cur_bucket = 0;
-  bool unpooled = false;
-  for (int ci = (int)net->convs.size() - 1; ci >= 0; --ci) {
-    const ConvT& cv = net->convs[ci];
-    const int B = net->conv_batch(cv);  // (a window net's backbone cells: B * k frames)
-    const int bk = bucket_of(cv);
-    if (bk != cur_bucket) {
-      if (int rc = emit_bucket(cur_bucket)) return rc;
-      cur_bucket = bk;
-    }
-    if (net->window_k && !unpooled && net->params[cv.p_weight].info.backbone) {
-      // the heads are done: the pooled routes' gradients (cat2 / cat1 route channels, the pooled stride-32 plane) are
-      // final.  window_pool_bwd writes the per-frame route planes' gradients; stages.1.0 / stages.2.0 accumulate onto them
-      HIP_TRY(vy_launch_window_pool_bwd(net->pool_args(reinterpret_cast<float*>(net->dev_ws + c.t->g_off)), c.s));
-      for (int i = 0; i < 3; ++i) touched[net->frame_routes[i]].push_back({0, net->planes[net->frame_routes[i]].C});
-      unpooled = true;
-    }
-    const float* dzp;
-    int dz_cs, dzH, dzW;
-    if (cv.p_gamma < 0) {
-      // prediction conv: dz = d(loss)/d(pred) as written by the loss kernel
-      const PlaneT& pp = net->planes[cv.out_plane];
-      dzp = c.gplane(cv.out_plane);
-      dz_cs = pp.C;
-      dzH = pp.H;
-      dzW = pp.W;
-      const int chunks = vy_colsum_chunks(B, pp.H, pp.W, kBwdChunk);
-      HIP_TRY(vy_launch_colsum(dzp, B, pp.H, pp.W, pp.C, 0, cv.cout, kBwdChunk, c.partials(), c.s));
-      HIP_TRY(vy_launch_reduce_partials(c.partials(), chunks, cv.cout, c.sums_local(), c.s));
-      HIP_TRY(vy_launch_f64_to_f32(c.sums_local(), c.grad_of(cv.p_bias), cv.cout, c.s));
-    } else {
-      const ZPlane& zp = c.t->z[ci];
-      const PlaneT& op = net->planes[cv.out_plane];
-      if (covered(cv.out_plane, cv.out_co, cv.out_co + cv.cout) != 1)
-        return fail(VY_ERR_STATE, "internal: gradient of '%s' output was never produced", cv.name.c_str());
-      BnBwdArgs bb;
-      memset(&bb, 0, sizeof bb);
-      bb.g = c.gplane(cv.out_plane);
-      bb.z = c.zplane(ci);
-      bb.scale = net->dev_params + cv.scale_off;
-      bb.shift = net->dev_params + cv.shift_off;
-      bb.save_mean = c.save(ci);
-      bb.save_invstd = c.save(ci) + ((cv.cout + 63) & ~63);
-      bb.coef = c.coef();
-      bb.partials = c.partials();
-      bb.B = B;
-      bb.H = zp.H;
-      bb.W = zp.W;
-      bb.C = cv.cout;
-      bb.g_Hp = zp.H * cv.ups + 2;
-      bb.g_Wp = zp.W * cv.ups + 2;
-      bb.g_cs = op.C;
-      bb.g_co = cv.out_co;
-      bb.ups = cv.ups;
-      bb.chunk = vy_bn_bwd_rows_per_chunk(B, zp.H, cv.cout);
-      if (!(train_abl(net) & 1)) HIP_TRY(vy_launch_bn_bwd_reduce(bb, c.s));
-      const bool exchange = sync_exchange(c.t) && is_sync_layer(cv);
-      double count = (double)B * zp.H * zp.W;
-      const double* use_sums = nullptr;
-      if (exchange) {
-        HIP_TRY(vy_launch_reduce_partials(c.partials(), vy_bn_bwd_chunks(bb), 2 * cv.cout, c.sums_local(), c.s));
-        if (int rc = combine_sums(c, cv, 2 * cv.cout, &count, &use_sums)) return rc;
-      }
-      BnBwdFinalizeArgs f;
-      memset(&f, 0, sizeof f);
-      f.sums = use_sums;
-      f.local_sums = c.sums_local();
-      f.count = count;
-      f.gamma = net->dev_params + net->params[cv.p_gamma].info.offset;
-      f.save_invstd = bb.save_invstd;
-      f.dgamma = c.grad_of(cv.p_gamma);
-      f.dbeta = c.grad_of(cv.p_beta);
-      f.coef = c.coef();
-      f.C = cv.cout;
-      if (exchange)
-        HIP_TRY(vy_launch_bn_bwd_finalize(f, c.s));
-      else if (!(train_abl(net) & (1 | 64)))  // (64: the finalize launch alone skipped)
-        HIP_TRY(vy_launch_bn_bwd_reduce_finalize(c.partials(), vy_bn_bwd_chunks(bb), f, c.s));
-      if (!(train_abl(net) & 4)) HIP_TRY(vy_launch_bn_bwd_apply(bb, c.s));
-      dzp = c.zplane(ci);
-      dz_cs = zp.C;
-      dzH = zp.H;
-      dzW = zp.W;
-      if (cv.res_plane >= 0) skips.push_back({cv.res_plane, cv.res_co, cv.out_plane, cv.out_co});
-    }
-    // weight gradient
-    if (cv.is_stem) {
-      StemWgradArgs sw;
-      sw.x = x;
-      sw.dz = dzp;
-      sw.partials = c.partials();
-      sw.B = B;
-      sw.H = net->H;
-      sw.W = net->W;
-      HIP_TRY(vy_launch_stem_wgrad(sw, c.s));
-      HIP_TRY(vy_launch_reduce_partials(c.partials(), vy_stem_wgrad_blocks(B, net->H, net->W), 864,
-                                        c.sums_local(), c.s));
-      HIP_TRY(vy_launch_f64_to_f32(c.sums_local(), c.grad_of(cv.p_weight), 864, c.s));
-      continue;  // no gradient w.r.t. the image
-    }
-    // dz is final on the main stream: the weight gradient (its own scratch: the slabs) goes to the side
-    // stream and overlaps with this layer's dgrad and the next layers' BatchNorm kernels
-    hipStream_t ws = c.t->side ? c.t->side : c.s;
-    if (c.t->side) {
-      HIP_TRY(hipEventRecord(c.t->ev_main, c.s));
-      HIP_TRY(hipStreamWaitEvent(c.t->side, c.t->ev_main, 0));
-    }
-    if (int rc = launch_wgrad(c, (size_t)ci, dzp, dz_cs, dzH, dzW, ws)) return rc;
-    // data gradient into the input view.  A heads-only net computes none into its imported routes: yolo_blocks.0.body.0
-    // (input: the stride-32 route) gets no data gradient at all, yolo_blocks.1/2.body.0 only the one of the upsampled
-    // transition channels [0, co) in front of the route in their concat plane (a narrower N: every output is the same
-    // fp32 chain whatever the tile, so these channels are bit-identical to the full net's)
-    const int lo = cv.in_co;
-    int hi = cv.in_co + cv.cin;
-    if (net->heads_only)
-      for (const auto& r : net->routes)
-        if (r.plane == cv.in_plane && r.co < hi) hi = std::max(lo, r.co);
-    if (hi == lo) continue;
-    const int cov = covered(cv.in_plane, lo, hi);
-    if (cov < 0) return fail(VY_ERR_STATE, "internal: partial gradient overlap at '%s'", cv.name.c_str());
-    const float* addend = nullptr;
-    int add_cs = 0, add_co = 0;
-    int skip_i = -1;
-    for (size_t k = 0; k < skips.size(); ++k)
-      if (skips[k].plane == cv.in_plane && skips[k].co == cv.in_co) skip_i = (int)k;
-    if (skip_i >= 0) {
-      if (cov == 1) return fail(VY_ERR_STATE, "internal: skip + accumulate at '%s'", cv.name.c_str());
-      addend = c.gplane(skips[skip_i].src_plane);
-      add_cs = net->planes[skips[skip_i].src_plane].C;
-      add_co = skips[skip_i].src_co;
-      skips.erase(skips.begin() + skip_i);
-    } else if (cov == 1) {
-      addend = c.gplane(cv.in_plane);
-      add_cs = net->planes[cv.in_plane].C;
-      add_co = cv.in_co;
-    }
-    BwdDgrad dg = make_dgrad(c, cv, dzp, dz_cs, dzH, dzW, addend, add_cs, add_co);
-    if (hi - lo != cv.cin)
-      for (int k = 0; k < dg.n; ++k) {
-        dg.a[k].N = hi - lo;
-        dg.a[k].w_split = nullptr;  // (the split kernel's data-gradient images are tiled for the whole cin)
-      }
-    for (int k = 0; k < dg.n; ++k) {
-      if (!g_labels_done) g_labels.note(net, "dgrad", cv.name, dg.a[k].M, dg.a[k].N, (double)dg.a[k].ntaps * dg.a[k].Kc);
-      if (train_abl(net) & 16) continue;  // (bound measurement: no data-gradient kernel)
-      if (int rc = launch_conv(dg.a[k], c.s)) return rc;
-    }
-    if (cov == 0) touched[cv.in_plane].push_back({lo, hi});
+  for (int i = 0; i < 3; ++i) st.whole(net, net->head_plane[i]);
+  VY_TRY(backward_cells(c, st, net->n_backbone, (int)net->convs.size(), x));
+  if (net->window_k) {
+    // the heads are done: the pooled routes' gradients (cat2 / cat1 route channels, the pooled stride-32 plane) are
+    // final.  window_pool_bwd writes the per-frame route planes' gradients; stages.1.0 / stages.2.0 accumulate onto them
+    HIP_TRY(vy_launch_window_pool_bwd(net->pool_args(c.gplanes()), c.s));
+    for (int i = 0; i < 3; ++i) st.whole(net, net->frame_routes[i]);
   }
-  if (int rc = emit_bucket(cur_bucket)) return rc;
-  if (int rc = join_side()) return rc;
-  if (!skips.empty()) return fail(VY_ERR_STATE, "internal: unresolved skip gradient");
-  if (!g_labels_done && g_labels.f) {
-    g_labels.close_step();
-    g_labels_done = true;
-  }
+  VY_TRY(backward_cells(c, st, 0, net->n_backbone, x));
+  VY_TRY(join_side(c));
+  if (!st.skips.empty()) return fail(VY_ERR_STATE, "internal: unresolved skip gradient");
+  g_labels.close_step();
   return 0;
+}
+
+// VY_ERR_STATE unless vy_net_bind_train bound the gradient buffers — and, same_shape: its plan is the one the workspace
+// is bound with now (the step entries; `hint` completes the message)
+int bound_train(const vy_net* net, bool same_shape, const char* hint) {
+  const VyTrain* t = net->train;
+  if (!t || !t->grads || (same_shape && (t->plan.B != net->B || t->plan.H != net->H || t->plan.W != net->W)))
+    return fail(VY_ERR_STATE, "training workspace not bound%s", hint);
+  return 0;
+}
+
+// the recorded forward, then the fused target-merge + loss + d(loss)/d(pred) kernel
+struct LossInputs {
+  const float *gt_boxes, *obj_t, *centers_t, *scales_t, *weights_t, *clas_t;
+  int32_t M;
+  float* losses;
+  bool ok() const { return obj_t && centers_t && scales_t && weights_t && clas_t && losses && (M <= 0 || gt_boxes); }
+};
+int train_forward(vy_net* net, const float* x, const float* const* routes, const LossInputs& in, hipStream_t s) {
+  VY_TRY(bound_train(net, true, " (vy_net_bind_train)"));
+  TrainCtx c(net, s);
+  VY_TRY(forward_train(c, x, routes));
+  const DetArgs d = net->det_args();
+  LossArgs la;
+  memset(&la, 0, sizeof la);
+  int N = 0;
+  for (int i = 0; i < 3; ++i) {
+    la.head[i] = d.head[i];
+    la.dpred[i] = c.gplane(net->head_plane[i]);
+    N += 3 * d.head[i].H * d.head[i].W;
+  }
+  la.gt_boxes = in.gt_boxes;
+  la.obj_t = in.obj_t;
+  la.centers_t = in.centers_t;
+  la.scales_t = in.scales_t;
+  la.weights_t = in.weights_t;
+  la.clas_t = in.clas_t;
+  la.partials = c.at<float>(c.p.loss_part_off);
+  la.B = net->B;
+  la.C = net->num_class;
+  la.M = in.M;
+  la.N = N;
+  la.ignore_iou_thresh = c.t->ignore_iou;
+  la.label_smooth = c.t->label_smooth;
+  HIP_TRY(vy_launch_loss(la, c.s));
+  HIP_TRY(vy_launch_loss_reduce(la.partials, vy_loss_blocks_per_image(N), net->B, in.losses, c.s));
+  c.t->forward_done = true;
+  c.t->M = in.M;
+  return 0;
+}
+
+// the training-mode forward without a recording: the raw predictions
+struct RawOutputs {
+  float *box_preds, *centers, *scales, *objness, *class_pred;
+  bool ok() const { return box_preds && centers && scales && objness && class_pred; }
+};
+int train_mode_forward(vy_net* net, const float* x, const float* const* routes, const RawOutputs& out, hipStream_t s) {
+  VY_TRY(bound_train(net, true, " (vy_net_bind_train)"));
+  TrainCtx c(net, s);
+  VY_TRY(forward_train(c, x, routes));
+  c.t->forward_done = false;  // nothing was recorded: no backward may follow
+  const DetArgs d = net->det_args();
+  RawPredArgs ra;
+  memset(&ra, 0, sizeof ra);
+  int N = 0;
+  for (int i = 0; i < 3; ++i) {
+    ra.head[i] = d.head[i];
+    N += 3 * d.head[i].H * d.head[i].W;
+  }
+  ra.box = out.box_preds;
+  ra.centers = out.centers;
+  ra.scales = out.scales;
+  ra.objness = out.objness;
+  ra.class_pred = out.class_pred;
+  ra.B = net->B;
+  ra.C = net->num_class;
+  ra.N = N;
+  HIP_TRY(vy_launch_raw_preds(ra, c.s));
+  return 0;
+}
+
+int train_backward(vy_net* net, const float* x, hipStream_t s) {
+  VyTrain* t = net->train;
+  if (!t || !t->forward_done) return fail(VY_ERR_STATE, "vy_net_train_backward without a recorded forward");
+  t->forward_done = false;
+  return backward_train(TrainCtx(net, s), x);
 }
 
 }  // namespace
@@ -911,7 +970,8 @@ size_t vy_net_train_workspace_bytes(const vy_net* net, int32_t batch, int32_t he
   if (!net) return 0;
   if (check_train_shape(height, width)) return 0;
   if (vy_net_workspace_bytes(net, batch, height, width) == 0) return 0;
-  return train_plan(const_cast<vy_net*>(net), batch, height, width, false);
+  vy_net* n = const_cast<vy_net*>(net);
+  return plan_train(n, *get_train(n), batch, height, width, false).total;
 }
 
 int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, int32_t height, int32_t width,
@@ -920,14 +980,14 @@ int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, in
   if (int rc = check_train_shape(height, width)) return rc;
   if (vy_net_workspace_bytes(net, batch, height, width) == 0) return VY_ERR_INVALID;
   if (int rc = net->bind_cus(dev_ws)) return rc;
-  const size_t need = train_plan(net, batch, height, width, false);
+  VyTrain* t = get_train(net);
+  const size_t need = plan_train(net, *t, batch, height, width, false).total;
   if (bytes < need) return fail(VY_ERR_INVALID, "training workspace too small: %zu < %zu bytes", bytes, need);
-  train_plan(net, batch, height, width, true);
-  VyTrain* t = net->train;
+  t->plan = plan_train(net, *t, batch, height, width, true);
+  t->sdesc_uploaded = t->tabs_built = t->seg_uploaded = false;  // (the workspace is zeroed below)
   t->grads = static_cast<float*>(dev_grads);
   t->mom = static_cast<float*>(dev_momentum);
   t->forward_done = false;
-  t->sdesc_uploaded = false;  // (the workspace is zeroed below)
   VY_TRY(net->commit_bind(dev_ws, bytes, need, static_cast<hipStream_t>(stream)));
   if (net->knobs.train_side_stream && !t->side) {
     // (The weight-gradient stream at the LOWEST queue priority was measured: +0.4 % on top of the raised issue priority of the
@@ -948,143 +1008,53 @@ int vy_net_set_train_options(vy_net* net, float ignore_iou_thresh, int32_t label
   return 0;
 }
 
-static int train_forward_impl(vy_net* net, const float* x, const float* const* routes, const float* gt_boxes, int32_t M,
-                              const float* obj_t, const float* centers_t, const float* scales_t, const float* weights_t,
-                              const float* clas_t, float* losses, void* stream) {
-  if (!net || !(routes ? routes[0] && routes[1] && routes[2] : x != nullptr) || !obj_t || !centers_t || !scales_t || !weights_t || !clas_t || !losses || (M > 0 && !gt_boxes))
-    return fail(VY_ERR_INVALID, "null argument");
-  if (int rc = net->check_ready()) return rc;
-  VyTrain* t = net->train;
-  if (!t || !t->grads || t->B != net->B || t->H != net->H || t->W != net->W)
-    return fail(VY_ERR_STATE, "training workspace not bound (vy_net_bind_train)");
-  TrainCtx c{net, t, static_cast<hipStream_t>(stream)};
-  if (int rc = forward_train(c, x, routes)) return rc;
-  const DetArgs d = net->det_args();
-  LossArgs la;
-  memset(&la, 0, sizeof la);
-  int N = 0;
-  for (int i = 0; i < 3; ++i) {
-    la.head[i] = d.head[i];
-    la.dpred[i] = c.gplane(net->head_plane[i]);
-    N += 3 * d.head[i].H * d.head[i].W;
-  }
-  la.gt_boxes = gt_boxes;
-  la.obj_t = obj_t;
-  la.centers_t = centers_t;
-  la.scales_t = scales_t;
-  la.weights_t = weights_t;
-  la.clas_t = clas_t;
-  la.partials = reinterpret_cast<float*>(net->dev_ws + t->loss_part_off);
-  la.B = net->B;
-  la.C = net->num_class;
-  la.M = M;
-  la.N = N;
-  la.ignore_iou_thresh = t->ignore_iou;
-  la.label_smooth = t->label_smooth;
-  HIP_TRY(vy_launch_loss(la, c.s));
-  HIP_TRY(vy_launch_loss_reduce(la.partials, vy_loss_blocks_per_image(N), net->B, losses, c.s));
-  t->forward_done = true;
-  t->M = M;
-  return 0;
-}
-
+// ---- the six step entries: the kind check, then the frame of the inference entries (run_entry) around the pass
 int vy_net_train_forward(vy_net* net, const float* x, const float* gt_boxes, int32_t M, const float* obj_t,
                          const float* centers_t, const float* scales_t, const float* weights_t,
                          const float* clas_t, float* losses, void* stream) {
-  if (int rc = vy_check_kind(net, false, "vy_net_train_forward")) return rc;
+  VY_TRY(vy_check_kind(net, false, "vy_net_train_forward"));
 #ifdef VY_TRAIN_ABL_BUILD
   ++g_abl_forwards;
 #endif
-  if (net)
-    if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
-  const int rc = train_forward_impl(net, x, nullptr, gt_boxes, M, obj_t, centers_t, scales_t, weights_t, clas_t, losses, stream);
-  return net ? net->sk_end(rc) : rc;
+  const LossInputs in{gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t, M, losses};
+  return run_entry(net, x && in.ok(), nullptr, stream, [&](hipStream_t s) { return train_forward(net, x, nullptr, in, s); });
 }
 
 int vy_net_train_forward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, const float* gt_boxes,
                                 int32_t M, const float* obj_t, const float* centers_t, const float* scales_t,
                                 const float* weights_t, const float* clas_t, float* losses, void* stream) {
-  if (int rc = vy_check_kind(net, true, "vy_net_train_forward_routes")) return rc;
-  if (net)
-    if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
+  VY_TRY(vy_check_kind(net, true, "vy_net_train_forward_routes"));
   const float* const routes[3] = {f0, f1, f2};
-  const int rc = train_forward_impl(net, nullptr, routes, gt_boxes, M, obj_t, centers_t, scales_t, weights_t, clas_t, losses,
-                                    stream);
-  return net ? net->sk_end(rc) : rc;
-}
-
-static int train_mode_forward_impl(vy_net* net, const float* x, const float* const* routes, float* box_preds, float* centers,
-                                   float* scales, float* objness, float* class_pred, void* stream) {
-  if (!net || !(routes ? routes[0] && routes[1] && routes[2] : x != nullptr) || !box_preds || !centers || !scales || !objness || !class_pred) return fail(VY_ERR_INVALID, "null argument");
-  if (int rc = net->check_ready()) return rc;
-  VyTrain* t = net->train;
-  if (!t || !t->grads || t->B != net->B || t->H != net->H || t->W != net->W)
-    return fail(VY_ERR_STATE, "training workspace not bound (vy_net_bind_train)");
-  TrainCtx c{net, t, static_cast<hipStream_t>(stream)};
-  if (int rc = forward_train(c, x, routes)) return rc;
-  t->forward_done = false;  // nothing was recorded: no backward may follow
-  const DetArgs d = net->det_args();
-  RawPredArgs ra;
-  memset(&ra, 0, sizeof ra);
-  int N = 0;
-  for (int i = 0; i < 3; ++i) {
-    ra.head[i] = d.head[i];
-    N += 3 * d.head[i].H * d.head[i].W;
-  }
-  ra.box = box_preds;
-  ra.centers = centers;
-  ra.scales = scales;
-  ra.objness = objness;
-  ra.class_pred = class_pred;
-  ra.B = net->B;
-  ra.C = net->num_class;
-  ra.N = N;
-  HIP_TRY(vy_launch_raw_preds(ra, c.s));
-  return 0;
+  const LossInputs in{gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t, M, losses};
+  return run_entry(net, f0 && f1 && f2 && in.ok(), nullptr, stream,
+                   [&](hipStream_t s) { return train_forward(net, nullptr, routes, in, s); });
 }
 
 int vy_net_train_mode_forward(vy_net* net, const float* x, float* box_preds, float* centers, float* scales,
                               float* objness, float* class_pred, void* stream) {
-  if (int rc = vy_check_kind(net, false, "vy_net_train_mode_forward")) return rc;
-  if (net)
-    if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
-  const int rc = train_mode_forward_impl(net, x, nullptr, box_preds, centers, scales, objness, class_pred, stream);
-  return net ? net->sk_end(rc) : rc;
+  VY_TRY(vy_check_kind(net, false, "vy_net_train_mode_forward"));
+  const RawOutputs out{box_preds, centers, scales, objness, class_pred};
+  return run_entry(net, x && out.ok(), nullptr, stream, [&](hipStream_t s) { return train_mode_forward(net, x, nullptr, out, s); });
 }
 
 int vy_net_train_mode_forward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* box_preds,
                                      float* centers, float* scales, float* objness, float* class_pred, void* stream) {
-  if (int rc = vy_check_kind(net, true, "vy_net_train_mode_forward_routes")) return rc;
-  if (net)
-    if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
+  VY_TRY(vy_check_kind(net, true, "vy_net_train_mode_forward_routes"));
   const float* const routes[3] = {f0, f1, f2};
-  const int rc = train_mode_forward_impl(net, nullptr, routes, box_preds, centers, scales, objness, class_pred, stream);
-  return net ? net->sk_end(rc) : rc;
-}
-
-static int train_backward_impl(vy_net* net, const float* x, void* stream) {
-  if (!net || (!x && !net->heads_only)) return fail(VY_ERR_INVALID, "null argument");
-  if (int rc = net->check_ready()) return rc;
-  VyTrain* t = net->train;
-  if (!t || !t->forward_done) return fail(VY_ERR_STATE, "vy_net_train_backward without a recorded forward");
-  TrainCtx c{net, t, static_cast<hipStream_t>(stream)};
-  t->forward_done = false;
-  return backward_train(c, x);
+  const RawOutputs out{box_preds, centers, scales, objness, class_pred};
+  return run_entry(net, f0 && f1 && f2 && out.ok(), nullptr, stream,
+                   [&](hipStream_t s) { return train_mode_forward(net, nullptr, routes, out, s); });
 }
 
 int vy_net_train_backward(vy_net* net, const float* x, void* stream) {
-  if (int rc = vy_check_kind(net, false, "vy_net_train_backward")) return rc;
-  if (net)
-    if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
-  const int rc = train_backward_impl(net, x, stream);
-  return net ? net->sk_end(rc) : rc;
+  VY_TRY(vy_check_kind(net, false, "vy_net_train_backward"));
+  return run_entry(net, x != nullptr, nullptr, stream, [&](hipStream_t s) { return train_backward(net, x, s); });
 }
 
 int vy_net_train_backward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, void* stream) {
-  if (int rc = vy_check_kind(net, true, "vy_net_train_backward_routes")) return rc;
-  if (!net || !f0 || !f1 || !f2) return fail(VY_ERR_INVALID, "null argument");
-  if (int rc = net->sk_begin(static_cast<hipStream_t>(stream))) return rc;
-  return net->sk_end(train_backward_impl(net, nullptr, stream));  // (nothing is read from the routes: see backward_train)
+  VY_TRY(vy_check_kind(net, true, "vy_net_train_backward_routes"));
+  // (nothing is read from the routes: see data_grad)
+  return run_entry(net, f0 && f1 && f2, nullptr, stream, [&](hipStream_t s) { return train_backward(net, nullptr, s); });
 }
 
 int vy_net_param_set_opt(vy_net* net, int32_t i, float lr_mult, float wd_mult, int32_t enabled) {
@@ -1093,53 +1063,47 @@ int vy_net_param_set_opt(vy_net* net, int32_t i, float lr_mult, float wd_mult, i
   t->lr_mult[i] = lr_mult;
   t->wd_mult[i] = wd_mult;
   t->enabled[i] = enabled ? 1 : 0;
-  // refresh the segment table in place if it is already planned
+  // refresh the segment table in place if it is already planned (a segment per trainable parameter, in order)
   int si = 0;
-  for (int p = 0; p < (int)net->params.size(); ++p) {
-    if (!net->params[p].info.trainable) continue;
-    if (p == i && si < (int)t->segs.size()) {
-      SgdSeg& sg = t->segs[si];
-      const int en = enabled ? 1 : 0;
-      if (sg.lr_mult != lr_mult || sg.wd_mult != wd_mult || sg.enabled != en) {  // re-upload only on a change
-        sg.lr_mult = lr_mult;
-        sg.wd_mult = wd_mult;
-        sg.enabled = en;
-        t->seg_uploaded = false;
-      }
-    }
-    ++si;
+  for (int p = 0; p < i; ++p) si += net->params[p].info.trainable ? 1 : 0;
+  if (!net->params[i].info.trainable || si >= (int)t->plan.segs.size()) return 0;
+  SgdSeg& sg = t->plan.segs[si];
+  const int en = enabled ? 1 : 0;
+  if (sg.lr_mult != lr_mult || sg.wd_mult != wd_mult || sg.enabled != en) {  // re-upload only on a change
+    sg.lr_mult = lr_mult;
+    sg.wd_mult = wd_mult;
+    sg.enabled = en;
+    t->seg_uploaded = false;
   }
   return 0;
 }
 
 int vy_net_sgd_step(vy_net* net, float lr, float momentum, float wd, float rescale_grad, void* stream) {
   if (!net) return fail(VY_ERR_INVALID, "net is null");
-  if (int rc = net->check_ready()) return rc;
-  VyTrain* t = net->train;
-  if (!t || !t->grads) return fail(VY_ERR_STATE, "training workspace not bound (vy_net_bind_train)");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  SgdSeg* segs = reinterpret_cast<SgdSeg*>(net->dev_ws + t->seg_off);
-  int32_t* chunks = reinterpret_cast<int32_t*>(net->dev_ws + t->chunk_off);
-  if (!t->seg_uploaded) {
-    HIP_TRY(hipMemcpyAsync(segs, t->segs.data(), t->segs.size() * sizeof(SgdSeg), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(chunks, t->chunk_seg.data(), t->chunk_seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));  // pageable host vectors; only when the table changed
-    t->seg_uploaded = true;
+  VY_TRY(net->check_ready());
+  VY_TRY(bound_train(net, false, " (vy_net_bind_train)"));
+  TrainCtx c(net, stream);
+  SgdSeg* segs = c.at<SgdSeg>(c.p.seg_off);
+  int32_t* chunks = c.at<int32_t>(c.p.chunk_off);
+  if (!c.t->seg_uploaded) {
+    HIP_TRY(hipMemcpyAsync(segs, c.p.segs.data(), c.p.segs.size() * sizeof(SgdSeg), hipMemcpyHostToDevice, c.s));
+    HIP_TRY(hipMemcpyAsync(chunks, c.p.chunk_seg.data(), c.p.chunk_seg.size() * sizeof(int32_t), hipMemcpyHostToDevice, c.s));
+    HIP_TRY(hipStreamSynchronize(c.s));  // pageable host vectors; only when the table changed
+    c.t->seg_uploaded = true;
   }
-  HIP_TRY(vy_launch_sgd(net->dev_params, t->grads, t->mom, segs, chunks, (int)(t->chunk_seg.size() / 2), lr, momentum,
-                        wd, rescale_grad, s));
+  HIP_TRY(vy_launch_sgd(net->dev_params, c.t->grads, c.t->mom, segs, chunks, (int)(c.p.chunk_seg.size() / 2), lr, momentum,
+                        wd, rescale_grad, c.s));
   net->split_dirty = net->dsplit_dirty = net->wino_dirty = true;  // conv mode VY_CONV_SPLIT_BF16X3: the weight images are stale now
   return 0;
 }
 
 int vy_net_grad_get(vy_net* net, int32_t i, float* host_dst, void* stream) {
   if (!net || !host_dst || i < 0 || i >= (int32_t)net->params.size()) return fail(VY_ERR_INVALID, "bad argument");
-  VyTrain* t = net->train;
-  if (!t || !t->grads) return fail(VY_ERR_STATE, "training workspace not bound");
+  VY_TRY(bound_train(net, false, ""));
   const vy_param_info& pi = net->params[i].info;
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::vector<float> tmp((size_t)pi.size);
-  HIP_TRY(hipMemcpyAsync(tmp.data(), t->grads + pi.offset, sizeof(float) * pi.size, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(tmp.data(), net->train->grads + pi.offset, sizeof(float) * pi.size, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (pi.ndim == 4) {
     const int O = pi.shape[0], I = pi.shape[1], kk = pi.shape[2] * pi.shape[3];
@@ -1154,10 +1118,9 @@ int vy_net_grad_get(vy_net* net, int32_t i, float* host_dst, void* stream) {
 
 int vy_net_read_grad_activation(vy_net* net, const char* name, float* dst_dev, void* stream) {
   if (!net || !name || !dst_dev) return fail(VY_ERR_INVALID, "bad argument");
-  if (int rc = net->check_ready()) return rc;
-  VyTrain* t = net->train;
-  if (!t || !t->grads) return fail(VY_ERR_STATE, "training workspace not bound");
-  TrainCtx c{net, t, static_cast<hipStream_t>(stream)};
+  VY_TRY(net->check_ready());
+  VY_TRY(bound_train(net, false, ""));
+  TrainCtx c(net, stream);
   if (const int i = vy_pool_tap(net, name); i >= 0) {
     const vy_net::RouteSlot& r = net->routes[i];
     const PlaneT& p = net->planes[r.plane];
@@ -1176,13 +1139,13 @@ int vy_net_read_grad_activation(vy_net* net, const char* name, float* dst_dev, v
 
 int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* dst_dev, int32_t* dims, void* stream) {
   if (!net || !name) return fail(VY_ERR_INVALID, "bad argument");
-  if (int rc = net->check_ready()) return rc;
-  VyTrain* t = net->train;
-  if (!t || !t->grads) return fail(VY_ERR_STATE, "training workspace not bound");
-  TrainCtx c{net, t, static_cast<hipStream_t>(stream)};
-  for (size_t ci = 0; ci < net->convs.size(); ++ci) {
+  VY_TRY(net->check_ready());
+  VY_TRY(bound_train(net, false, ""));
+  TrainCtx c(net, stream);
+  for (int ci = 0; ci < (int)net->convs.size(); ++ci) {
     const ConvT& cv = net->convs[ci];
     if (cv.name != name) continue;
+    const TrainCell& cell = c.cell(ci);
     const bool bn = cv.p_gamma >= 0;
     int32_t d[4] = {net->conv_batch(cv), cv.cout, 0, 0};
     const float* src = nullptr;
@@ -1190,10 +1153,10 @@ int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* d
     switch (which) {
       case VY_TAP_Z:
         if (!bn) return fail(VY_ERR_INVALID, "'%s' has no z plane", name);
-        src = c.zplane((int)ci);
-        d[2] = t->z[ci].H + 2;
-        d[3] = t->z[ci].W + 2;
-        cs = t->z[ci].C;
+        src = c.zplane(ci);
+        d[2] = cell.Ho + 2;
+        d[3] = cell.Wo + 2;
+        cs = cell.z_cs;
         break;
       case VY_TAP_BN:
         if (!bn) return fail(VY_ERR_INVALID, "'%s' has no BatchNorm", name);
@@ -1226,11 +1189,10 @@ int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* d
     if (dims) memcpy(dims, d, sizeof d);
     if (!dst_dev) return 0;
     if (which == VY_TAP_BN) {
-      const int C = cv.cout;
-      const float* rows[4] = {c.save((int)ci), c.save((int)ci) + ((C + 63) & ~63), net->dev_params + cv.scale_off,
-                              net->dev_params + cv.shift_off};
+      const BnViews v = c.bn_views(ci);
+      const float* rows[4] = {v.save_mean, v.save_invstd, v.scale, v.shift};
       for (int r = 0; r < 4; ++r)
-        HIP_TRY(hipMemcpyAsync(dst_dev + (size_t)r * C, rows[r], sizeof(float) * C, hipMemcpyDeviceToDevice, c.s));
+        HIP_TRY(hipMemcpyAsync(dst_dev + (size_t)r * cv.cout, rows[r], sizeof(float) * cv.cout, hipMemcpyDeviceToDevice, c.s));
       return 0;
     }
     HIP_TRY(vy_launch_padded_plane_to_nchw(src, d[0], d[2], d[3], cs, co, d[1], dst_dev, c.s));
@@ -1243,16 +1205,14 @@ int vy_net_train_conv_plan(const vy_net* net, int32_t i, int32_t* wgrad_splits, 
                            int32_t* bn_bwd_rows_per_chunk) {
   if (!net || i < 0 || i >= (int32_t)net->convs.size()) return fail(VY_ERR_INVALID, "bad argument");
   const VyTrain* t = net->train;
-  if (!t || t->splits.size() != net->convs.size()) return fail(VY_ERR_STATE, "no training plan");
+  if (!t || t->plan.cells.size() != net->convs.size()) return fail(VY_ERR_STATE, "no training plan");
   const ConvT& cv = net->convs[i];
-  int sp = t->splits[i], kps = t->kps[i];
-  if (cv.is_stem) {  // stem_wgrad_kernel: one fp32 accumulator per wave over 512 pixels, the four waves of a block added
-    sp = 4;            // in fp32, the blocks in double
-    kps = 512;
-  }
-  if (wgrad_splits) *wgrad_splits = sp;
-  if (wgrad_k_per_split) *wgrad_k_per_split = kps;
-  if (bn_bwd_rows_per_chunk) *bn_bwd_rows_per_chunk = cv.p_gamma >= 0 ? vy_bn_bwd_rows_per_chunk(t->B * net->planes[cv.out_plane].fm, t->z[i].H, cv.cout) : 0;
+  const TrainCell& cell = t->plan.cells[i];
+  // (stem_wgrad_kernel: one fp32 accumulator per wave over 512 pixels, the four waves of a block added in fp32, the
+  // blocks in double)
+  if (wgrad_splits) *wgrad_splits = cv.is_stem ? 4 : cell.splits;
+  if (wgrad_k_per_split) *wgrad_k_per_split = cv.is_stem ? 512 : cell.k_per_split;
+  if (bn_bwd_rows_per_chunk) *bn_bwd_rows_per_chunk = cv.p_gamma >= 0 ? vy_bn_bwd_rows_per_chunk(cell.B, cell.Ho, cv.cout) : 0;
   return 0;
 }
 
