@@ -128,37 +128,56 @@ def border_zero(kind, name, p):
 
 
 # ---------------------------------------------------------------- the graph
-def graph(num_class):
-    """Cells in forward order: dict(name, k, s, cin, cout, bn, ups, src, skip).  `src`: the producers whose outputs,
-    concatenated in this order, are the cell's input ("image" for the stem); `skip`: the producer whose output is
-    added to this cell's (residual blocks)."""
+ROUTE_CHANNELS = (256, 512, 1024)  # strides 8, 16, 32
+
+
+def graph(num_class, k=1, heads_only=False):
+    """Cells in forward order: dict(name, k, s, cin, cout, bn, ups, src, skip, fm).  `src`: the producers whose
+    outputs, concatenated in this order, are the cell's input ("image" for the stem); `skip`: the producer whose output
+    is added to this cell's (residual blocks); `fm`: the frame multiplier (PlaneT::fm), the cell runs on B * fm frames.
+
+    k > 1 is the window net: the stem and the stages run on the B * k frames (fm = k), and three pool nodes
+    "pool.0" .. "pool.2" (strides 8, 16, 32; dict(name, pool=True, src=[route cell], cout, fm=1)) stand between the
+    per-frame route cells and the head cells that read the routes; stages.1.0 / stages.2.0 keep reading the per-frame
+    routes.  heads_only is the heads net: the head cells alone, their route inputs named "route.0" .. "route.2"."""
+    if heads_only and k != 1:
+        raise ValueError("the heads net has no frames to pool")
     cells = []
 
-    def add(name, k, s, cin, cout, src, bn=True, ups=1, skip=None):
-        cells.append(dict(name=name, k=k, s=s, cin=cin, cout=cout, bn=bn, ups=ups, src=list(src), skip=skip))
+    def add(name, k_, s, cin, cout, src, bn=True, ups=1, skip=None, fm=1):
+        cells.append(dict(name=name, k=k_, s=s, cin=cin, cout=cout, bn=bn, ups=ups, src=list(src), skip=skip, fm=fm))
 
-    feats = O.darknet_feature_cells()
-    prev, routes = "image", []
-    for si, (lo, hi) in enumerate(O.STAGE_SLICES):
-        for j, f in enumerate(feats[lo:hi]):
-            pre = "stages.%d.%d" % (si, j)
-            if f[0] == "conv":
-                add(pre, f[3], f[4], f[1], f[2], [prev])
-                prev = pre
-            else:
-                c = f[1]
-                add(pre + ".body.0", 1, 1, c, c // 2, [prev])
-                add(pre + ".body.1", 3, 1, c // 2, c, [pre + ".body.0"], skip=prev)
-                prev = pre + ".body.1"
-        routes.append(prev)
-    chans = {c["name"]: c["cout"] for c in cells}
+    if heads_only:
+        routes = ["route.%d" % i for i in range(3)]
+        chans = dict(zip(routes, ROUTE_CHANNELS))
+    else:
+        feats = O.darknet_feature_cells()
+        prev, routes = "image", []
+        for si, (lo, hi) in enumerate(O.STAGE_SLICES):
+            for j, f in enumerate(feats[lo:hi]):
+                pre = "stages.%d.%d" % (si, j)
+                if f[0] == "conv":
+                    add(pre, f[3], f[4], f[1], f[2], [prev], fm=k)
+                    prev = pre
+                else:
+                    c = f[1]
+                    add(pre + ".body.0", 1, 1, c, c // 2, [prev], fm=k)
+                    add(pre + ".body.1", 3, 1, c // 2, c, [pre + ".body.0"], skip=prev, fm=k)
+                    prev = pre + ".body.1"
+            routes.append(prev)
+        chans = {c["name"]: c["cout"] for c in cells}
+        if k > 1:
+            for i, r in enumerate(routes):
+                cells.append(dict(name="pool.%d" % i, pool=True, src=[r], cin=chans[r], cout=chans[r], fm=1, skip=None))
+                chans["pool.%d" % i] = chans[r]
+            routes = ["pool.%d" % i for i in range(3)]
     x = [routes[2]]
     for i, ch in enumerate(O.HEAD_CHANNELS):
         cin = sum(chans[p] for p in x)
         for j in range(5):
-            oc, k = (ch, 1) if j % 2 == 0 else (2 * ch, 3)
+            oc, kk = (ch, 1) if j % 2 == 0 else (2 * ch, 3)
             name = "yolo_blocks.%d.body.%d" % (i, j)
-            add(name, k, 1, cin, oc, x)
+            add(name, kk, 1, cin, oc, x)
             x, cin = [name], oc
         route = x[0]
         add("yolo_blocks.%d.tip" % i, 3, 1, ch, 2 * ch, [route])
@@ -172,18 +191,83 @@ def graph(num_class):
     return cells
 
 
+def is_pool(c):
+    return bool(c.get("pool"))
+
+
 def consumers(cells):
-    """producer name -> [(consumer cell, channel offset of the producer inside the consumer's input)] and
-    producer name -> [cells whose skip it is]"""
+    """producer name -> [(consumer, channel offset of the producer inside the consumer's input)] and
+    producer name -> [cells whose skip it is].  A consumer is a conv cell or a pool node (is_pool); the producers are
+    cells, pool nodes, "image" and the heads net's imported routes "route.i"."""
+    width = {c["name"]: c["cout"] for c in cells}
+    width["image"] = 3
+    width.update({"route.%d" % i: ch for i, ch in enumerate(ROUTE_CHANNELS)})
     cons, skips = {}, {}
     for c in cells:
         off = 0
         for p in c["src"]:
             cons.setdefault(p, []).append((c, off))
-            off += next((q["cout"] for q in cells if q["name"] == p), 3)
+            off += width[p]
         if c["skip"]:
             skips.setdefault(c["skip"], []).append(c)
     return cons, skips
+
+
+# ---------------------------------------------------------------- temporal pooling (temporal.hip)
+def pool_forward(frames, k, join):
+    """TemporalPooling 'direct' over each clip's k frames (frame t of clip b is frame b*k + t) in temporal.hip's pinned
+    fp32 arithmetic: max is strict > in frame order (ties keep the earliest frame's bits), mean is
+    acc = x0; acc += x1; ...; acc / float32(k)."""
+    f = np.asarray(frames, F32)
+    f = f.reshape((-1, k) + f.shape[1:])
+    acc = f[:, 0].copy()
+    for t in range(1, k):
+        v = f[:, t]
+        if join == "max":
+            m = v > acc
+            acc[m] = v[m]
+        else:
+            acc = (acc + v).astype(F32)
+    if join == "mean":
+        acc = (acc / F32(k)).astype(F32)
+    return acc
+
+
+def pool_backward(g_pooled, frames, pooled, k, join):
+    """Per-frame route gradients (B*k, ...) window_pool_bwd writes: mean gives g / float32(k) to every frame, max gives g
+    to every frame with x_t == pooled (IEEE equality: every tied frame gets the full g) and +0 to the others."""
+    g = np.asarray(g_pooled, F32)
+    f = np.asarray(frames, F32)
+    f = f.reshape((-1, k) + f.shape[1:])
+    if join == "mean":
+        out = np.repeat((g / F32(k)).astype(F32)[:, None], k, axis=1)
+    else:
+        out = np.where(f == np.asarray(pooled, F32)[:, None], g[:, None], F32(0.0)).astype(F32)
+    return np.ascontiguousarray(out.reshape((-1,) + f.shape[2:]))
+
+
+def check_pool_forward(name, frames, k, join, pooled_got):
+    """the pooled route on the device's own per-frame route values: bit-equal"""
+    return _exact("pool forward", name, pooled_got, pool_forward(frames, k, join))
+
+
+def pool_wins(frames, k):
+    """(wins, ties) of (B*k, ...) per-frame values: wins[t] = the number of elements where frame t alone holds the
+    clip's maximum, ties = the number of elements where more than one frame holds it"""
+    f = np.asarray(frames, F32)
+    f = f.reshape((-1, k) + f.shape[1:])
+    hold = f == f.max(axis=1, keepdims=True)
+    n_hold = hold.sum(axis=1, keepdims=True)
+    wins = [int(np.count_nonzero(hold[:, t:t + 1] & (n_hold == 1))) for t in range(k)]
+    return wins, int(np.count_nonzero(n_hold > 1))
+
+
+def check_pool_backward(name, g_pooled, frames, pooled, k, join, got):
+    """window_pool_bwd's output on the device's own pooled gradient, per-frame route values and pooled values:
+    bit-equal.  Returns (Result, wins, ties) with pool_wins' counts of one route."""
+    res = _exact("pool backward", name, got, pool_backward(g_pooled, frames, pooled, k, join))
+    wins, ties = pool_wins(frames, k)
+    return res, wins, ties
 
 
 # ---------------------------------------------------------------- per-kernel checks

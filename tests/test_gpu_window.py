@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import frames
+from oracle.train_cells64 import pool_forward as np_pool
 from test_oracle_train_vs_torch import TorchYolo3Train
 
 pytestmark = pytest.mark.gpu
@@ -62,23 +63,6 @@ def _bits(t):
 def _same(a, b):
     import torch
     return a.shape == b.shape and a.dtype == b.dtype and torch.equal(_bits(a), _bits(b))
-
-
-def np_pool(f, k, join):
-    """The pinned order: max keeps the earliest frame on ties (strict >), mean adds in frame order then divides by k."""
-    f = np.asarray(f, np.float32)
-    f = f.reshape((-1, k) + f.shape[1:])
-    acc = f[:, 0].copy()
-    for t in range(1, k):
-        v = f[:, t]
-        if join == "max":
-            m = v > acc
-            acc[m] = v[m]
-        else:
-            acc = (acc + v).astype(np.float32)
-    if join == "mean":
-        acc = (acc / np.float32(k)).astype(np.float32)
-    return acc
 
 
 @pytest.fixture(scope="module")

@@ -3,7 +3,12 @@
 Small synthetic cells — stride 1 and 2, 1x1 and 3x3, a residual skip, a x2 transition, a plane with two consumers —
 with a "device" side computed in fp32 in a blocked order different from the reference's (split-K slabs, row chunks,
 fp32 convolutions).  It must pass every check.  Each of eight mutations of a kernel must fail one; the test also
-records whether the end-to-end bar (max|got - want| < 2e-3 max|want| over the tensor) would have caught it."""
+records whether the end-to-end bar (max|got - want| < 2e-3 max|want| over the tensor) would have caught it.
+
+A toy window step (k = 3) does the same for the window net's checks: a per-frame route cell with its batch statistics,
+the pool, one head consumer of the pooled plane, a stride-2 consumer of the per-frame route whose data gradient
+accumulates onto what the pool backward wrote, and a route with no other contributor (the stride-32 case).  Some
+elements of the clips tie and some do not.  Eight more mutations must each fail a check."""
 import numpy as np
 import pytest
 import torch
@@ -179,6 +184,149 @@ def test_every_mutation_fails_the_per_cell_check(mut):
     caught = old and not all(old)
     print("%s: fails %s; the 2e-3-of-max bar %s" % (mut, sorted(set(r.kind for r in bad)),
                                                     "catches it" if caught else "MISSES it"))
+
+
+# ---------------------------------------------------------------- the toy window step
+def dev_pool(frames, B, k, join, frame_of=lambda b, t, B, k: b * k + t):
+    """the pool kernel's loop over one clip's frames, clip by clip"""
+    out = np.empty((B,) + frames.shape[1:], F32)
+    for b in range(B):
+        acc = frames[frame_of(b, 0, B, k)].copy()
+        for t in range(1, k):
+            v = frames[frame_of(b, t, B, k)]
+            acc = np.where(v > acc, v, acc) if join == "max" else (acc + v).astype(F32)
+        out[b] = acc if join == "max" else (acc / F32(k)).astype(F32)
+    return out
+
+
+def dev_pool_bwd(g, frames, pooled, B, k, join, mut=None):
+    out = np.zeros_like(frames)
+    for b in range(B):
+        fr = frames[b * k:(b + 1) * k]
+        if join == "mean":
+            out[b * k:(b + 1) * k] = g[b] if mut == "mean_backward_without_the_division" else (g[b] / F32(k)).astype(F32)
+            continue
+        hold = fr == pooled[b]
+        if mut == "max_backward_to_first_maximal_frame_only":
+            hold &= np.cumsum(hold, axis=0) == 1
+        gb = np.broadcast_to(g[b], fr.shape)
+        if mut == "max_backward_split_among_ties":
+            gb = (gb / hold.sum(axis=0).astype(F32)).astype(F32)
+        out[b * k:(b + 1) * k] = np.where(hold, gb, F32(0))
+    return out
+
+
+WINDOW_MUTATIONS = ["max_backward_to_first_maximal_frame_only", "max_backward_split_among_ties",
+                    "mean_backward_without_the_division", "frames_taken_as_t_times_B_plus_b",
+                    "data_gradient_overwrites_pool_gradient", "pool_gradient_overwrites_data_gradient",
+                    "backbone_statistics_counted_over_B", "nonzero_value_in_route_gradient_border"]
+
+
+def _window_case():
+    rng = np.random.default_rng(11)
+    r = lambda *s: rng.standard_normal(s).astype(F32)  # noqa: E731
+    B, k, C, S = 2, 3, 8, 12
+    c = dict(B=B, k=k, C=C, S=S)
+    for key in ("route", "route32"):  # per-frame route values: some elements tie (two frames, or all three), most do not
+        f = r(B, k, C, S, S)
+        tie2, tie3 = rng.random((B, C, S, S)) < 0.15, rng.random((B, C, S, S)) < 0.05
+        f[:, 2] = np.where(tie2, f[:, 0], f[:, 2])
+        f[:, 1] = np.where(tie3, f[:, 0], f[:, 1])
+        f[:, 2] = np.where(tie3, f[:, 0], f[:, 2])
+        c[key] = f.reshape(B * k, C, S, S)
+    c["z"] = r(B * k, C, S, S)                            # raw conv output of the route cell, B*k frames
+    c["gam"], c["bet"] = (1 + 0.2 * r(C)).astype(F32), (0.3 * r(C)).astype(F32)
+    c["wh"] = (r(C, C, 1, 1) * 0.3).astype(F32)           # head consumer of the pooled plane, on B clips
+    c["dzh"] = r(B, C, S, S)
+    c["ws"] = (r(2 * C, C, 3, 3) * 0.2).astype(F32)       # the next stage's first conv: stride 2, on B*k frames
+    c["dzs"] = r(B * k, 2 * C, S // 2, S // 2)
+    c["g32"] = r(B, C, S // 2, S // 2)                    # pooled gradient of the route without another contributor
+    c["route32"] = c["route32"][:, :, :S // 2, :S // 2].copy()
+    return c
+
+
+def _run_window(join, mut=None):
+    c = _window_case()
+    B, k, S = c["B"], c["k"], c["S"]
+    res = []
+    # backbone statistics over the B*k frames
+    z = c["z"]
+    bn = dev_stats(z, c["gam"], c["bet"])
+    if mut == "backbone_statistics_counted_over_B":  # the sums run over every frame, the count is B * H * W
+        z64 = z.astype(np.float64)
+        n = B * S * S
+        mean = z64.sum(axis=(0, 2, 3)) / n
+        var = np.maximum((z64 * z64).sum(axis=(0, 2, 3)) / n - mean * mean, 0)
+        mf = mean.astype(F32)
+        inv = (F32(1) / np.sqrt(var.astype(F32) + F32(1e-5))).astype(F32)
+        sc = (c["gam"] * inv).astype(F32)
+        bn = np.stack([mf, inv, sc, R.fmaf(-mf, sc, c["bet"])])
+    res.append(R.check_stats("route cell", z, bn[0], bn[1], c["gam"], c["bet"], bn[2], bn[3]))
+    # the pool and its head consumer
+    order = (lambda b, t, B_, k_: t * B_ + b) if mut == "frames_taken_as_t_times_B_plus_b" else (lambda b, t, B_, k_: b * k_ + t)
+    frames = c["route"]
+    pooled = dev_pool(frames, B, k, join, order)
+    res.append(R.check_pool_forward("pool", frames, k, join, pooled))
+    g_pool = dev_dgrad(c["dzh"], c["wh"], 1, (S, S))
+    res.append(R.check_dgrad("pool", g_pool, [(c["dzh"], c["wh"], 1, 0)]))
+    # the per-frame route gradient: the pool backward writes, the stride-2 consumer's data gradient accumulates
+    gp = dev_pool_bwd(g_pool, frames, pooled, B, k, join, mut)
+    gd = dev_dgrad(c["dzs"], c["ws"], 2, (S, S))
+    g_route = (gp + gd).astype(F32)
+    if mut == "data_gradient_overwrites_pool_gradient":
+        g_route = gd
+    if mut == "pool_gradient_overwrites_data_gradient":
+        g_route = gp
+    g_pad = pad(g_route)
+    if mut == "nonzero_value_in_route_gradient_border":
+        g_pad[1, 2, 0, 3] = F32(1e-3)
+    res.append(R.border_zero("borders", "route grad", g_pad))
+    res.append(R.check_dgrad("route", R.interior(g_pad), [(c["dzs"], c["ws"], 2, 0)],
+                             [R.pool_backward(g_pool, frames, pooled, k, join)]))
+    # a route whose gradient is the pool backward's alone: bit-equal
+    f32_, g32 = c["route32"], c["g32"]
+    p32 = dev_pool(f32_, B, k, join, order)
+    res.append(R.check_pool_forward("pool32", f32_, k, join, p32))
+    r, wins, ties = R.check_pool_backward("pool32", g32, f32_, p32, k, join, dev_pool_bwd(g32, f32_, p32, B, k, join, mut))
+    res.append(r)
+    return res, wins, ties
+
+
+@pytest.mark.parametrize("join", ["max", "mean"])
+def test_toy_window_step_passes_every_check(join):
+    res, wins, ties = _run_window(join)
+    bad = [r for r in res if not r.ok]
+    assert not bad, bad
+    # the clips hold both kinds of element: every frame wins some on its own, and some are tied
+    assert min(wins) > 0 and ties > 0, (wins, ties)
+    assert all(r.headroom < 50 for r in res)
+
+
+def test_pool_reference_on_ties():
+    """the numpy pool in temporal.hip's arithmetic: ties keep the earliest frame and every tied frame gets the full g"""
+    f = np.array([[1, 3, -2, 0.0], [1, 2, -2, -0.0], [0, 3, -5, 0.0]], F32).reshape(3, 1, 1, 4)
+    g = np.array([10, 20, 30, 40], F32).reshape(1, 1, 1, 4)
+    m = R.pool_forward(f, 3, "max")
+    assert np.array_equal(m.ravel(), [1, 3, -2, 0]) and not np.signbit(m.ravel()[3])
+    assert np.array_equal(R.pool_backward(g, f, m, 3, "max").reshape(3, 4), [[10, 20, 30, 40], [10, 0, 30, 40], [0, 20, 0, 40]])
+    mean = R.pool_forward(f, 3, "mean")
+    want = ((f[0] + f[1]).astype(F32) + f[2]).astype(F32) / F32(3)
+    assert np.array_equal(mean[0], want)
+    assert np.array_equal(R.pool_backward(g, f, mean, 3, "mean"), np.repeat((g / F32(3)).astype(F32), 3, axis=0))
+    assert R.pool_wins(f, 3) == ([0, 0, 0], 4)
+
+
+@pytest.mark.parametrize("mut", WINDOW_MUTATIONS)
+def test_every_window_mutation_fails_a_check(mut):
+    join = "mean" if mut.startswith("mean") else "max"
+    res, _, _ = _run_window(join, mut)
+    bad = [r for r in res if not r.ok]
+    assert bad, "mutation %s passed every check" % mut
+    # the end-to-end bar is judged on the bounded checks that fail; a border value and a bit-equality of the pool have
+    # no counterpart there, so a mutation that only fails those gets no verdict
+    old = [r.old_bar_ok for r in bad if r.kind not in ("borders", "pool forward", "pool backward")]
+    verdict = "is not applicable" if not old else ("MISSES it" if all(old) else "catches it")
+    print("%s: fails %s; the 2e-3-of-max bar %s" % (mut, sorted(set(r.kind for r in bad)), verdict))
 
 
 def test_fmaf_emulation_is_exact():
