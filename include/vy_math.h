@@ -22,8 +22,10 @@
 
 #if defined(__HIPCC__)
 #define VY_HD __host__ __device__ __forceinline__
+#define VY_UNROLL _Pragma("unroll") /* small fixed loops over register arrays: constant indices on the device */
 #else
 #define VY_HD static inline
+#define VY_UNROLL
 #endif
 
 VY_HD float vy_bits_to_f32(uint32_t u) {
@@ -157,6 +159,58 @@ VY_HD float vy_box_iou(float ax1, float ay1, float ax2, float ay2, float bx1, fl
   float ab = (bx2 - bx1) * (by2 - by1);
   float uni = (aa + ab) - inter;
   return (uni <= 0.0f) ? 0.0f : inter / uni;
+}
+
+/* sin(a), cos(a) for a in [0, pi/4]: Taylor polynomials in Horner form with explicit fmaf (truncation below 2e-10,
+ * under half an ulp of the results, which lie in [0, 0.71] and [0.70, 1]). */
+VY_HD float vy_sin_q(float a) {
+  const float z = a * a;
+  float p = 2.7557319224e-6f;      /* 1/9! */
+  p = fmaf(p, z, -1.9841269841e-4f); /* -1/7! */
+  p = fmaf(p, z, 8.3333333333e-3f);  /* 1/5! */
+  p = fmaf(p, z, -1.6666666667e-1f); /* -1/3! */
+  return fmaf(a * z, p, a);
+}
+VY_HD float vy_cos_q(float a) {
+  const float z = a * a;
+  float p = -2.7557319224e-7f;     /* -1/10! */
+  p = fmaf(p, z, 2.4801587302e-5f);  /* 1/8! */
+  p = fmaf(p, z, -1.3888888889e-3f); /* -1/6! */
+  p = fmaf(p, z, 4.1666666667e-2f);  /* 1/4! */
+  p = fmaf(p, z, -0.5f);
+  return fmaf(z, p, 1.0f);
+}
+
+/* The eight Lanczos-4 weights of the taps s-3 .. s+4 for the fractional source position x in [0, 1): OpenCV's
+ * interpolateLanczos4 [UPSTREAM-RECALLED] — x < FLT_EPSILON gives a unit weight at tap 3; otherwise tap i, at distance
+ * d = x + 3 - i, gets sin(pi d) sin(pi d / 4) / d^2 up to a factor common to the taps, and the weights are divided by
+ * their sum.  sin(pi d) = +-sin(pi x) is that common factor; sin(pi d / 4) is one of +-sin / +-cos of v = x pi/4 and of
+ * u = (1 - x) pi/4.  OpenCV forms the numerators in double from ONE sin / cos pair (of -(x + 3) pi/4) through an angle
+ * sum; that sum cancels for the taps next to the sample (d -> 0), harmlessly in double and ruinously in fp32, so here
+ * each of u and v gets its own polynomial pair and no numerator is a difference. */
+VY_HD void vy_lanczos4_weights(float x, float w[8]) {
+  /* x >= 1 is the sample one tap further on (position s + 1, x = 0): a source coordinate a hair below an integer
+   * rounds to floor + 1.0f in float.  Without this, tap 4 would be 0 / 0. */
+  if (x < 1.1920928955e-7f || x >= 1.0f) {
+    const int unit = x >= 1.0f ? 4 : 3;
+    VY_UNROLL
+    for (int i = 0; i < 8; ++i) w[i] = i == unit ? 1.0f : 0.0f;
+    return;
+  }
+  const float kPi4 = 0.78539816339744831f;
+  const float v = x * kPi4, u = (1.0f - x) * kPi4;
+  const float sv = vy_sin_q(v), cv = vy_cos_q(v), su = vy_sin_q(u), cu = vy_cos_q(u);
+  const float num[8] = {-su, cv, -cu, sv, su, -cv, cu, -sv};
+  float sum = 0.0f;
+  VY_UNROLL
+  for (int i = 0; i < 8; ++i) {
+    const float d = x + (float)(3 - i);
+    w[i] = num[i] / (d * d);
+    sum = sum + w[i];
+  }
+  sum = 1.0f / sum;
+  VY_UNROLL
+  for (int i = 0; i < 8; ++i) w[i] = w[i] * sum;
 }
 
 #endif /* VY_MATH_H */

@@ -319,6 +319,54 @@ int vy_preprocess_resize_frames(const uint8_t* frames_hwc, int32_t src_height, i
                                 int32_t batch, int32_t height, int32_t width, const float* mean3, const float* std3,
                                 void* stream);
 
+/* The frames side of YOLO3VideoTrainTransform.__call__ (models/definitions/yolo/transforms.py:199-245) for a batch of
+ * clips in one launch: colour distortion -> expansion onto a filled canvas -> crop -> resize with one of five
+ * interpolations -> horizontal flip -> to_tensor -> normalize.  The random draws are the caller's
+ * (videoyolo_amd.transforms.YOLO3VideoTrainTransform.draw); a vy_train_aug holds one sample's.  No intermediate image
+ * exists: a thread per destination pixel walks back to its source taps.  After the colour step the reference's frames are
+ * float32, so nothing is rounded or clamped on the way [UPSTREAM-RECALLED arithmetic, DESIGN.md §13;
+ * tests/train_transform_ref.py states it op by op and is what the tests compare with, bit for bit].
+ *
+ * Geometry of a descriptor: the sample's k frames (src_h, src_w, 3) uint8 lie one after another from byte src_offset of
+ * `frames`; the source is pasted at (paste_x, paste_y) into a canvas_w x canvas_h canvas of the fill colour (no
+ * expansion: the canvas is the source, paste 0); the crop rectangle (crop_x, crop_y, crop_w, crop_h) of the canvas is
+ * resized to (height, width) with `interp` (0 nearest, 1 linear, 2 cubic, 3 area, 4 Lanczos-4; OpenCV's numbering) and
+ * mirrored when `flip`.  Colour ops run in the order listed on every source pixel read (the fill is not distorted):
+ *   VY_AUG_BRIGHTNESS  v + a          VY_AUG_CONTRAST  v * a
+ *   VY_AUG_SATURATION  g = ((r * 0.299 + g * 0.587) + b * 0.114) * b_arg ; v * a + g      (b_arg = 1 - alpha)
+ *   VY_AUG_HUE         out[c] = (r * hue[0][c] + g * hue[1][c]) + b * hue[2][c] */
+#define VY_AUG_BRIGHTNESS 1
+#define VY_AUG_CONTRAST 2
+#define VY_AUG_SATURATION 3
+#define VY_AUG_HUE 4
+#define VY_AUG_MAX_OPS 4
+typedef struct vy_train_aug {
+  int64_t src_offset;
+  int32_t src_h, src_w;
+  int32_t paste_x, paste_y;
+  int32_t canvas_w, canvas_h;
+  int32_t crop_x, crop_y, crop_w, crop_h;
+  int32_t interp, flip;
+  int32_t num_ops;
+  int32_t op[VY_AUG_MAX_OPS];
+  float a[VY_AUG_MAX_OPS];
+  float b[VY_AUG_MAX_OPS];
+  float hue[3][3];
+} vy_train_aug;
+/* The descriptors travel in the kernel arguments (no device memory of the library's, no copy, no synchronisation):
+ * VY_AUG_CHUNK of them (144 bytes each) fit the 4 KB argument segment, and a larger batch goes out as several launches. */
+#define VY_AUG_CHUNK 24
+/* frames: device bytes; augs: HOST array of `batch` descriptors; out: device (batch, k, 3, height, width) fp32;
+ * fill3 / mean3 / std3: host pointers to 3 floats (the fill in 0..255 units, mean * 255 in the reference).  Every
+ * descriptor is checked before anything is launched — sizes >= 1, the paste and the crop inside the canvas, interp in
+ * 0..4, known op codes, at most VY_AUG_MAX_OPS of them, a non-negative offset — else VY_ERR_INVALID and no launch. */
+int vy_train_transform(const uint8_t* frames, const vy_train_aug* augs, int32_t batch, int32_t k, float* out,
+                       int32_t height, int32_t width, const float* fill3, const float* mean3, const float* std3,
+                       void* stream);
+/* Host-only (no device is touched): include/vy_math.h's vy_lanczos4_weights, the eight Lanczos-4 tap weights the
+ * kernel uses for the fractional position x, for checkers. */
+void vy_math_lanczos4(float x, float* w8);
+
 /* Prefetch target generation on the device: YOLOV3PrefetchTargetGenerator.forward,
  * models/definitions/yolo/yolo_target.py:31-148 (called per sample from the DataLoader transform,
  * transforms.py:259-277), for a whole batch.  gt_boxes (batch,num_gt,4) corner pixels of the

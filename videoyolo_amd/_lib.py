@@ -114,6 +114,26 @@ SIGNATURES.update({
     "vy_net_video_read_slot": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
 })
 
+
+VY_AUG_BRIGHTNESS, VY_AUG_CONTRAST, VY_AUG_SATURATION, VY_AUG_HUE = 1, 2, 3, 4
+VY_AUG_MAX_OPS = 4
+VY_AUG_CHUNK = 24
+
+
+class TrainAug(ctypes.Structure):
+    """vy_train_aug (include/vyolo.h): one sample's draw of the training transform."""
+    _fields_ = [("src_offset", ctypes.c_int64), ("src_h", _i32), ("src_w", _i32), ("paste_x", _i32), ("paste_y", _i32),
+                ("canvas_w", _i32), ("canvas_h", _i32), ("crop_x", _i32), ("crop_y", _i32), ("crop_w", _i32),
+                ("crop_h", _i32), ("interp", _i32), ("flip", _i32), ("num_ops", _i32), ("op", _i32 * VY_AUG_MAX_OPS),
+                ("a", _f32 * VY_AUG_MAX_OPS), ("b", _f32 * VY_AUG_MAX_OPS), ("hue", (_f32 * 3) * 3)]
+
+
+SIGNATURES.update({
+    # the training transform (videoyolo_amd/transforms.py, csrc/augment.hip)
+    "vy_train_transform": (ctypes.c_int, [_vp, ctypes.POINTER(TrainAug), _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "vy_math_lanczos4": (None, [_f32, ctypes.POINTER(_f32)]),
+})
+
 _lib = None
 
 
