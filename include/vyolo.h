@@ -88,7 +88,17 @@ int vy_net_create_heads(int32_t num_class, vy_net** out);
 #define VY_JOIN_MAX 0
 #define VY_JOIN_MEAN 1
 int vy_net_create_window(int32_t num_class, int32_t k, int32_t join, vy_net** out);
-/* k and join of a window net; k = 0 for any other net. */
+/* yolo3_no_backbone(classes, k=k, k_join_type=..., k_join_pos='early') — the head half of vy_net_create_window, for
+ * train_yolov3.py --features_dir --window k (datasets/imgnetvid.py:146-174 stacks the k frames' saved routes): a heads-only
+ * net whose routes are pooled over a window of k stored per-frame routes on the way in.  k >= 2, join VY_JOIN_MAX or
+ * VY_JOIN_MEAN; anything else is VY_ERR_INVALID.  The parameter table, conv list, plan, vy_net_workspace_bytes,
+ * vy_net_train_workspace_bytes and vy_net_train_conv_plan are vy_net_create_heads', number for number: no per-frame plane
+ * exists.  `batch` counts clips.  Its forward entries are the *_bank ones below; vy_net_train_backward_routes serves it
+ * (route arguments ignored, NULL allowed).  Image entries, the other *_routes entries and the video entries fail on it
+ * with VY_ERR_STATE, doing nothing — as the *_bank entries do on every other kind of net.  Conv modes as on a heads-only
+ * net.  Taps: "pool.0" .. "pool.2" as on a window net. */
+int vy_net_create_heads_window(int32_t num_class, int32_t k, int32_t join, vy_net** out);
+/* k and join of a window net (of either kind); k = 0 for any other net. */
 int vy_net_window(const vy_net* net, int32_t* k, int32_t* join);
 void vy_net_destroy(vy_net* net);
 
@@ -226,6 +236,20 @@ int vy_net_forward_features(vy_net* net, const float* x, float* f0, float* f1, f
  * vy_net_forward_infer.  Asynchronous on `stream`. */
 int vy_net_forward_infer_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* ids, float* scores,
                                 float* bboxes, int32_t* keep_idx, void* stream);
+
+/* Windowed heads-only nets (vy_net_create_heads_window): a bank of stored per-frame routes and a table of clips.
+ *   f0 (n_frames, 256, ceil(H/8), ceil(W/8))   f1 (n_frames, 512, ceil(H/16), ceil(W/16))   f2 (n_frames, 1024, ceil(H/32), ceil(W/32))
+ * device fp32 NCHW, dense; table: host array of batch * k entries in [0, n_frames), clip b = frames table[b * k + t], t < k,
+ * pooled in that order (TemporalPooling 'direct', layers.py:193-204: mean = x0 + x1 + ... then / k; max keeps the earliest
+ * frame's bits on a tie).  A frame may repeat in a row.  One launch gathers, pools and transposes all three routes into the
+ * planes the heads read: bit for bit what vy_net_forward_infer_routes gives for the pooled routes, and what
+ * vy_net_forward_infer of a window net gives for the clips those frames came from.  batch * k <= VY_VIDEO_TABLE_MAX (the
+ * table travels in the kernel arguments: the library holds no device memory for it, copies nothing and does not
+ * synchronise); the table is range-checked before anything is launched (VY_ERR_INVALID) and consumed before the call
+ * returns.  The banks are only read.  Outputs as vy_net_forward_infer at batch clips.  Asynchronous on `stream`. */
+int vy_net_forward_infer_bank(vy_net* net, const float* f0, const float* f1, const float* f2, int32_t n_frames,
+                              const int32_t* table, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
+                              void* stream);
 
 /* Video plans: a window net (vy_net_create_window) run over a video, the backbone once per frame.
  * detect_yolo3.py with --window k,step builds one k-frame clip per frame of a video (datasets/imgnetvid.py:480-506: centred
@@ -417,6 +441,12 @@ int vy_net_train_forward_routes(vy_net* net, const float* f0, const float* f1, c
                                 int32_t M, const float* obj_t, const float* centers_t, const float* scales_t,
                                 const float* weights_t, const float* clas_t, float* losses, void* stream);
 
+/* ... of a windowed heads-only net on a bank of per-frame routes and a table (vy_net_forward_infer_bank). */
+int vy_net_train_forward_bank(vy_net* net, const float* f0, const float* f1, const float* f2, int32_t n_frames,
+                              const int32_t* table, const float* gt_boxes, int32_t M, const float* obj_t,
+                              const float* centers_t, const float* scales_t, const float* weights_t, const float* clas_t,
+                              float* losses, void* stream);
+
 /* net(x) under autograd.train_mode() without recording — yolo3.py:1189-1192, the branch the DataLoader
  * transform drives (transforms.py:190-193): the network runs with BatchNorm on batch statistics (running
  * stats updated, as mxnet's BatchNorm does whenever is_training), and the per-anchor tensors of
@@ -430,6 +460,10 @@ int vy_net_train_mode_forward(vy_net* net, const float* x, float* box_preds, flo
 /* ... of a heads-only net on the three route tensors. */
 int vy_net_train_mode_forward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* box_preds,
                                      float* centers, float* scales, float* objness, float* class_pred, void* stream);
+/* ... of a windowed heads-only net on a bank of per-frame routes and a table. */
+int vy_net_train_mode_forward_bank(vy_net* net, const float* f0, const float* f1, const float* f2, int32_t n_frames,
+                                   const int32_t* table, float* box_preds, float* centers, float* scales, float* objness,
+                                   float* class_pred, void* stream);
 
 /* autograd.backward(sum_losses) (train_yolov3.py:631): fills the gradient buffer (every trainable
  * tensor, device layout) from the state left by the last vy_net_train_forward.  `x` is the same
@@ -437,7 +471,8 @@ int vy_net_train_mode_forward_routes(vy_net* net, const float* f0, const float* 
 int vy_net_train_backward(vy_net* net, const float* x, void* stream);
 /* ... of a heads-only net: the head cells' gradients only — no data gradient into the routes (yolo_blocks.0.body.0 gets
  * none, yolo_blocks.1/2.body.0 only that of the upsampled-transition channels of their concat input).  The routes are the
- * ones of the recorded forward; nothing is read from them here. */
+ * ones of the recorded forward; nothing is read from them here.  Also the backward of a windowed heads-only net
+ * (vy_net_train_forward_bank), which ignores f0, f1, f2: NULL is allowed there. */
 int vy_net_train_backward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, void* stream);
 
 /* Per-parameter optimizer attributes: Parameter.lr_mult / wd_mult (train_yolov3.py:496-497) and

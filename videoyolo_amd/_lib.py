@@ -106,6 +106,13 @@ SIGNATURES.update({
     # k-frame clip nets (yolo3_darknet53 with k > 1, early join)
     "vy_net_create_window": (ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(_vp)]),
     "vy_net_window": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    # windowed heads-only nets: a bank of stored per-frame routes and a (B, k) table (yolo3_no_backbone with k > 1)
+    "vy_net_create_heads_window": (ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(_vp)]),
+    "vy_net_forward_infer_bank": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, ctypes.POINTER(_i32), _vp, _vp, _vp, _vp, _vp]),
+    "vy_net_train_forward_bank": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, ctypes.POINTER(_i32), _vp, _i32, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp]),
+    "vy_net_train_mode_forward_bank": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, ctypes.POINTER(_i32), _vp, _vp, _vp, _vp, _vp,
+                                                      _vp]),
     # video plans of a window net: the backbone once per frame, routes in a ring (videoyolo_amd/video.py)
     "vy_net_video_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
     "vy_net_bind_video": (ctypes.c_int, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -188,6 +188,20 @@ struct RouteArgs {
 hipError_t vy_launch_route_import(const RouteArgs& a, hipStream_t s);
 hipError_t vy_launch_route_export(const RouteArgs& a, hipStream_t s);
 
+// ---- a window of stored per-frame routes into the heads' planes (routes.hip): route_import fused with window_pool.
+// r[i].nchw is a bank (T, C, H, W) of per-frame routes; clip b's k frames table[b * k + t] are pooled (temporal.hip's
+// arithmetic, in table order) and land where route_import puts a single frame.  The table travels in the kernel arguments
+// (at most VY_ROUTE_TABLE_MAX entries, range-checked by the launcher); a frame may repeat in a row.
+#define VY_ROUTE_TABLE_MAX 512
+struct RoutePoolArgs {
+  RouteXfer r[3];      // nchw: the bank (read only)
+  int n;               // routes in this launch (1..3)
+  int B, k, join, T;   // clips, frames per clip, VY_JOIN_*, frames of the bank
+  int tile_end[3];     // filled by the launcher
+  int table[VY_ROUTE_TABLE_MAX];  // clip b, position t -> frame table[b * k + t] of the bank
+};
+hipError_t vy_launch_route_import_pool(const RoutePoolArgs& a, hipStream_t s);
+
 // ---- temporal window pooling (temporal.hip): a window net's backbone runs on B*k frames (frame t of clip b is frame
 // b*k + t); its three per-frame route planes are pooled over each clip's k frames into the planes the heads read.
 // Interiors only, channels [co, co + C) of the destination: borders and other channels are never written.  C, cs and co

@@ -26,17 +26,21 @@ int vy_fail(int code, const char* fmt, ...) {
 }
 #define fail vy_fail
 
-int vy_check_kind(const vy_net* net, bool routes_entry, const char* entry) {
-  if (net && net->heads_only != routes_entry)
-    return fail(VY_ERR_STATE, net->heads_only ? "%s takes an image batch: this is a heads-only net (vy_net_create_heads), "
-                                                "use the *_routes entry points"
-                                              : "%s takes route tensors: this is a full net (vy_net_create)", entry);
-  return 0;
+int vy_check_kind(const vy_net* net, int takes, const char* entry) {
+  if (!net) return 0;  // (the entry's own argument check reports it)
+  const int kind = !net->heads_only ? VY_TAKES_IMAGES : net->window_k ? VY_TAKES_BANK : VY_TAKES_ROUTES;
+  if (kind == takes) return 0;
+  static const char* const what[3] = {"takes an image batch", "takes the route tensors of single frames",
+                                      "takes a bank of per-frame routes and a table"};
+  static const char* const is[3] = {"a full net (vy_net_create / vy_net_create_window)",
+                                    "a heads-only net (vy_net_create_heads), use the *_routes entry points",
+                                    "a windowed heads-only net (vy_net_create_heads_window), use the *_bank entry points"};
+  return fail(VY_ERR_STATE, "%s %s: this is %s", entry, what[takes], is[kind]);
 }
 
 // VY_ERR_STATE for a window net (vy_net_create_window) at an entry point that does not serve one
 static int refuse_window(const vy_net* net, const char* entry) {
-  if (net && net->window_k)
+  if (net && net->clip_net())
     return fail(VY_ERR_STATE, "%s does not take a window net (vy_net_create_window): use vy_net_create for single frames",
                 entry);
   return 0;
@@ -69,7 +73,7 @@ static int infer_sequence(vy_net* net, const float* x, float* ids, float* scores
                           hipStream_t s, Hook& hook) {
   VY_TRY(net->prepare(s, hook, true));
   VY_TRY(net->run_cells(0, net->n_backbone, x, s, hook));
-  if (net->window_k) VY_TRY(net->window_pool(s, hook));
+  if (net->clip_net()) VY_TRY(net->window_pool(s, hook));
   VY_TRY(net->run_cells(net->n_backbone, (int)net->convs.size(), nullptr, s, hook));
   return net->detect_tail(ids, scores, bboxes, keep_idx, s, hook);
 }
@@ -98,6 +102,16 @@ int vy_net_create_window(int32_t num_class, int32_t k, int32_t join, vy_net** ou
   if (join != VY_JOIN_MAX && join != VY_JOIN_MEAN)
     return fail(VY_ERR_INVALID, "join %d: VY_JOIN_MAX (%d) or VY_JOIN_MEAN (%d)", join, VY_JOIN_MAX, VY_JOIN_MEAN);
   *out = create(num_class, false, k, join);
+  return 0;
+}
+
+int vy_net_create_heads_window(int32_t num_class, int32_t k, int32_t join, vy_net** out) {
+  VY_TRY(check_create(num_class, out));
+  if (k < 2 || k > 64)
+    return fail(VY_ERR_INVALID, "window k = %d: a windowed heads net has 2 ... 64 frames (k = 1: vy_net_create_heads)", k);
+  if (join != VY_JOIN_MAX && join != VY_JOIN_MEAN)
+    return fail(VY_ERR_INVALID, "join %d: VY_JOIN_MAX (%d) or VY_JOIN_MEAN (%d)", join, VY_JOIN_MAX, VY_JOIN_MEAN);
+  *out = create(num_class, true, k, join);
   return 0;
 }
 
@@ -252,7 +266,7 @@ int vy_net_set_keep_activations(vy_net* net, int32_t keep) {
 int vy_net_set_conv_mode(vy_net* net, int32_t mode) {
   if (!net) return fail(VY_ERR_INVALID, "net is null");
   if (mode < VY_CONV_EXACT_FP32 || mode > VY_CONV_SPLIT_BF16X3_TRAIN) return fail(VY_ERR_INVALID, "conv mode %d", mode);
-  if (net->window_k && mode != VY_CONV_EXACT_FP32)
+  if (net->clip_net() && mode != VY_CONV_EXACT_FP32)
     return fail(VY_ERR_UNSUPPORTED, "conv mode %d: a window net runs the exact fp32 kernels only", mode);
   if (mode != net->conv_mode) {
     net->conv_mode = mode;
@@ -317,11 +331,25 @@ int vy_net_forward_infer_routes(vy_net* net, const float* f0, const float* f1, c
   });
 }
 
+int vy_net_forward_infer_bank(vy_net* net, const float* f0, const float* f1, const float* f2, int32_t n_frames,
+                              const int32_t* table, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
+                              void* stream) {
+  VY_TRY(vy_check_kind(net, VY_TAKES_BANK, "vy_net_forward_infer_bank"));
+  const BankRef bank{{f0, f1, f2}, n_frames, table};
+  return run_entry(net, bank.ok() && ids && scores && bboxes, nullptr, stream, [&](hipStream_t s) {
+    VY_TRY(vy_check_bank(net, "vy_net_forward_infer_bank", bank));
+    VY_TRY(net->prepare(s, plain, false));
+    VY_TRY(net->import_pool(bank, s, plain));
+    VY_TRY(net->run_cells(0, (int)net->convs.size(), nullptr, s, plain));
+    return net->detect_tail(ids, scores, bboxes, keep_idx, s, plain);
+  });
+}
+
 // ---- video plans
 // VY_ERR_STATE unless `net` is a window net: the video entries serve nothing else
 static int need_window(const vy_net* net, const char* entry) {
   if (!net) return fail(VY_ERR_INVALID, "net is null");
-  if (!net->window_k)
+  if (!net->clip_net())
     return fail(VY_ERR_STATE, "%s takes a window net (vy_net_create_window): this net has no temporal window", entry);
   return 0;
 }

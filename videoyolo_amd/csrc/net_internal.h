@@ -21,8 +21,19 @@ int vy_fail(int code, const char* fmt, ...);
 #define fail vy_fail
 
 struct vy_net;
-// VY_ERR_STATE unless `net` is of the kind the entry point serves: heads-only (routes_entry) or full (defined in net.hip)
-int vy_check_kind(const vy_net* net, bool routes_entry, const char* entry);
+// VY_ERR_STATE unless `net` is of the kind the entry point serves (defined in net.hip): a full net takes images (false /
+// VY_TAKES_IMAGES), a heads-only net its three routes (true / VY_TAKES_ROUTES), a windowed heads-only net a bank of
+// per-frame routes and a table (VY_TAKES_BANK)
+enum { VY_TAKES_IMAGES = 0, VY_TAKES_ROUTES = 1, VY_TAKES_BANK = 2 };
+int vy_check_kind(const vy_net* net, int takes, const char* entry);
+
+// the inputs of a *_bank entry: three banks of per-frame routes (n_frames, C, h, w) and the (B, k) table of frames
+struct BankRef {
+  const float* f[3];
+  int32_t n_frames;
+  const int32_t* table;
+  bool ok() const { return f[0] && f[1] && f[2] && table; }
+};
 
 #define HIP_TRY(expr)                                                                  \
   do {                                                                                 \
@@ -162,6 +173,11 @@ struct vy_net {
   // (temporal.hip) pools over each clip into `routes` — the slices the heads read — once, after the last stage cell
   int window_k = 0;  // 0: not a window net
   int window_join = 0;
+  // vy_net_create_heads_window: heads_only with window_k set.  The plan is the heads-only net's, number for number: there
+  // is no backbone to run on B*k frames and no per-frame plane; route_import_pool (routes.hip) pools each clip's k frames
+  // out of the caller's bank of stored routes on the way into the planes route_import fills.  Everything that concerns
+  // the B*k-frame backbone of a window net keys on clip_net()
+  bool clip_net() const { return window_k && !heads_only; }
   int frame_routes[3] = {-1, -1, -1};
 
   // video plan of a window net (vy_net_bind_video): the stem and stage planes hold video_F single frames, the
@@ -318,7 +334,7 @@ struct vy_net {
     };
     routes[0] = {cat2, 128, 256};
     routes[1] = {cat1, 256, 512};
-    const int bfm = window_k ? window_k : 1;  // frames per batch entry of the backbone planes
+    const int bfm = clip_net() ? window_k : 1;  // frames per batch entry of the backbone planes
     int cur = add_plane(heads_only ? 1024 : 32, heads_only ? 32 : 1, bfm), cur_co = 0;
     if (!heads_only) add_conv(feat_name(feat++), -1, 0, 3, cur, 0, 32, 3, 1, true, 1);
     int div = 1;
@@ -336,7 +352,7 @@ struct vy_net {
         // the last block of stages 0 and 1 (features[14], features[23]) writes the route straight
         // into its concat plane (a window net: into a per-frame route plane, pooled into the concat plane later)
         int outp, outco = 0;
-        if (window_k && (feat - 1 == 14 || feat - 1 == 23)) {
+        if (clip_net() && (feat - 1 == 14 || feat - 1 == 23)) {
           outp = add_plane(ch, div, bfm);
           frame_routes[feat - 1 == 14 ? 0 : 1] = outp;
         } else if (feat - 1 == 14) {
@@ -353,7 +369,7 @@ struct vy_net {
         cur_co = outco;
       }
     }
-    if (window_k) {  // the heads read the pooled stride-32 route
+    if (clip_net()) {  // the heads read the pooled stride-32 route
       frame_routes[2] = cur;
       cur = add_plane(1024, 32);
       cur_co = 0;
@@ -447,7 +463,7 @@ struct vy_net {
     for (int i = 0; i < 3; ++i) last[head_plane[i]] = kLive;  // read by decode + NMS (and vy_net_read_head) afterwards
     if (heads_only || window_k)  // the routes are imported / pooled outside the conv list: those planes own their storage
       for (int i = 0; i < 3; ++i) def[routes[i].plane] = -1;
-    if (window_k)  // ... and window_pool reads the per-frame routes after the last stage cell
+    if (clip_net())  // ... and window_pool reads the per-frame routes after the last stage cell
       for (int i = 0; i < 3; ++i) last[frame_routes[i]] = kLive;
     std::vector<int> order(np);
     for (int i = 0; i < np; ++i) order[i] = i;
@@ -840,6 +856,26 @@ struct vy_net {
     HOOKED(hook, "route_import", 0.0, 0.0, vy_launch_route_import(route_args(nchw), s));
     return 0;
   }
+  // windowed heads-only nets (the caller has checked the table): each clip's k frames of the bank, pooled, into the same planes
+  template <typename Hook>
+  int import_pool(const BankRef& bank, hipStream_t s, Hook& hook) {
+    RoutePoolArgs ra;
+    memset(&ra, 0, sizeof ra);
+    const RouteArgs r = route_args(bank.f);
+    double floats = 0;
+    for (int i = 0; i < 3; ++i) {
+      ra.r[i] = r.r[i];
+      floats += (double)r.r[i].C * r.r[i].H * r.r[i].W;
+    }
+    ra.n = 3;
+    ra.B = B;
+    ra.k = window_k;
+    ra.join = window_join;
+    ra.T = bank.n_frames;
+    memcpy(ra.table, bank.table, sizeof(int32_t) * B * window_k);
+    HOOKED(hook, "route_import_pool", 0.0, 4.0 * (window_k + 1) * B * floats, vy_launch_route_import_pool(ra, s));
+    return 0;
+  }
   // full nets, after the last stage cell: the three routes out to the caller's tensors
   template <typename Hook>
   int route_export(const float* const* nchw, hipStream_t s, Hook& hook) {
@@ -916,6 +952,20 @@ int run_entry(vy_net* net, bool args_ok, const char* video_entry, void* stream, 
   int rc = net->sk_begin(s);
   if (rc == 0) rc = run(s);
   return net->sk_end(rc);
+}
+
+// VY_ERR_INVALID unless the bank and the table of a *_bank entry fit the bound plan: B * k table entries (they travel in the
+// kernel arguments), each a frame of the bank.  Before anything is launched
+inline int vy_check_bank(const vy_net* net, const char* entry, const BankRef& bank) {
+  const long long n = (long long)net->B * net->window_k;
+  if (n > VY_ROUTE_TABLE_MAX)
+    return fail(VY_ERR_INVALID, "%s: clips * k = %d x %d exceeds %d table entries (they travel in the kernel arguments)", entry,
+                net->B, net->window_k, VY_ROUTE_TABLE_MAX);
+  if (bank.n_frames < 1) return fail(VY_ERR_INVALID, "%s: a bank of %d frames", entry, bank.n_frames);
+  for (int i = 0; i < (int)n; ++i)
+    if (bank.table[i] < 0 || bank.table[i] >= bank.n_frames)
+      return fail(VY_ERR_INVALID, "%s: entry %d of the table is %d, outside [0, %d)", entry, i, bank.table[i], bank.n_frames);
+  return 0;
 }
 
 // the pooled route `name` = "pool.<i>" of a window net (the taps of vy_net_read_activation / read_grad_activation): 0..2, or -1

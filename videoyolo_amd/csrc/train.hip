@@ -521,13 +521,15 @@ int train_cells(const TrainCtx& c, int first, int last, const float* x) {
   return 0;
 }
 
-// routes (heads-only nets): the three route tensors, imported into their planes in front of the first conv
-int forward_train(const TrainCtx& c, const float* x, const float* const* routes) {
+// routes (heads-only nets): the three route tensors, imported into their planes in front of the first conv; bank (windowed
+// heads-only nets): each clip's frames of the bank, pooled into the same planes
+int forward_train(const TrainCtx& c, const float* x, const float* const* routes, const BankRef* bank = nullptr) {
   vy_net* net = c.net;
   VY_TRY(refresh_split_images(c));
   if (routes) VY_TRY(net->route_import(routes, c.s, plain));
+  if (bank) VY_TRY(net->import_pool(*bank, c.s, plain));
   VY_TRY(train_cells(c, 0, net->n_backbone, x));
-  if (net->window_k) VY_TRY(net->window_pool(c.s, plain));  // the stages are done: pool the routes
+  if (net->clip_net()) VY_TRY(net->window_pool(c.s, plain));  // the stages are done: pool the routes
   return train_cells(c, net->n_backbone, (int)net->convs.size(), nullptr);
 }
 
@@ -855,7 +857,7 @@ int backward_train(const TrainCtx& c, const float* x) {
   // the prediction planes' gradients were written by the loss kernel
   for (int i = 0; i < 3; ++i) st.whole(net, net->head_plane[i]);
   VY_TRY(backward_cells(c, st, net->n_backbone, (int)net->convs.size(), x));
-  if (net->window_k) {
+  if (net->clip_net()) {
     // the heads are done: the pooled routes' gradients (cat2 / cat1 route channels, the pooled stride-32 plane) are
     // final.  window_pool_bwd writes the per-frame route planes' gradients; stages.1.0 / stages.2.0 accumulate onto them
     HIP_TRY(vy_launch_window_pool_bwd(net->pool_args(c.gplanes()), c.s));
@@ -884,10 +886,11 @@ struct LossInputs {
   float* losses;
   bool ok() const { return obj_t && centers_t && scales_t && weights_t && clas_t && losses && (M <= 0 || gt_boxes); }
 };
-int train_forward(vy_net* net, const float* x, const float* const* routes, const LossInputs& in, hipStream_t s) {
+int train_forward(vy_net* net, const float* x, const float* const* routes, const LossInputs& in, hipStream_t s,
+                  const BankRef* bank = nullptr) {
   VY_TRY(bound_train(net, true, " (vy_net_bind_train)"));
   TrainCtx c(net, s);
-  VY_TRY(forward_train(c, x, routes));
+  VY_TRY(forward_train(c, x, routes, bank));
   const DetArgs d = net->det_args();
   LossArgs la;
   memset(&la, 0, sizeof la);
@@ -922,10 +925,11 @@ struct RawOutputs {
   float *box_preds, *centers, *scales, *objness, *class_pred;
   bool ok() const { return box_preds && centers && scales && objness && class_pred; }
 };
-int train_mode_forward(vy_net* net, const float* x, const float* const* routes, const RawOutputs& out, hipStream_t s) {
+int train_mode_forward(vy_net* net, const float* x, const float* const* routes, const RawOutputs& out, hipStream_t s,
+                       const BankRef* bank = nullptr) {
   VY_TRY(bound_train(net, true, " (vy_net_bind_train)"));
   TrainCtx c(net, s);
-  VY_TRY(forward_train(c, x, routes));
+  VY_TRY(forward_train(c, x, routes, bank));
   c.t->forward_done = false;  // nothing was recorded: no backward may follow
   const DetArgs d = net->det_args();
   RawPredArgs ra;
@@ -1046,15 +1050,42 @@ int vy_net_train_mode_forward_routes(vy_net* net, const float* f0, const float* 
                    [&](hipStream_t s) { return train_mode_forward(net, nullptr, routes, out, s); });
 }
 
+int vy_net_train_forward_bank(vy_net* net, const float* f0, const float* f1, const float* f2, int32_t n_frames,
+                              const int32_t* table, const float* gt_boxes, int32_t M, const float* obj_t,
+                              const float* centers_t, const float* scales_t, const float* weights_t, const float* clas_t,
+                              float* losses, void* stream) {
+  VY_TRY(vy_check_kind(net, VY_TAKES_BANK, "vy_net_train_forward_bank"));
+  const BankRef bank{{f0, f1, f2}, n_frames, table};
+  const LossInputs in{gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t, M, losses};
+  return run_entry(net, bank.ok() && in.ok(), nullptr, stream, [&](hipStream_t s) {
+    VY_TRY(vy_check_bank(net, "vy_net_train_forward_bank", bank));
+    return train_forward(net, nullptr, nullptr, in, s, &bank);
+  });
+}
+
+int vy_net_train_mode_forward_bank(vy_net* net, const float* f0, const float* f1, const float* f2, int32_t n_frames,
+                                   const int32_t* table, float* box_preds, float* centers, float* scales, float* objness,
+                                   float* class_pred, void* stream) {
+  VY_TRY(vy_check_kind(net, VY_TAKES_BANK, "vy_net_train_mode_forward_bank"));
+  const BankRef bank{{f0, f1, f2}, n_frames, table};
+  const RawOutputs out{box_preds, centers, scales, objness, class_pred};
+  return run_entry(net, bank.ok() && out.ok(), nullptr, stream, [&](hipStream_t s) {
+    VY_TRY(vy_check_bank(net, "vy_net_train_mode_forward_bank", bank));
+    return train_mode_forward(net, nullptr, nullptr, out, s, &bank);
+  });
+}
+
 int vy_net_train_backward(vy_net* net, const float* x, void* stream) {
   VY_TRY(vy_check_kind(net, false, "vy_net_train_backward"));
   return run_entry(net, x != nullptr, nullptr, stream, [&](hipStream_t s) { return train_backward(net, x, s); });
 }
 
 int vy_net_train_backward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, void* stream) {
-  VY_TRY(vy_check_kind(net, true, "vy_net_train_backward_routes"));
-  // (nothing is read from the routes: see data_grad)
-  return run_entry(net, f0 && f1 && f2, nullptr, stream, [&](hipStream_t s) { return train_backward(net, nullptr, s); });
+  // (nothing is read from the routes: see data_grad — so a windowed heads-only net, whose forward read a bank, is served
+  // too, and may pass NULL)
+  const bool windowed = net && net->heads_only && net->window_k;
+  if (!windowed) VY_TRY(vy_check_kind(net, VY_TAKES_ROUTES, "vy_net_train_backward_routes"));
+  return run_entry(net, windowed || (f0 && f1 && f2), nullptr, stream, [&](hipStream_t s) { return train_backward(net, nullptr, s); });
 }
 
 int vy_net_param_set_opt(vy_net* net, int32_t i, float lr_mult, float wd_mult, int32_t enabled) {

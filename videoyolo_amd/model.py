@@ -1145,6 +1145,128 @@ class YOLOV3Window(YOLOV3):
     extract_features = detect_two_streams = profile = _not_windowed
 
 
+class YOLOV3NoBackboneWindow(YOLOV3NoBackbone):
+    """``yolo3_no_backbone(classes, k=k, k_join_type=..., k_join_pos='early')``: the head half of ``YOLOV3Window``, for the
+    reference's ``--features_dir --window k`` workflow (datasets/imgnetvid.py:146-174 stacks the k frames' saved routes
+    into ``(k, C, h, w)``).  With the early join and max / mean pooling the heads of a window net see nothing but the pooled
+    routes, so this net pools a window of stored per-frame routes on the way in (one launch for the three routes, no
+    per-frame plane: its plan is the heads net's) and is otherwise ``YOLOV3NoBackbone``, parameter names included.
+
+    ``net(f1, f2, f3, *targets)`` takes the routes as ``(B, k, C, h, w)``; ``net.from_bank(f1, f2, f3, table, *targets)``
+    takes ``(T, C, h, w)`` banks of per-frame routes that stay on the device and a ``(B, k)`` host table of frame indices
+    (rows may repeat a frame).  The mode follows ``autograd``.  ``B * k`` is at most ``_lib.VY_VIDEO_TABLE_MAX``."""
+
+    _CREATE = "vy_net_create_heads_window"
+    _TRAIN_ENTRY = "_bank"
+    _ONE_RANK = "a windowed heads-only net (yolo3_no_backbone with k > 1)"
+    _JOINS = YOLOV3Window._JOINS
+
+    def __init__(self, classes, *args, k=2, k_join_type="max", **kwargs):
+        if int(k) < 2 or k_join_type not in self._JOINS:
+            raise ValueError("windowed heads net: k >= 2 and k_join_type in %s (got k=%r, %r)"
+                             % (sorted(self._JOINS), k, k_join_type))
+        self._k, self._join_type = int(k), k_join_type
+        self._bank_args = None  # (frames of the bank, ctypes table) of the call in progress
+        super().__init__(classes, *args, **kwargs)
+
+    k = property(lambda self: self._k)
+    k_join_type = property(lambda self: self._join_type)
+
+    def _create_handle(self, num_class, out):
+        return self._lib.vy_net_create_heads_window(num_class, self._k, self._JOINS[self._join_type], out)
+
+    def _ctor_kwargs(self):
+        return dict(k=self._k, k_join_type=self._join_type)
+
+    def _as_bank(self, f1, f2, f3, table=None):
+        """Check a call's routes and table (before anything launches; the table is a host array: nothing here touches the
+        device) -> (the three banks as (T, C, h, w) device tensors, (B, H, W) of the plan).  ``table=None``: the routes
+        are (B, k, C, h, w), a bank of B * k frames with the identity table."""
+        fs = [tuple(f.shape) if hasattr(f, "shape") else tuple(np.shape(f)) for f in (f1, f2, f3)]
+        rank = 5 if table is None else 4
+        if any(len(s) != rank for s in fs):
+            raise ValueError("route shapes %s: expected %s" % (fs, "three (B, k, C, h, w) tensors" if table is None else
+                                                               "three (T, C, h, w) banks next to a table"))
+        if table is None:
+            if any(s[1] != self._k for s in fs) or len({s[0] for s in fs}) != 1:
+                raise ValueError("route shapes %s: expected (B, k, C, h, w) with k = %d and one B" % (fs, self._k))
+            b = fs[0][0]
+            fs = [(s[0] * s[1],) + s[2:] for s in fs]
+            tab = np.arange(b * self._k, dtype=np.int32).reshape(b, self._k)
+        else:
+            tab = np.asarray(table)
+            if tab.ndim != 2 or tab.shape[1] != self._k or tab.dtype.kind not in "iu":
+                raise ValueError("table of shape %s, dtype %s: expected a (B, k) integer array with k = %d"
+                                 % (tab.shape, tab.dtype, self._k))
+            b = tab.shape[0]
+        t, h8, w8 = fs[0][0], fs[0][2], fs[0][3]
+        want = [(t, 256, h8, w8), (t, 512, -(-h8 // 2), -(-w8 // 2)), (t, 1024, -(-h8 // 4), -(-w8 // 4))]
+        if fs != want or t < 1 or min(h8, w8) < 4 or max(h8, w8) > 512:
+            raise ValueError("route shapes %s are not the three Darknet-53 routes of the same frames: expected (.., 256, h, w), "
+                             "(.., 512, ceil(h/2), ceil(w/2)), (.., 1024, ceil(h/4), ceil(w/4)) with h, w in [4, 512]" % (fs,))
+        if b < 1 or b * self._k > _lib.VY_VIDEO_TABLE_MAX:
+            raise ValueError("B * k = %d x %d: between 1 and %d table entries (they travel in the kernel arguments)"
+                             % (b, self._k, _lib.VY_VIDEO_TABLE_MAX))
+        if tab.size and (int(tab.min()) < 0 or int(tab.max()) >= t):
+            raise ValueError("table entries must lie in [0, %d), the frames of the bank (got %d ... %d)"
+                             % (t, int(tab.min()), int(tab.max())))
+        if self._device is None:
+            raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
+        flat = np.ascontiguousarray(tab, dtype=np.int32).reshape(-1)
+        self._bank_args = (t, (ctypes.c_int32 * flat.size).from_buffer_copy(flat.tobytes()))
+        return [self._dev(f).reshape(s) for f, s in zip((f1, f2, f3), fs)], (b, 8 * h8, 8 * w8)
+
+    _train_inputs = _as_bank
+
+    def _train_entry(self, name):
+        fn = getattr(self._lib, name + self._TRAIN_ENTRY)
+        n_frames, table = self._bank_args
+        return lambda h, f0, f1, f2, *rest: fn(h, f0, f1, f2, n_frames, table, *rest)
+
+    def backward(self):
+        """As ``YOLOV3.backward``: nothing is back-propagated into the routes, so the library takes none here."""
+        torch = _torch()
+        if self._train_x is None:
+            raise RuntimeError("backward() without a recorded forward")
+        with torch.cuda.device(self._device):
+            _lib.check(self._lib.vy_net_train_backward_routes(self._h, None, None, None, self._stream()))
+        self._train_x = None
+
+    def from_bank(self, f1, f2, f3, table, *args, return_index=False):
+        """``net(...)`` on windows gathered out of banks: ``f1, f2, f3`` are ``(T, 256 | 512 | 1024, h, w)`` per-frame routes
+        (``YOLOV3.extract_features`` of T frames; tensors already on the device are used in place), ``table`` a ``(B, k)``
+        integer host array: clip b pools frames ``table[b]`` in that order.  Mode by the autograd state."""
+        if table is None:
+            raise ValueError("from_bank needs a (B, k) table")
+        if autograd.is_training():
+            if autograd.is_recording():
+                if len(args) != 6:
+                    raise ValueError("training call: net.from_bank(f1, f2, f3, table, gt_boxes, obj_t, centers_t, scales_t, "
+                                     "weights_t, clas_t)")
+                return self.forward_train(f1, f2, f3, table, *args)
+            return self.forward_train_mode(f1, f2, f3, table)
+        return self.detect(f1, f2, f3, return_index=return_index, table=table)
+
+    def detect(self, f1, f2, f3, return_index=False, table=None):
+        """Inference branch: (ids, scores, bboxes[, keep_idx]) per clip, exactly as ``YOLOV3Window.detect`` returns them."""
+        torch = _torch()
+        fs, (b, h, w) = self._as_bank(f1, f2, f3, table)
+        n_frames, tab = self._bank_args
+        with torch.cuda.device(self._device):
+            self._ensure_plan(b, h, w)
+            outs = self._detect_outputs(b, self._out_rows(), return_index)
+            p = _ptrs(tuple(fs) + outs)
+            _lib.check(self._lib.vy_net_forward_infer_bank(self._h, p[0], p[1], p[2], n_frames, tab, *p[3:], self._stream()))
+        return outs if return_index else outs[:3]
+
+    def detect_video_features(self, f1, f2, f3, step=1, clips_per_step=16, return_index=False):
+        """``(ids, scores, bboxes)`` for every frame of a stored video, ``f1, f2, f3`` its ``(T, C, h, w)`` routes: the clips
+        of ``video.window_indices(T, k, step)``, ``clips_per_step`` at a time — bit for bit
+        ``YOLOV3Window.detect_video(frames, step)`` on the frames the routes came from."""
+        from .video import detect_video_features
+        return detect_video_features(self, f1, f2, f3, step=step, clips_per_step=clips_per_step, return_index=return_index)
+
+
 def _darknet_roots(root=None):
     """Where ``get_model_file('darknet53', root=...)`` would look: the reference's default root
     (three_darknet.py:234 ``models/definitions/darknet/weights``), gluoncv's cache, VY_MODEL_ROOT."""
@@ -1187,10 +1309,20 @@ def darknet53_to_stage_names(arrays):
     return out
 
 
-def yolo3_no_backbone(classes, norm_layer=BatchNorm, norm_kwargs=None, **kwargs):
+def yolo3_no_backbone(classes, norm_layer=BatchNorm, norm_kwargs=None, k=None, k_join_type=None, k_join_pos=None, **kwargs):
     """Drop-in for models/definitions/yolo/wrappers.py:133-161: the yolo3_darknet53 heads without the backbone
     (``YOLOV3_noback``), for training and validating on saved Darknet-53 features.  ``norm_layer`` may be
-    ``SyncBatchNorm``: the heads hold none of the cells it applies to, so nothing is exchanged."""
+    ``SyncBatchNorm``: the heads hold none of the cells it applies to, so nothing is exchanged.
+
+    ``k >= 2`` with ``k_join_type`` 'max' or 'mean' and ``k_join_pos='early'`` returns a ``YOLOV3NoBackboneWindow``, which
+    pools windows of k stored per-frame routes (``--features_dir --window k``); any other temporal combination raises
+    NotImplementedError."""
+    if k not in (None, 1) or k_join_type is not None or k_join_pos is not None:
+        if k in (None, 1) or int(k) < 2 or k_join_type not in YOLOV3Window._JOINS or k_join_pos != 'early':
+            raise NotImplementedError("yolo3_no_backbone: k=%r, k_join_type=%r, k_join_pos=%r — only k >= 2 with k_join_type "
+                                      "'max' or 'mean' and k_join_pos='early' is built" % (k, k_join_type, k_join_pos))
+        return YOLOV3NoBackboneWindow(classes, norm_layer=norm_layer, norm_kwargs=norm_kwargs, k=int(k),
+                                      k_join_type=k_join_type, **kwargs)
     return YOLOV3NoBackbone(classes, norm_layer=norm_layer, norm_kwargs=norm_kwargs, **kwargs)
 
 

@@ -253,3 +253,28 @@ class VideoSession:
             if self._sched.pushed:
                 self._ensure_bound(*self._hw)
             return self._join(self._run(self._sched.flush(), None, 0, return_index), return_index)
+
+
+def detect_video_features(net, f1, f2, f3, step=1, clips_per_step=16, return_index=False):
+    """``YOLOV3NoBackboneWindow.detect_video_features``: every frame of a stored video from its ``(T, C, h, w)`` routes.  The
+    clips are ``window_indices(T, k, step)``, ``clips_per_step`` rows per call on one plan; the last chunk is padded by
+    repeating its last row, whose output is dropped.  The banks go to the device once and are read in place."""
+    import torch
+    b = int(clips_per_step)
+    if b < 1 or b * net.k > _lib.VY_VIDEO_TABLE_MAX:
+        raise ValueError("clips_per_step %d x k %d: between 1 and %d table entries" % (b, net.k, _lib.VY_VIDEO_TABLE_MAX))
+    shape = tuple(f1.shape) if hasattr(f1, "shape") else tuple(np.shape(f1))
+    if len(shape) != 4 or shape[0] < 1:
+        raise ValueError("expected (T, C, h, w) routes with T >= 1, got %s" % (shape,))
+    table = window_indices(shape[0], net.k, step)
+    if net._device is not None:
+        f1, f2, f3 = (net._dev(f) for f in (f1, f2, f3))
+    outs = []
+    for i in range(0, len(table), b):
+        rows = table[i:i + b]
+        m = len(rows)
+        if m < b:
+            rows = np.concatenate([rows, np.repeat(rows[-1:], b - m, axis=0)], 0)
+        got = net.from_bank(f1, f2, f3, rows, return_index=return_index)
+        outs.append(tuple(t[:m] for t in got))
+    return tuple(torch.cat(ts, 0) for ts in zip(*outs))
