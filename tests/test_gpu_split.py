@@ -443,7 +443,7 @@ def test_split_gradients_under_the_products_routing_at_a_realistic_shape(tmp_pat
     via_dgrad = [lines[i + 1] for i, ln in enumerate(lines[:-1]) if ln.startswith("dgrad ") and lines[i + 1].startswith("# via")]
     assert any(v.startswith("# via split 256x64") for v in via_dgrad), "no data gradient ran on the 256x64 split tile"
     assert any(v.startswith("# via split") and int(v.rsplit("k", 1)[1]) > 1 for v in via_dgrad), "no data gradient ran as a k-split launch"
-    assert any(v == "# via exact" for v in via_dgrad)          # the routing really is per launch
+    assert any(v.startswith("# via exact ") for v in via_dgrad)  # the routing really is per launch
     assert r["differ"] > r["n"] // 2, r                          # the split kernels did produce the gradients
     assert r["worst"] < 2e-3, r
 

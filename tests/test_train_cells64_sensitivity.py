@@ -8,7 +8,11 @@ records whether the end-to-end bar (max|got - want| < 2e-3 max|want| over the te
 A toy window step (k = 3) does the same for the window net's checks: a per-frame route cell with its batch statistics,
 the pool, one head consumer of the pooled plane, a stride-2 consumer of the per-frame route whose data gradient
 accumulates onto what the pool backward wrote, and a route with no other contributor (the stride-32 case).  Some
-elements of the clips tie and some do not.  Eight more mutations must each fail a check."""
+elements of the clips tie and some do not.  Eight more mutations must each fail a check.
+
+Two more planted bugs are the ways a broken stream-K hand-off would show: a data gradient whose chain misses one
+32-channel k-step of one tap on one 64x64 tile (check_dgrad), and one tile's rows missing from the per-tile statistics
+sums (check_stats)."""
 import numpy as np
 import pytest
 import torch
@@ -184,6 +188,61 @@ def test_every_mutation_fails_the_per_cell_check(mut):
     caught = old and not all(old)
     print("%s: fails %s; the 2e-3-of-max bar %s" % (mut, sorted(set(r.kind for r in bad)),
                                                     "catches it" if caught else "MISSES it"))
+
+
+# ---------------------------------------------------------------- a broken stream-K hand-off
+# A stream-K launch hands a tile's accumulators from the block that starts it to the block that finishes it.  If a
+# hand-off is wrong, the finished tile lacks the k-steps of one piece: on a data gradient one 64x64 tile (64 pixels in
+# (b, y, x) order x 64 input channels) misses 32 output channels of one tap; on the training forward the tile's rows
+# are missing from the per-tile statistics sums.
+HAND_OFF_MUTATIONS = ["dgrad_chain_misses_one_k_step_on_one_tile", "one_tile_rows_missing_from_statistics_sums"]
+TILE = 64
+
+
+def _run_hand_off(mut=None):
+    rng = np.random.default_rng(17)
+    r = lambda *s: rng.standard_normal(s).astype(F32)  # noqa: E731
+    B, Cout, Cin, S = 2, 64, 96, 12        # data gradient: M = 288 pixels (4.5 tiles), N = 96 (1.5 tiles), K = 9 taps x 2 k-steps
+    dz, w = r(B, Cout, S, S), (r(Cout, Cin, 3, 3) * 0.1).astype(F32)
+    got = dev_dgrad(dz, w, 1, (S, S))
+    if mut == "dgrad_chain_misses_one_k_step_on_one_tile":
+        w_lost = w.copy()
+        w_lost[32:64, :, 2, 0] = 0         # the second k-step (output channels 32 .. 63) of tap (2, 0)
+        lost = dev_dgrad(dz, w_lost, 1, (S, S))
+        flat, flat_lost = got.transpose(0, 2, 3, 1).reshape(B * S * S, Cin), lost.transpose(0, 2, 3, 1).reshape(B * S * S, Cin)
+        flat = flat.copy()
+        flat[TILE:2 * TILE, :TILE] = flat_lost[TILE:2 * TILE, :TILE]   # pixel tile 1, channel tile 0
+        got = np.ascontiguousarray(flat.reshape(B, S, S, Cin).transpose(0, 3, 1, 2))
+    res = [R.check_dgrad("P", got, [(dz, w, 1, 0)])]
+    C, Sz = 16, 24                         # statistics: 1152 pixels = 18 tiles of 64 rows
+    z, gam, bet = r(B, C, Sz, Sz), (1 + 0.2 * r(C)).astype(F32), (0.3 * r(C)).astype(F32)
+    rows = z.transpose(0, 2, 3, 1).reshape(B * Sz * Sz, C).astype(np.float64)
+    keep = np.ones(len(rows), bool)
+    if mut == "one_tile_rows_missing_from_statistics_sums":
+        keep[5 * TILE:6 * TILE] = False    # the sums lack tile 5; the count is still every pixel
+    n = len(rows)
+    mean = rows[keep].sum(axis=0) / n
+    var = np.maximum((rows[keep] ** 2).sum(axis=0) / n - mean * mean, 0)
+    mf = mean.astype(F32)
+    inv = (F32(1) / np.sqrt(var.astype(F32) + F32(1e-5))).astype(F32)
+    sc = (gam * inv).astype(F32)
+    res.append(R.check_stats("cell", z, mf, inv, gam, bet, sc, R.fmaf(-mf, sc, bet)))
+    return res
+
+
+def test_hand_off_case_passes_unmutated():
+    res = _run_hand_off()
+    assert all(r.ok for r in res), res
+    assert all(r.headroom < 50 for r in res)
+
+
+@pytest.mark.parametrize("mut", HAND_OFF_MUTATIONS)
+def test_a_broken_stream_k_hand_off_fails_its_check(mut):
+    res = _run_hand_off(mut)
+    bad = [r.kind for r in res if not r.ok]
+    assert bad == ["data gradient" if mut.startswith("dgrad") else "forward stats"], (mut, res)
+    old = [r.old_bar_ok for r in res if not r.ok]
+    print("%s: fails %s; the 2e-3-of-max bar %s" % (mut, bad, "MISSES it" if all(old) else "catches it"))
 
 
 # ---------------------------------------------------------------- the toy window step

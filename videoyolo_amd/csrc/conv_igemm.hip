@@ -35,6 +35,7 @@
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "kernels.h"
@@ -881,8 +882,10 @@ static VySkPolicy sk_policy(const ConvArgs& a) {
 }
 
 // `sk_query` != nullptr: nothing is launched, *sk_query tells whether the launch would be a stream-K one (the profile's label)
+// `form` (with sk_query): the LDS stages and the runs of K of this instance as well
 template <int BM, int BN, int WM, int WN, int NS = 2>
-static hipError_t launch_cfg(const ConvArgs& a_in, hipStream_t s, bool* sk_query = nullptr, int* ks_query = nullptr) {
+static hipError_t launch_cfg(const ConvArgs& a_in, hipStream_t s, bool* sk_query = nullptr, int* ks_query = nullptr,
+                             VyConvForm* form = nullptr) {
   ConvArgs a = a_in;
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
   const long long tiles = (long long)tiles_m * tiles_n;
@@ -892,6 +895,10 @@ static hipError_t launch_cfg(const ConvArgs& a_in, hipStream_t s, bool* sk_query
   const int ksplit_S = a.dgrad ? 1 : vy_conv_runs(a.ntaps, a.Kc >> 5);
   a.k_chunk = 0;
   if (ks_query) *ks_query = 0;
+  if (form) {
+    form->ns = NS;
+    form->ck = ksplit_S > 1 ? ksplit_S : 0;
+  }
   if (ksplit_S > 1) {
     a.k_chunk = T_runs / ksplit_S;
     // a workgroup that runs more than one run of a tile parks the finished runs' sum in the tile's scratch
@@ -1018,20 +1025,20 @@ static VyFastDiv make_fastdiv(unsigned d) {
 }
 
 // tile choice -> template instance; `sk_query`: see launch_cfg
-static hipError_t run_cfg(const ConvArgs& a, hipStream_t s, bool* sk_query, int* ks_query = nullptr) {
+static hipError_t run_cfg(const ConvArgs& a, hipStream_t s, bool* sk_query, int* ks_query = nullptr, VyConvForm* form = nullptr) {
   int bm, bn;
   select_cfg(a, &bm, &bn);
   if (sk_query) *sk_query = false;
   if (ks_query) *ks_query = 0;
-  if (bn == 32) return launch_cfg<128, 32, 4, 1>(a, s, sk_query, ks_query);
-  if (bm == 128 && bn == 64) return launch_cfg<128, 64, 2, 2>(a, s, sk_query, ks_query);
+  if (bn == 32) return launch_cfg<128, 32, 4, 1>(a, s, sk_query, ks_query, form);
+  if (bm == 128 && bn == 64) return launch_cfg<128, 64, 2, 2>(a, s, sk_query, ks_query, form);
   if (bm == 64) {
     // few blocks (at most two per CU) and a k-loop long enough to fill it: the four-stage pipeline
     const long long nb = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-    if (nb <= 512 && a.ntaps * (a.Kc >> 5) >= 8) return launch_cfg<64, 64, 2, 2, 4>(a, s, sk_query, ks_query);
-    return launch_cfg<64, 64, 2, 2>(a, s, sk_query, ks_query);
+    if (nb <= 512 && a.ntaps * (a.Kc >> 5) >= 8) return launch_cfg<64, 64, 2, 2, 4>(a, s, sk_query, ks_query, form);
+    return launch_cfg<64, 64, 2, 2>(a, s, sk_query, ks_query, form);
   }
-  return launch_cfg<128, 128, 2, 2>(a, s, sk_query, ks_query);
+  return launch_cfg<128, 128, 2, 2>(a, s, sk_query, ks_query, form);
 }
 
 bool vy_conv_streamk(const ConvArgs& a) {
@@ -1043,6 +1050,27 @@ int vy_conv_ksplit(const ConvArgs& a) {
   bool sk = false;
   int ks = 0;
   return run_cfg(a, nullptr, &sk, &ks) == hipSuccess ? ks : 0;
+}
+
+void vy_conv_form(const ConvArgs& a, VyConvForm* f) {
+  bool sk = false;
+  int ks = 0;
+  memset(f, 0, sizeof *f);
+  select_cfg(a, &f->bm, &f->bn);
+  if (run_cfg(a, nullptr, &sk, &ks, f) != hipSuccess) return;
+  f->sk = sk;
+  f->ks = ks;
+  if (ks) f->ck = 0;  // one workgroup per run: nothing is parked
+}
+
+void vy_conv_form_label(const ConvArgs& a, char* buf, size_t n) {
+  VyConvForm f;
+  vy_conv_form(a, &f);
+  char sched[24] = "";
+  if (f.ks) snprintf(sched, sizeof sched, "ks%d", f.ks);
+  else if (f.ck) snprintf(sched, sizeof sched, "ck%d%s", f.ck, f.sk ? "sk" : "");
+  else if (f.sk) snprintf(sched, sizeof sched, "sk");
+  snprintf(buf, n, "%dx%d%s%s", f.bm, f.bn, f.ns == 4 ? "s4" : "", sched);
 }
 
 size_t vy_conv_chunk_scratch_bytes(long long M, int N, int runs) {

@@ -92,6 +92,14 @@ static inline int vy_args_cus(const ConvArgs& a) { return a.cus > 0 ? a.cus : vy
 static inline const VyKnobs& vy_args_knobs(const ConvArgs& a) { return a.knobs ? *a.knobs : vy_knobs_default(); }
 bool vy_conv_streamk(const ConvArgs& a);                  // ... and whether it will be a stream-K launch (label "<BM>x<BN>sk")
 int vy_conv_ksplit(const ConvArgs& a);                    // ... or a split-K one: the S workgroups per tile (label "<BM>x<BN>ks<S>"), else 0
+// ... the whole form in one query (the training step's launch labels): block tile, LDS stages (2 / 4), and the schedule —
+// sk: stream-K; ks: split-K workgroups per tile; ck: the runs of K one workgroup takes in turn with parked chains (0: K
+// is one run, or the launch is split-K).  Label "<BM>x<BN>[s4][sk | ks<S> | ck<S> | ck<S>sk]"
+struct VyConvForm {
+  int bm, bn, ns, sk, ks, ck;
+};
+void vy_conv_form(const ConvArgs& a, VyConvForm* f);
+void vy_conv_form_label(const ConvArgs& a, char* buf, size_t n);
 size_t vy_conv_chunk_scratch_bytes(long long M, int N, int runs);   // ck_scratch bytes a conv of M x N outputs summed in `runs` runs may need (any tile)
 
 // stream-K is enabled per net only after this has seen the MI355X's SPX placement (8 XCDs, blocks L and L + 8 on one
@@ -399,6 +407,7 @@ hipError_t vy_launch_wgrad_table(void* tab, int M, int n_entries, int Ho, int Wo
                                  int stride, int B, int k_per_split, hipStream_t s);
 // dst[i] = sum_s slabs[s][i]  (fixed order)
 hipError_t vy_launch_slab_reduce(const float* slabs, int splits, long long n, float* dst, hipStream_t s);
+int vy_slab_reduce_groups(int splits);  // thread groups of the slab reduce it launches: 32 / 8 (slab_reduce_wide_kernel<G>), 0: the plain one
 
 // stem weight gradient (Cin = 3): partials [blocks][32*27] then vy_launch_reduce_partials
 struct StemWgradArgs {

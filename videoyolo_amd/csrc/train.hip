@@ -97,25 +97,47 @@ namespace {
 
 // Profiling aid (tools/train_layers.py): with VY_TRAIN_LABELS=<path> the first training step appends one line per
 // matrix-core launch — kind (fwd / wgrad / dgrad), cell name, FLOPs, GEMM dims — so that a rocprofv3 kernel trace
-// can be joined with the layers by launch order within each kernel class.  Once per process: `done`.
+// can be joined with the layers by launch order within each kernel class.  Once per path: the first step of the first
+// net that names a path fills it (`done`); a later net that names another path (the GPU tests: one file per case) gets
+// its own first step.
 struct LabelLog {
   FILE* f = nullptr;
-  bool done = false;
+  std::string path, done;  // the file being written; the last one finished
   void note(const vy_net* net, const char* kind, const std::string& name, double M, double N, double K) {
-    if (done || net->knobs.train_labels.empty()) return;
-    if (!f) f = fopen(net->knobs.train_labels.c_str(), "w");
+    const std::string& want = net->knobs.train_labels;
+    if (want.empty() || want == done) return;
+    if (!f && (f = fopen(want.c_str(), "w"))) path = want;
     if (f) fprintf(f, "%s %s %.0f %.0f %.0f %.0f\n", kind, name.c_str(), 2.0 * M * N * K, M, N, K);
   }
-  // "# via split 128x128 k2" / "# via exact": which kernel the preceding fwd / dgrad line went to (tests assert that the
-  // launches they mean to cover really ran; tools/train_layers.py skips '#' lines)
+  // which kernel the preceding line went to, and in which form (tests assert that the launches they mean to cover really
+  // ran; tools/train_layers.py skips '#' lines):
+  //   "# via split 128x128 k2"          fwd / dgrad on the split-fp32 kernel
+  //   "# via exact 128x64sk"            fwd / dgrad on the exact kernel: vy_conv_form_label's tile, stages and schedule
+  //   "# via wgrad_kernel<32,64> splits 14 reduce wide<8> stream side"   wgrad: the kernel instance, its slabs, their
+  //                                     reduce (plain / wide<8> / wide<32>) and the stream both went to (side / main)
   void via(const char* text) {
     if (f) fprintf(f, "# via %s\n", text);
+  }
+  void via_exact(const ConvArgs& a) {
+    if (!f) return;
+    char form[48], t[64];
+    vy_conv_form_label(a, form, sizeof form);
+    snprintf(t, sizeof t, "exact %s", form);
+    via(t);
+  }
+  void via_wgrad(const char* kernel, int splits, bool side) {
+    if (!f) return;
+    const int g = vy_slab_reduce_groups(splits);
+    char t[112];
+    snprintf(t, sizeof t, "%s splits %d reduce %s stream %s", kernel, splits, g == 32 ? "wide<32>" : g == 8 ? "wide<8>" : "plain",
+             side ? "side" : "main");
+    via(t);
   }
   void close_step() {
     if (!f) return;
     fclose(f);
     f = nullptr;
-    done = true;
+    done = path;
   }
 };
 LabelLog g_labels;
@@ -400,7 +422,7 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
     }
     HIP_TRY(vy_launch_conv_split(a, s));
   } else {
-    g_labels.via("exact");
+    g_labels.via_exact(a);
     HIP_TRY(vy_launch_conv_igemm(a, s));
   }
   return 0;
@@ -412,6 +434,7 @@ int pred_conv(const TrainCtx& c, int ci) {
   const ConvT& cv = c.net->convs[ci];
   const ConvArgs a = c.net->conv_args(cv);
   g_labels.note(c.net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
+  g_labels.via_exact(a);
   HIP_TRY(vy_launch_conv_igemm(a, c.s));
   return 0;
 }
@@ -657,8 +680,10 @@ int launch_wgrad(const TrainCtx& c, int ci, DzView dz, hipStream_t ws) {
     // (bound measurements: no weight-gradient kernel at all / none for the early cells — N <= 128, K <= 576: stages.0.1 ... 0.5 —
     // whose output tile is mostly padding: what would a perfect kernel for them return to the step?)
   } else if (net->knobs.split_wgrad && net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && vy_wgrad_split_supported(w)) {
+    g_labels.via_wgrad("wgrad_split_kernel", w.splits, ws != c.s);
     HIP_TRY(vy_launch_wgrad_split(w, ws));
   } else {
+    g_labels.via_wgrad(vy_wgrad_tile_rows(w.Cout, w.k, w.Cin) == 64 ? "wgrad_kernel<32,64>" : "wgrad_kernel<32,128>", w.splits, ws != c.s);
     HIP_TRY(vy_launch_wgrad(w, ws));
   }
   HIP_TRY(vy_launch_slab_reduce(c.slabs(), w.splits, (long long)cv.cout * cv.k * cv.k * cv.cin, c.grad_of(cv.p_weight), ws));

@@ -343,10 +343,13 @@ __global__ __launch_bounds__(32 * G) void slab_reduce_wide_kernel(const float* _
   }
 }
 
+int vy_slab_reduce_groups(int splits) { return splits >= 64 ? 32 : splits >= 12 ? 8 : 0; }
+
 hipError_t vy_launch_slab_reduce(const float* slabs, int splits, long long n, float* dst, hipStream_t s) {
-  if (splits >= 64)
+  const int groups = vy_slab_reduce_groups(splits);
+  if (groups == 32)
     hipLaunchKernelGGL(slab_reduce_wide_kernel<32>, dim3((unsigned)((n + 31) / 32)), dim3(1024), 0, s, slabs, splits, n, dst);
-  else if (splits >= 12)
+  else if (groups == 8)
     hipLaunchKernelGGL(slab_reduce_wide_kernel<8>, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s, slabs, splits, n, dst);
   else
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, slabs, splits, n, dst);
