@@ -391,6 +391,38 @@ int vy_train_transform(const uint8_t* frames, const vy_train_aug* augs, int32_t 
  * kernel uses for the fractional position x, for checkers. */
 void vy_math_lanczos4(float x, float* w8);
 
+/* The matching step of the ImageNet-VID motion / area mAP (metrics/imgnetvid.py:191-276, vid_eval_motion) for a batch of
+ * frames on the device: in every (motion range, area range) slice a frame's detections claim its ground truths greedily
+ * in score order.  videoyolo_amd/metrics.py states the rule (vid_match_host); the kernel (csrc/vid_metric.hip) walks one
+ * (frame, slice) chain per lane, all float64, and gives the same values.  Needs no vy_net.
+ *
+ * Detections — device arrays over all rows of the batch: det_box (n, 4) float64 corners, det_label (n) int32, det_score
+ * (n) float64; frame i owns rows det_off[i] .. det_off[i + 1], ALREADY in descending score order.  A row with a negative
+ * label or a score that is not >= conf_thresh is skipped wherever it lies: its outputs are 0.
+ * Ground truths — device tables over a whole dataset of n_gt_frames frames: gt_box (G, 4) float64, gt_label (G) int32,
+ * gt_thr (G) the IoU a match needs, gt_motion (G) motion IoU, and gt_nig (n_gt_frames, n_motion) int32, per frame and
+ * motion range the number of its ground truths outside the range (its own count: with a class map the reference counts
+ * the unmapped list).  Row r owns ground truths gt_off[r] .. gt_off[r + 1]; frame i of the batch is row gt_frame[i].
+ * motion_ranges (n_motion, 2) and area_ranges (n_area, 2) are [lo, hi] pairs, both ends inside; empty_weight (n_motion)
+ * is the false-positive weight of an unmatched detection in a frame without ground truth.  Slice s = motion * n_area +
+ * area.  det_off, gt_frame, gt_off, the ranges and empty_weight are HOST arrays and travel in the kernel arguments,
+ * VY_VID_CHUNK frames per launch.
+ * flags: device scratch of flags_bytes >= (ground truths of the batch's frames) * n_motion * n_area bytes, one detected
+ * flag per (ground truth, slice); the kernel clears what it uses.  tp (n, slices) uint8 and fp (n, slices) float64,
+ * device: every element of the batch's rows is written.
+ * Checked before anything is launched, else VY_ERR_INVALID: null pointers, negative counts, 1..VY_VID_MAX_RANGES ranges
+ * of each kind with lo <= hi, ascending det_off, gt_frame inside the table, ascending gt_off at every row used, enough
+ * flag bytes.  No frames or no rows: VY_OK without a launch.  Asynchronous on `stream`; no device memory of the
+ * library's, no copy, no synchronisation. */
+#define VY_VID_MAX_RANGES 8
+#define VY_VID_CHUNK 64
+int vy_vid_match(int32_t n_frames, const int64_t* det_off, const double* det_box, const int32_t* det_label,
+                 const double* det_score, double conf_thresh, const int32_t* gt_frame, int32_t n_gt_frames,
+                 const int64_t* gt_off, const double* gt_box, const int32_t* gt_label, const double* gt_thr,
+                 const double* gt_motion, const int32_t* gt_nig, int32_t n_motion, const double* motion_ranges,
+                 int32_t n_area, const double* area_ranges, const double* empty_weight, uint8_t* flags,
+                 int64_t flags_bytes, uint8_t* tp, double* fp, void* stream);
+
 /* Prefetch target generation on the device: YOLOV3PrefetchTargetGenerator.forward,
  * models/definitions/yolo/yolo_target.py:31-148 (called per sample from the DataLoader transform,
  * transforms.py:259-277), for a whole batch.  gt_boxes (batch,num_gt,4) corner pixels of the

@@ -150,3 +150,379 @@ class VOC07MApMetric(VOCMApMetric):
             hit = rec >= t
             ap += (np.max(p[hit]) if hit.any() else 0.0) / 11.0
         return float(ap)
+
+
+# ====================================================================================================================
+# ImageNet-VID motion / area mAP: metrics/imgnetvid.py in the reference, the metric its detect
+# driver builds for its main dataset (detect_yolo3.py:181-195) and its model README reports.  mAP over motion-IoU ranges
+# x box-area ranges; a frame's detections claim ground truths greedily in score order, separately in every slice.
+# Pinned by the reference's own vid_eval_motion: tests/golden/make_vid_metric_golden.py.
+# ====================================================================================================================
+VID_MOTION_RANGES = ((0.0, 1.0), (0.0, 0.7), (0.7, 0.9), (0.9, 1.0))
+VID_AREA_RANGES = ((0, 1e5 * 1e5), (0, 50 * 50), (50 * 50, 150 * 150), (150 * 150, 1e5 * 1e5))
+
+
+def vid_match_host(det_boxes, det_labels, gt_boxes, gt_labels, gt_thr, gt_motion, motion_ranges, area_ranges,
+                   empty_weight, n_ig_motion=None):
+    """The matching rule of the VID metric for ONE frame, every (motion range, area range) slice at once: the definition
+    the device kernel (csrc/vid_metric.hip, vy_vid_match) is held to, value for value.
+
+    det_boxes (D, 4) / det_labels (D): the frame's kept detections in descending score order.  gt_boxes (G, 4),
+    gt_labels (G), gt_thr (G) the IoU a match needs, gt_motion (G) motion IoU.  motion_ranges (M, 2), area_ranges (A, 2):
+    [lo, hi], both ends inside.  empty_weight (M): the weight of a miss in a frame without ground truth.  n_ig_motion (M):
+    how many of the frame's ground truths lie outside each motion range (default: counted from gt_motion; the metric
+    passes the count over the frame's unmapped list, which a class map makes longer than G).  Returns ``tp`` (D, M * A)
+    uint8 and ``fp`` (D, M * A) float64, slice = motion * A + area.
+
+    All float64, in this order (pixel boxes, both corners inside):
+      iw = min(b2, g2) - max(b0, g0) + 1, ih likewise; both > 0: ov = iw * ih / ((bw * bh + gw * gh) - iw * ih), else 0
+      per detection, ground truths in index order: a candidate has ov >= thr, is not yet detected in the slice and has
+      the detection's label; the largest ov wins, the lowest index on a tie
+      match: the ground truth is detected; tp = 1 unless it is outside the motion or the area range; fp = 0
+      miss: fp = 0 if the detection's own area is outside the area range; else 1 if its best overlap with an in-range
+      ground truth exceeds that with an out-of-range one, 0 if the reverse; else (equal, -1 when there is none)
+      empty_weight if G == 0, else n_ig_motion / G
+    """
+    db = np.asarray(det_boxes, np.float64).reshape(-1, 4)
+    dl = np.asarray(det_labels).reshape(-1).astype(np.int64)
+    gb = np.asarray(gt_boxes, np.float64).reshape(-1, 4)
+    gl = np.asarray(gt_labels).reshape(-1).astype(np.int64)
+    thr = np.asarray(gt_thr, np.float64).reshape(-1)
+    mo = np.asarray(gt_motion, np.float64).reshape(-1)
+    mr = np.asarray(motion_ranges, np.float64).reshape(-1, 2)
+    ar = np.asarray(area_ranges, np.float64).reshape(-1, 2)
+    n_m, n_a = len(mr), len(ar)
+    m0, m1 = np.repeat(mr[:, 0], n_a), np.repeat(mr[:, 1], n_a)
+    a0, a1 = np.tile(ar[:, 0], n_m), np.tile(ar[:, 1], n_m)
+    n_d, n_g, n_s = len(db), len(gb), n_m * n_a
+    tp = np.zeros((n_d, n_s), np.uint8)
+    fp = np.zeros((n_d, n_s), np.float64)
+    ig_m = (mo[None, :] < m0[:, None]) | (mo[None, :] > m1[:, None])              # (S, G)
+    gw, gh = gb[:, 2] - gb[:, 0] + 1, gb[:, 3] - gb[:, 1] + 1
+    g_area = gh * gw
+    ig_a = (g_area[None, :] < a0[:, None]) | (g_area[None, :] > a1[:, None])
+    if n_g == 0:
+        miss = np.repeat(np.asarray(empty_weight, np.float64).reshape(-1), n_a)
+    else:
+        n_ig = ig_m.sum(axis=1) if n_ig_motion is None else np.repeat(np.asarray(n_ig_motion).reshape(-1), n_a)
+        miss = n_ig / float(n_g)
+    detected = np.zeros((n_s, n_g), bool)
+    rows = np.arange(n_s)
+    for j in range(n_d):   # the chain: sequential in the detections, whole-array in ground truths and slices
+        b = db[j]
+        if n_g:
+            iw = np.minimum(b[2], gb[:, 2]) - np.maximum(b[0], gb[:, 0]) + 1
+            ih = np.minimum(b[3], gb[:, 3]) - np.maximum(b[1], gb[:, 1]) + 1
+            ua = (b[2] - b[0] + 1) * (b[3] - b[1] + 1) + gw * gh - iw * ih
+            with np.errstate(divide='ignore', invalid='ignore'):
+                ov = np.where((iw > 0) & (ih > 0), iw * ih / ua, 0.0)
+            cand = ((ov >= thr) & (gl == dl[j]))[None, :] & ~detected
+            kmax = np.where(cand, ov[None, :], -1.0).argmax(axis=1)                 # first index of the largest
+            hit = cand.any(axis=1)
+            ov_ig = np.where(ig_m, ov[None, :], -1.0).max(axis=1)
+            ov_nig = np.where(ig_m, -1.0, ov[None, :]).max(axis=1)
+            detected[rows[hit], kmax[hit]] = True
+            tp[j] = hit & ~ig_m[rows, kmax] & ~ig_a[rows, kmax]
+        else:
+            hit = np.zeros(n_s, bool)
+            ov_ig = ov_nig = np.full(n_s, -1.0)
+        b_area = (b[3] - b[1] + 1) * (b[2] - b[0] + 1)
+        outside = (b_area < a0) | (b_area > a1)
+        f = np.where(ov_nig > ov_ig, 1.0, np.where(ov_ig > ov_nig, 0.0, miss))
+        fp[j] = np.where(hit | outside, 0.0, f)
+    return tp, fp
+
+
+def _vid_ap(rec, prec):
+    """Area under the monotone precision envelope (imgnetvid.py:40-65), whole-array."""
+    mrec = np.concatenate(([0.], rec, [1.]))
+    mpre = np.concatenate(([0.], prec, [0.]))
+    mpre = np.maximum.accumulate(mpre[::-1])[::-1]
+    i = np.flatnonzero(mrec[1:] != mrec[:-1])
+    return np.sum((mrec[i + 1] - mrec[i]) * mpre[i + 1])
+
+
+class VIDDetectionMetric(object):
+    """ImageNet-VID mean AP by motion-IoU range x box-area range: the reference's ``VIDDetectionMetric``
+    (metrics/imgnetvid.py:357-472), same constructor, ``update`` / ``get`` / ``reset`` and ``get()`` strings.
+
+    ``dataset`` is duck-typed: ``get_sample_ids()`` (with ``offset`` the entries are lists and the id is
+    ``w[offset + 2]``), ``get_label(id)`` -> (n, >= 5) rows ``[x1, y1, x2, y2, cls, ...]``, ``wn_classes``, ``classes``
+    and ``motion_ious[str(id)]``, one value per ground truth.  The ground-truth tables of the whole dataset are built here,
+    once.  ``update``'s ground-truth arguments are accepted and ignored, as in the reference: ground truth comes from the
+    dataset.  ``sid`` is the frame's id for a batch of 1, or a sequence of B ids.
+
+    When the predictions are device tensors ``update`` matches them on the device (vy_vid_match): the per-frame sort and
+    the float64 casts are torch calls, nothing is copied to the host and nothing synchronises; the outputs stay device
+    tensors until ``get()`` copies them once.  Host arrays go through ``vid_match_host``.  Both give the same values.
+
+    Where this differs from the reference, on purpose:
+      * a ``sid`` the dataset does not have, or one seen before (since ``reset``), raises ``ValueError``.  The reference
+        silently drops the rows of an unknown id and merges the rows of a repeated one into one frame.
+      * equal scores keep their order (stable sorts; frames in the dataset's sample-id order).  The reference's
+        ``argsort`` leaves ties to the sort's internals.
+      * the ranges are constructor keywords (defaults: the reference's hard-set ones).
+    ``class_map`` / ``agnostic`` compute what the reference computes, including that with a class map a frame's ``thr``,
+    motion IoU and out-of-range count come from its unmapped label list (imgnetvid.py:204-220, :265) and that a dropped
+    class reads the positives of the last one (:347).
+
+    After ``get()``, ``metric.ap`` is the (motion ranges, area ranges, classes) array; -1: no positives in the slice.
+    """
+
+    def __init__(self, dataset, conf_score_thresh=0.05, iou_thresh=0.5, class_map=None, agnostic=False, offset=None,
+                 motion_ranges=VID_MOTION_RANGES, area_ranges=VID_AREA_RANGES):
+        self.name = 'ImgNetVIDMeanAP'
+        self.dataset = dataset
+        self._conf_score_thresh = float(conf_score_thresh)
+        self._iou_thresh = iou_thresh
+        self._class_map = class_map
+        self._agnostic = agnostic
+        self._offset = offset
+        self._motion_ranges = [list(r) for r in motion_ranges]
+        self._area_ranges = [list(r) for r in area_ranges]
+        self._mr = np.asarray(self._motion_ranges, np.float64).reshape(-1, 2)
+        self._ar = np.asarray(self._area_ranges, np.float64).reshape(-1, 2)
+        if not (1 <= len(self._mr) <= 8 and 1 <= len(self._ar) <= 8):
+            raise ValueError("between 1 and 8 motion ranges and area ranges")
+        if (self._mr[:, 0] > self._mr[:, 1]).any() or (self._ar[:, 0] > self._ar[:, 1]).any():
+            raise ValueError("a range with lo > hi")
+        self._build_tables()
+        self._device_tables = {}
+        self.reset()
+
+    # ------------------------------------------------------------------ the dataset's ground truth, once
+    def _build_tables(self):
+        ds = self.dataset
+        ids = list(ds.get_sample_ids())
+        if len(ids) and isinstance(ids[0], list):
+            ids = [w[self._offset + 2] for w in ids]
+        self._ids = ids
+        self._row = {}
+        for r, i in enumerate(ids):
+            if i in self._row:
+                raise ValueError("sample id %r appears twice in the dataset" % (i,))
+            self._row[i] = r
+        self._names = ['agnostic'] if self._agnostic else list(ds.wn_classes)
+        cm = self._class_map
+        n_pos = len(self._names) if cm is None else max(cm) + 1
+        boxes, labels, thrs, motions, counts, all_motion, all_count = [], [], [], [], [], [], []
+        for i in ids:
+            lab = np.asarray(ds.get_label(i), np.float64)
+            lab = lab.reshape(-1, lab.shape[-1] if lab.ndim == 2 else 5)
+            box, raw = lab[:, :4], lab[:, 4].astype(np.int64)
+            w, h = box[:, 2] - box[:, 0] + 1, box[:, 3] - box[:, 1] + 1
+            thr = np.minimum((w * h) / ((w + 10) * (h + 10)), self._iou_thresh)
+            mo = np.asarray(ds.motion_ious[str(i)], np.float64).reshape(-1)
+            if len(mo) != len(lab):
+                raise ValueError("sample %r: %d motion IoUs for %d ground truths" % (i, len(mo), len(lab)))
+            if cm is not None:
+                raw = np.array([cm[int(l)] for l in raw], np.int64).reshape(-1)
+                valid = np.flatnonzero(raw >= 0)
+                box, raw = box[valid], raw[valid]
+            if self._agnostic:
+                raw = raw * 0
+            n = len(raw)
+            boxes.append(box), labels.append(raw), thrs.append(thr[:n]), motions.append(mo[:n]), counts.append(n)
+            all_motion.append(mo), all_count.append(len(mo))
+        cat = lambda parts, shape, dt: np.concatenate(parts).astype(dt) if parts else np.zeros(shape, dt)  # noqa: E731
+        self._gt_box = np.ascontiguousarray(cat(boxes, (0, 4), np.float64).reshape(-1, 4))
+        self._gt_label = cat(labels, (0,), np.int32)
+        self._gt_thr = cat(thrs, (0,), np.float64)
+        self._gt_motion = cat(motions, (0,), np.float64)
+        self._gt_off = np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64))]).astype(np.int64)
+        if self._gt_label.size and (self._gt_label.min() < 0 or self._gt_label.max() >= n_pos):
+            raise ValueError("a ground-truth label outside the %d classes" % n_pos)
+        n_m, n_a = len(self._mr), len(self._ar)
+        # per frame and motion range: ground truths of the UNMAPPED list outside the range; the share inside it, dataset-wide
+        am = cat(all_motion, (0,), np.float64)
+        frame_of = np.repeat(np.arange(len(ids)), np.asarray(all_count, np.int64))
+        self._gt_nig = np.zeros((len(ids), n_m), np.int32)
+        self._empty_weight = np.zeros(n_m, np.float64)
+        for m in range(n_m):
+            out = (am < self._mr[m, 0]) | (am > self._mr[m, 1])
+            self._gt_nig[:, m] = np.bincount(frame_of[out], minlength=len(ids))
+            if len(am):
+                self._empty_weight[m] = int((~out).sum()) / float(len(am))
+        # positives per slice and class: the dataset's count minus the ground truths ignored in the slice
+        base = np.bincount(self._gt_label, minlength=n_pos).astype(np.float64)
+        area = (self._gt_box[:, 3] - self._gt_box[:, 1] + 1) * (self._gt_box[:, 2] - self._gt_box[:, 0] + 1)
+        self._npos = np.zeros((n_m * n_a, n_pos), np.float64)
+        for m in range(n_m):
+            ig_m = (self._gt_motion < self._mr[m, 0]) | (self._gt_motion > self._mr[m, 1])
+            for a in range(n_a):
+                ig = ig_m | (area < self._ar[a, 0]) | (area > self._ar[a, 1])
+                self._npos[m * n_a + a] = base - np.bincount(self._gt_label[ig], minlength=n_pos)
+
+    def _tables_on(self, dev):
+        t = self._device_tables.get(dev)
+        if t is None:
+            import torch
+            pad = lambda a: a if a.size else np.zeros((1,) + a.shape[1:], a.dtype)  # noqa: E731
+            t = [torch.from_numpy(pad(a)).to(dev) for a in (self._gt_box, self._gt_label, self._gt_thr, self._gt_motion,
+                                                             self._gt_nig)]
+            self._device_tables[dev] = t
+        return t
+
+    def reset(self):
+        self._chunks = []     # per update: (rows, labels, scores, tp, fp), numpy or device tensors
+        self._seen = set()
+        self.ap = None
+
+    # ------------------------------------------------------------------ accumulation
+    def _rows_of(self, sid, batch):
+        if sid is None:
+            raise ValueError("update needs sid: the frame's id, or one id per frame of the batch")
+        if hasattr(sid, "tolist"):
+            sid = sid.tolist()
+        sids = list(sid) if isinstance(sid, (list, tuple, range)) else [sid]
+        if len(sids) != batch:
+            raise ValueError("%d ids for a batch of %d frames" % (len(sids), batch))
+        rows = []
+        for s in sids:
+            if s not in self._row:
+                raise ValueError("sid %r is not one of the dataset's sample ids" % (s,))
+            if s in self._seen or self._row[s] in rows:
+                raise ValueError("sid %r was given before" % (s,))
+            rows.append(self._row[s])
+        return sids, np.asarray(rows, np.int64)
+
+    @staticmethod
+    def _gather(x):
+        if isinstance(x, (list, tuple)) and len(x) and all(hasattr(t, "is_cuda") for t in x):
+            import torch
+            return torch.cat([t.to(x[0].device) for t in x], 0)
+        return x
+
+    def update(self, pred_bboxes, pred_labels, pred_scores, gt_bboxes=None, gt_ids=None, gt_difficults=None, sid=None):
+        """pred_bboxes (B, N, 4), pred_labels and pred_scores (B, N) or (B, N, 1): numpy, torch, or lists of them (one per
+        device, joined along the batch).  Rows with label < 0 or score < conf_score_thresh are dropped."""
+        pb, pl, ps = (self._gather(x) for x in (pred_bboxes, pred_labels, pred_scores))
+        on_device = all(getattr(x, "is_cuda", False) for x in (pb, pl, ps))
+        if not on_device:
+            pb, pl, ps = (np.asarray(_to_numpy(x)) for x in (pb, pl, ps))
+        batch = int(pb.shape[0])
+        sids, rows = self._rows_of(sid, batch)
+        n = int(np.prod(pl.shape[1:])) if batch else 0
+        if batch and n:
+            pb, pl, ps = pb.reshape(batch, n, 4), pl.reshape(batch, n), ps.reshape(batch, n)
+            self._chunks.append(self._update_device(pb, pl, ps, rows) if on_device else self._update_host(pb, pl, ps, rows))
+        self._seen.update(sids)
+
+    def _update_host(self, pb, pl, ps, rows):
+        out = [[], [], [], [], []]
+        for b, r in enumerate(rows):
+            score = ps[b].astype(np.float64)
+            keep = np.flatnonzero((pl[b] >= 0) & (score >= self._conf_score_thresh))
+            keep = keep[np.argsort(-score[keep], kind='stable')]
+            label = pl[b][keep].astype(np.int64) * (0 if self._agnostic else 1)
+            g0, g1 = self._gt_off[r], self._gt_off[r + 1]
+            tp, fp = vid_match_host(pb[b][keep].astype(np.float64), label, self._gt_box[g0:g1], self._gt_label[g0:g1],
+                                    self._gt_thr[g0:g1], self._gt_motion[g0:g1], self._mr, self._ar, self._empty_weight,
+                                    self._gt_nig[r])
+            for o, v in zip(out, (np.full(len(keep), r, np.int64), label.astype(np.int32), score[keep], tp, fp)):
+                o.append(v)
+        return tuple(np.concatenate(o) for o in out)
+
+    def _update_device(self, pb, pl, ps, rows):
+        import ctypes
+        import torch
+        from . import _lib
+        lib = _lib.load()
+        dev = pb.device
+        batch, n = pl.shape
+        n_s = len(self._mr) * len(self._ar)
+        score = ps.to(torch.float64)
+        order = torch.sort(score, dim=1, descending=True, stable=True).indices
+        score = score.gather(1, order).contiguous()
+        lab = pl.gather(1, order)
+        lab_i = lab.to(torch.int32)
+        label = torch.where(lab >= 0, torch.zeros_like(lab_i) if self._agnostic else lab_i, torch.full_like(lab_i, -1))
+        box = pb.to(torch.float64).gather(1, order[:, :, None].expand(batch, n, 4)).contiguous()
+        tp = torch.empty((batch * n, n_s), dtype=torch.uint8, device=dev)
+        fp = torch.empty((batch * n, n_s), dtype=torch.float64, device=dev)
+        flag_bytes = int((self._gt_off[rows + 1] - self._gt_off[rows]).sum()) * n_s
+        flags = torch.empty(max(flag_bytes, 1), dtype=torch.uint8, device=dev)
+        gt_box, gt_label, gt_thr, gt_motion, gt_nig = self._tables_on(dev)
+        det_off = np.arange(batch + 1, dtype=np.int64) * n
+        gt_frame = rows.astype(np.int32)
+        host = lambda a: a.ctypes.data_as(ctypes.c_void_p)    # noqa: E731
+        devp = lambda t: ctypes.c_void_p(t.data_ptr())        # noqa: E731
+        with torch.cuda.device(dev):
+            _lib.check(lib.vy_vid_match(
+                batch, host(det_off), devp(box), devp(label), devp(score), self._conf_score_thresh, host(gt_frame),
+                len(self._ids), host(self._gt_off), devp(gt_box), devp(gt_label), devp(gt_thr), devp(gt_motion), devp(gt_nig),
+                len(self._mr), host(self._mr), len(self._ar), host(self._ar), host(self._empty_weight), devp(flags),
+                flag_bytes, devp(tp), devp(fp), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return np.repeat(rows, n), label.reshape(-1), score.reshape(-1), tp, fp
+
+    # ------------------------------------------------------------------ evaluation
+    def matches(self):
+        """Every kept detection so far as ``(row, label, score, tp, fp)`` numpy arrays: frames in the dataset's sample-id
+        order (``row`` indexes it), a frame's detections by descending score; tp (n, slices) uint8, fp (n, slices)
+        float64, slice = motion range * area ranges + area range.  Device results are copied here, once."""
+        n_s = len(self._mr) * len(self._ar)
+        parts = [[], [], [], [], []]
+        dev_chunks = [c for c in self._chunks if not isinstance(c[3], np.ndarray)]
+        if dev_chunks:
+            import torch
+            joined = [torch.cat([c[k].to(dev_chunks[0][3].device) for c in dev_chunks], 0).cpu().numpy() for k in range(1, 5)]
+            label, score = joined[0], joined[1]
+            keep = np.flatnonzero((label >= 0) & (score >= self._conf_score_thresh))
+            parts[0].append(np.concatenate([c[0] for c in dev_chunks])[keep])
+            for k in range(4):
+                parts[k + 1].append(joined[k][keep])
+        for c in self._chunks:
+            if isinstance(c[3], np.ndarray):
+                for k in range(5):
+                    parts[k].append(c[k])
+        empty = (np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float64), np.zeros((0, n_s), np.uint8),
+                 np.zeros((0, n_s), np.float64))
+        out = [np.concatenate(p) if p else e for p, e in zip(parts, empty)]
+        order = np.argsort(out[0], kind='stable')
+        return tuple(a[order] for a in out)
+
+    def _average_precisions(self):
+        _, label, score, tp, fp = self.matches()
+        n_m, n_a, n_c = len(self._mr), len(self._ar), len(self._names)
+        by_score = np.argsort(-score, kind='stable')
+        by_class = np.argsort(label[by_score], kind='stable')
+        idx = by_score[by_class]                      # class by class, descending score inside a class
+        sorted_label = label[idx]
+        tp, fp = np.ascontiguousarray(tp[idx].T), np.ascontiguousarray(fp[idx].T)
+        cm = self._class_map if self._class_map is not None else list(range(n_c))
+        eps = np.finfo(np.float64).eps
+        ap = np.zeros((n_m * n_a, n_c))
+        for c in range(n_c):
+            lo, hi = np.searchsorted(sorted_label, cm[c], 'left'), np.searchsorted(sorted_label, cm[c], 'right')
+            for s in range(n_m * n_a):
+                npos = self._npos[s][cm[c]]
+                if npos <= 0:
+                    ap[s, c] = -1
+                    continue
+                tpc = np.cumsum(tp[s, lo:hi], dtype=np.float64)
+                fpc = np.cumsum(fp[s, lo:hi])
+                ap[s, c] = _vid_ap(tpc / npos, tpc / np.maximum(tpc + fpc, eps))
+        return ap.reshape(n_m, n_a, n_c)
+
+    def get(self):
+        """``(names, values)`` with the reference's strings (imgnetvid.py:402-426): the summary of every slice's mean AP
+        over the classes with positives, then AP x 100 of every class in the first slice."""
+        ap = self.ap = self._average_precisions()
+        names, values = ['~~~~ Summary metrics ~~~~\n'], []
+        info_str = ''
+        for mi, mr in enumerate(self._motion_ranges):
+            for ai, ar in enumerate(self._area_ranges):
+                lo, hi = np.sqrt(ar[0]), np.sqrt(ar[1])
+                info_str += 'motion [{0:.1f} {1:.1f}], area [{2} {3} {4} {5}]\n'.format(mr[0], mr[1], lo, lo, hi, hi)
+                scored = ap[mi, ai][ap[mi, ai] >= 0]
+                mean = np.mean(scored) if len(scored) else float('nan')
+                info_str += 'Mean AP@{:.1f} = {:.4f}\n\n'.format(self._iou_thresh, mean)
+        values.append(info_str)
+        if self._agnostic:
+            names.append('agnostic')
+            values.append('{:.1f}'.format(100 * ap[0, 0, 0]))
+            return names, values
+        for c, cls_name in enumerate(self.dataset.classes):
+            names.append(cls_name)
+            values.append('{:.1f}'.format(100 * ap[0, 0, c]))
+        return names, values
