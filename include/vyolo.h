@@ -464,7 +464,10 @@ int vy_net_set_train_options(vy_net* net, float ignore_iou_thresh, int32_t label
  * vy_net_train_backward only has to walk the network.
  *   x (B,3,H,W)  gt_boxes (B,M,4) corner px, -1 padded   obj_t (B,N,1)  centers_t/scales_t/weights_t
  *   (B,N,2)  clas_t (B,N,C) — N anchors in the reference order (stride 32,16,8; cell; anchor)
- *   losses: device (4,B): obj, center, scale, cls per sample. */
+ *   losses: device (4,B): obj, center, scale, cls per sample.
+ *   M <= 4096 (more is an error return): the loss kernel stages one image's gt rows in LDS, 16 M bytes next to its 64
+ *   static ones — 65,600 bytes at the cap, inside the 160 KiB a workgroup may hold on gfx950 (granted there:
+ *   tests/test_gpu_loss_cells.py runs the cap and cap + 1). */
 int vy_net_train_forward(vy_net* net, const float* x, const float* gt_boxes, int32_t M,
                          const float* obj_t, const float* centers_t, const float* scales_t,
                          const float* weights_t, const float* clas_t, float* losses, void* stream);

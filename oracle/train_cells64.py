@@ -432,6 +432,250 @@ def check_head_grad(name, got, want, exempt, ulps=4):
                   "%d exempt (IoU within 1e-6 of the threshold)" % int(np.count_nonzero(exempt)))
 
 
+# ---------------------------------------------------------------- loss values (loss_kernel, loss_reduce_kernel)
+# Rounding counts of one anchor's term, read off train_kernels.hip (bce_logits, loss_kernel) with -ffp-contract=off, in
+# units of u times the term's absolute sum A.  vy_expf is pinned to 2 ulp = 4u relative (test_vy_math_against_libm);
+# vy_logf on [1, 2], the only arguments the loss gives it, is within 5u relative by its code (m - 1 exact, m + 1, the
+# divide, s^2, the last fma of the polynomial, p * s: 5 roundings that reach the result at full weight, the earlier
+# polynomial steps are damped by s^2 <= 0.03; fe * ln2 is 0 or one exact-constant fma pair below log 2) —
+# tests/test_train_cells64_sensitivity.py holds both figures on a dense grid.
+#   BCE term ((relu(x) - x z) + log(1 + exp(-|x|))) * mask, A = (relu(x) + |x z| + log 2) * mask:
+#     on relu(x) + |x z|:  x*z (1), the subtraction (1)                                            = 2
+#     on log 2:            exp, 4u e / (1 + e) <= 2u = 2.89 u log 2; the add 1 + e, u = 1.45 u log 2;
+#                          vy_logf 5u log(1 + e) <= 5 u log 2                                      <= 9.34
+#     on the whole:        the outer add (1), the product with the mask (1)                        = 2
+#     -> 12 (the log 2 part is the worst).  log(1 + e) -> 0 where 1 + e rounds to 1 and e -> 0 at the exp cut-off drop
+#     at most u, far inside u log 2.
+#   objectness: the mask is 1, 0 or obj_t itself                                                   T = 12
+#   centre:     mask = weights_t * obj_t (1), two terms added (1)                                  T = 14
+#   class:      mask = 1 * obj_t (exact), C terms accumulated in the thread (C - 1)                T = 11 + C
+#   scale term |raw - t| * w, A = (|raw| + |t|) * w: the difference (1), w = weights_t * obj_t (1), the product (1),
+#               two terms added (1)                                                                T = 4
+# The label-smoothed class target is formed in fp32 exactly as the kernel forms it (one correctly rounded divide and
+# subtraction of constants), so both sides hold the same z.
+TREE_LEVELS = 9  # 256-term block tree: six shuffles, two adds over the four waves; and the final cast of the double sum
+
+
+def loss_counts(num_class):
+    """(objectness, centre, scale, class) rounding counts T of one anchor's term (derivation above)"""
+    return (12, 14, 4, 11 + num_class)
+
+
+def bce64(x, z):
+    """the true relu(x) - x z + log1p(exp(-|x|)) in float64"""
+    x, z = np.asarray(x, np.float64), np.asarray(z, np.float64)
+    return np.maximum(x, 0.0) - x * z + np.log1p(np.exp(-np.abs(x)))
+
+
+def _bce_abs(x, z):
+    x, z = np.asarray(x, np.float64), np.asarray(z, np.float64)
+    return np.maximum(x, 0.0) + np.abs(x * z) + np.log(2.0)
+
+
+def smoothed_class_targets(clas_t, num_class, label_smooth):
+    """class targets as loss_kernel forms them, in fp32: smooth = min(1/C, 1/40); 1 -> 1 - smooth, 0 -> smooth, -1 kept"""
+    ct = np.asarray(clas_t, F32)
+    if not label_smooth:
+        return ct
+    sm = min(F32(1.0) / F32(num_class), F32(1.0) / F32(40.0))
+    ct = np.where(ct > F32(0.5), (ct - sm).astype(F32), ct)
+    return np.where((ct < F32(-0.5)) | (ct > F32(0.5)), ct, sm).astype(F32)
+
+
+def loss_terms64(num_class, preds, gt_boxes, targets, ignore_iou_thresh=0.7, label_smooth=False, near=1e-6):
+    """Per-anchor float64 terms of the four losses on the device's own raw predictions (net.read_head(i)), targets and
+    gt_boxes.  dict: terms / absum (4, B, N) in the order objectness, centre, scale, class (absum: a BCE term's
+    (relu(x) + |x z| + log 2) mask, a scale term's (|raw| + |target|) weight); decision (B, N): 1 positive, -1 ignored, 0
+    negative; exempt (B, N): not positive and the max IoU within `near` of the threshold without being the fp32 threshold
+    itself; exempt_term (B, N): what the
+    objectness term of an exempt anchor can be at most (its value as a plain negative; 0 as an ignored one);
+    fractional (B, N): positives with obj_t < 1; counts: loss_counts.  The ignore decision is O.batch_iou's, in fp32 on
+    the oracle's fp32 decode, as head_grads takes it; everything after it is float64 on the fp32 inputs."""
+    from .yolo3_train_oracle import OracleYolo3Train
+    f64 = np.float64
+    orc = OracleYolo3Train(num_class, {}, ignore_iou_thresh=ignore_iou_thresh, label_smooth=label_smooth)
+    obj_t, centers_t, scales_t, weights_t, clas_t = [np.asarray(t, F32) for t in targets]
+    with np.errstate(invalid="ignore", over="ignore"):  # a saturated rw / rh decodes to an infinite box
+        pr = orc.split_preds(preds)
+        ious = O.batch_iou(pr["box"], np.asarray(gt_boxes, F32))
+    ious_max = np.fmax.reduce(ious, axis=-1, keepdims=True, initial=F32(-1.0))  # fmaxf from best = -1: a NaN never wins
+    pos = obj_t > 0
+    ign = ~pos & (ious_max > F32(ignore_iou_thresh))
+    # exempt as head_grads exempts, but for an IoU that IS the fp32 threshold bit for bit: both sides evaluate the same
+    # pinned fp32 sequence on bit-equal boxes, and that value is the one point where `>` and `>=` part
+    exempt = ~pos & (np.abs(ious_max.astype(f64) - ignore_iou_thresh) < near) & (ious_max != F32(ignore_iou_thresh))
+    o64 = np.where(pos, obj_t, 0).astype(f64)
+    hard = np.where(pos, 1.0, np.where(ign, -1.0, 0.0))
+    omask = np.where(pos, o64, np.where(ign, 0.0, 1.0))
+    w = weights_t.astype(f64) * o64
+    ct = smoothed_class_targets(clas_t, num_class, label_smooth)
+    cm = np.where(ct >= 0, 1.0, 0.0) * o64
+    xo, xy, wh, xc = [pr[k].astype(f64) for k in ("obj", "xy", "wh", "cls")]
+    ct64, st64 = centers_t.astype(f64), scales_t.astype(f64)
+    terms = np.stack([(bce64(xo, hard) * omask).sum(-1), (bce64(xy, ct64) * w).sum(-1),
+                      (np.abs(wh - st64) * w).sum(-1), (bce64(xc, ct) * cm).sum(-1)])
+    absum = np.stack([(_bce_abs(xo, hard) * omask).sum(-1), (_bce_abs(xy, ct64) * w).sum(-1),
+                      ((np.abs(wh) + np.abs(st64)) * w).sum(-1), (_bce_abs(xc, ct) * cm).sum(-1)])
+    return dict(terms=terms, absum=absum, decision=np.where(pos, 1, np.where(ign, -1, 0))[..., 0].astype(np.int8),
+                exempt=exempt[..., 0], exempt_term=np.where(exempt, bce64(xo, 0.0), 0.0)[..., 0],
+                fractional=(pos & (obj_t < 1))[..., 0], counts=loss_counts(num_class), ious_max=ious_max[..., 0])
+
+
+LOSS_NAMES = ("objectness", "centre", "scale", "class")
+
+
+def check_losses(name, got, terms):
+    """The (4, B) loss values against the float64 sums of the per-anchor terms: per image and per loss
+        |got - sum terms| <= gamma(T + 9) sum A_i + sum_exempt |term|,
+    T = loss_counts (one term's roundings), 9 = TREE_LEVELS: every term passes the eight add levels of its block's
+    256-term tree, and the sum over the blocks, taken in double, is rounded once by the final cast.  A NaN or an
+    infinite loss fails (its ratio is NaN / inf).  One Result per loss, the worst image."""
+    got = np.asarray(got, np.float64)
+    out = []
+    for q in range(4):
+        want = terms["terms"][q].sum(axis=-1)
+        absum = terms["absum"][q].sum(axis=-1)
+        n = terms["counts"][q] + TREE_LEVELS
+        allow = terms["exempt_term"].sum(axis=-1) if q == 0 else 0.0
+        err = np.abs(got[q] - want)
+        bound = gamma(n) * absum + allow
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where(err == 0, 0.0, err / bound)
+            h = np.where(err == 0, 0.0, err / (U * np.sqrt(n) * absum + allow))
+        bad = ~np.isfinite(got[q])
+        r, h = np.where(bad, np.inf, r), np.where(bad, np.inf, h)
+        out.append(Result("loss value", "%s %s" % (name, LOSS_NAMES[q]), r.max(initial=0.0), h.max(initial=0.0),
+                          err.max(initial=0.0), np.abs(want).max(initial=0.0)))
+    return out
+
+
+def loss_census(terms):
+    """how many anchors took each branch of the decision, how many are exempt, how many positives are fractional"""
+    d = terms["decision"]
+    return dict(positive=int(np.count_nonzero(d == 1)), ignored=int(np.count_nonzero(d == -1)),
+                negative=int(np.count_nonzero(d == 0)), exempt=int(np.count_nonzero(terms["exempt"])),
+                fractional=int(np.count_nonzero(terms["fractional"])))
+
+
+# ---------------------------------------------------------------- raw predictions (raw_preds_kernel)
+# Rounding count of a decoded box corner, from raw_preds_kernel: the centre (sigmoid(r) + x) * stride — exp 4u of e,
+# 1 + e (1), the divide (1): sigmoid within 6u; the add of the cell offset (1); the stride is a power of two — is within
+# 7u |centre|; the half extent exp(r) * anchor / 2 — exp 4u, the product (1), the halving exact — within 5u |half|;
+# the corner centre -+ half adds one rounding of the result: 8u (|centre| + |half extent|) bounds both.
+T_BOX = 8
+
+
+def exp64_cut(x):
+    """exp in float64 with vy_expf's cut-offs, which are part of the operation (vy_math.h): +inf above 88.5, 0 below -86"""
+    x = np.asarray(x, np.float64)
+    with np.errstate(over="ignore"):
+        return np.where(x > 88.5, np.inf, np.where(x >= -86.0, np.exp(np.clip(x, -100.0, 100.0)), 0.0))
+
+
+def raw_layout(preds, num_class):
+    """the head planes (B, A*P, H, W), strides 32, 16, 8, as the (B, N, P) rows raw_preds_kernel walks: scale -> cell ->
+    anchor; and each row's cell x, y, stride and anchor size"""
+    A, P = 3, 5 + num_class
+    rows, geo = [], []
+    for i, pred in enumerate(preds):
+        B, _, H, W = pred.shape
+        rows.append(pred.reshape(B, A, P, H * W).transpose(0, 3, 1, 2).reshape(B, H * W * A, P))
+        cell = np.repeat(np.arange(H * W), A)
+        anc = np.tile(np.array(O.ANCHORS[::-1][i], np.float64).reshape(A, 2), (H * W, 1))
+        geo.append(np.stack([cell % W, cell // W, np.full(cell.shape, float(O.STRIDES[::-1][i])), anc[:, 0], anc[:, 1]], -1))
+    return np.concatenate(rows, 1), np.concatenate(geo, 0)
+
+
+def check_raw_preds(name, preds, box, centers, scales, objness, class_pred):
+    """The train-mode tensors of raw_preds_kernel against the head planes `preds` of the same forward: the four raw
+    tensors bit-equal to the planes in the stride 32 -> 16 -> 8, cell, anchor order; every box corner within
+    gamma(T_BOX) (|centre| + |half extent|) of a float64 decode of the device's raw values (exp64_cut); an infinite
+    extent (the exp's cut-off, or exp(r) * anchor beyond fp32) infinite with the same sign on both sides; no NaN."""
+    C = class_pred.shape[-1]
+    rows, geo = raw_layout([np.asarray(p, F32) for p in preds], C)
+    bits = lambda a: np.ascontiguousarray(a, F32).view(np.int32)  # noqa: E731
+    out = []
+    for label, got, want in (("centers", centers, rows[..., 0:2]), ("scales", scales, rows[..., 2:4]),
+                             ("objness", objness, rows[..., 4:5]), ("class_pred", class_pred, rows[..., 5:])):
+        got = np.asarray(got, F32)
+        if got.shape != want.shape:
+            out.append(Result("raw predictions", "%s %s" % (name, label), np.inf, 0.0, detail="shape %s" % (got.shape,)))
+            continue
+        out.append(_exact("raw predictions", "%s %s" % (name, label), bits(got), bits(want)))
+    r64 = rows.astype(np.float64)
+    gx, gy, stride, aw, ah = [geo[:, i][None] for i in range(5)]
+    cx = (1.0 / (1.0 + exp64_cut(-r64[..., 0])) + gx) * stride
+    cy = (1.0 / (1.0 + exp64_cut(-r64[..., 1])) + gy) * stride
+
+    def half(r, anchor):
+        """the extent exp(r) * anchor overflows fp32 before it is halved: beyond FLT_MAX it is infinite on the device; within
+        the exp's 4u + 1 of FLT_MAX either is right (second value: that band)"""
+        ext, top = exp64_cut(r) * anchor, float(np.finfo(F32).max)
+        edge = np.abs(ext / top - 1.0) <= gamma(5)
+        return np.where(ext > top, np.inf, ext) / 2.0, edge
+
+    (hw, ex), (hh, ey) = half(r64[..., 2], aw), half(r64[..., 3], ah)
+    want = np.stack([cx - hw, cy - hh, cx + hw, cy + hh], -1)
+    scale = np.stack([np.abs(cx) + hw, np.abs(cy) + hh] * 2, -1)
+    edge = np.stack([ex, ey] * 2, -1)
+    got = np.asarray(box, np.float64)
+    inf = np.isinf(want)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        err = np.where(inf | edge, 0.0, np.abs(got - want))
+        ratio = np.where(err == 0, 0.0, err / (gamma(T_BOX) * scale))
+    bad = (inf & ~edge & (got != want)) | np.isnan(got)
+    ratio = np.where(bad, np.inf, ratio)
+    out.append(Result("decoded boxes", name, ratio.max(initial=0.0), ratio.max(initial=0.0) * np.sqrt(T_BOX),
+                      np.nanmax(err, initial=0.0), np.abs(want[~inf]).max(initial=0.0),
+                      "%d infinite corners" % int(np.count_nonzero(inf))))
+    return out
+
+
+# ---------------------------------------------------------------- SGD (sgd_kernel)
+# One element of sgd_kernel: gg = g * rescale + wd_k * w; m' = momentum * m - lr_k * gg; w' = w + m', with
+# lr_k = lr * lr_mult and wd_k = wd * wd_mult formed in fp32 in the kernel.  Roundings on the way to m', per addend:
+#   wd_k w:  wd_k (1), the product (1), the add to gg (1), lr_k (1), lr_k * gg (1), the subtraction (1)   = 6
+#   g r:     the product (1), the add (1), lr_k (1), lr_k * gg (1), the subtraction (1)                    = 5
+#   mu m:    the product (1), the subtraction (1)                                                          = 2
+# so c = 6 covers every addend.  The build pins -ffp-contract=off; had the compiler fused g * rescale + (wd_k w) or
+# mu m - (lr_k gg) into fmas, each fusion would drop one rounding, so the count holds either way.  lr, momentum, wd
+# and rescale reach the kernel as fp32 arguments: the reference takes their fp32 values.
+C_SGD = 6
+
+
+class SgdRef:
+    """Float64 carrier of one parameter's momentum across steps: m_0 = 0, b_0 = 0;
+        m_t = mu m_{t-1} - lr_k (g r + wd_k w_{t-1}),   w_{t-1} the device's own bits,
+        b_t = mu b_{t-1} + gamma(C_SGD) (mu |m_{t-1}| + lr_k (|g r| + |wd_k w_{t-1}|))
+    bounds the device momentum's distance from m_t, and the step must satisfy |w_t - (w_{t-1} + m_t)| <= b_t + u |w_t|
+    (the last add is rounded once).  A disabled step (grad_req 'null') leaves m, b and w as they are: bit-equal.
+    lr_mult = 0 moves m only by mu m, and from m = 0 the parameter stays bit-equal."""
+
+    def __init__(self, shape):
+        self.m = np.zeros(shape, np.float64)
+        self.b = np.zeros(shape, np.float64)
+
+    def step(self, name, w_before, g, w_after, lr, momentum, wd, rescale, lr_mult, wd_mult, enabled):
+        if not enabled:
+            return _exact("sgd frozen", name, w_after, w_before)
+        f = lambda v: np.float64(F32(v))  # noqa: E731
+        mu, lr_k, wd_k, r = f(momentum), f(lr) * f(lr_mult), f(wd) * f(wd_mult), f(rescale)
+        w0, g64 = w_before.astype(np.float64), g.astype(np.float64)
+        m_new = mu * self.m - lr_k * (g64 * r + wd_k * w0)
+        self.b = mu * self.b + gamma(C_SGD) * (mu * np.abs(self.m) + lr_k * (np.abs(g64 * r) + np.abs(wd_k * w0)))
+        self.m = m_new
+        w1 = w_after.astype(np.float64)
+        err = np.abs(w1 - (w0 + m_new))
+        bound = self.b + U * np.abs(w1)
+        if lr_mult == 0 and not np.any(m_new):
+            return _exact("sgd lr_mult 0", name, w_after, w_before)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(err == 0, 0.0, err / bound)
+        ratio = np.where(np.isfinite(w1), ratio, np.inf)
+        return Result("sgd step", name, ratio.max(initial=0.0), ratio.max(initial=0.0), err.max(initial=0.0),
+                      np.abs(m_new).max(initial=0.0))
+
+
 def summarize(results):
     """per kernel class: the worst err/bound and err/(u sqrt(n) S)"""
     by = {}

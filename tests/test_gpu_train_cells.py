@@ -7,7 +7,10 @@ forward conv (bit-equal, first and last image), batch statistics (<= 1 ulp), for
 backward (dgamma, dbeta, dz: per element, gamma_d from the plan's chunking), weight gradients (output channels 0,
 Cout-1 and 6 random ones; gamma from the split-K plan), every producer's data gradient (first and last image, all
 channels, summed over its consumers plus the skip addend), prediction-conv bias gradients, the stem's weight
-gradient, d(loss)/d(pred) (a few ulp) and the zero borders of every z / dz / gradient / input plane.  Large cells are
+gradient, d(loss)/d(pred) (a few ulp), the four loss values per image (R.check_losses: gamma(T + 9) times the absolute
+sum of the per-anchor float64 terms; the census of the ignore decision is printed) and the zero borders of every z / dz /
+gradient / input plane.  The constructed branches of the loss kernel, the raw predictions and the SGD step are
+tests/test_gpu_loss_cells.py's.  Large cells are
 checked in channel blocks so that the host never holds more than a few float64 copies of one block.
 
 One walker serves all three: a builder makes the net, runs the step and names the graph (R.graph).  A cell runs on
@@ -58,13 +61,14 @@ def _inputs(C, B, H, W, seed):
 
 
 def _record(net, cells, inputs, gt_boxes, tg):
-    """One recorded step; z of every BatchNorm cell is tapped between the forward and the backward."""
+    """One recorded step; z of every BatchNorm cell is tapped between the forward and the backward.  Returns the taps and
+    the four (B,) loss tensors as one (4, B) array."""
     from videoyolo_amd import autograd
     with autograd.record():
         losses = net(*inputs, gt_boxes, *tg)
         z_fwd = {c["name"]: net.read_train_tap(c["name"], "z").clone() for c in cells if c.get("bn")}
         autograd.backward([losses[0] + losses[1] + losses[2] + losses[3]])
-    return z_fwd
+    return z_fwd, np.stack([_host(l) for l in losses])
 
 
 def _step(C, B, H, W, seed=7):
@@ -78,8 +82,8 @@ def _step(C, B, H, W, seed=7):
     net.set_parameters(params)
     net.collect_params().reset_ctx("cuda:0")
     cells = R.graph(C)
-    z_fwd = _record(net, cells, (x,), gt_boxes, tg)
-    return dict(net=net, params=params, cells=cells, frames=x, gt_boxes=gt_boxes, tg=tg, z_fwd=z_fwd, C=C, B=B, k=1)
+    z_fwd, losses = _record(net, cells, (x,), gt_boxes, tg)
+    return dict(net=net, params=params, cells=cells, frames=x, gt_boxes=gt_boxes, tg=tg, z_fwd=z_fwd, losses=losses, C=C, B=B, k=1)
 
 
 def _step_window(join, k, B, H, W, C=WINDOW_CLASSES, seed=7):
@@ -95,9 +99,9 @@ def _step_window(join, k, B, H, W, C=WINDOW_CLASSES, seed=7):
     net.set_parameters(params)
     net.collect_params().reset_ctx("cuda:0")
     cells = R.graph(C, k=k)
-    z_fwd = _record(net, cells, (x,), gt_boxes, tg)
+    z_fwd, losses = _record(net, cells, (x,), gt_boxes, tg)
     return dict(net=net, params=params, cells=cells, frames=x.reshape((B * k, 3, H, W)), gt_boxes=gt_boxes, tg=tg,
-                z_fwd=z_fwd, C=C, B=B, k=k, join=join)
+                z_fwd=z_fwd, losses=losses, C=C, B=B, k=k, join=join)
 
 
 def _step_heads(C, B, H, W, seed=7):
@@ -118,12 +122,12 @@ def _step_heads(C, B, H, W, seed=7):
     net.set_parameters({n: v for n, v in params.items() if not n.startswith("stages.")})
     net.collect_params().reset_ctx("cuda:0")
     cells = R.graph(C, heads_only=True)
-    z_fwd = _record(net, cells, routes, gt_boxes, tg)
+    z_fwd, losses = _record(net, cells, routes, gt_boxes, tg)
     torch.cuda.synchronize()
     res = [R._exact("caller's route", "route.%d" % i, _host(r), b0) for i, (r, b0) in enumerate(zip(routes, before))]
     del full
-    return dict(net=net, params=params, cells=cells, frames=None, gt_boxes=gt_boxes, tg=tg, z_fwd=z_fwd, C=C, B=B, k=1,
-                routes={"route.%d" % i: b0 for i, b0 in enumerate(before)}, res=res)
+    return dict(net=net, params=params, cells=cells, frames=None, gt_boxes=gt_boxes, tg=tg, z_fwd=z_fwd, losses=losses, C=C,
+                B=B, k=1, routes={"route.%d" % i: b0 for i, b0 in enumerate(before)}, res=res)
 
 
 def _blocks(C, per_channel):
@@ -137,7 +141,8 @@ def _sel(B, fm):
 
 
 def _walk(st):
-    """Every check of one recorded step `st` (a builder's dict) -> (results, pool counts {route: (wins, ties, clips counted)})."""
+    """Every check of one recorded step `st` (a builder's dict) -> (results, pool counts {route: (wins, ties, clips counted)}).
+    The loss census (R.loss_census) of the step is left in st["census"]."""
     from oracle import train_cells64 as R
     net, params, cells, z_fwd = st["net"], st["params"], st["cells"], st["z_fwd"]
     C, B, k, join = st["C"], st["B"], st["k"], st.get("join")
@@ -263,18 +268,25 @@ def _walk(st):
 
     # d(loss)/d(pred) on the device's own raw predictions
     preds = [_host(net.read_head(i)) for i in range(3)]
-    want, exempt = R.head_grads(C, preds, st["gt_boxes"], [np.asarray(t) for t in st["tg"]])
+    opts = dict(ignore_iou_thresh=st.get("thresh", 0.7), label_smooth=st.get("label_smooth", False))
+    targets = [np.asarray(t) for t in st["tg"]]
+    want, exempt = R.head_grads(C, preds, st["gt_boxes"], targets, **opts)
     for i in range(3):
         name = "yolo_outputs.%d.prediction" % i
         res.append(R.check_head_grad(name, R.interior(tap(name, "grad")), want[i], exempt[i]))
+    # the four loss values, per image, against the float64 sums of the per-anchor terms
+    terms = R.loss_terms64(C, preds, st["gt_boxes"], targets, **opts)
+    res += R.check_losses("losses", st["losses"], terms)
+    st["census"], st["terms"] = R.loss_census(terms), terms
     return res, pools
 
 
 def _check_net(C, B, H, W):
-    return _walk(_step(C, B, H, W))[0]
+    st = _step(C, B, H, W)
+    return _walk(st)[0], st["census"]
 
 
-def _report(title, res, t0, pools=None):
+def _report(title, res, t0, pools=None, census=None):
     from oracle import train_cells64 as R
     print("\n%s: %d checks in %.0f s, peak host RSS %.1f GiB"
           % (title, len(res), time.time() - t0, resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2.0 ** 20))
@@ -284,8 +296,11 @@ def _report(title, res, t0, pools=None):
     for name, (wins, ties, scope) in sorted((pools or {}).items()):
         print("  %s, %s: elements won by frame t alone %s, elements with tied frames %d" % (name, scope, wins, ties))
     for r in res:
-        if r.kind == "loss gradient":
+        if r.kind in ("loss gradient", "loss value"):
             print("  ", r)
+    if census is not None:
+        print("   anchors by decision: %(positive)d positive (%(fractional)d fractional), %(ignored)d ignored, %(negative)d "
+              "negative; %(exempt)d exempt" % census)
     bad = [r for r in res if not r.ok]
     assert not bad, "\n".join(repr(r) for r in bad[:40])
 
@@ -293,15 +308,17 @@ def _report(title, res, t0, pools=None):
 @pytest.mark.parametrize("C,B,H,W", CASES)
 def test_every_training_cell_against_float64(C, B, H, W):
     t0 = time.time()
-    res = _check_net(C, B, H, W)
-    _report("%dx%d batch %d, %d classes" % (H, W, B, C), res, t0)
+    res, census = _check_net(C, B, H, W)
+    _report("%dx%d batch %d, %d classes" % (H, W, B, C), res, t0, census=census)
 
 
 @pytest.mark.parametrize("join,k,B,H,W", WINDOW_CASES)
 def test_every_window_cell_against_float64(join, k, B, H, W):
     t0 = time.time()
-    res, pools = _walk(_step_window(join, k, B, H, W))
-    _report("window %s k=%d, %d clips of %dx%d, %d classes" % (join, k, B, H, W, WINDOW_CLASSES), res, t0, pools)
+    st = _step_window(join, k, B, H, W)
+    res, pools = _walk(st)
+    _report("window %s k=%d, %d clips of %dx%d, %d classes" % (join, k, B, H, W, WINDOW_CLASSES), res, t0, pools,
+            st["census"])
     # not vacuous: all three routes were pooled and back-propagated; with max, every frame index of the checked clips
     # wins elements of every route on its own (a gradient sent to the wrong frame, or to all of them, cannot pass)
     assert sorted(pools) == ["pool.0", "pool.1", "pool.2"], sorted(pools)
@@ -313,7 +330,8 @@ def test_every_window_cell_against_float64(join, k, B, H, W):
 @pytest.mark.parametrize("C,B,H,W", HEADS_CASES)
 def test_every_heads_cell_against_float64(C, B, H, W):
     t0 = time.time()
-    res, _ = _walk(_step_heads(C, B, H, W))
-    _report("heads net, routes of %dx%d batch %d, %d classes" % (H, W, B, C), res, t0)
+    st = _step_heads(C, B, H, W)
+    res, _ = _walk(st)
+    _report("heads net, routes of %dx%d batch %d, %d classes" % (H, W, B, C), res, t0, census=st["census"])
     views = [r for r in res if r.kind == "route view"]
     assert len(views) == 3 and len([r for r in res if r.kind == "caller's route"]) == 3

@@ -12,7 +12,14 @@ elements of the clips tie and some do not.  Eight more mutations must each fail 
 
 Two more planted bugs are the ways a broken stream-K hand-off would show: a data gradient whose chain misses one
 32-channel k-step of one tap on one 64x64 tile (check_dgrad), and one tile's rows missing from the per-tile statistics
-sums (check_stats)."""
+sums (check_stats).
+
+The two ends of the step get the same treatment: loss_kernel + loss_reduce_kernel, raw_preds_kernel and sgd_kernel are
+restated in fp32 numpy (vy_math's exp / log, the 256-lane butterfly, the blocks summed in double; four momentum steps
+with a multiplier change) and must pass check_losses / check_head_grad / check_raw_preds / SgdRef; nine loss faults, one
+decode fault and four SGD faults must each fail one with ratio > 1.  The accuracies of vy_expf / vy_logf that the loss
+terms' rounding counts rest on are held on dense grids, and the census conditions of every constructed case of
+tests/test_gpu_loss_cells.py (tests/loss_cases.py) are settled here on the CPU oracle's train-mode heads forward."""
 import numpy as np
 import pytest
 import torch
@@ -403,3 +410,263 @@ def test_fmaf_emulation_is_exact():
         exact = Fraction(float(a[i])) * Fraction(float(b[i])) + Fraction(float(c[i]))
         want = np.float32(float(exact))  # float(Fraction) rounds once to double; exactness checked below
         assert got[i] == want or abs(Fraction(float(got[i])) - exact) <= abs(Fraction(float(want)) - exact), i
+
+
+# ---------------------------------------------------------------- the loss kernels and the SGD kernel
+# The rounding counts of the loss terms (oracle/train_cells64.py) rest on two accuracies of include/vy_math.h on the
+# arguments the loss gives them; both are held here on dense grids.
+def test_vy_math_accuracies_the_loss_counts_rest_on():
+    from oracle import yolo3_oracle as O
+    x = -np.concatenate([np.linspace(0, 86, 400001), np.abs(np.random.default_rng(0).standard_normal(200000)) * 3]).astype(F32)
+    e, true = O.exp(x).astype(np.float64), np.exp(x.astype(np.float64))
+    assert (np.abs(e - true) / true).max() <= 4 * R.U                       # vy_expf: 2 ulp
+    y = np.linspace(1, 2, 400001).astype(F32)[1:]
+    lg, true = O.log(y).astype(np.float64), np.log(y.astype(np.float64))
+    assert (np.abs(lg - true) / true).max() <= 5 * R.U                      # vy_logf on (1, 2]: five roundings
+    assert O.log(np.ones(1, F32))[0] == 0 and O.exp(np.array([-86.5, 88.6], F32)).tolist() == [0.0, np.inf]
+
+
+import loss_cases as L  # noqa: E402
+
+TOY = dict(C=80, smooth=True, thresh=0.5, M=16, valid=12, B=2, H=128, W=128, seed=21)   # N = 1008: four blocks, tail 240
+LOSS_MUTATIONS = ["anchor_term_dropped", "above_threshold_anchor_taken_as_negative", "ge_instead_of_gt_at_the_threshold",
+                  "smoothing_constant_1_40_at_80_classes", "omask_not_scaled_by_fractional_obj_t",
+                  "box_weights_not_scaled_by_fractional_obj_t", "zero_scale_difference_given_gradient_plus_w",
+                  "tail_lanes_read_the_last_anchor_again", "loss_reduce_skips_the_last_block",
+                  "slot_1_anchor_decoded_with_slot_2_size"]
+
+
+def _toy_heads(case):
+    """random head planes with loss_cases.SATURATE's values; one stride-8 anchor of the untouched slot has raw box
+    predictions 0, so its box is exact: centre 8 x + 4, sides 33 x 23"""
+    rng = np.random.default_rng(case["seed"])
+    P = 5 + case["C"]
+    preds = []
+    for i, s in enumerate((32, 16, 8)):
+        p = (rng.standard_normal((case["B"], 3 * P, case["H"] // s, case["W"] // s)) * 1.5).astype(F32)
+        for (si, slot), chans in L.SATURATE.items():
+            if si == i:
+                for ch, v in chans.items():
+                    p[:, slot * P + ch] += F32(v)
+        preds.append(p)
+    preds[2][0, 2 * P:2 * P + 4, 5, 7] = 0
+    return preds
+
+
+def _plane_rows(rows, preds, C):
+    """(B, N, P) rows back into the head-plane layout"""
+    out, n0 = [], 0
+    for p in preds:
+        B, _, H, W = p.shape
+        n1 = n0 + 3 * H * W
+        out.append(np.ascontiguousarray(rows[:, n0:n1].reshape(B, H * W, 3 * (5 + C)).transpose(0, 2, 1).reshape(p.shape)))
+        n0 = n1
+    return out
+
+
+def dev_loss(case, preds, gt, tg, made, mut=None):
+    """loss_kernel + loss_reduce_kernel in fp32 numpy (vy_math's exp / log through the oracle library): per-anchor terms
+    in the kernel's operation order, the 256-lane butterfly per block, the blocks summed in double -> (losses (4, B),
+    d(loss)/d(pred) planes)"""
+    from oracle import yolo3_oracle as O
+    from oracle.yolo3_train_oracle import OracleYolo3Train
+    C, B, thresh = case["C"], case["B"], F32(case["thresh"])
+    rows, _ = R.raw_layout(preds, C)
+    N = rows.shape[1]
+    obj_t, ctr_t, scl_t, wgt_t, cls_t = [np.asarray(t, F32) for t in tg]
+    with np.errstate(over="ignore", invalid="ignore"):
+        box = OracleYolo3Train(C, {}).split_preds(preds)["box"]
+        best = np.fmax.reduce(O.batch_iou(box, gt), axis=-1, initial=F32(-1))
+    pos = obj_t[..., 0] > 0
+    ign = (best >= thresh) if mut == "ge_instead_of_gt_at_the_threshold" else (best > thresh)
+    if mut == "above_threshold_anchor_taken_as_negative":
+        b, n = next((b, n) for b, n, k, _ in made if k == "above")
+        ign[b, n] = False
+    objness = np.where(pos, obj_t[..., 0], np.where(ign, F32(-1), F32(0))).astype(F32)
+
+    def bce(x, z):
+        return ((np.maximum(x, F32(0)) - x * z).astype(F32) + O.log((F32(1) + O.exp(-np.abs(x))).astype(F32))).astype(F32)
+
+    def sig(x):
+        return O.sigmoid(np.ascontiguousarray(x, F32))
+
+    hard = np.where(objness > 0, F32(1), objness)
+    omask = np.where(objness > 0, F32(1) if mut == "omask_not_scaled_by_fractional_obj_t" else objness,
+                     (objness >= 0).astype(F32)).astype(F32)
+    ro = rows[..., 4]
+    t = np.zeros((4, B, N), F32)
+    d = np.zeros_like(rows)
+    t[0] = bce(ro, hard) * omask
+    d[..., 4] = (sig(ro) - hard) * omask
+    scale = F32(1) if mut == "box_weights_not_scaled_by_fractional_obj_t" else objness
+    w = np.where(pos[..., None], wgt_t * scale[..., None], F32(0)).astype(F32)
+    l0, l1 = bce(rows[..., 0], ctr_t[..., 0]) * w[..., 0], bce(rows[..., 1], ctr_t[..., 1]) * w[..., 1]
+    t[1] = (l0.astype(F32) + l1.astype(F32)).astype(F32)
+    d[..., 0:2] = (sig(rows[..., 0:2]) - ctr_t) * w
+    diff = (rows[..., 2:4] - scl_t).astype(F32)
+    t[2] = ((np.abs(diff[..., 0]) * w[..., 0]).astype(F32) + (np.abs(diff[..., 1]) * w[..., 1]).astype(F32)).astype(F32)
+    zero = w if mut == "zero_scale_difference_given_gradient_plus_w" else F32(0)
+    d[..., 2:4] = np.where(diff > 0, w, np.where(diff < 0, -w, zero))
+    sm = F32(1) / F32(40) if mut == "smoothing_constant_1_40_at_80_classes" else min(F32(1) / F32(C), F32(1) / F32(40))
+    ct = cls_t
+    if case["smooth"]:
+        ct = np.where(ct > F32(0.5), (ct - sm).astype(F32), ct)
+        ct = np.where((ct < F32(-0.5)) | (ct > F32(0.5)), ct, sm).astype(F32)
+    cm = np.where(pos[..., None], (ct >= 0).astype(F32) * objness[..., None], F32(0)).astype(F32)
+    lc = (bce(rows[..., 5:], ct) * cm).astype(F32)
+    acc = np.zeros((B, N), F32)
+    for c in range(C):
+        acc = (acc + lc[..., c]).astype(F32)
+    t[3] = acc
+    d[..., 5:] = (sig(rows[..., 5:]) - ct) * cm
+    if mut == "anchor_term_dropped":  # a plain negative of the untouched slot, in the third block
+        n = next(n for n in range(512, 768) if objness[1, n] == 0 and (n - 240) % 3 == 2)
+        t[:, 1, n] = 0
+    # the block tree
+    nb = -(-N // 256)
+    lanes = np.zeros((4, B, nb * 256), F32)
+    lanes[..., :N] = t
+    if mut == "tail_lanes_read_the_last_anchor_again":
+        lanes[..., N:] = t[..., N - 1:N]
+    v = lanes.reshape(4, B, nb, 4, 64)
+    idx = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        v = (v + v[..., idx ^ off]).astype(F32)
+    r = v[..., 0]
+    part = ((r[..., 0] + r[..., 1]).astype(F32) + (r[..., 2] + r[..., 3]).astype(F32)).astype(F32)  # (4, B, nb)
+    if mut == "loss_reduce_skips_the_last_block":
+        part = part[..., :-1]
+    return part.astype(np.float64).sum(-1).astype(F32), _plane_rows(d, preds, C)
+
+
+def dev_raw_preds(preds, C, mut=None):
+    """raw_preds_kernel in fp32 numpy"""
+    from oracle import yolo3_oracle as O
+    rows, geo = R.raw_layout(preds, C)
+    gx, gy, stride, aw, ah = [geo[:, i].astype(F32)[None] for i in range(5)]
+    if mut == "slot_1_anchor_decoded_with_slot_2_size":
+        aw = aw.copy()
+        aw[0, 1::3] = aw[0, 2::3]
+    sg = lambda v: O.sigmoid(np.ascontiguousarray(v, F32))  # noqa: E731
+    ex = lambda v: O.exp(np.ascontiguousarray(v, F32))  # noqa: E731
+    with np.errstate(over="ignore"):
+        cx, cy = ((sg(rows[..., 0]) + gx).astype(F32) * stride).astype(F32), ((sg(rows[..., 1]) + gy).astype(F32) * stride).astype(F32)
+        hw, hh = ((ex(rows[..., 2]) * aw).astype(F32) / F32(2)).astype(F32), ((ex(rows[..., 3]) * ah).astype(F32) / F32(2)).astype(F32)
+        box = np.stack([cx - hw, cy - hh, cx + hw, cy + hh], -1).astype(F32)
+    return box, rows[..., 0:2], rows[..., 2:4], rows[..., 4:5], rows[..., 5:]
+
+
+@pytest.fixture(scope="module")
+def toy_loss_case():
+    from oracle.yolo3_train_oracle import OracleYolo3Train
+    case = TOY
+    preds = _toy_heads(case)
+    with np.errstate(over="ignore"):
+        pr = OracleYolo3Train(case["C"], {}).split_preds(preds)
+    gt, tg, made = L.construct(case, pr["box"], pr["wh"], pr["obj"])
+    # a gt row whose IoU with the exact anchor is 0.5 = the threshold in every fp32 step: the left half of its box
+    n = 3 * (4 * 4 + 8 * 8) + (5 * 16 + 7) * 3 + 2
+    assert pr["box"][0, n].tolist() == [60 - 16.5, 44 - 11.5, 60 + 16.5, 44 + 11.5] and not tg[0][0, n, 0] > 0
+    gt[0, case["valid"]] = [60 - 16.5, 44 - 11.5, 60, 44 + 11.5]
+    terms = R.loss_terms64(case["C"], preds, gt, tg, case["thresh"], case["smooth"])
+    assert terms["ious_max"][0, n] == F32(0.5) and terms["decision"][0, n] == 0 and not terms["exempt"][0, n]
+    L.conditions(case, terms, made)
+    want = R.head_grads(case["C"], preds, gt, tg, case["thresh"], case["smooth"])
+    return case, preds, gt, tg, made, terms, want
+
+
+def _run_loss(toy, mut=None):
+    case, preds, gt, tg, made, terms, (want, exempt) = toy
+    losses, dpred = dev_loss(case, preds, gt, tg, made, mut)
+    res = R.check_losses("toy", losses, terms)
+    res += [R.check_head_grad("head %d" % i, dpred[i], want[i], exempt[i]) for i in range(3)]
+    res += R.check_raw_preds("toy", preds, *dev_raw_preds(preds, case["C"], mut))
+    return res
+
+
+def test_loss_restatement_passes_every_check(toy_loss_case):
+    res = _run_loss(toy_loss_case)
+    bad = [r for r in res if not r.ok]
+    assert not bad, bad
+    for r in res:
+        print(r)
+    assert len([r for r in res if r.kind == "loss value"]) == 4 and all(np.isfinite(r.ratio) for r in res)
+
+
+@pytest.mark.parametrize("mut", LOSS_MUTATIONS)
+def test_every_loss_mutation_fails_a_check(toy_loss_case, mut):
+    res = _run_loss(toy_loss_case, mut)
+    bad = [r for r in res if not r.ok]
+    assert bad and all(r.ratio > 1 for r in bad), "mutation %s passed every check" % mut
+    kinds = {"zero_scale_difference_given_gradient_plus_w": "loss gradient",
+             "slot_1_anchor_decoded_with_slot_2_size": "decoded boxes"}
+    assert kinds.get(mut, "loss value") in {r.kind for r in bad}, (mut, bad)
+    print("%s: fails %s, worst err/bound %.3g" % (mut, sorted(set(r.name for r in bad)), max(r.ratio for r in bad)))
+
+
+@pytest.mark.parametrize("case", L.CASES + [L.CAP_CASE], ids=L.case_id)
+def test_census_conditions_of_the_constructed_cases_hold_on_the_oracle(case):
+    """The device's raw head predictions are bit-equal to the oracle's train-mode forward on the same inputs, so the
+    construction the GPU test makes from the device's boxes is this one: its conditions are settled here."""
+    from oracle.yolo3_train_oracle import OracleYolo3Train
+    C = case["C"]
+    preds = L.oracle_heads_forward(C, L.heads_params(C), L.routes(case["B"], case["H"], case["W"], case["seed"]))
+    with np.errstate(over="ignore"):
+        pr = OracleYolo3Train(C, {}).split_preds(preds)
+    gt, tg, made = L.construct(case, pr["box"], pr["wh"], pr["obj"])
+    terms = R.loss_terms64(C, preds, gt, tg, case["thresh"], case["smooth"])
+    print(L.case_id(case), L.conditions(case, terms, made))
+    assert np.isinf(pr["box"]).any() and not np.isnan(pr["box"]).any() and np.isfinite(terms["terms"]).all()
+    assert (gt[:, case["valid"]:case["M"] - 1] == -1).all()           # -1 padding behind the valid rows
+
+
+# sgd_kernel in fp32 numpy: 4 steps on toy segments of 21 and 21 x 64 elements, multipliers changed before step 3
+SGD_MUTATIONS = ["lr_mult_ignored", "wd_applied_with_wd_mult_0", "momentum_reset_at_the_multiplier_change",
+                 "last_size_mod_4_elements_not_updated"]
+
+
+def _run_sgd(mut=None):
+    rng = np.random.default_rng(3)
+    lr, mu, wd, resc = F32(1e-3), F32(0.9), F32(5e-4), F32(1.0 / 3)
+    segs = {"bias": 21, "weight": 21 * 64, "gamma": 512, "frozen": 64}
+    mult = {"bias": (10.0, 0.0), "weight": (0.1, 1.0), "gamma": (0.0, 1.0), "frozen": (1.0, 1.0)}
+    enabled = {n: n != "frozen" for n in segs}
+    w = {n: rng.standard_normal(s).astype(F32) for n, s in segs.items()}
+    m = {n: np.zeros(s, F32) for n, s in segs.items()}
+    refs = {n: R.SgdRef((s,)) for n, s in segs.items()}
+    res = []
+    for step in range(1, 5):
+        if step == 3:
+            mult.update(bias=(1.0, 1.0), weight=(10.0, 0.0), gamma=(1.0, 0.0))
+            enabled.update(frozen=True, gamma=True)
+            if mut == "momentum_reset_at_the_multiplier_change":
+                m = {n: np.zeros_like(v) for n, v in m.items()}
+        for n, s in segs.items():
+            g = rng.standard_normal(s).astype(F32)
+            before = w[n].copy()
+            if enabled[n]:
+                lm, wm = mult[n]
+                lr_k = lr if mut == "lr_mult_ignored" else (lr * F32(lm)).astype(F32)
+                wd_k = wd if mut == "wd_applied_with_wd_mult_0" else (wd * F32(wm)).astype(F32)
+                gg = ((g * resc).astype(F32) + (wd_k * w[n]).astype(F32)).astype(F32)
+                mm = ((mu * m[n]).astype(F32) - (lr_k * gg).astype(F32)).astype(F32)
+                upd = slice(0, s - s % 4) if mut == "last_size_mod_4_elements_not_updated" else slice(None)
+                m[n][upd] = mm[upd]
+                w[n][upd] = (w[n] + mm).astype(F32)[upd]
+            res.append(refs[n].step("%s step %d" % (n, step), before, g, w[n], lr, mu, wd, resc, mult[n][0], mult[n][1],
+                                    enabled[n]))
+    return res
+
+
+def test_sgd_restatement_passes_every_check():
+    res = _run_sgd()
+    assert all(r.ok for r in res), [r for r in res if not r.ok]
+    assert {r.kind for r in res} == {"sgd step", "sgd frozen", "sgd lr_mult 0"}
+    assert max(r.ratio for r in res if r.kind == "sgd step") > 0.01   # the bound is within two orders of the error
+
+
+@pytest.mark.parametrize("mut", SGD_MUTATIONS)
+def test_every_sgd_mutation_fails_a_check(mut):
+    bad = [r for r in _run_sgd(mut) if not r.ok]
+    assert bad and all(r.ratio > 1 for r in bad), "mutation %s passed every check" % mut
+    print("%s: fails %s" % (mut, sorted(set(r.name for r in bad))[:6]))
