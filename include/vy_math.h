@@ -161,6 +161,22 @@ VY_HD float vy_box_iou(float ax1, float ay1, float ax2, float ay2, float bx1, fl
   return (uni <= 0.0f) ? 0.0f : inter / uni;
 }
 
+/* The same with the +1 pixel convention (boxes as inclusive pixel ranges): +1 on the overlap's width and height and on
+ * both boxes' widths and heights.  [UPSTREAM-RECALLED] box_nms is recalled to use none; vy_semantics.nms_iou_plus_one
+ * selects this one.  Operation for operation in fp32: iw = (min - max) + 1, areas (x2 - x1 + 1) * (y2 - y1 + 1),
+ * uni = (aa + ab) - inter; 0 without a positive overlap or with uni <= 0. */
+VY_HD float vy_box_iou_plus1(float ax1, float ay1, float ax2, float ay2, float bx1, float by1, float bx2,
+                             float by2) {
+  float iw = (fminf(ax2, bx2) - fmaxf(ax1, bx1)) + 1.0f;
+  float ih = (fminf(ay2, by2) - fmaxf(ay1, by1)) + 1.0f;
+  if (!(iw > 0.0f) || !(ih > 0.0f)) return 0.0f;
+  float inter = iw * ih;
+  float aa = ((ax2 - ax1) + 1.0f) * ((ay2 - ay1) + 1.0f);
+  float ab = ((bx2 - bx1) + 1.0f) * ((by2 - by1) + 1.0f);
+  float uni = (aa + ab) - inter;
+  return (uni <= 0.0f) ? 0.0f : inter / uni;
+}
+
 /* sin(a), cos(a) for a in [0, pi/4]: Taylor polynomials in Horner form with explicit fmaf (truncation below 2e-10,
  * under half an ulp of the results, which lie in [0, 0.71] and [0.70, 1]). */
 VY_HD float vy_sin_q(float a) {

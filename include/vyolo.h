@@ -116,6 +116,31 @@ void vy_net_destroy(vy_net* net);
 #define VY_MAX_TOPK 1024
 int vy_net_set_nms(vy_net* net, float nms_thresh, int32_t nms_topk, int32_t post_nms);
 
+/* The choices of contrib.box_nms and BatchNorm that this library restates from memory of mxnet's source
+ * ([UPSTREAM-RECALLED]), each switchable per net so that a deployment can be set to what its mxnet
+ * does (tests/golden/RUNBOOK.md: one kit case per choice).  All 0 = what the library has always computed.
+ * Every entry that ends in the detection tail (vy_net_forward_infer, *_routes, *_bank, vy_net_video_detect,
+ * vy_net_detect_heads, vy_net_profile_infer) honours the five nms_* fields from its next call on; every recorded training
+ * forward honours bn_running_var_unbiased.  The setting needs no bound plan and survives every bind.  A launch sequence
+ * captured into a HIP graph holds the setting it was captured with.
+ * box_nms's treatment of rows with id -1 ("background") has no flag: ids on this path are 0 .. C-1 (yolo3.py:194), no such
+ * row reaches the operator. */
+typedef struct vy_semantics {
+  int32_t nms_valid_ge;          /* 0: score >  valid_thresh (default)   1: >=                              */
+  int32_t nms_overlap_ge;        /* 0: iou   >  overlap_thresh (default) 1: >=                              */
+  int32_t nms_tie_descending;    /* 0: equal scores in ascending candidate row (default)  1: descending     */
+  int32_t nms_topk_after;        /* 0: top-k cut before suppression (default)  1: after, survivors refill   */
+  int32_t nms_iou_plus_one;      /* 0: corner IoU without +1 (default)  1: +1 on widths and heights         */
+  int32_t bn_running_var_unbiased; /* 0: biased batch variance into running_var (default)  1: x n/(n-1)     */
+  int32_t reserved[10];          /* must be 0 */
+} vy_semantics;
+/* VY_ERR_INVALID, changing nothing: a null pointer, a field outside {0, 1}, a non-zero reserved word.
+ * nms_topk_after: every valid candidate goes through suppression (the chunked kernel of nms_topk <= 0), the survivors are
+ * cut at nms_topk, then the post_nms slice follows; the output row count is that of vy_net_set_nms, rows past the cut are
+ * -1 filler. */
+int vy_net_set_semantics(vy_net* net, const vy_semantics* s);
+int vy_net_get_semantics(const vy_net* net, vy_semantics* out);
+
 /* collect_params(): number of tensors, and row i. */
 int32_t vy_net_num_params(const vy_net* net);
 int vy_net_param_info(const vy_net* net, int32_t i, vy_param_info* out);

@@ -39,6 +39,13 @@ class LaunchStat(ctypes.Structure):
                 ("bytes", ctypes.c_double)]
 
 
+class Semantics(ctypes.Structure):
+    """vy_semantics (include/vyolo.h): the recalled box_nms / BatchNorm choices of one net, each 0 (default) or 1."""
+    _fields_ = [("nms_valid_ge", ctypes.c_int32), ("nms_overlap_ge", ctypes.c_int32), ("nms_tie_descending", ctypes.c_int32),
+                ("nms_topk_after", ctypes.c_int32), ("nms_iou_plus_one", ctypes.c_int32),
+                ("bn_running_var_unbiased", ctypes.c_int32), ("reserved", ctypes.c_int32 * 10)]
+
+
 _vp, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_size_t
 
 # name -> (restype, argtypes); the single source of truth for the exported-symbols test
@@ -48,6 +55,8 @@ SIGNATURES = {
     "vy_net_create": (ctypes.c_int, [_i32, ctypes.POINTER(_vp)]),
     "vy_net_destroy": (None, [_vp]),
     "vy_net_set_nms": (ctypes.c_int, [_vp, _f32, _i32, _i32]),
+    "vy_net_set_semantics": (ctypes.c_int, [_vp, ctypes.POINTER(Semantics)]),
+    "vy_net_get_semantics": (ctypes.c_int, [_vp, ctypes.POINTER(Semantics)]),
     "vy_net_num_params": (_i32, [_vp]),
     "vy_net_param_info": (ctypes.c_int, [_vp, _i32, ctypes.POINTER(ParamInfo)]),
     "vy_net_num_convs": (_i32, [_vp]),

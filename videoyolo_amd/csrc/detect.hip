@@ -9,7 +9,8 @@
 // Candidate r of image b (the row index of the reference's detection tensor) is
 //   r = cand_base[scale] + c*(H*W*A) + (y*W + x)*A + a
 // and its sort key is (score, -r): box_nms orders by score descending and this implementation
-// breaks score ties by ascending r (a stable sort of the reference's tensor).
+// breaks score ties by ascending r (a stable sort of the reference's tensor) — by default: that order, the two threshold
+// compares, the place of the top-k cut and the IoU convention are per-net settings (vy_semantics; the det_* helpers).
 //
 // Pipeline per batch (all images in parallel), five launches:
 //   1. hist (pass 0): decode every class score once from the 3 head planes, keep it ([B][C][anchors] fp32,
@@ -28,6 +29,8 @@
 //   5. sort_nms: one workgroup per image: rank sort by key, pair mask + word-wise greedy per-class IoU suppression,
 //      compaction, write the first post_nms rows (-1 filler).
 // HBM-bound integer/byte work: coalesced channel-contiguous reads, LDS histograms, no MFMA.
+#include <type_traits>
+
 #include "kernels.h"
 #include "../../include/vy_math.h"
 
@@ -85,6 +88,52 @@ __host__ __device__ inline Scratch carve(void* base, int B) {
   s.score = (float*)p;
   return s;
 }
+
+// ---- the recalled choices of contrib.box_nms (vy_semantics, include/vyolo.h; DetArgs carries them, uniform per launch).
+// One helper per choice, used at every site: no kernel below compares with valid_thresh or nms_thresh, forms or inverts a
+// key's low word, or calls an IoU itself.  Each is written so that the default setting costs a scalar operation per
+// thread, hoisted out of the loops, and the per-element work stays what it was:
+//
+// valid test: s > valid_thresh, or s >= valid_thresh.  For a positive finite threshold t, s >= t is s > pred(t), the next
+// float below t (its bit pattern minus one): the kernels compare with one exclusive floor either way.  valid_thresh is
+// 0.01f (yolo3.py:1199).  The histogram, k_eff = min(topk, #valid) and every sweep use this one test: a candidate that one
+// kernel counts and another drops would corrupt the select.
+__device__ __forceinline__ float det_valid_floor(const DetArgs& d) {
+  return vy_bits_to_f32(vy_f32_to_bits(d.valid_thresh) - (uint32_t)d.valid_ge);
+}
+__device__ __forceinline__ bool det_valid(const DetArgs& d, float s) { return s > det_valid_floor(d); }
+
+// pair test: does a kept box suppress a later one of its class?  iou > nms_thresh or iou >= nms_thresh — the same floor
+// form; nms_thresh lies in (0, 1) whenever the tail suppresses at all —, the IoU with or without the +1 pixel convention.
+// Which IoU is a template parameter of the helper: the two kernels that suppress enter their suppression phase once, by a
+// uniform branch on DetArgs::iou_plus1 (det_with_iou), so the loops of the default setting are the loops without the
+// choice.  (As a branch inside the helper, taken per pair, it cost the serial greedy loops 3 % and one frame's tail at
+// nms_topk 400 1.5 %: profiles/semantics_tail_ab.txt.)
+template <bool kPlus1>
+__device__ __forceinline__ bool det_suppresses(const DetArgs& d, float ax1, float ay1, float ax2, float ay2, float bx1,
+                                               float by1, float bx2, float by2) {
+  const float lim = vy_bits_to_f32(vy_f32_to_bits(d.nms_thresh) - (uint32_t)d.overlap_ge);
+  const float iou = kPlus1 ? vy_box_iou_plus1(ax1, ay1, ax2, ay2, bx1, by1, bx2, by2)
+                           : vy_box_iou(ax1, ay1, ax2, ay2, bx1, by1, bx2, by2);
+  return iou > lim;
+}
+// run `phase(std::true_type / std::false_type)` — a suppression phase written once over det_suppresses<decltype(p)::value>
+template <typename Phase>
+__device__ __forceinline__ void det_with_iou(const DetArgs& d, Phase&& phase) {
+  if (__builtin_expect(d.iou_plus1 == 0, 1))  // the default's code first, falling through: a lone workgroup runs it cold
+    phase(std::false_type{});
+  else
+    phase(std::true_type{});
+}
+
+// tie order: the low word of a candidate's key.  Larger keys come first, so the inverted row (2^kIdxBits - 1) - r puts
+// equal scores in ascending row order (default) and r itself in descending order.  For r < 2^kIdxBits the inversion is
+// r ^ (2^kIdxBits - 1): both orders are one xor with a uniform mask, and det_key_row undoes det_key_word.  The radix
+// passes 4-6 and the chunk bounds of nms_all_kernel work on the word, whatever it holds.
+__device__ __forceinline__ uint32_t det_key_word(const DetArgs& d, uint32_t r) {
+  return r ^ (d.tie_desc ? 0u : (1u << kIdxBits) - 1u);
+}
+__device__ __forceinline__ uint32_t det_key_row(const DetArgs& d, uint32_t word) { return det_key_word(d, word); }
 
 __device__ __forceinline__ uint32_t score_bucket(float s) {
   int b = (int)(s * 1024.0f);
@@ -196,7 +245,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const DetArgs d, voi
     const int c = idx / nit, i = idx - c * nit;  // i = pixel * 3 + anchor inside the block: the candidate order
     const float sv = vy_sigmoidf(tile[(i / 3) * hv.cs + (i % 3) * P + 5 + c]) * conf[i];
     cache[(size_t)c * n_items + i] = sv;
-    if (sv > d.valid_thresh) atomicAdd(&lh[score_bucket(sv)], 1u);
+    if (det_valid(d, sv)) atomicAdd(&lh[score_bucket(sv)], 1u);
   }
   (void)cstride;
   __syncthreads();
@@ -344,11 +393,11 @@ __global__ __launch_bounds__(kHistThreads) void compact_kernel(const DetArgs d, 
       for (int u = 0; u < 8; ++u) {
         const float s = s8[u];
         const int c = c0 + u;
-        if (c >= d.C || !(s > d.valid_thresh)) continue;
+        if (c >= d.C || !det_valid(d, s)) continue;
         const uint32_t bucket = score_bucket(s);
         if (bucket < Tb) continue;
         const uint32_t sbits = vy_f32_to_bits(s);
-        const uint32_t inv = ((1u << kIdxBits) - 1u) - (uint32_t)(im.cand0 + c * im.cstride);
+        const uint32_t inv = det_key_word(d, (uint32_t)(im.cand0 + c * im.cstride));
         if (bucket > Tb) {
           put_entry(d, ent, stp, im, c, sbits, inv);
         } else if (fits) {
@@ -386,7 +435,7 @@ __global__ __launch_bounds__(kBins) void refine_kernel(const DetArgs d, void* sc
       return true;
     }
     const float s = cache[idx];
-    if (!(s > d.valid_thresh) || score_bucket(s) != st.Tb) return false;
+    if (!det_valid(d, s) || score_bucket(s) != st.Tb) return false;
     const int c = idx / n_items, it = idx - c * n_items;
     uint32_t r;
     if (it < n0)
@@ -396,7 +445,7 @@ __global__ __launch_bounds__(kBins) void refine_kernel(const DetArgs d, void* sc
     else
       r = (uint32_t)(d.head[2].cand_base + c * (n_items - n0 - n1) + (it - n0 - n1));
     sbits = vy_f32_to_bits(s);
-    inv = ((1u << kIdxBits) - 1u) - r;
+    inv = det_key_word(d, r);
     return true;
   };
   for (int pass = 1; pass < 7; ++pass) {
@@ -445,7 +494,7 @@ __global__ __launch_bounds__(kBins) void refine_kernel(const DetArgs d, void* sc
     if (!(sbits > st.Ts || (sbits == st.Ts && inv >= st.Ti))) continue;
     Item im;
     int c;
-    locate_cand(d, b, ((1u << kIdxBits) - 1u) - inv, im, c);
+    locate_cand(d, b, det_key_row(d, inv), im, c);
     put_entry(d, ent, stp, im, c, sbits, inv);
   }
 }
@@ -532,85 +581,87 @@ __global__ __launch_bounds__(kNmsThreads) void sort_nms_kernel(const DetArgs d, 
   }
   __syncthreads();
   NMS_STAMP(3);
-  if (d.do_nms && k <= kMaskRows) {
-    // the usual case (topk 400): all pairwise "i would suppress j" bits in parallel, then the greedy pass, whose only
-    // serial dependency is the alive mask.  Word w of row i is needed only if it can hold a j > i: i < 32 (w + 1).
-    // Items are enumerated word by word, rows innermost: a wave works on consecutive rows of one word and reads the
-    // same candidate j in every step (LDS broadcasts), its lanes differ only in the row they hold in registers.
-    const int words = (k + 31) >> 5;
-    const int full = k >> 5;  // words w with 32 (w + 1) <= k
-    const int total = 16 * full * (full + 1) + (words > full ? k : 0);
-    for (int idx = t; idx < total; idx += kNmsThreads) {
-      int w = 0, i = idx;
-      for (;;) {
-        const int n_w = 32 * (w + 1) < k ? 32 * (w + 1) : k;
-        if (i < n_w) break;
-        i -= n_w;
-        ++w;
-      }
-      const float ac = bcls[i], ax1 = bx1[i], ay1 = by1[i], ax2 = bx2[i], ay2 = by2[i];
-      uint32_t m = 0;
-#pragma unroll 4
-      for (int bit = 0; bit < 32; ++bit) {
-        const int j = 32 * w + bit;
-        if (j > i && j < k && bcls[j] == ac &&
-            vy_box_iou(ax1, ay1, ax2, ay2, bx1[j], by1[j], bx2[j], by2[j]) > d.nms_thresh)
-          m |= 1u << bit;
-      }
-      mask[i][w] = m;
-    }
-    __syncthreads();
-    NMS_STAMP(4);
-    if (t < 64) {
-      // alive bits: word l in lane l.  Words are settled in order.  Word wb, once every earlier survivor has been applied
-      // to it: a 32-step chain over its own candidates on the scalar unit (lane l holds the diagonal word of row 32 wb + l,
-      // v_readlane with a constant lane), then the rows of its survivors are or-ed into all later words at once
-      // (32 independent LDS reads per lane, selected by an all-ones / all-zeros scalar).  Rows at or past k are never
-      // selected (their alive bits start as 0); mask[i][w] with w < i / 32 is never read.
-      uint32_t aw = 0;
-      if (t < words) aw = (32 * t + 32 <= k) ? 0xffffffffu : ((1u << (k - 32 * t)) - 1u);
-      const int tw = t < words ? t : 0;
-      for (int wb = 0; wb < words; ++wb) {
-        uint32_t cur = (uint32_t)__builtin_amdgcn_readlane((int)aw, wb);
-        if (cur == 0u) continue;  // uniform
-        const int di = 32 * wb + (t & 31);
-        const uint32_t diag = di < k ? mask[di][wb] : 0u;
-        if (__builtin_amdgcn_ballot_w64(diag != 0u) != 0ull) {  // (no pair inside this word overlaps: nothing to settle)
-#pragma unroll
-          for (int bit = 0; bit < 32; ++bit) {
-            const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)diag, bit);
-            const uint32_t sel = 0u - ((cur >> bit) & 1u);
-            cur &= ~(row & sel);
-          }
+  if (d.do_nms) det_with_iou(d, [&](auto plus1) {
+    constexpr bool kPlus1 = decltype(plus1)::value;
+    if (k <= kMaskRows) {
+      // the usual case (topk 400): all pairwise "i would suppress j" bits in parallel, then the greedy pass, whose only
+      // serial dependency is the alive mask.  Word w of row i is needed only if it can hold a j > i: i < 32 (w + 1).
+      // Items are enumerated word by word, rows innermost: a wave works on consecutive rows of one word and reads the
+      // same candidate j in every step (LDS broadcasts), its lanes differ only in the row they hold in registers.
+      const int words = (k + 31) >> 5;
+      const int full = k >> 5;  // words w with 32 (w + 1) <= k
+      const int total = 16 * full * (full + 1) + (words > full ? k : 0);
+      for (int idx = t; idx < total; idx += kNmsThreads) {
+        int w = 0, i = idx;
+        for (;;) {
+          const int n_w = 32 * (w + 1) < k ? 32 * (w + 1) : k;
+          if (i < n_w) break;
+          i -= n_w;
+          ++w;
         }
-        uint32_t acc0 = 0u, acc1 = 0u;
-        if (wb + 1 < words) {
-#pragma unroll
-          for (int bit = 0; bit < 32; bit += 2) {
-            acc0 |= mask[32 * wb + bit][tw] & (0u - ((cur >> bit) & 1u));
-            acc1 |= mask[32 * wb + bit + 1][tw] & (0u - ((cur >> (bit + 1)) & 1u));
-          }
+        const float ac = bcls[i], ax1 = bx1[i], ay1 = by1[i], ax2 = bx2[i], ay2 = by2[i];
+        uint32_t m = 0;
+  #pragma unroll 4
+        for (int bit = 0; bit < 32; ++bit) {
+          const int j = 32 * w + bit;
+          if (j > i && j < k && bcls[j] == ac &&
+              det_suppresses<kPlus1>(d, ax1, ay1, ax2, ay2, bx1[j], by1[j], bx2[j], by2[j]))
+            m |= 1u << bit;
         }
-        if (t == wb) aw = cur;
-        else if (t > wb) aw &= ~(acc0 | acc1);
-      }
-      if (t < words)
-        for (int bit = 0; bit < 32 && 32 * t + bit < k; ++bit) alive[32 * t + bit] = (uint8_t)((aw >> bit) & 1u);
-    }
-    __syncthreads();
-  } else if (d.do_nms) {
-    for (int i = 0; i < k; ++i) {
-      if (!alive[i]) continue;  // uniform: alive[] is only written before the barrier below
-      const float ax1 = bx1[i], ay1 = by1[i], ax2 = bx2[i], ay2 = by2[i], ac = bcls[i];
-      for (int j = i + 1 + t; j < k; j += kNmsThreads) {
-        if (alive[j] && bcls[j] == ac) {
-          const float iou = vy_box_iou(ax1, ay1, ax2, ay2, bx1[j], by1[j], bx2[j], by2[j]);
-          if (iou > d.nms_thresh) alive[j] = 0;
-        }
+        mask[i][w] = m;
       }
       __syncthreads();
+      NMS_STAMP(4);
+      if (t < 64) {
+        // alive bits: word l in lane l.  Words are settled in order.  Word wb, once every earlier survivor has been applied
+        // to it: a 32-step chain over its own candidates on the scalar unit (lane l holds the diagonal word of row 32 wb + l,
+        // v_readlane with a constant lane), then the rows of its survivors are or-ed into all later words at once
+        // (32 independent LDS reads per lane, selected by an all-ones / all-zeros scalar).  Rows at or past k are never
+        // selected (their alive bits start as 0); mask[i][w] with w < i / 32 is never read.
+        uint32_t aw = 0;
+        if (t < words) aw = (32 * t + 32 <= k) ? 0xffffffffu : ((1u << (k - 32 * t)) - 1u);
+        const int tw = t < words ? t : 0;
+        for (int wb = 0; wb < words; ++wb) {
+          uint32_t cur = (uint32_t)__builtin_amdgcn_readlane((int)aw, wb);
+          if (cur == 0u) continue;  // uniform
+          const int di = 32 * wb + (t & 31);
+          const uint32_t diag = di < k ? mask[di][wb] : 0u;
+          if (__builtin_amdgcn_ballot_w64(diag != 0u) != 0ull) {  // (no pair inside this word overlaps: nothing to settle)
+  #pragma unroll
+            for (int bit = 0; bit < 32; ++bit) {
+              const uint32_t row = (uint32_t)__builtin_amdgcn_readlane((int)diag, bit);
+              const uint32_t sel = 0u - ((cur >> bit) & 1u);
+              cur &= ~(row & sel);
+            }
+          }
+          uint32_t acc0 = 0u, acc1 = 0u;
+          if (wb + 1 < words) {
+  #pragma unroll
+            for (int bit = 0; bit < 32; bit += 2) {
+              acc0 |= mask[32 * wb + bit][tw] & (0u - ((cur >> bit) & 1u));
+              acc1 |= mask[32 * wb + bit + 1][tw] & (0u - ((cur >> (bit + 1)) & 1u));
+            }
+          }
+          if (t == wb) aw = cur;
+          else if (t > wb) aw &= ~(acc0 | acc1);
+        }
+        if (t < words)
+          for (int bit = 0; bit < 32 && 32 * t + bit < k; ++bit) alive[32 * t + bit] = (uint8_t)((aw >> bit) & 1u);
+      }
+      __syncthreads();
+    } else {
+      for (int i = 0; i < k; ++i) {
+        if (!alive[i]) continue;  // uniform: alive[] is only written before the barrier below
+        const float ax1 = bx1[i], ay1 = by1[i], ax2 = bx2[i], ay2 = by2[i], ac = bcls[i];
+        for (int j = i + 1 + t; j < k; j += kNmsThreads) {
+          if (alive[j] && bcls[j] == ac) {
+            if (det_suppresses<kPlus1>(d, ax1, ay1, ax2, ay2, bx1[j], by1[j], bx2[j], by2[j])) alive[j] = 0;
+          }
+        }
+        __syncthreads();
+      }
     }
-  }
+  });
   // compaction: inclusive scan of alive[] (k <= 1024, one element per thread)
   NMS_STAMP(5);
   __syncthreads();  // (the rank counters in pos[] were last read before the barriers above)
@@ -635,7 +686,7 @@ __global__ __launch_bounds__(kNmsThreads) void sort_nms_kernel(const DetArgs d, 
     bboxes[o * 4 + 1] = by1[i];
     bboxes[o * 4 + 2] = bx2[i];
     bboxes[o * 4 + 3] = by2[i];
-    if (keep_idx) keep_idx[o] = (int32_t)(((1u << kIdxBits) - 1u) - (uint32_t)(key[i] & 0xffffffffull));
+    if (keep_idx) keep_idx[o] = (int32_t)det_key_row(d, (uint32_t)(key[i] & 0xffffffffull));
   }
   for (int r = n_keep + t; r < rows; r += kNmsThreads) {
     const size_t o = (size_t)b * rows + r;
@@ -685,6 +736,9 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
   const int n0 = d.head[0].H * d.head[0].W * 3, n1 = d.head[1].H * d.head[1].W * 3;
   const int total = d.C * n_items;
   const bool kept_in_lds = rows <= VY_NMS_MAX_TOPK;
+  // rows that suppression may keep: all `rows` of the output, or — the top-k cut applied AFTER suppression (topk_after: the
+  // host passes no candidate cut then) — the first nms_topk survivors; rows past that are filler
+  const int keep_cap = (d.topk_after && d.topk > 0 && d.topk < rows) ? d.topk : rows;
   // candidate row of cached score idx = c*n_items + item
   auto cand_of = [&](int idx, int& c, int& it) -> uint32_t {
     c = idx / n_items;
@@ -715,10 +769,10 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
       __syncthreads();
       for (int idx = t; idx < total; idx += kAllThreads) {
         const float s = cache[idx];
-        if (!(s > d.valid_thresh)) continue;
+        if (!det_valid(d, s)) continue;
         int c, it;
         const uint32_t sbits = vy_f32_to_bits(s);
-        const uint32_t inv = ((1u << kIdxBits) - 1u) - cand_of(idx, c, it);
+        const uint32_t inv = det_key_word(d, cand_of(idx, c, it));
         if (!first && !(sbits < bound_s || (sbits == bound_s && inv < bound_i))) continue;
         const uint32_t bucket = score_bucket(s);
         if (!prefix_match(st, pass, bucket, sbits, inv)) continue;
@@ -766,10 +820,10 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
     // ---- collect + decode the chunk
     for (int idx = t; idx < total; idx += kAllThreads) {
       const float s = cache[idx];
-      if (!(s > d.valid_thresh)) continue;
+      if (!det_valid(d, s)) continue;
       int c, it;
       const uint32_t sbits = vy_f32_to_bits(s);
-      const uint32_t inv = ((1u << kIdxBits) - 1u) - cand_of(idx, c, it);
+      const uint32_t inv = det_key_word(d, cand_of(idx, c, it));
       if (!first && !(sbits < bound_s || (sbits == bound_s && inv < bound_i))) continue;
       const uint32_t bucket = score_bucket(s);
       const bool take = bucket > st.Tb || (bucket == st.Tb && (sbits > st.Ts || (sbits == st.Ts && inv >= st.Ti)));
@@ -814,35 +868,38 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
     // post_nms <= 0 or > 1024) IS the list of kept rows, so they are read back from it (written by this workgroup,
     // fenced at workgroup scope below)
     const int nk = n_kept;
-    if (t < k) {
-      const int e = perm[t];
-      bool ok = true;
-      if (kept_in_lds) {
-        for (int j = 0; j < nk && ok; ++j)
-          if (kcls[j] == bcls[e] && vy_box_iou(kx1[j], ky1[j], kx2[j], ky2[j], bx1[e], by1[e], bx2[e], by2[e]) > d.nms_thresh)
-            ok = false;
-      } else {
-        const float* kb = bboxes + (size_t)b * rows * 4;
-        const float* kc = ids + (size_t)b * rows;
-        for (int j = 0; j < nk && ok; ++j)
-          if (kc[j] == bcls[e] &&
-              vy_box_iou(kb[j * 4 + 0], kb[j * 4 + 1], kb[j * 4 + 2], kb[j * 4 + 3], bx1[e], by1[e], bx2[e], by2[e]) > d.nms_thresh)
-            ok = false;
-      }
-      alive[t] = ok ? 1 : 0;
-    }
-    __syncthreads();
-    for (int i = 0; i < k; ++i) {
-      if (!alive[i]) continue;  // uniform
-      const int ei = perm[i];
-      const float ax1 = bx1[ei], ay1 = by1[ei], ax2 = bx2[ei], ay2 = by2[ei], ac = bcls[ei];
-      for (int j = i + 1 + t; j < k; j += kAllThreads) {
-        const int ej = perm[j];
-        if (alive[j] && bcls[ej] == ac && vy_box_iou(ax1, ay1, ax2, ay2, bx1[ej], by1[ej], bx2[ej], by2[ej]) > d.nms_thresh)
-          alive[j] = 0;
+    det_with_iou(d, [&](auto plus1) {
+      constexpr bool kPlus1 = decltype(plus1)::value;
+      if (t < k) {
+        const int e = perm[t];
+        bool ok = true;
+        if (kept_in_lds) {
+          for (int j = 0; j < nk && ok; ++j)
+            if (kcls[j] == bcls[e] && det_suppresses<kPlus1>(d, kx1[j], ky1[j], kx2[j], ky2[j], bx1[e], by1[e], bx2[e], by2[e]))
+              ok = false;
+        } else {
+          const float* kb = bboxes + (size_t)b * rows * 4;
+          const float* kc = ids + (size_t)b * rows;
+          for (int j = 0; j < nk && ok; ++j)
+            if (kc[j] == bcls[e] &&
+                det_suppresses<kPlus1>(d, kb[j * 4 + 0], kb[j * 4 + 1], kb[j * 4 + 2], kb[j * 4 + 3], bx1[e], by1[e], bx2[e], by2[e]))
+              ok = false;
+        }
+        alive[t] = ok ? 1 : 0;
       }
       __syncthreads();
-    }
+      for (int i = 0; i < k; ++i) {
+        if (!alive[i]) continue;  // uniform
+        const int ei = perm[i];
+        const float ax1 = bx1[ei], ay1 = by1[ei], ax2 = bx2[ei], ay2 = by2[ei], ac = bcls[ei];
+        for (int j = i + 1 + t; j < k; j += kAllThreads) {
+          const int ej = perm[j];
+          if (alive[j] && bcls[ej] == ac && det_suppresses<kPlus1>(d, ax1, ay1, ax2, ay2, bx1[ej], by1[ej], bx2[ej], by2[ej]))
+            alive[j] = 0;
+        }
+        __syncthreads();
+      }
+    });
     // ---- append the survivors in order
     pos[t] = (t < k && alive[t]) ? 1 : 0;
     __syncthreads();
@@ -855,7 +912,7 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
     const int add = pos[VY_NMS_MAX_TOPK - 1];
     if (t < k && alive[t]) {
       const int r = nk + pos[t] - 1;
-      if (r < rows) {
+      if (r < keep_cap) {
         const int e = perm[t];
         if (kept_in_lds) {
           kx1[r] = bx1[e];
@@ -871,18 +928,18 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
         bboxes[o * 4 + 1] = by1[e];
         bboxes[o * 4 + 2] = bx2[e];
         bboxes[o * 4 + 3] = by2[e];
-        if (keep_idx) keep_idx[o] = (int32_t)(((1u << kIdxBits) - 1u) - (uint32_t)(key[t] & 0xffffffffull));
+        if (keep_idx) keep_idx[o] = (int32_t)det_key_row(d, (uint32_t)(key[t] & 0xffffffffull));
       }
     }
     // next chunk: everything strictly below this chunk's smallest key
     const unsigned long long last = key[k - 1];
     if (!kept_in_lds) __threadfence_block();  // the rows just written are the next chunk's kept list
     __syncthreads();
-    if (t == 0) n_kept = (nk + add < rows) ? nk + add : rows;
+    if (t == 0) n_kept = (nk + add < keep_cap) ? nk + add : keep_cap;
     __syncthreads();
     consumed += k;
     // enough rows, or the candidates are exhausted, or the topk best have all been through
-    if (n_kept >= rows || k < k_limit || (topk_cap > 0 && consumed >= topk_cap)) break;
+    if (n_kept >= keep_cap || k < k_limit || (topk_cap > 0 && consumed >= topk_cap)) break;
     bound_s = (uint32_t)(last >> 32);
     bound_i = (uint32_t)(last & 0xffffffffull);
     first = false;
@@ -946,8 +1003,9 @@ hipError_t vy_launch_detect(const DetArgs& a, void* scratch, float* ids, float* 
                             int32_t* keep_idx, hipStream_t s) {
   if (a.n_cand >= (1 << kIdxBits)) return hipErrorInvalidValue;
   // nms_topk <= 0 or > VY_NMS_MAX_TOPK: the chunked kernel (kept rows in LDS for outputs of <= VY_NMS_MAX_TOPK rows,
-  // read back from the output itself for longer ones)
-  const bool chunked = a.topk <= 0 || a.topk > VY_NMS_MAX_TOPK;
+  // read back from the output itself for longer ones).  Also whenever the top-k cut follows suppression (topk_after):
+  // every valid candidate is then a candidate, as for nms_topk <= 0, and the kernel cuts the survivors at nms_topk
+  const bool chunked = a.topk <= 0 || a.topk > VY_NMS_MAX_TOPK || a.topk_after;
   // rows of the output: post_nms, else nms_topk (no slice, yolo3.py:1201-1202), else — both "disabled" — all N*C rows
   const int rows = a.post_nms > 0 ? a.post_nms : (a.topk > 0 ? a.topk : a.n_cand);
   // state + histogram region back to zero (entries need no clearing)
@@ -969,7 +1027,7 @@ hipError_t vy_launch_detect(const DetArgs& a, void* scratch, float* ids, float* 
   if (chunked) {  // every valid candidate (or the topk > 1024 best) goes through NMS: pass 0 only fills the score cache
     hipLaunchKernelGGL(hist_kernel, hgrid, dim3(kHistThreads), 0, s, a, scratch, 0, n_items);
     hipLaunchKernelGGL(nms_all_kernel, dim3(a.B), dim3(kAllThreads), 0, s, a, scratch, n_items, rows,
-                       a.topk > 0 ? a.topk : 0, ids, scores, bboxes, keep_idx);
+                       (a.topk > 0 && !a.topk_after) ? a.topk : 0, ids, scores, bboxes, keep_idx);
     return hipGetLastError();
   }
   hipLaunchKernelGGL(hist_kernel, hgrid, dim3(kHistThreads), 0, s, a, scratch, 0, n_items);

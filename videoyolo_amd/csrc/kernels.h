@@ -284,6 +284,13 @@ struct DetArgs {
   float valid_thresh, nms_thresh;
   int topk, post_nms;
   int do_nms;           // 0: nms disabled (nms_thresh outside (0,1)): return first post_nms rows
+  // the recalled box_nms choices (vy_semantics, include/vyolo.h), each 0 (default) or 1; uniform per launch.  detect.hip
+  // reads them through its det_* helpers only
+  int valid_ge;         // score >= valid_thresh is valid (default: >)
+  int overlap_ge;       // iou >= nms_thresh suppresses (default: >)
+  int tie_desc;         // equal scores in descending candidate row (default: ascending)
+  int topk_after;       // the top-k cut follows suppression (default: precedes it)
+  int iou_plus1;        // IoU with +1 on widths and heights (default: without)
 };
 size_t vy_det_scratch_bytes(int B, int n_items, int C);  // n_items = anchors per image (N), C = classes
 // full tail: decode -> radix select of the top-k valid scores -> sort -> per-class NMS -> outputs
@@ -319,6 +326,7 @@ struct BnFinalizeArgs {
   float* save_invstd;
   int C;
   float eps, momentum;
+  int var_unbiased;       // vy_semantics.bn_running_var_unbiased: running_var takes batch variance x n / (n - 1), n = count
 };
 hipError_t vy_launch_bn_finalize(const BnFinalizeArgs& a, hipStream_t s);
 // ordered reduce of the [n_part][2][C] partial sums + finalize (per-device BatchNorm): one launch, or — more than

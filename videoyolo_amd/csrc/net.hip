@@ -136,6 +136,24 @@ int vy_net_set_nms(vy_net* net, float nms_thresh, int32_t nms_topk, int32_t post
   return 0;
 }
 
+int vy_net_set_semantics(vy_net* net, const vy_semantics* s) {
+  if (!net || !s) return fail(VY_ERR_INVALID, "null argument");
+  const int32_t f[6] = {s->nms_valid_ge,   s->nms_overlap_ge,   s->nms_tie_descending,
+                        s->nms_topk_after, s->nms_iou_plus_one, s->bn_running_var_unbiased};
+  for (int i = 0; i < 6; ++i)
+    if (f[i] != 0 && f[i] != 1) return fail(VY_ERR_INVALID, "vy_semantics: field %d is %d, expected 0 or 1", i, f[i]);
+  for (int i = 0; i < 10; ++i)
+    if (s->reserved[i] != 0) return fail(VY_ERR_INVALID, "vy_semantics: reserved[%d] is %d, must be 0", i, s->reserved[i]);
+  net->sem = *s;
+  return 0;
+}
+
+int vy_net_get_semantics(const vy_net* net, vy_semantics* out) {
+  if (!net || !out) return fail(VY_ERR_INVALID, "null argument");
+  *out = net->sem;
+  return 0;
+}
+
 int32_t vy_net_num_params(const vy_net* net) { return net ? (int32_t)net->params.size() : 0; }
 
 int vy_net_param_info(const vy_net* net, int32_t i, vy_param_info* out) {

@@ -104,6 +104,9 @@ struct vy_net {
   int num_class = 0;
   float nms_thresh = 0.45f;  // YOLOV3T.__init__ defaults, yolo3.py:959-963
   int nms_topk = 400, post_nms = 100;
+  // vy_net_set_semantics: the recalled box_nms / BatchNorm choices of this net, all 0 by default.  Not part of any plan:
+  // det_args() and bn_forward (train.hip) read them at every launch, so they survive every bind
+  vy_semantics sem = {};
   std::vector<ParamT> params;
   std::vector<PlaneT> planes;
   std::vector<ConvT> convs;
@@ -757,6 +760,11 @@ struct vy_net {
     d.topk = nms_topk;
     d.post_nms = post_nms;
     d.do_nms = 1;
+    d.valid_ge = sem.nms_valid_ge;
+    d.overlap_ge = sem.nms_overlap_ge;
+    d.tie_desc = sem.nms_tie_descending;
+    d.topk_after = sem.nms_topk_after;
+    d.iou_plus1 = sem.nms_iou_plus_one;
     return d;
   }
 

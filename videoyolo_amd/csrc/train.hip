@@ -502,6 +502,7 @@ int bn_forward(const TrainCtx& c, int ci, int n_part) {
   f.C = C;
   f.eps = 1e-5f;
   f.momentum = 0.9f;  // layers.py:68
+  f.var_unbiased = net->sem.bn_running_var_unbiased;  // vy_net_set_semantics: read at every launch
   if (f.sums)
     HIP_TRY(vy_launch_bn_finalize(f, c.s));
   else if (!(train_abl(net) & 128))  // (128: the finalize launch of the forward statistics skipped)

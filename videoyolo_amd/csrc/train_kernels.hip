@@ -73,7 +73,16 @@ __device__ __forceinline__ void bn_finalize_channel(const BnFinalizeArgs& a, int
   a.save_mean[c] = mf;
   a.save_invstd[c] = invstd;
   a.running_mean[c] = a.running_mean[c] * a.momentum + mf * (1.0f - a.momentum);
-  a.running_var[c] = a.running_var[c] * a.momentum + vf * (1.0f - a.momentum);
+  // what goes into running_var [UPSTREAM-RECALLED]: the biased batch variance (default), or — var_unbiased — that variance
+  // times n / (n - 1).  The factor is formed in double from the count (max(n - 1, 1) below it), rounded to fp32 once, and
+  // multiplies the fp32 variance: the CPU checker's order under RUNNING_VAR_UNBIASED.  Normalisation (invstd above) and
+  // the saved statistics keep the biased variance either way
+  float rv = vf;
+  if (a.var_unbiased) {
+    const double nm1 = a.count - 1.0;
+    rv = vf * (float)(a.count / (nm1 > 1.0 ? nm1 : 1.0));
+  }
+  a.running_var[c] = a.running_var[c] * a.momentum + rv * (1.0f - a.momentum);
 }
 
 __global__ void bn_finalize_kernel(const BnFinalizeArgs a) {

@@ -488,6 +488,59 @@ class YOLOV3(object):
         """yolo3.py:1208-1228"""
         self.nms_thresh, self.nms_topk, self.post_nms = nms_thresh, nms_topk, post_nms
         _lib.check(self._lib.vy_net_set_nms(self._h, nms_thresh, nms_topk, post_nms))
+        self._graphs = {}  # a captured forward holds the old values in its kernel arguments
+
+    # keyword of set_semantics -> (field of vy_semantics, the keyword's value that means field == 0).  Names and polarities
+    # are those of the switchable plain-Python box_nms of tests/test_mxnet_kit_sensitivity.py, so a red case of the golden
+    # kit (tests/golden/RUNBOOK.md) names the keyword to flip.
+    _SEMANTICS = (("strict_valid", "nms_valid_ge", True), ("strict_iou", "nms_overlap_ge", True),
+                  ("tie_ascending", "nms_tie_descending", True), ("topk_first", "nms_topk_after", True),
+                  ("plus_one", "nms_iou_plus_one", False), ("running_var_unbiased", "bn_running_var_unbiased", False))
+
+    def set_semantics(self, *, strict_valid=None, strict_iou=None, tie_ascending=None, topk_first=None, plus_one=None,
+                      running_var_unbiased=None):
+        """The choices of ``contrib.box_nms`` and ``BatchNorm`` that this library restates from memory of mxnet
+        (``vy_net_set_semantics``), per net; an omitted keyword keeps its value.  Defaults:
+
+        ``strict_valid=True``   a candidate is valid if score > 0.01 (False: >=)
+        ``strict_iou=True``     a kept box suppresses at IoU > nms_thresh (False: >=)
+        ``tie_ascending=True``  equal scores are taken in ascending row order of the detection tensor (False: descending)
+        ``topk_first=True``     the ``nms_topk`` cut precedes suppression (False: follows it; survivors refill the cut)
+        ``plus_one=False``      corner IoU without the +1 pixel convention (True: with it)
+        ``running_var_unbiased=False``  ``running_var`` takes the biased batch variance (True: times n / (n - 1))
+
+        Every inference entry, ``detect_heads`` and video sessions included, follows the first five from the next call on;
+        recorded training forwards follow the last.  ``box_nms``'s handling of id -1 rows has no switch: ids here are
+        0 .. C-1 (yolo3.py:194)."""
+        given = dict(strict_valid=strict_valid, strict_iou=strict_iou, tie_ascending=tie_ascending, topk_first=topk_first,
+                     plus_one=plus_one, running_var_unbiased=running_var_unbiased)
+        for k, v in given.items():
+            if v is not None and not isinstance(v, (bool, np.bool_)):
+                raise TypeError("set_semantics(%s=%r): a bool" % (k, v))
+        st = self._read_semantics(self._h)
+        for kw, field, zero in self._SEMANTICS:
+            if given[kw] is not None:
+                setattr(st, field, int(bool(given[kw]) != zero))
+        self._write_semantics(st)
+
+    def _read_semantics(self, handle):
+        st = _lib.Semantics()
+        _lib.check(self._lib.vy_net_get_semantics(handle, ctypes.byref(st)))
+        return st
+
+    def _write_semantics(self, st):
+        """One setting into this net's handle and its two-stream twin's; captured forwards hold the old one."""
+        _lib.check(self._lib.vy_net_set_semantics(self._h, ctypes.byref(st)))
+        self._graphs = {}
+        tw = getattr(self, "_twin", None)
+        if tw is not None:
+            _lib.check(self._lib.vy_net_set_semantics(tw["h"], ctypes.byref(st)))
+
+    @property
+    def semantics(self):
+        """The setting of ``set_semantics`` as a dict of its keywords, read back from the library."""
+        st = self._read_semantics(self._h)
+        return {kw: bool(getattr(st, field)) != zero for kw, field, zero in self._SEMANTICS}
 
     def reset_class(self, classes, reuse_weights=None):
         """yolo3.py:1230-1302 + YOLOOutputV3.reset_class yolo3.py:76-129: new class list, fresh
@@ -516,6 +569,7 @@ class YOLOV3(object):
             reuse_weights = {classes.index(n): old_classes.index(n) for n in both}
         old_vals = {p.name: self._get_param(p.index) for p in self._params.values()}
         device = self._device
+        semantics = self._read_semantics(self._h)
         fresh = type(self)(classes, self.nms_thresh, self.nms_topk, self.post_nms, self._pos_iou_thresh,
                        self._ignore_iou_thresh, self._norm_layer, self._norm_kwargs, self._alloc_size, **self._ctor_kwargs())
         new_vals = _init.uniform_params(fresh.param_table())  # prediction.initialize(), yolo3.py:110
@@ -549,6 +603,7 @@ class YOLOV3(object):
             _lib.check(self._lib.vy_net_set_keep_activations(self._h, 1))
         if getattr(self, "_conv_mode", "exact") != "exact":
             self.set_conv_mode(self._conv_mode)
+        self._write_semantics(semantics)  # the new library handle starts from the defaults
         for k, v in new_vals.items():
             self._params[k].set_data(v)
         if device is not None:
@@ -563,6 +618,7 @@ class YOLOV3(object):
             for p in self._params.values():
                 twin._params[p.name].set_data(self._get_param(p.index))
         twin._target_generator._label_smooth = self._target_generator._label_smooth
+        twin._write_semantics(self._read_semantics(self._h))
         return twin
 
     # ------------------------------------------------------------------ execution
@@ -888,6 +944,8 @@ class YOLOV3(object):
                 tw = self._twin = dict(h=th, dev=self._dev_params, ws=None, plan=None, raw_stream=sp,
                                        stream=torch.cuda.ExternalStream(sp.value, device=self._device))
             _lib.check(self._lib.vy_net_set_nms(tw["h"], self.nms_thresh, self.nms_topk, self.post_nms))
+            sem = self._read_semantics(self._h)
+            _lib.check(self._lib.vy_net_set_semantics(tw["h"], ctypes.byref(sem)))
             cur = torch.cuda.current_stream(self._device)
             if tw["plan"] != (hb, h, w):
                 need = self._lib.vy_net_workspace_bytes(tw["h"], hb, h, w)
