@@ -448,6 +448,31 @@ int vy_vid_match(int32_t n_frames, const int64_t* det_off, const double* det_box
                  int32_t n_area, const double* area_ranges, const double* empty_weight, uint8_t* flags,
                  int64_t flags_bytes, uint8_t* tp, double* fp, void* stream);
 
+/* The matching step of the PASCAL-VOC mAP (metrics/pascalvoc.py:84-170, VOCMApMetric.update; the metric both drivers
+ * build, train_yolov3.py:181 and detect_yolo3.py:183, and validate() feeds per batch, train_yolov3.py:434-490) for a batch
+ * of images on the device, one launch.  videoyolo_amd/metrics.py states the rule (voc_match_host); the kernel
+ * (csrc/voc_metric.hip) runs one 256-thread workgroup per image and gives the same values.  Needs no vy_net.
+ *
+ * Detections — device arrays as the detector returns them: det_box (batch, rows, 4) fp32 corners, det_label (batch, rows)
+ * fp32 class index, det_score (batch, rows) fp32, in any order; a row whose label is not >= 0 is padding wherever it lies.
+ * Ground truths — device arrays: gt_box (batch, n_gt, 4) fp32, gt_label (batch, n_gt) int32, ALREADY class-mapped, < 0 =
+ * skip, gt_difficult (batch, n_gt) bytes, non-zero = difficult, or NULL (none is).
+ * Per row: its candidate is the ground truth of its own label with the largest IoU (fp32, no +1 pixel offset, in
+ * pairwise_iou's operation order; the first index on a tie, a NaN IoU counting as the largest), or none when that IoU
+ * < iou_thresh (false for NaN).  best (batch, rows) int32: the candidate's index in the image's n_gt, or -1.
+ * flags (batch, rows) int8: -2 padding; 0 no candidate; -1 the candidate is difficult; else 1 unless another row of the image
+ * with the same candidate comes before this one (a higher score; at equal scores the lower row), then 0.  Every element of
+ * both outputs is written, in input row order.
+ * rows <= VY_VOC_ROWS_MAX per image: score and candidate of every row of an image are held in LDS, 8 bytes per row, 8 KiB
+ * at the limit.  n_gt is not limited.
+ * Checked before anything is launched, else VY_ERR_INVALID: null pointers (gt_difficult excepted), negative counts, rows
+ * above the limit, iou_thresh not finite.  batch == 0 or rows == 0: VY_OK without a launch.  Asynchronous on `stream`; no
+ * device memory of the library's, no copy, no synchronisation. */
+#define VY_VOC_ROWS_MAX 1024
+int vy_voc_match(int32_t batch, int32_t rows, int32_t n_gt, const float* det_box, const float* det_label,
+                 const float* det_score, const float* gt_box, const int32_t* gt_label, const uint8_t* gt_difficult,
+                 float iou_thresh, int32_t* best, int8_t* flags, void* stream);
+
 /* Prefetch target generation on the device: YOLOV3PrefetchTargetGenerator.forward,
  * models/definitions/yolo/yolo_target.py:31-148 (called per sample from the DataLoader transform,
  * transforms.py:259-277), for a whole batch.  gt_boxes (batch,num_gt,4) corner pixels of the

@@ -160,6 +160,13 @@ SIGNATURES.update({
                                     _vp, _vp, _i64, _vp, _vp, _vp]),
 })
 
+VY_VOC_ROWS_MAX = 1024
+
+SIGNATURES.update({
+    # the PASCAL-VOC metric's matching step (videoyolo_amd/metrics.py, csrc/voc_metric.hip)
+    "vy_voc_match": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+})
+
 _lib = None
 
 

@@ -11,7 +11,8 @@ were produced by running the reference's own class (mxnet stubbed out) — see
 tests/golden/make_voc_metric_golden.py.
 
 Accepts numpy arrays, torch tensors (any device) or lists of them (one per device, concatenated
-along the batch axis like utils/general.py:6-17 ``as_numpy``).
+along the batch axis like utils/general.py:6-17 ``as_numpy``).  float32 tensors on a GPU are matched there
+(``voc_match_host`` states the rule, csrc/voc_metric.hip applies it) and copied once, by ``get()``.
 """
 import numpy as np
 
@@ -38,23 +39,96 @@ def pairwise_iou(a, b):
     return inter / (area_a[:, None] + area_b[None, :] - inter)
 
 
+def voc_match_host(boxes, labels, scores, gt_boxes, gt_labels, gt_difficults, iou_thresh, return_best=False):
+    """The matching rule of the VOC metric for ONE image, row by row: ``VOCMApMetric._update_image`` restated per input
+    row, and the definition the device kernel (csrc/voc_metric.hip, vy_voc_match) is held to, value for value.
+
+    boxes (R, 4), labels (R), scores (R): the image's rows in any order, label < 0 = padding.  gt_boxes (M, 4), gt_labels
+    (M) already class-mapped, gt_difficults (M) or None.  Returns one int8 per row, in row order: 1 true positive, 0 false
+    positive, -1 ignored (matched a difficult ground truth), -2 not a detection (label < 0); with ``return_best`` also the
+    candidate of every row, an index into the M ground truths given, or -1.
+
+      rows kept: ground truths with label >= 0
+      candidate: g = argmax of pairwise_iou over the kept ground truths of the row's own label; the first index wins a
+        tie, a NaN IoU counts as the maximum (np.argmax); g = -1 when that maximum < iou_thresh, which is false for NaN
+      flag: g < 0 gives 0; a difficult g gives -1; else 1 if no row of the image with the same g comes before this one,
+        0 if one does.  Before = a higher score; at equal scores the lower row (``_update_image`` leaves equal scores to
+        an unstable argsort).
+      dtype: the arithmetic runs in the arrays' own dtype, as pairwise_iou does; iou_thresh is rounded to that dtype.
+    """
+    boxes, gt_boxes = np.asarray(boxes).reshape(-1, 4), np.asarray(gt_boxes).reshape(-1, 4)
+    labels, scores = np.asarray(labels).reshape(-1), np.asarray(scores).reshape(-1)
+    gt_labels = np.asarray(gt_labels).reshape(-1)
+    gdiff = np.zeros(len(gt_labels), bool) if gt_difficults is None else np.asarray(gt_difficults).reshape(-1) != 0
+    flags = np.full(len(labels), -2, np.int8)
+    best = np.full(len(labels), -1, np.int64)
+    det = np.flatnonzero(labels >= 0)
+    flags[det] = 0
+    dl = labels[det].astype(int)
+    gkeep = np.flatnonzero(gt_labels >= 0)
+    gl = gt_labels[gkeep].astype(int)
+    for c in np.unique(dl):
+        rows, gts = det[dl == c], gkeep[gl == c]
+        if len(gts) == 0:
+            continue
+        with np.errstate(divide='ignore', invalid='ignore'):
+            iou = pairwise_iou(boxes[rows], gt_boxes[gts])
+        g = iou.argmax(axis=1)
+        g[iou.max(axis=1) < iou.dtype.type(iou_thresh)] = -1
+        best[rows] = np.where(g >= 0, gts[g], -1)
+    hit = np.flatnonzero(best >= 0)
+    flags[hit[gdiff[best[hit]]]] = -1
+    claim = hit[~gdiff[best[hit]]]
+    claim = claim[np.lexsort((claim, -scores[claim].astype(np.float64)))]   # before first: higher score, then lower row
+    first = claim[np.unique(best[claim], return_index=True)[1]]              # the first claimant of every ground truth
+    flags[first] = 1
+    return (flags, best) if return_best else flags
+
+
+def _itemsize(dtype):
+    return np.dtype(dtype).itemsize
+
+
+def _is_gpu_f32(t):
+    import torch
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+
+
 class VOCMApMetric(object):
-    """Mean average precision, area under the monotone precision envelope (VOC 2010+ style)."""
+    """Mean average precision, area under the monotone precision envelope (VOC 2010+ style).
+
+    ``update`` on float32 tensors of one GPU (predictions and ground-truth boxes; labels and difficults of any numeric
+    dtype there; at most 1024 rows per image; ``class_map`` None or a sequence) matches them on the device (vy_voc_match)
+    on the current stream: nothing is copied to the host and nothing synchronises, the flags stay device tensors until
+    ``get()`` copies them once.  Everything else — numpy, other dtypes, tensors of several devices outside a list, more
+    rows, a dict ``class_map`` — takes the host path below, unchanged; both may feed one metric.
+    ``device_updates`` counts the launches since construction.  The one stated difference between the paths: among EQUAL
+    scores the device takes the lower row first, the host path's unstable argsort whatever the sort gives.  (And a
+    ground-truth label outside a sequence ``class_map`` is skipped on the device; on the host it is an IndexError.)"""
 
     def __init__(self, iou_thresh=0.5, class_names=None, class_map=None):
         self.iou_thresh = iou_thresh
         self.class_names = list(class_names) if class_names is not None else None
         self.class_map = class_map
         self.name = 'VOCMeanAP' if class_names is None else self.class_names + ['mAP']
+        self.device_updates = 0
+        self._class_luts = {}
         self.reset()
 
     def reset(self):
         self._n_pos = {}     # class -> number of non-difficult ground truths
         self._scores = {}    # class -> list of detection scores
         self._flags = {}     # class -> list of +1 (TP) / 0 (FP) / -1 (ignored: matched a difficult gt)
+        self._chunks = []    # per device update: (labels, scores, mapped gt labels, flags, gt difficults or None, rows)
 
     # ------------------------------------------------------------------ accumulation
     def update(self, pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults=None):
+        if self._update_device(pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults):
+            return
+        self._fold()         # keep the order of arrival
+        self._update_host(pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults)
+
+    def _update_host(self, pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults=None):
         pb, pl, ps, gb, gl = [_to_numpy(x) for x in (pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels)]
         gd = _to_numpy(gt_difficults) if gt_difficults is not None else None
         for i in range(len(pb)):
@@ -99,8 +173,107 @@ class VOCMApMetric(object):
                     flags.append(0 if taken[g] else 1)
                     taken[g] = True
 
+    # ------------------------------------------------------------------ accumulation on the device
+    def _update_device(self, pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults):
+        """Matches the batch on the device and returns True, or returns False: the call is the host path's."""
+        cm = self.class_map
+        if not (cm is None or isinstance(cm, (list, tuple, np.ndarray))):
+            return False
+        args = [VIDDetectionMetric._gather(x) for x in (pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels,
+                                                        gt_difficults)]
+        if not all(hasattr(x, "is_cuda") for x in args[:5]):
+            return False
+        import torch
+        pb, pl, ps, gb, gl, gd = args
+        if not all(_is_gpu_f32(x) for x in (pb, pl, ps, gb)):
+            return False
+        others = [gl] if gd is None else [gl, gd]
+        if not all(isinstance(x, torch.Tensor) and not x.is_complex() for x in others):
+            return False
+        dev = pb.device
+        if any(x.device != dev for x in (pl, ps, gb) + tuple(others)):
+            return False
+        from . import _lib
+        batch = int(pb.shape[0])
+        rows = int(np.prod(pl.shape[1:])) if batch else 0
+        n_gt = int(np.prod(gl.shape[1:])) if batch else 0
+        if rows > _lib.VY_VOC_ROWS_MAX or pb.numel() != batch * rows * 4 or ps.numel() != batch * rows or \
+                gb.numel() != batch * n_gt * 4 or gl.shape[0] != batch or (gd is not None and gd.numel() != batch * n_gt):
+            return False
+        if batch == 0:
+            return True
+        import ctypes
+        gl = gl.reshape(batch, n_gt)
+        if cm is None:
+            mapped = torch.where(gl >= 0, gl.to(torch.int32), -1)
+        else:
+            lut = self._class_luts.get(dev)
+            if lut is None:
+                lut = self._class_luts[dev] = torch.tensor([int(v) for v in cm], dtype=torch.int32).to(dev)
+            n = len(lut)
+            idx = gl.to(torch.int64)                                  # a negative label counts from the end, as on the host
+            inside = (idx >= -n) & (idx < n)
+            if n:
+                mapped = torch.where(inside, lut[torch.where(inside, idx, 0)], -1)
+            else:
+                mapped = torch.full_like(idx, -1, dtype=torch.int32)
+        mapped = mapped.contiguous()
+        diff = None if gd is None else (gd.reshape(batch, n_gt) != 0).to(torch.uint8).contiguous()
+        pl, ps = pl.reshape(batch, rows).contiguous(), ps.reshape(batch, rows).contiguous()
+        if rows:
+            lib = _lib.load()
+            pb, gb = pb.reshape(batch, rows, 4).contiguous(), gb.reshape(batch, n_gt, 4).contiguous()
+            best = torch.empty((batch, rows), dtype=torch.int32, device=dev)
+            flags = torch.empty((batch, rows), dtype=torch.int8, device=dev)
+            spare = best                                              # a valid address for arrays without elements
+            devp = lambda t: ctypes.c_void_p((t if t.numel() else spare).data_ptr())     # noqa: E731
+            with torch.cuda.device(dev):
+                _lib.check(lib.vy_voc_match(batch, rows, n_gt, devp(pb), devp(pl), devp(ps), devp(gb), devp(mapped),
+                                            None if diff is None else devp(diff), float(self.iou_thresh), devp(best),
+                                            devp(flags), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            self.device_updates += 1
+        else:
+            flags = torch.empty((batch, 0), dtype=torch.int8, device=dev)
+        self._chunks.append((pl.reshape(-1), ps.reshape(-1), mapped.reshape(-1), flags.reshape(-1),
+                             None if diff is None else diff.reshape(-1), rows))
+        return True
+
+    def _fold(self):
+        """Folds the device chunks into _scores / _flags / _n_pos: one copy to the host, then whole-array numpy.  A class
+        gets its entries as _update_image makes them: image after image, a class's rows by descending score."""
+        if not self._chunks:
+            return
+        import torch
+        chunks, self._chunks = self._chunks, []
+        dev = chunks[0][0].device
+        kinds = (np.float32, np.float32, np.int32, np.int8, np.uint8)    # labels, scores, gt labels, flags, gt difficults
+        chunks = [c if c[4] is not None else c[:4] + (torch.zeros_like(c[2], dtype=torch.uint8), c[5]) for c in chunks]
+        # kind by kind, the 4-byte kinds first: every host view below is aligned
+        raw = torch.cat([torch.cat([c[k].to(dev).reshape(-1) for c in chunks]).view(torch.uint8) for k in range(5)]).cpu().numpy()
+        host, at = {}, 0
+        for k in range(5):
+            for i, c in enumerate(chunks):
+                size = c[k].numel() * _itemsize(kinds[k])
+                host[k, i] = raw[at:at + size].view(kinds[k])
+                at += size
+        for i, c in enumerate(chunks):
+            labels, scores, glabels, flags, gdiff = (host[k, i] for k in range(5))
+            det = np.flatnonzero(flags != -2)
+            dl = labels[det].astype(int)
+            order = np.lexsort((-scores[det].astype(np.float64), det // max(c[5], 1), dl))   # class, image, score
+            det, dl = det[order], dl[order]
+            gkeep = glabels >= 0
+            counts = np.bincount(glabels[gkeep & (gdiff == 0)])
+            for cls in np.unique(np.concatenate([dl, glabels[gkeep]]).astype(int)):
+                cls = int(cls)
+                lo, hi = np.searchsorted(dl, cls, 'left'), np.searchsorted(dl, cls, 'right')
+                self._n_pos[cls] = self._n_pos.get(cls, 0) + (int(counts[cls]) if cls < len(counts) else 0)
+                self._scores.setdefault(cls, []).extend(scores[det[lo:hi]])
+                self._flags.setdefault(cls, []).extend(flags[det[lo:hi]].tolist())
+
     # ------------------------------------------------------------------ evaluation
     def _curves(self):
+        self._fold()
         n_cls = max(self._n_pos) + 1 if self._n_pos else 0
         rec, prec = [None] * n_cls, [None] * n_cls
         for c in self._n_pos:
