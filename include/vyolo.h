@@ -473,6 +473,41 @@ int vy_voc_match(int32_t batch, int32_t rows, int32_t n_gt, const float* det_box
                  const float* det_score, const float* gt_box, const int32_t* gt_label, const uint8_t* gt_difficult,
                  float iou_thresh, int32_t* best, int8_t* flags, void* stream);
 
+/* The matching step of the COCO detection metric (metrics/mscoco.py, COCODetectionMetric: the second metric the detect
+ * driver builds by default, detect_yolo3.py:185; the reference hands the evaluation to pycocotools' COCOeval, iouType
+ * 'bbox', whose per-image rule is restated in videoyolo_amd/metrics.py, coco_match_host, [UPSTREAM-RECALLED]) for a batch
+ * of images on the device, one launch per VY_COCO_CHUNK images.  The kernel (csrc/coco_metric.hip) runs one 256-thread
+ * workgroup per image and gives coco_match_host's values.  Needs no vy_net.
+ *
+ * Detections — device arrays: det_xywh (batch, rows, 4) float64 [x, y, w, h], det_cat (batch, rows) int32 category index
+ * (a position in the ground-truth file's sorted category ids), < 0 = the row takes no part wherever it lies, det_score
+ * (batch, rows) float64, in any order.
+ * Ground truths — device tables over a whole dataset of n_images images: gt_xywh (G, 4) float64, gt_cat (G) int32 category
+ * index (< 0: never matched), gt_area (G) float64 the file's area, gt_crowd (G) bytes, gt_id (G) int64 the annotation's
+ * id.  Row r owns ground truths gt_off[r] .. gt_off[r + 1]; image i of the batch is row gt_image[i].  iou_thrs (n_thr)
+ * and area_ranges (n_area, 2), [lo, hi] with both ends inside, are float64.  gt_image, gt_off, iou_thrs and area_ranges
+ * are HOST arrays and travel in the kernel arguments.
+ * Per image and category the kept rows are taken in stable descending score order (a NaN last), the first max_det of
+ * them; in every (area range, threshold) pair they claim ground truths of their category as COCOeval.evaluateImg does.
+ * rank (batch, rows) int32: the row's position in that order, -1 for a row that takes no part or whose position is
+ * >= max_det.  flags (batch, rows, n_area, n_thr) bytes: bit 0 the row is matched to an annotation whose id is not 0,
+ * bit 1 the row is ignored; 0 where rank is -1.  Every element of both is written, in input row order.
+ * taken: device scratch of taken_bytes >= (ground truths of the batch's images) * n_area * n_thr bytes; the kernel clears
+ * what it uses.  rows <= VY_COCO_ROWS_MAX per image (score, category and order table in LDS, 16 bytes per row).
+ * Checked before anything is launched, else VY_ERR_INVALID: null pointers, negative counts, rows above the limit,
+ * 1..VY_COCO_MAX_THRS finite thresholds, 1..VY_COCO_MAX_RANGES ranges with lo <= hi, gt_image inside the table, ascending
+ * gt_off at every row used, enough taken bytes.  batch == 0 or rows == 0: VY_OK without a launch.  Asynchronous on
+ * `stream`; no device memory of the library's, no copy, no synchronisation. */
+#define VY_COCO_ROWS_MAX 1024
+#define VY_COCO_MAX_THRS 16
+#define VY_COCO_MAX_RANGES 8
+#define VY_COCO_CHUNK 128
+int vy_coco_match(int32_t batch, int32_t rows, const double* det_xywh, const int32_t* det_cat, const double* det_score,
+                  const int32_t* gt_image, int32_t n_images, const int64_t* gt_off, const double* gt_xywh,
+                  const int32_t* gt_cat, const double* gt_area, const uint8_t* gt_crowd, const int64_t* gt_id,
+                  int32_t n_thr, const double* iou_thrs, int32_t n_area, const double* area_ranges, int32_t max_det,
+                  uint8_t* taken, int64_t taken_bytes, int32_t* rank, uint8_t* flags, void* stream);
+
 /* Prefetch target generation on the device: YOLOV3PrefetchTargetGenerator.forward,
  * models/definitions/yolo/yolo_target.py:31-148 (called per sample from the DataLoader transform,
  * transforms.py:259-277), for a whole batch.  gt_boxes (batch,num_gt,4) corner pixels of the

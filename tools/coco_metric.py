@@ -1,0 +1,248 @@
+"""Cost of the COCO metric's device path (videoyolo_amd/metrics.py COCODetectionMetric.update on device tensors,
+csrc/coco_metric.hip) next to the detecting it scores and next to the host path.  Written to --out (default
+profiles/coco_metric.txt).  In a fresh child process on the GPU:
+
+  (a) the device time of update() for 64 frames x 100 rows x 8 ground truths by events, ALTERNATING with the batch-64
+      detect step at 416 x 416 of a single-frame net in the same process (same clocks), --rounds rounds;
+  (c) the host path's update() on the same device tensors, by the wall clock, copy to the host included;
+  (d) a synthetic validation set of --images images end to end (every update() in batches of 64, then get()) on both
+      paths, by the wall clock, and that the two get() results are equal.
+With --stats a second child runs such updates under `rocprofv3 --kernel-trace --stats` (no counters in that run) and
+  (b) the kernel's own mean time is added.
+
+    python tools/coco_metric.py [--stats] [--images 1024] [--out PATH]
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+CHILD_TIMEOUT_S = 600
+N_CLS = 20
+
+
+class Synthetic(object):
+    """`images` images of size x size with 1..n_gt ground truths each (a tenth crowds), and float32 rows
+    (images, rows, 4), (images, rows, 1), (images, rows, 1) that are jittered copies of them or clutter, a tenth padding."""
+
+    def __init__(self, seed, images, rows=100, n_gt=8, size=416):
+        rng = np.random.default_rng(seed)
+        self.sample_ids = list(range(images))
+        self.classes = ["c%02d" % c for c in range(N_CLS)]
+        xy = rng.uniform(0, size * 0.6, (images, n_gt, 2))
+        gb = np.concatenate([xy, xy + rng.uniform(16, size * 0.4, (images, n_gt, 2))], 2)
+        gl = rng.integers(0, N_CLS, (images, n_gt))
+        count = rng.integers(1, n_gt + 1, images)
+        anns = []
+        for i in range(images):
+            for g in range(count[i]):
+                x1, y1, x2, y2 = gb[i, g].tolist()
+                anns.append({'id': len(anns), 'image_id': i, 'category_id': int(gl[i, g]), 'bbox': [x1, y1, x2 - x1, y2 - y1],
+                             'area': (x2 - x1) * (y2 - y1), 'iscrowd': int(rng.random() < 0.1)})
+        self.coco = type('Coco', (), {'dataset': {'images': [{'id': i} for i in self.sample_ids], 'annotations': anns,
+                                                    'categories': [{'id': c} for c in range(N_CLS)]}})()
+        src = rng.integers(0, n_gt, (images, rows))
+        boxes = np.take_along_axis(gb, src[:, :, None], 1) + rng.normal(0, 6.0, (images, rows, 4))
+        labels = np.take_along_axis(gl, src, 1).astype(np.float64)
+        clutter = (rng.random((images, rows)) < 0.3) | (src >= count[:, None])
+        cxy = rng.uniform(0, size * 0.6, (images, rows, 2))
+        boxes[clutter] = np.concatenate([cxy, cxy + rng.uniform(16, size * 0.4, (images, rows, 2))], 2)[clutter]
+        labels[clutter] = rng.integers(0, N_CLS, int(clutter.sum()))
+        scores = np.round(rng.random((images, rows)), 2)                   # hundredths: ties inside and across images
+        pad = rng.random((images, rows)) < 0.1
+        boxes[pad], labels[pad], scores[pad] = -1, -1, -1
+        f = np.float32
+        self.rows = (boxes.astype(f), labels.astype(f)[:, :, None], scores.astype(f)[:, :, None])
+
+
+def _timed(torch, fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def measure(args):
+    import warnings
+    import torch
+    import videoyolo_amd as vy
+    from videoyolo_amd.metrics import COCODetectionMetric
+    warnings.simplefilter("ignore")
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))  # noqa: E731
+    out = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds}
+
+    # ---- (a) update() for 64 frames x 100 rows x 8 ground truths, alternating with the detect step
+    batch = 64
+    data = Synthetic(1, batch * args.updates)
+    sets = [tuple(torch.from_numpy(a[u * batch:(u + 1) * batch]).to(dev) for a in data.rows) for u in range(args.updates)]
+    metric = COCODetectionMetric(data)
+    state = {"u": 0}
+
+    def update():
+        u = state["u"] % args.updates
+        if u == 0:
+            metric.reset()
+        metric.update(*sets[u])
+        state["u"] += 1
+
+    for _ in range(args.updates):
+        update()
+    torch.cuda.synchronize()
+    assert metric.device_updates == args.updates
+    print("updates warmed up", file=sys.stderr, flush=True)
+    if args.updates_only:
+        return out
+    net = vy.yolo3_darknet53(data.classes, pretrained_base=False)
+    net.initialize(init="synthetic", seed=233, obj_bias=-2.0)
+    net.collect_params().reset_ctx(dev)
+    net.set_nms(0.45, 400, 100)
+    upd_ms, det_ms = [], []
+    x = torch.randn((batch, 3, 416, 416), device=dev)
+    for _ in range(2):
+        net(x)
+    torch.cuda.synchronize()
+    for _ in range(args.rounds):
+        upd_ms.append(_timed(torch, update, args.updates))
+        det_ms.append(_timed(torch, lambda: net(x), args.steps))
+    t0 = time.perf_counter()
+    for _ in range(args.updates):
+        update()
+    call_ms = (time.perf_counter() - t0) / args.updates * 1e3      # the host's side of a call: nothing waits for the device
+    torch.cuda.synchronize()
+    del net, x
+
+    # ---- (c) the host path on the same device tensors: copy, then numpy
+    host = COCODetectionMetric(data)
+    host_ms = []
+    for _ in range(args.rounds):
+        host.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for u in range(args.updates):
+            host.update(*[t.cpu().numpy() for t in sets[u]])
+        host_ms.append((time.perf_counter() - t0) / args.updates * 1e3)
+    metric.reset()
+    for u in range(args.updates):
+        metric.update(*sets[u])
+    same_small = metric.get() == host.get() and np.array_equal(metric.precision, host.precision)
+    out["update"] = {"batch": batch, "rows": 100, "n_gt": 8, "ms": round(med(upd_ms), 4), "ms_rounds": [round(v, 4) for v in upd_ms],
+                     "call_ms": round(call_ms, 3), "host_path_ms": round(med(host_ms), 2),
+                     "host_path_ms_rounds": [round(v, 2) for v in host_ms], "equal": bool(same_small),
+                     "detect_ms": round(med(det_ms), 3), "detect_ms_rounds": [round(t, 3) for t in det_ms]}
+    print("update and detect steps timed: %s" % json.dumps(out["update"]), file=sys.stderr, flush=True)
+
+    # ---- (d) a validation set end to end on both paths
+    val = Synthetic(99, args.images)
+    rows = [torch.from_numpy(a).to(dev) for a in val.rows]
+    res, arrays = {}, {}
+    for path in ("device", "host"):
+        m = COCODetectionMetric(val)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for lo in range(0, args.images, batch):
+            part = [a[lo:lo + batch] for a in rows]
+            m.update(*(part if path == "device" else [t.cpu().numpy() for t in part]))
+        t1 = time.perf_counter()
+        res[path] = m.get()
+        t2 = time.perf_counter()
+        arrays[path] = (m.precision, m.recall)
+        out["val_" + path] = {"update_s": round(t1 - t0, 4), "get_s": round(t2 - t1, 4), "launches": m.device_updates}
+    equal = res["device"] == res["host"] and all(np.array_equal(a, b) for a, b in zip(arrays["device"], arrays["host"]))
+    out["val"] = {"images": args.images, "equal": bool(equal), "mAP": res["device"][1][-1]}
+    return out
+
+
+def kernel_stats():
+    out = tempfile.mkdtemp(prefix="coco_metric_")
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable,
+           os.path.abspath(__file__), "--child", "--updates-only"]
+    try:
+        p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True,
+                           timeout=CHILD_TIMEOUT_S)
+    except subprocess.TimeoutExpired:
+        return {"error": "rocprofv3 run did not finish within %d s" % CHILD_TIMEOUT_S}
+    if p.returncode != 0:
+        return {"error": "rocprofv3 run failed (%d)" % p.returncode, "tail": p.stdout[-1500:]}
+    for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
+        with open(path) as f:
+            for r in csv.DictReader(f):
+                if "coco_match_kernel" in (r.get("Name") or r.get("KernelName") or ""):
+                    return {"calls": int(r["Calls"]), "mean_us": round(float(r["AverageNs"]) / 1e3, 2),
+                            "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2), "max_us": round(float(r.get("MaxNs", 0)) / 1e3, 2)}
+    return {"error": "no coco_match_kernel row in the kernel statistics"}
+
+
+def report(res, stats):
+    u, v = res["update"], res["val"]
+    d416 = u["detect_ms"]
+    lines = ["COCO detection metric: cost of the device path (tools/coco_metric.py)", "",
+             "%s; device events, median of %d rounds, update() and detect steps alternating in one process" % (
+                 res["device"], res["rounds"]),
+             "Before this path existed the library had no COCO metric at all: there is no earlier figure to compare with.", "",
+             "(a) update(), %d frames x %d rows x %d ground truths (casts, lookup, xywh, vy_coco_match; 4 x 10 chains): %.4f ms "
+             "(rounds %s)" % (u["batch"], u["rows"], u["n_gt"], u["ms"], u["ms_rounds"]),
+             "    the host's side of one call: %.3f ms (nothing waits for the device)" % u["call_ms"],
+             "    detect step, batch %d, 416 x 416: %.3f ms (%.0f frames/s; rounds %s)" % (
+                 u["batch"], d416, 1e3 * u["batch"] / d416, u["detect_ms_rounds"]),
+             "    update / detect step at 416: %.3f%% (bar: 2%%) -> %s" % (
+                 100 * u["ms"] / d416, "within" if u["ms"] <= 0.02 * d416 else "MISSED")]
+    if stats is not None:
+        lines.append("(b) rocprofv3 --kernel-trace --stats, coco_match_kernel alone over such updates: %s" % json.dumps(stats))
+    lines += ["(c) the host path's update() on the same rows (copy to the host, then numpy), wall clock: %.2f ms per "
+              "batch (rounds %s) = %.0f us per image; results equal: %s" % (
+                  u["host_path_ms"], u["host_path_ms_rounds"], 1e3 * u["host_path_ms"] / u["batch"], u["equal"]),
+              "    host path / device path per batch: %.0fx by device time, %.0fx by the caller's time" % (
+                  u["host_path_ms"] / u["ms"], u["host_path_ms"] / u["call_ms"]),
+              "(d) synthetic validation set, %d images x %d rows x 1..%d ground truths in batches of %d, wall clock:" % (
+                  v["images"], u["rows"], u["n_gt"], u["batch"])]
+    for path in ("device", "host"):
+        r = res["val_" + path]
+        lines.append("    %-6s path: update() calls %.3f s, get() %.3f s, total %.3f s (%d launches)" % (
+            path, r["update_s"], r["get_s"], r["update_s"] + r["get_s"], r["launches"]))
+    lines.append("    get() results, precision and recall equal: %s (mean AP x 100: %s)" % (v["equal"], v["mAP"]))
+    return "\n".join(lines) + "\n"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=1024)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--updates", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--stats", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "coco_metric.txt"))
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--updates-only", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        print(json.dumps(measure(args)))
+        return
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--images", str(args.images), "--rounds",
+                        str(args.rounds), "--updates", str(args.updates), "--steps", str(args.steps)], cwd=ROOT,
+                       stdout=subprocess.PIPE, universal_newlines=True, timeout=CHILD_TIMEOUT_S)  # a hung child ends the tool
+    if p.returncode != 0:
+        sys.exit(p.returncode)
+    res = json.loads(p.stdout.strip().splitlines()[-1])
+    text = report(res, kernel_stats() if args.stats else None)
+    with open(args.out, "w") as f:
+        f.write(text)
+    print(text)
+    if not (res["update"]["equal"] and res["val"]["equal"]):
+        sys.exit("device and host paths differ")
+
+
+if __name__ == "__main__":
+    main()

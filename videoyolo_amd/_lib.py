@@ -167,6 +167,16 @@ SIGNATURES.update({
     "vy_voc_match": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
 })
 
+VY_COCO_ROWS_MAX = 1024
+VY_COCO_MAX_THRS, VY_COCO_MAX_RANGES = 16, 8
+VY_COCO_CHUNK = 128
+
+SIGNATURES.update({
+    # the COCO metric's matching step (videoyolo_amd/metrics.py, csrc/coco_metric.hip)
+    "vy_coco_match": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
+                                     _i32, _vp, _i64, _vp, _vp, _vp]),
+})
+
 _lib = None
 
 

@@ -13,6 +13,9 @@ tests/golden/make_voc_metric_golden.py.
 Accepts numpy arrays, torch tensors (any device) or lists of them (one per device, concatenated
 along the batch axis like utils/general.py:6-17 ``as_numpy``).  float32 tensors on a GPU are matched there
 (``voc_match_host`` states the rule, csrc/voc_metric.hip applies it) and copied once, by ``get()``.
+
+Further down: the ImageNet-VID motion / area mAP (``VIDDetectionMetric``) and the COCO detection metric
+(``COCODetectionMetric``), each with its matching rule stated on the host and applied on the device the same way.
 """
 import numpy as np
 
@@ -698,4 +701,547 @@ class VIDDetectionMetric(object):
         for c, cls_name in enumerate(self.dataset.classes):
             names.append(cls_name)
             values.append('{:.1f}'.format(100 * ap[0, 0, c]))
+        return names, values
+
+
+# ====================================================================================================================
+# COCO detection metric (SURVEY.md §8f): metrics/mscoco.py in the reference, the second metric its detect driver builds by
+# default (detect_yolo3.py:53, :185) on every dataset, each of which writes a COCO-style ground-truth file for it
+# (build_coco_json).  The reference hands the evaluation to pycocotools' COCOeval (iouType 'bbox', useCats 1), which
+# cannot be run here: everything below that restates COCOeval is [UPSTREAM-RECALLED] — evaluateImg in coco_match_host,
+# accumulate in coco_accumulate, summarize in COCODetectionMetric._summarize.  tests/golden/make_coco_metric_golden.py
+# records the real COCOeval's values on a machine that has it.
+# ====================================================================================================================
+COCO_IOU_THRS = np.linspace(.5, .95, 10)
+COCO_REC_THRS = np.linspace(0, 1, 101)
+COCO_MAX_DETS = (1, 10, 100)
+COCO_AREA_RANGES = ((0, 1e10), (0, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e10))
+COCO_AREA_NAMES = ('all', 'small', 'medium', 'large')
+_COCO_LUT_MAX = 1 << 20
+
+
+def _coco_iou(d, g, crowd):
+    """[UPSTREAM-RECALLED] maskUtils.iou on xywh boxes: one detection against (G, 4) ground truths, float64."""
+    w = np.minimum(d[0] + d[2], g[:, 0] + g[:, 2]) - np.maximum(d[0], g[:, 0])
+    h = np.minimum(d[1] + d[3], g[:, 1] + g[:, 3]) - np.maximum(d[1], g[:, 1])
+    w, h = np.where(w <= 0, 0.0, w), np.where(h <= 0, 0.0, h)
+    inter = w * h
+    da = d[2] * d[3]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return inter / np.where(crowd, da, (da + g[:, 2] * g[:, 3]) - inter)
+
+
+def coco_match_host(det_xywh, det_cat, det_score, gt_xywh, gt_cat, gt_area, gt_crowd, gt_id, iou_thrs, area_ranges,
+                    max_det):
+    """[UPSTREAM-RECALLED] The matching rule of the COCO metric for ONE image, row by row: ``COCOeval.evaluateImg``
+    (iouType 'bbox') for every category, area range and IoU threshold at once, and the definition the device kernel
+    (csrc/coco_metric.hip, vy_coco_match) is held to, value for value.
+
+    det_xywh (R, 4), det_cat (R) category index, < 0 = the row takes no part, det_score (R): the image's rows in any
+    order.  gt_xywh (G, 4), gt_cat (G), gt_area (G) the file's area, gt_crowd (G), gt_id (G) the annotations' ids.
+    iou_thrs (T), area_ranges (A, 2) [lo, hi], both ends inside.  Returns, in input row order, ``rank`` (R) int32 — the
+    row's position among the image's kept rows of its category in the stable descending score order
+    (``argsort(-score, kind='mergesort')``), -1 for a row that takes no part or a position >= max_det — and ``flags``
+    (R, A, T) uint8: bit 0 ``dtm != 0``, bit 1 ``dtIg``; 0 where rank is -1.
+
+    All float64:
+      iou: w = min(dx + dw, gx + gw) - max(dx, gx), 0 if w <= 0, h likewise; i = w * h; u = dw * dh for a crowd, else
+        (dw * dh + gw * gh) - i; iou = i / u
+      per (category, area range): a ground truth is ignored when it is a crowd or its area < lo or > hi; the ones that are
+        not ignored come first (stable)
+      per threshold t, the category's first max_det rows in score order: best = min(t, 1 - 1e-10), m = none; over the
+        ground truths in that order: one taken at this (range, t) that is no crowd is passed over; with m set and not
+        ignored, the first ignored one ends the walk; iou < best is passed over; else best = iou, m = it.  With m set the
+        row's dtIg is m's, its dtm is m's ID, and m is taken
+      afterwards dtIg |= dtm == 0 and the row's own area dw * dh < lo or > hi
+    ``dtm == 0`` is COCOeval's test for "unmatched": a row matched to the annotation whose id is 0 takes that ground truth
+    and its ignore flag, and counts as unmatched from then on.
+    """
+    d = np.asarray(det_xywh, np.float64).reshape(-1, 4)
+    dc = np.asarray(det_cat).reshape(-1).astype(np.int64)
+    ds = np.asarray(det_score, np.float64).reshape(-1)
+    g = np.asarray(gt_xywh, np.float64).reshape(-1, 4)
+    gc = np.asarray(gt_cat).reshape(-1).astype(np.int64)
+    ga = np.asarray(gt_area, np.float64).reshape(-1)
+    gcrowd = np.asarray(gt_crowd).reshape(-1) != 0
+    gid = np.asarray(gt_id).reshape(-1).astype(np.int64)
+    thr = np.asarray(iou_thrs, np.float64).reshape(-1)
+    ar = np.asarray(area_ranges, np.float64).reshape(-1, 2)
+    n_r, n_a, n_t = len(dc), len(ar), len(thr)
+    rank = np.full(n_r, -1, np.int32)
+    flags = np.zeros((n_r, n_a, n_t), np.uint8)
+    kept = np.flatnonzero(dc >= 0)
+    kept = kept[np.argsort(-ds[kept], kind='mergesort')]
+    start = np.minimum(thr, 1 - 1e-10)
+    floor = start.min() if n_t else 0.0
+    g_ig = gcrowd[None, :] | (ga[None, :] < ar[:, :1]) | (ga[None, :] > ar[:, 1:])               # (A, G)
+    d_area = d[:, 2] * d[:, 3]
+    for c in np.unique(dc[kept]):
+        rows = kept[dc[kept] == c][:max_det]
+        rank[rows] = np.arange(len(rows))
+        gs = np.flatnonzero(gc == c)
+        ig, crowd, named = g_ig[:, gs], gcrowd[gs], gid[gs] != 0
+        taken = np.zeros((n_a, n_t, len(gs)), bool)
+        for r in rows:   # the chain: sequential in rows and ground truths, whole-array in (range, threshold)
+            iou = _coco_iou(d[r], g[gs], crowd)
+            best = np.tile(start, (n_a, 1))
+            m = np.full((n_a, n_t), -1, np.int64)
+            for second in (False, True):
+                still = m < 0        # the walk reaches the ignored ones only where none of the others matched
+                for j in np.flatnonzero(~(iou < floor)):
+                    cond = (ig[:, j] == second)[:, None] & still & ~(iou[j] < best) & (~taken[:, :, j] | crowd[j])
+                    best[cond], m[cond] = iou[j], j
+            hit = m >= 0
+            mm = np.where(hit, m, 0)
+            a_idx = np.arange(n_a)[:, None]
+            dt_ig = hit & ig[a_idx, mm] if len(gs) else np.zeros((n_a, n_t), bool)
+            matched = hit & named[mm] if len(gs) else np.zeros((n_a, n_t), bool)
+            if len(gs):
+                aa, tt = np.nonzero(hit)
+                taken[aa, tt, m[aa, tt]] = True
+            outside = (d_area[r] < ar[:, 0]) | (d_area[r] > ar[:, 1])
+            dt_ig = dt_ig | (~matched & outside[:, None])
+            flags[r] = matched.astype(np.uint8) | (dt_ig.astype(np.uint8) << 1)
+    return rank, flags
+
+
+def coco_accumulate(image, cat, score, rank, flags, npig, rec_thrs, max_dets):
+    """[UPSTREAM-RECALLED] ``COCOeval.accumulate`` over whole arrays.  One entry per detection row that took part
+    (rank >= 0): image (N) its image's position among the evaluated images, cat (N) category index, score (N), rank (N)
+    and flags (N, A, T) as coco_match_host gives them; npig (K, A) the ground truths not ignored per category and range.
+    Returns ``precision`` (T, R, K, A, M) and ``recall`` (T, K, A, M), -1 where npig is 0.
+
+    Per category, range and max_dets entry md: the rows with rank < md — image after image, by rank inside an image —
+    sorted by -score (stable); tp = dtm != 0 and not dtIg, fp = dtm == 0 and not dtIg, summed cumulatively as float;
+    rc = tp / npig, pr = tp / (fp + tp + spacing(1)); recall = rc[-1] (0 without rows); pr made non-increasing from the
+    right; precision[r] = pr[searchsorted(rc, rec_thrs[r], 'left')], the assignment stopping at the first index past the
+    end and leaving zeros."""
+    image, cat, rank = np.asarray(image), np.asarray(cat), np.asarray(rank)
+    score = np.asarray(score, np.float64)
+    rec_thrs = np.asarray(rec_thrs, np.float64)
+    n_k, n_a = npig.shape
+    n_t, n_r, n_m = flags.shape[2], len(rec_thrs), len(max_dets)
+    precision = -np.ones((n_t, n_r, n_k, n_a, n_m))
+    recall = -np.ones((n_t, n_k, n_a, n_m))
+    order = np.lexsort((rank, image, -score, cat))       # category; then -score, ties by image and rank: the stable sort
+    cat_s, rank_s = cat[order], rank[order]
+    eps = np.spacing(1)
+    for k in range(n_k):
+        if not npig[k].any():
+            continue
+        idx = order[np.searchsorted(cat_s, k, 'left'):np.searchsorted(cat_s, k, 'right')]
+        rk = rank[idx]
+        for mi, md in enumerate(max_dets):
+            sel = idx[rk < md]
+            f = flags[sel]                               # (n, A, T)
+            n = len(sel)
+            for a in range(n_a):
+                if npig[k, a] == 0:
+                    continue
+                tp = np.cumsum(f[:, a, :] == 1, axis=0).astype(np.float64)        # matched and not ignored
+                fp = np.cumsum(f[:, a, :] == 0, axis=0).astype(np.float64)        # unmatched and not ignored
+                rc = tp / npig[k, a]
+                pr = tp / (fp + tp + eps)
+                pr = np.maximum.accumulate(pr[::-1], axis=0)[::-1]
+                for t in range(n_t):
+                    recall[t, k, a, mi] = rc[-1, t] if n else 0
+                    q = np.zeros(n_r)
+                    inds = np.searchsorted(rc[:, t], rec_thrs, side='left')
+                    past = np.flatnonzero(inds >= n)
+                    stop = past[0] if len(past) else n_r
+                    q[:stop] = pr[inds[:stop], t]
+                    precision[t, :, k, a, mi] = q
+    return precision, recall
+
+
+class COCODetectionMetric(object):
+    """The COCO bbox metric: the reference's ``COCODetectionMetric`` (metrics/mscoco.py), same ``update`` / ``get`` /
+    ``reset`` and ``get()`` strings, with the evaluation pycocotools does for the reference restated here
+    ([UPSTREAM-RECALLED]: coco_match_host, coco_accumulate, _summarize).
+
+    ``dataset`` is duck-typed: ``sample_ids``, ``classes``, ``build_coco_json()`` -> the path of a COCO-style ground-truth
+    file (or ``dataset.coco.dataset``, the loaded dict), ``image_size(id)`` -> (width, height) when ``data_shape`` is
+    given, and optionally ``contiguous_id_to_json``.  The ground-truth tables are built once, here.  Per annotation
+    ``image_id``, ``category_id``, ``bbox`` (xywh), ``area`` (the file's), ``iscrowd`` and ``id`` are read; an ``ignore``
+    key has no effect.  All images of the file are evaluated, in sorted id order; category k is the k-th of the file's
+    sorted category ids.
+
+    ``update`` takes a batch's images in ``sorted(dataset.sample_ids)`` order by a running counter, as the reference does;
+    ``sid`` (one id per image) names them instead.  Rows with label < 0, a label outside ``contiguous_id_to_json`` or
+    score < score_thresh are dropped; with ``data_shape`` (h, w) boxes are scaled to the image's own size; then
+    w = x2 - (x1 - 1), h likewise (the reference's +1).  float32 tensors of one GPU with at most 1024 rows per image are
+    matched on the device (vy_coco_match) on the current stream: the casts, the scale gather, the xywh step and the label
+    lookup are torch calls, nothing is copied to the host and nothing synchronises; the outputs stay device tensors until
+    ``get()`` copies them once.  Everything else takes the host path (coco_match_host).  Both may feed one metric, in any
+    order, and give identical results: every order in the rule is a stable one.  ``device_updates`` counts the launches.
+
+    Where this differs from the reference, on purpose: ``save_prefix`` may be None (nothing is written); a ``sid`` or a
+    sample id the ground-truth file does not have, a repeated one, or more images than the dataset has raise
+    ``ValueError``; thresholds, ranges and max_dets are constructor keywords (defaults: COCO's); category ids and label
+    keys lie in [0, 2**20).
+
+    After ``get()``: ``metric.stats`` (12), ``metric.precision`` (T, 101, K, A, M), ``metric.recall`` (T, K, A, M).
+    """
+
+    def __init__(self, dataset, save_prefix=None, use_time=True, cleanup=False, score_thresh=0.05, data_shape=None,
+                 iou_thrs=COCO_IOU_THRS, area_ranges=COCO_AREA_RANGES, max_dets=COCO_MAX_DETS):
+        self.name = 'COCOMeanAP'
+        self.dataset = dataset
+        self._img_ids = sorted(dataset.sample_ids)
+        self._cleanup = cleanup
+        self._score_thresh = float(score_thresh)
+        if isinstance(data_shape, (tuple, list)):
+            assert len(data_shape) == 2, "Data shape must be (height, width)"
+        elif not data_shape:
+            data_shape = None
+        else:
+            raise ValueError("data_shape must be None or tuple of int as (height, width)")
+        self._data_shape = data_shape
+        self._thr = np.array(iou_thrs, np.float64).reshape(-1)
+        self._ar = np.array([list(r) for r in area_ranges], np.float64).reshape(-1, 2)
+        self._max_dets = [int(m) for m in max_dets]
+        self._rec_thrs = COCO_REC_THRS
+        if not (1 <= len(self._thr) <= 16 and 1 <= len(self._ar) <= 8):
+            raise ValueError("between 1 and 16 IoU thresholds and 1 and 8 area ranges")
+        if not np.isfinite(self._thr).all() or not (self._ar[:, 0] <= self._ar[:, 1]).all():
+            raise ValueError("a threshold that is not finite or a range with lo > hi")
+        if not self._max_dets or min(self._max_dets) < 0 or sorted(self._max_dets) != self._max_dets:
+            raise ValueError("max_dets must ascend")
+        self._filename = None
+        if save_prefix is not None:
+            import datetime
+            import os
+            t = datetime.datetime.now().strftime('_%Y_%m_%d_%H_%M_%S') if use_time else ''
+            self._filename = os.path.abspath(os.path.expanduser(save_prefix) + t + '.json')
+            try:
+                open(self._filename, 'w').close()
+            except IOError as e:
+                raise RuntimeError("Unable to open json file to dump. What(): {}".format(str(e)))
+        self._build_tables()
+        self._device_tables = {}
+        self._scales = None
+        self.device_updates = 0
+        self.stats = self.precision = self.recall = None
+        self.reset()
+
+    def __del__(self):
+        if getattr(self, '_cleanup', False) and getattr(self, '_filename', None):
+            import os
+            try:
+                os.remove(self._filename)
+            except OSError:
+                pass
+
+    # ------------------------------------------------------------------ the dataset's ground truth, once
+    def _build_tables(self):
+        ds = self.dataset
+        if hasattr(ds, 'coco'):
+            data = ds.coco.dataset
+        else:
+            import json
+            with open(ds.build_coco_json()) as f:
+                data = json.load(f)
+        self._eval_ids = sorted(im['id'] for im in data.get('images', []))
+        self._row = {i: r for r, i in enumerate(self._eval_ids)}
+        if len(self._row) != len(self._eval_ids):
+            raise ValueError("an image id appears twice in the ground-truth file")
+        for i in self._img_ids:
+            if i not in self._row:
+                raise ValueError("sample id %r is not an image of the ground-truth file" % (i,))
+        self._cat_ids = sorted(c['id'] for c in data.get('categories', []))
+        cat_k = {c: k for k, c in enumerate(self._cat_ids)}
+        per_image = [[] for _ in self._eval_ids]
+        for ann in data.get('annotations', []):
+            r = self._row.get(ann['image_id'])
+            if r is not None:
+                per_image[r].append(ann)
+        anns = [a for lst in per_image for a in lst]
+        self._gt_off = np.concatenate([[0], np.cumsum([len(lst) for lst in per_image], dtype=np.int64)]).astype(np.int64)
+        self._gt_xywh = np.array([a['bbox'] for a in anns], np.float64).reshape(-1, 4)
+        self._gt_cat = np.array([cat_k.get(a['category_id'], -1) for a in anns], np.int32).reshape(-1)
+        self._gt_area = np.array([a['area'] for a in anns], np.float64).reshape(-1)
+        self._gt_crowd = np.array([1 if a.get('iscrowd', 0) else 0 for a in anns], np.uint8).reshape(-1)
+        self._gt_id = np.array([a['id'] for a in anns], np.int64).reshape(-1)
+        n_k, n_a = len(self._cat_ids), len(self._ar)
+        self._npig = np.zeros((n_k, n_a), np.int64)
+        named = self._gt_cat >= 0
+        for a in range(n_a):
+            ok = named & (self._gt_crowd == 0) & ~((self._gt_area < self._ar[a, 0]) | (self._gt_area > self._ar[a, 1]))
+            self._npig[:, a] = np.bincount(self._gt_cat[ok], minlength=n_k)
+        # label -> category id of the file and category index, as tables: the same lookup on the host and on the device
+        to_json = getattr(ds, 'contiguous_id_to_json', None)
+        self._has_map = to_json is not None
+        pairs = [(int(k), int(v)) for k, v in to_json.items()] if self._has_map else [(c, c) for c in self._cat_ids]
+        if any(not (0 <= k < _COCO_LUT_MAX) for k, _ in pairs) or any(not (0 <= c < _COCO_LUT_MAX) for c in self._cat_ids):
+            raise ValueError("category ids and label keys must lie in [0, %d)" % _COCO_LUT_MAX)
+        size = max([k for k, _ in pairs] + [0]) + 1
+        self._lut_json = np.zeros(size, np.int64)
+        self._lut_k = np.full(size, -1, np.int32)
+        self._lut_has = np.zeros(size, bool)
+        for k, v in pairs:
+            self._lut_json[k], self._lut_k[k], self._lut_has[k] = v, cat_k.get(v, -1), True
+
+    def _scale_table(self):
+        """(images of the file, 4) float64 [width, height, width, height] scales of data_shape, once."""
+        if self._scales is None:
+            s = np.ones((len(self._eval_ids), 4), np.float64)
+            for i in self._img_ids:
+                orig_width, orig_height = self.dataset.image_size(i)
+                ws, hs = float(orig_width) / self._data_shape[1], float(orig_height) / self._data_shape[0]
+                s[self._row[i]] = (ws, hs, ws, hs)
+            self._scales = s
+        return self._scales
+
+    def _tables_on(self, dev):
+        t = self._device_tables.get(dev)
+        if t is None:
+            import torch
+            pad = lambda a: a if a.size else np.zeros((1,) + a.shape[1:], a.dtype)  # noqa: E731
+            names = ('_gt_xywh', '_gt_cat', '_gt_area', '_gt_crowd', '_gt_id', '_lut_json', '_lut_k', '_lut_has')
+            t = {n: torch.from_numpy(pad(getattr(self, n))).to(dev) for n in names}
+            if self._data_shape is not None:
+                t['scale'] = torch.from_numpy(pad(self._scale_table())).to(dev)
+            self._device_tables[dev] = t
+        return t
+
+    def reset(self):
+        self._current_id = 0
+        self._chunks = []     # per update: (image rows, category index, score, rank, flags, file category, xywh)
+        self._seen = set()
+
+    # ------------------------------------------------------------------ accumulation
+    def _rows_of(self, sid, batch):
+        if sid is None:
+            if self._current_id + batch > len(self._img_ids):
+                raise ValueError("%d images after %d: the dataset has %d" % (batch, self._current_id, len(self._img_ids)))
+            sids = self._img_ids[self._current_id:self._current_id + batch]
+        else:
+            if hasattr(sid, "tolist"):
+                sid = sid.tolist()
+            sids = list(sid) if isinstance(sid, (list, tuple, range)) else [sid]
+            if len(sids) != batch:
+                raise ValueError("%d ids for a batch of %d images" % (len(sids), batch))
+        rows = []
+        for s in sids:
+            if s not in self._row:
+                raise ValueError("sid %r is not an image of the ground-truth file" % (s,))
+            if self._row[s] in self._seen or self._row[s] in rows:
+                raise ValueError("sid %r was given before" % (s,))
+            rows.append(self._row[s])
+        if sid is None:
+            self._current_id += batch
+        return np.asarray(rows, np.int64)
+
+    def update(self, pred_bboxes, pred_labels, pred_scores, *args, **kwargs):
+        """pred_bboxes (B, N, 4) corners, pred_labels and pred_scores (B, N) or (B, N, 1): numpy, torch, or lists of them
+        (one per device, joined along the batch).  Further positional arguments are accepted and ignored, as in the
+        reference; ``sid=`` names the images."""
+        sid = kwargs.pop('sid', None)
+        pb, pl, ps = (VIDDetectionMetric._gather(x) for x in (pred_bboxes, pred_labels, pred_scores))
+        on_device = all(hasattr(x, "is_cuda") and _is_gpu_f32(x) for x in (pb, pl, ps)) and \
+            pb.device == pl.device == ps.device
+        if not on_device:
+            pb, pl, ps = (np.asarray(_to_numpy(x)) for x in (pb, pl, ps))
+        batch = int(pb.shape[0])
+        n = int(np.prod(pl.shape[1:])) if batch else 0
+        if on_device and n > 1024:
+            on_device = False
+            pb, pl, ps = (np.asarray(_to_numpy(x)) for x in (pb, pl, ps))
+        rows = self._rows_of(sid, batch)
+        if batch and n:
+            pb, pl, ps = pb.reshape(batch, n, 4), pl.reshape(batch, n), ps.reshape(batch, n)
+            self._chunks.append((self._update_device if on_device else self._update_host)(pb, pl, ps, rows))
+        self._seen.update(rows.tolist())
+
+    def _update_host(self, pb, pl, ps, rows):
+        batch, n = pl.shape
+        n_a, n_t = len(self._ar), len(self._thr)
+        size = len(self._lut_k)
+        valid = pl >= 0
+        with np.errstate(invalid='ignore'):
+            li = np.where(valid, pl, 0).astype(np.float64)
+            file_cat = li.astype(np.int64)
+            li = np.minimum(li, size).astype(np.int64)
+        inside = li < size
+        lic = np.where(inside, li, 0)
+        k = np.where(inside, self._lut_k[lic], -1)
+        has = valid
+        if self._has_map:
+            has, file_cat = valid & inside & self._lut_has[lic], self._lut_json[lic]
+        score = ps.astype(np.float64)
+        keep = has & ~(score < self._score_thresh)
+        box = pb.astype(np.float64)
+        if self._data_shape is not None:
+            box = box * self._scale_table()[rows][:, None, :]
+        xywh = np.concatenate([box[..., :2], box[..., 2:] - (box[..., :2] - 1)], -1)
+        cat = np.where(keep, k, -1).astype(np.int32)
+        file_cat = np.where(keep, file_cat, -1)
+        rank = np.zeros((batch, n), np.int32)
+        flags = np.zeros((batch, n, n_a, n_t), np.uint8)
+        for b, r in enumerate(rows):
+            g0, g1 = self._gt_off[r], self._gt_off[r + 1]
+            rank[b], flags[b] = coco_match_host(xywh[b], cat[b], score[b], self._gt_xywh[g0:g1], self._gt_cat[g0:g1],
+                                                self._gt_area[g0:g1], self._gt_crowd[g0:g1], self._gt_id[g0:g1], self._thr,
+                                                self._ar, self._max_dets[-1])
+        return rows, cat, score, rank, flags, keep, file_cat, xywh
+
+    def _update_device(self, pb, pl, ps, rows):
+        import ctypes
+        import torch
+        from . import _lib
+        lib = _lib.load()
+        dev = pb.device
+        batch, n = pl.shape
+        n_a, n_t = len(self._ar), len(self._thr)
+        t = self._tables_on(dev)
+        size = len(self._lut_k)
+        valid = pl >= 0
+        li = torch.where(valid, pl, torch.zeros_like(pl)).to(torch.float64)
+        file_cat = li.to(torch.int64)
+        li = li.clamp(max=size).to(torch.int64)
+        inside = li < size
+        lic = torch.where(inside, li, torch.zeros_like(li))
+        k = torch.where(inside, t['_lut_k'][lic], torch.full_like(lic, -1, dtype=torch.int32))
+        has = valid
+        if self._has_map:
+            has, file_cat = valid & inside & t['_lut_has'][lic], t['_lut_json'][lic]
+        score = ps.to(torch.float64).contiguous()
+        keep = has & ~(score < self._score_thresh)
+        box = pb.to(torch.float64)
+        if self._data_shape is not None:
+            if len(rows) and (np.diff(rows) == 1).all():
+                scale = t['scale'][int(rows[0]):int(rows[0]) + batch]
+            else:
+                scale = t['scale'][torch.from_numpy(rows).to(dev)]
+            box = box * scale[:, None, :]
+        xywh = torch.cat([box[..., :2], box[..., 2:] - (box[..., :2] - 1)], -1).contiguous()
+        cat = torch.where(keep, k, torch.full_like(k, -1)).contiguous()
+        file_cat = torch.where(keep, file_cat, torch.full_like(file_cat, -1))
+        rank = torch.empty((batch, n), dtype=torch.int32, device=dev)
+        flags = torch.empty((batch, n, n_a, n_t), dtype=torch.uint8, device=dev)
+        taken_bytes = int((self._gt_off[rows + 1] - self._gt_off[rows]).sum()) * n_a * n_t
+        taken = torch.empty(max(taken_bytes, 1), dtype=torch.uint8, device=dev)
+        gt_image = rows.astype(np.int32)
+        host = lambda a: a.ctypes.data_as(ctypes.c_void_p)    # noqa: E731
+        devp = lambda x: ctypes.c_void_p(x.data_ptr())        # noqa: E731
+        with torch.cuda.device(dev):
+            _lib.check(lib.vy_coco_match(
+                batch, n, devp(xywh), devp(cat), devp(score), host(gt_image), len(self._eval_ids), host(self._gt_off),
+                devp(t['_gt_xywh']), devp(t['_gt_cat']), devp(t['_gt_area']), devp(t['_gt_crowd']), devp(t['_gt_id']),
+                n_t, host(self._thr), n_a, host(np.ascontiguousarray(self._ar)), self._max_dets[-1], devp(taken), taken_bytes,
+                devp(rank), devp(flags), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self.device_updates += 1
+        return rows, cat, score, rank, flags, keep, file_cat, xywh
+
+    # ------------------------------------------------------------------ evaluation
+    def _fold(self, with_boxes):
+        """Every row so far, update after update: image row, category index, score, rank, flags (and kept, file category,
+        xywh for the results file) as numpy arrays.  Device results are copied here, once per kind."""
+        n_a, n_t = len(self._ar), len(self._thr)
+        kinds = range(1, 8 if with_boxes else 5)
+        parts = {k: [None] * len(self._chunks) for k in kinds}
+        dev_chunks = [i for i, c in enumerate(self._chunks) if not isinstance(c[1], np.ndarray)]
+        if dev_chunks:
+            import torch
+            dev = self._chunks[dev_chunks[0]][1].device
+            for k in kinds:
+                tail = (4,) if k == 7 else (n_a, n_t) if k == 4 else ()
+                joined = torch.cat([self._chunks[i][k].to(dev).reshape((-1,) + tail) for i in dev_chunks], 0).cpu().numpy()
+                at = 0
+                for i in dev_chunks:
+                    size = self._chunks[i][1].numel()
+                    parts[k][i] = joined[at:at + size]
+                    at += size
+        for i, c in enumerate(self._chunks):
+            if isinstance(c[1], np.ndarray):
+                for k in kinds:
+                    tail = (4,) if k == 7 else (n_a, n_t) if k == 4 else ()
+                    parts[k][i] = c[k].reshape((-1,) + tail)
+        empty = {1: np.zeros(0, np.int32), 2: np.zeros(0, np.float64), 3: np.zeros(0, np.int32),
+                 4: np.zeros((0, n_a, n_t), np.uint8), 5: np.zeros(0, bool), 6: np.zeros(0, np.int64),
+                 7: np.zeros((0, 4), np.float64)}
+        out = [np.concatenate([np.repeat(c[0], c[1].shape[1]) for c in self._chunks]) if self._chunks
+               else np.zeros(0, np.int64)]
+        for k in kinds:
+            out.append(np.concatenate(parts[k]) if self._chunks else empty[k])
+        return out
+
+    def _write_results(self, image, keep, file_cat, xywh, score):
+        """The results file the reference writes: one entry per kept row in the order of arrival (a dummy one if none)."""
+        import json
+        results = [{'image_id': self._eval_ids[image[i]], 'category_id': int(file_cat[i]), 'bbox': xywh[i].tolist(),
+                    'score': float(score[i])} for i in np.flatnonzero(keep)]
+        if not results and self._img_ids:
+            results.append({'image_id': self._img_ids[0], 'category_id': 0, 'bbox': [0, 0, 0, 0], 'score': 0})
+        try:
+            with open(self._filename, 'w') as f:
+                json.dump(results, f)
+        except IOError as e:
+            raise RuntimeError("Unable to dump json file, ignored. What(): {}".format(str(e)))
+
+    def _summarize(self):
+        """[UPSTREAM-RECALLED] ``COCOeval.summarize``: the twelve numbers and their printed lines."""
+        thr, names = self._thr, COCO_AREA_NAMES
+        template = ' {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'
+
+        def one(ap, iou_thr, area, md):
+            a = names.index(area)
+            m = [i for i, v in enumerate(self._max_dets) if v == md]
+            if ap:
+                s = self.precision
+                if iou_thr is not None:
+                    s = s[np.where(iou_thr == thr)[0]]
+                s = s[:, :, :, a:a + 1 if a < len(self._ar) else 0, m]
+            else:
+                s = self.recall
+                if iou_thr is not None:
+                    s = s[np.where(iou_thr == thr)[0]]
+                s = s[:, :, a:a + 1 if a < len(self._ar) else 0, m]
+            mean = np.mean(s[s > -1]) if len(s[s > -1]) else -1
+            iou_str = '{:0.2f}:{:0.2f}'.format(thr[0], thr[-1]) if iou_thr is None else '{:0.2f}'.format(iou_thr)
+            line = template.format('Average Precision' if ap else 'Average Recall', '(AP)' if ap else '(AR)', iou_str,
+                                   area, md, mean)
+            return mean, line
+
+        md = self._max_dets
+        last = md[-1]
+        ask = [(1, None, 'all', last), (1, .5, 'all', last), (1, .75, 'all', last), (1, None, 'small', last),
+               (1, None, 'medium', last), (1, None, 'large', last), (0, None, 'all', md[0]),
+               (0, None, 'all', md[min(1, len(md) - 1)]), (0, None, 'all', md[min(2, len(md) - 1)]),
+               (0, None, 'small', last), (0, None, 'medium', last), (0, None, 'large', last)]
+        got = [one(*q) for q in ask]
+        self.stats = np.array([g[0] for g in got], np.float64)
+        return '\n'.join(g[1] for g in got)
+
+    def get(self):
+        """``(names, values)`` with the reference's strings (mscoco.py:117-162): COCOeval's summary block, AP x 100 of every
+        class of ``dataset.classes`` over all thresholds at the first area range and the last max_dets, and the mean."""
+        if len(self._seen) != len(self._img_ids):
+            import warnings
+            warnings.warn('Recorded {} out of {} validation images, incomplete results'.format(
+                len(self._seen), len(self._img_ids)))
+        with_boxes = self._filename is not None
+        folded = self._fold(with_boxes)
+        image, cat, score, rank, flags = folded[:5]
+        if with_boxes:
+            self._write_results(image, folded[5], folded[6], folded[7], score)
+        part = rank >= 0
+        self.precision, self.recall = coco_accumulate(image[part], cat[part], score[part], rank[part], flags[part],
+                                                      self._npig, self._rec_thrs, self._max_dets)
+        summary = self._summarize()
+        near = lambda v: np.flatnonzero((self._thr > v - 1e-5) & (self._thr < v + 1e-5))   # noqa: E731
+        lo, hi = near(0.5), near(0.95)
+        ind_lo, ind_hi = (lo[0] if len(lo) else 0), (hi[0] if len(hi) else len(self._thr) - 1)
+
+        def mean_ap(p):
+            p = p[p > -1]
+            return float(np.mean(p)) if len(p) else float('nan')
+
+        names, values = ['~~~~ Summary metrics ~~~~\n'], [summary.strip()]
+        for cls_ind, cls_name in enumerate(self.dataset.classes):
+            ap = mean_ap(self.precision[ind_lo:ind_hi + 1, :, cls_ind, 0, -1]) if cls_ind < len(self._cat_ids) else float('nan')
+            names.append(cls_name)
+            values.append('{:.1f}'.format(100 * ap))
+        names.append('~~~~ MeanAP @ IoU=[{:.2f},{:.2f}] ~~~~\n'.format(0.5, 0.95))
+        values.append('{:.1f}'.format(100 * mean_ap(self.precision[ind_lo:ind_hi + 1, :, :, 0, -1])))
         return names, values
