@@ -22,6 +22,12 @@ the product) are left out.  The bars here are therefore tolerances, and each is 
                      k-split the cost model picks): 1 x 416 x 416, seed 233: rows 10505 / 11591 (scores 0.885419488 /
                      0.885419548, one ulp apart) swap output slots 84 / 85; 30 classes, nms (0.6, 1000, 300): rows 6298 /
                      9541 (3.6e-7 apart) swap.  Everything else — 12 fixtures — identical.
+
+These are END-TO-END bars.  What each kernel computes per element — every launch form of conv_split_kernel, conv_wino_kernel,
+splitk_finish_kernel and wgrad_split_kernel against the six partial products in float64, with a rounding bound derived from
+the number format, a census of the six products and a measured typical-rounding bar — is held by
+tests/test_gpu_split_cells.py (bars and their derivation: oracle/split_oracle.py; measured numbers:
+profiles/split_cells.txt).  The four cells of test_kernel_computes_the_six_products keep their own 2^-22 bar here.
 """
 import os
 

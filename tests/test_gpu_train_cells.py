@@ -71,8 +71,8 @@ def _record(net, cells, inputs, gt_boxes, tg):
     return z_fwd, np.stack([_host(l) for l in losses])
 
 
-def _step(C, B, H, W, seed=7):
-    """The single-frame net."""
+def _step(C, B, H, W, seed=7, mode=None):
+    """The single-frame net (mode: a conv mode to train in, tests/test_gpu_split_cells.py; default: the exact path)."""
     import videoyolo_amd as vy
     from oracle import train_cells64 as R
     params, gt_boxes, tg = _inputs(C, B, H, W, seed)
@@ -81,6 +81,8 @@ def _step(C, B, H, W, seed=7):
     net = vy.yolo3_darknet53(["c%d" % i for i in range(C)], pretrained_base=False)
     net.set_parameters(params)
     net.collect_params().reset_ctx("cuda:0")
+    if mode:
+        net.set_conv_mode(mode)
     cells = R.graph(C)
     z_fwd, losses = _record(net, cells, (x,), gt_boxes, tg)
     return dict(net=net, params=params, cells=cells, frames=x, gt_boxes=gt_boxes, tg=tg, z_fwd=z_fwd, losses=losses, C=C, B=B, k=1)
@@ -140,10 +142,18 @@ def _sel(B, fm):
     return sorted(set(range(fm)) | set(range((B - 1) * fm, B * fm)))
 
 
-def _walk(st):
+def _walk(st, split=None):
     """Every check of one recorded step `st` (a builder's dict) -> (results, pool counts {route: (wins, ties, clips counted)}).
-    The loss census (R.loss_census) of the step is left in st["census"]."""
+    The loss census (R.loss_census) of the step is left in st["census"].
+
+    split (tests/test_gpu_split_cells.py): the launches of the step that ran on the split-fp32 kernels, from its label
+    log — dict(fwd={cell: k-split}, dgrad={cell: k-split}, wgrad={cell: splits}).  For those launches three checks are
+    replaced by their split counterparts (oracle/split_oracle.py: check_split, three Results each): "forward conv
+    bit-equal", the data gradient and the weight gradient; a consumer the exact kernel served keeps its exact term inside
+    the same gradient plane's sum.  Every other check runs unchanged."""
+    from oracle import split_oracle as S
     from oracle import train_cells64 as R
+    split = split or dict(fwd={}, dgrad={}, wgrad={})
     net, params, cells, z_fwd = st["net"], st["params"], st["cells"], st["z_fwd"]
     C, B, k, join = st["C"], st["B"], st["k"], st.get("join")
     by_name = {c["name"]: c for c in cells}
@@ -195,9 +205,16 @@ def _walk(st):
         wname = name + (".0.weight" if c["bn"] else ".weight")
         w = params[wname]
         plan = net.train_conv_plan(name)
+        def wgrad_check(dz_):
+            if name in split["wgrad"]:  # 16-pixel groups of six products within a slab, the slabs added in order
+                assert split["wgrad"][name] == plan[0], (name, split["wgrad"][name], plan)
+                parts, ab = S.wgrad_parts(dz_, a, kk, s, sel_o)
+                return S.check_split("split weight gradient", name, grad(wname)[sel_o], parts, ab, 6 * plan[1] + plan[0] + 2)
+            return [R.check_wgrad(name, dz_, a, kk, s, sel_o, grad(wname)[sel_o], plan[0], plan[1])]
+
         if not c["bn"]:  # prediction conv: dz is the loss kernel's head gradient
             res.append(R.check_bias_grad(name, g, grad(name + ".bias")))
-            res.append(R.check_wgrad(name, g, a, kk, s, sel_o, grad(wname)[sel_o], plan[0], plan[1]))
+            res += wgrad_check(g)
             continue
         zf_pad = _host(z_fwd.pop(name))
         dz_pad = tap(name, "z")
@@ -210,7 +227,14 @@ def _walk(st):
         gam, bet = params[name + ".1.gamma"], params[name + ".1.beta"]
         out = _host(net.read_activation(name))
         skip = _host(net.read_activation(c["skip"])) if c["skip"] else None
-        res.append(R.check_forward_conv(name, a[sel_img], w, s, z[sel_img]))
+        if name in split["fwd"]:  # the raw conv on conv_split_kernel: no epilogue, per-tile statistics, never k-split
+            ch = S.sample_channels(c["cout"], name, z[sel_img][:, 0].size)
+            a_s = np.ascontiguousarray(a[sel_img])
+            res += S.check_split("split forward conv", name, z[sel_img][:, ch], S.six_parts(a_s, w[ch], s, kk // 2),
+                                 S.absum(a_s, w[ch], s, kk // 2), 6 * kk * kk * c["cin"] + split["fwd"][name])
+            del a_s
+        else:
+            res.append(R.check_forward_conv(name, a[sel_img], w, s, z[sel_img]))
         dgam, dbet = grad(name + ".1.gamma"), grad(name + ".1.beta")
         per = z.shape[0] * z.shape[2] * z.shape[3]
         parts = {}
@@ -229,7 +253,7 @@ def _walk(st):
             res.append(R.check_wgrad(name, dz, a, kk, s, list(range(c["cout"])), grad(wname), plan[0], plan[1],
                                      kind="stem weight gradient"))
         else:
-            res.append(R.check_wgrad(name, dz, a, kk, s, sel_o, grad(wname)[sel_o], plan[0], plan[1]))
+            res += wgrad_check(dz)
         del dz, a
 
     # data gradients: every producer's gradient plane, first and last clip
@@ -262,9 +286,28 @@ def _walk(st):
                 continue
             dzq = R.interior(tap(q["name"], "z" if q["bn"] else "grad"))[sel_img]
             wq = params[q["name"] + (".0.weight" if q["bn"] else ".weight")]
-            terms.append((dzq, wq, q["s"], lo))
-        if terms:
-            res.append(R.check_dgrad(name, got, terms, adds))
+            terms.append((dzq, wq, q["s"], lo, q["name"]))
+        if terms and not any(t[4] in split["dgrad"] for t in terms):
+            res.append(R.check_dgrad(name, got, [t[:4] for t in terms], adds))
+        elif terms:
+            # consumers on conv_split_kernel ([cout][cin] images, flipped taps, one launch per parity class at stride 2,
+            # cout zero-padded to a multiple of 32): their six products each; consumers on the exact kernel: their
+            # float64 term and its own bound; the skip addends and the accumulation into the plane: one rounding each
+            C_, hw = got.shape[1], got.shape[2:]
+            groups, names, exact, ab_all, n = [], [], [], 0.0, 0
+            for dzq, wq, sq, lo, qname in terms:
+                wv = np.ascontiguousarray(wq[:, lo:lo + C_])
+                if qname in split["dgrad"]:
+                    parts, ab = S.dgrad_parts(dzq, wv, sq, hw)
+                    groups.append(parts)
+                    names.append(qname)
+                    ab_all = ab_all + ab
+                    n += 6 * ((wq.shape[0] + 31) // 32 * 32) * wq.shape[2] * wq.shape[3] + split["dgrad"][qname]
+                else:
+                    want, ab = R.dgrad64(dzq, wv, sq, hw)
+                    exact.append((want, ab, wq.shape[0] * wq.shape[2] * wq.shape[3] + 2))
+            res += S.check_split("split data gradient", name, got, groups, ab_all, n, S.Epilogue(addends=adds),
+                                 exact_terms=exact, launches=names)
 
     # d(loss)/d(pred) on the device's own raw predictions
     preds = [_host(net.read_head(i)) for i in range(3)]

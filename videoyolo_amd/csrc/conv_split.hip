@@ -632,7 +632,21 @@ static long long split_max_ksplit(const ConvArgs& a) {
 }
 
 void vy_conv_split_cfg(const ConvArgs& a, int* bm, int* bn, int* ksplit) {
-  vy_predict_split(a.M, a.N, (double)a.ntaps * a.Kc, (int)std::min<long long>(split_max_ksplit(a), 64), bm, bn, ksplit, vy_args_cus(a));
+  const long long max_ks = std::min<long long>(split_max_ksplit(a), 64);
+  vy_predict_split(a.M, a.N, (double)a.ntaps * a.Kc, (int)max_ks, bm, bn, ksplit, vy_args_cus(a));
+  // VY_SPLIT_FORCE (tests: the forms no small shape reaches): the named tile where the launch's channels divide by it;
+  // the named k-split as far as the slabs' scratch, the per-tile statistics (whole sums) and the k-steps allow
+  // NOTE: this reaches forms the cost model never picks — 256x64 on layers of 128 channels and more (the model keeps the
+  // 256-row tile for the 64-channel layers) and k-slices down to ONE k-step (the model wants steps / S >= 6; T = 1 is
+  // served by the k-loop's tail, and the clamp below keeps T >= 1).  The kernel is correct on them, and the per-cell tests
+  // that run under this knob certify them too; the census ties plans to walked forms only as (tile, k1 | k>1).
+  const VyKnobs& k = vy_args_knobs(a);
+  if (k.split_force_bm && a.N % k.split_force_bn == 0) {
+    *bm = k.split_force_bm;
+    *bn = k.split_force_bn;
+  }
+  if (k.split_force_ks)
+    *ksplit = (int)std::max<long long>(1, std::min<long long>({(long long)k.split_force_ks, max_ks, (long long)a.ntaps * (a.Kc >> 4)}));
 }
 
 bool vy_conv_split_pays(const ConvArgs& a) {

@@ -20,6 +20,8 @@ struct VyKnobs {
   int split_wino = 1;    // VY_SPLIT_WINO: 1 where the cost models say Winograd wins, 0 never, 2 (tests) wherever supported
   int split_train = 1;   // VY_SPLIT_TRAIN: 0 none, 1 forward + data gradients, 2 forward only, 3 data gradients only
   int split_wgrad = 1;   // VY_SPLIT_WGRAD=0: the weight gradients stay exact
+  // VY_SPLIT_FORCE=256x64k4 (tests): every conv_split_kernel launch on that block tile and / or k-split (0: the model's)
+  int split_force_bm = 0, split_force_bn = 0, split_force_ks = 0;
   // training step (train.hip)
   int train_side_stream = 1;  // VY_TRAIN_SIDE_STREAM=0: weight gradients on the main stream
   std::string train_labels;   // VY_TRAIN_LABELS=<path>: the first training step's launch labels go there (empty: none)
@@ -59,6 +61,17 @@ inline VyKnobs vy_knobs_read() {
   geti("VY_SPLIT_WINO", k.split_wino);
   geti("VY_SPLIT_TRAIN", k.split_train);
   geti("VY_SPLIT_WGRAD", k.split_wgrad);
+  if (const char* s = getenv("VY_SPLIT_FORCE")) {  // "<BM>x<BN>", "<BM>x<BN>k<S>" or "k<S>"; the tiles conv_split instantiates only
+    int bm = 0, bn = 0, ks = 0;
+    const int n = sscanf(s, "%dx%dk%d", &bm, &bn, &ks);
+    if (n >= 2 && ((bm == 128 && (bn == 64 || bn == 128)) || (bm == 256 && bn == 64))) {
+      k.split_force_bm = bm;
+      k.split_force_bn = bn;
+      if (n == 3 && ks >= 1 && ks <= 64) k.split_force_ks = ks;
+    } else if (sscanf(s, "k%d", &ks) == 1 && ks >= 1 && ks <= 64) {
+      k.split_force_ks = ks;
+    }
+  }
   geti("VY_TRAIN_SIDE_STREAM", k.train_side_stream);
   if (const char* s = getenv("VY_TRAIN_LABELS")) k.train_labels = s;
 #ifdef VY_TRAIN_ABL_BUILD
