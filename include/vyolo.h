@@ -184,7 +184,9 @@ int vy_net_param_get(vy_net* net, int32_t i, float* host_dst, void* stream);
  * concatenated with (slice_like, yolo3.py:1177), so the heads have ceil(h / 32), ceil(h / 16), ceil(h / 8) rows. */
 size_t vy_net_workspace_bytes(const vy_net* net, int32_t batch, int32_t height, int32_t width);
 /* Bind a caller-owned device workspace of at least that size and plan for that shape.  Zeroes the
- * workspace (asynchronously, on `stream`): the padded activation planes rely on zero borders. */
+ * workspace (asynchronously, on `stream`): the padded activation planes rely on zero borders.  A refused bind changes
+ * nothing.  The bind lays the workspace out anew, so it ends a training plan (vy_net_bind_train) even at the same
+ * shape: the training step entries return VY_ERR_STATE until vy_net_bind_train is called again. */
 int vy_net_bind_workspace(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, int32_t height,
                           int32_t width, void* stream);
 
@@ -292,7 +294,9 @@ size_t vy_net_video_workspace_bytes(const vy_net* net, int32_t frames, int32_t c
                                     int32_t width);
 /* Binds (and zeroes, borders included, as vy_net_bind_workspace) a video plan.  The net then serves the video entries and
  * the taps only: vy_net_forward_infer and the training entries return VY_ERR_STATE until vy_net_bind_workspace /
- * vy_net_bind_train bind a clip plan again — which in turn ends the video plan; the ring's contents do not survive. */
+ * vy_net_bind_train bind a clip plan again — which in turn ends the video plan; the ring's contents do not survive.
+ * Like vy_net_bind_workspace it ends a training plan bound before it: the training step entries return VY_ERR_STATE
+ * until vy_net_bind_train is called again. */
 int vy_net_bind_video(vy_net* net, void* dev_ws, size_t bytes, int32_t frames, int32_t clips, int32_t ring, int32_t height,
                       int32_t width, void* stream);
 /* The per-frame half of detect_yolo3.py's loop: stem and stages on x (frames, 3, height, width), then the three routes of
@@ -535,7 +539,9 @@ int vy_prefetch_targets(const float* gt_boxes, const float* gt_ids, const float*
 size_t vy_net_train_workspace_bytes(const vy_net* net, int32_t batch, int32_t height, int32_t width);
 /* Binds the training workspace (also serves inference at that shape), the gradient buffer and the
  * momentum buffer (the caller zero-initialises the momentum once); zeroes the workspace
- * asynchronously on `stream`. */
+ * asynchronously on `stream`.  The training plan holds while this bind is the net's last: after vy_net_bind_workspace
+ * or vy_net_bind_video, at whatever shape, vy_net_train_forward* / vy_net_train_mode_forward* return VY_ERR_STATE
+ * ("training workspace not bound") until vy_net_bind_train is called again. */
 int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, int32_t height,
                       int32_t width, void* dev_grads, void* dev_momentum, void* stream);
 

@@ -38,6 +38,13 @@ int vy_check_kind(const vy_net* net, int takes, const char* entry) {
   return fail(VY_ERR_STATE, "%s %s: this is %s", entry, what[takes], is[kind]);
 }
 
+int vy_check_shape(int32_t batch, int32_t h, int32_t w) {
+  if (batch < 1) return fail(VY_ERR_INVALID, "batch %d < 1", batch);
+  if (h < 32 || w < 32 || h > 4096 || w > 4096)
+    return fail(VY_ERR_INVALID, "input %dx%d: height and width must lie in [32, 4096]", h, w);
+  return 0;
+}
+
 // VY_ERR_STATE for a window net (vy_net_create_window) at an entry point that does not serve one
 static int refuse_window(const vy_net* net, const char* entry) {
   if (net && net->clip_net())
@@ -241,33 +248,26 @@ int vy_net_param_get(vy_net* net, int32_t i, float* host_dst, void* stream) {
   return 0;
 }
 
-static int check_shape(int32_t batch, int32_t h, int32_t w) {
-  if (batch < 1) return fail(VY_ERR_INVALID, "batch %d < 1", batch);
-  if (h < 32 || w < 32 || h > 4096 || w > 4096)
-    return fail(VY_ERR_INVALID, "input %dx%d: height and width must lie in [32, 4096]", h, w);
-  return 0;
-}
-
 size_t vy_net_workspace_bytes(const vy_net* net, int32_t batch, int32_t height, int32_t width) {
-  if (!net || check_shape(batch, height, width)) return 0;
-  const_cast<vy_net*>(net)->resolve_cus();
-  return const_cast<vy_net*>(net)->plan(batch, height, width, false, net->keep_activations);
+  if (!net || vy_check_shape(batch, height, width)) return 0;
+  net->resolve_cus();
+  return net->plan(batch, height, width, net->keep_activations).total;
 }
 
-// size the plan, check the caller's workspace against it, commit it and take the workspace.  frames, ring: vy_net::plan
+// plan, check the caller's workspace against the plan, commit it and take the workspace.  frames, ring: vy_net::plan
 static int bind_plan(vy_net* net, void* dev_ws, size_t bytes, int b, int h, int w, int frames, int ring, const char* what,
                      void* stream) {
   VY_TRY(net->bind_cus(dev_ws));
-  const size_t need = net->plan(b, h, w, false, net->keep_activations, frames, ring);
+  NetPlan plan = net->plan(b, h, w, net->keep_activations, frames, ring);
+  const size_t need = plan.total;
   if (bytes < need) return fail(VY_ERR_INVALID, "%sworkspace too small: %zu < %zu bytes", what, bytes, need);
-  net->plan(b, h, w, true, net->keep_activations, frames, ring);
-  return net->commit_bind(dev_ws, bytes, need, static_cast<hipStream_t>(stream));
+  return net->commit_bind(std::move(plan), dev_ws, bytes, need, static_cast<hipStream_t>(stream));
 }
 
 int vy_net_bind_workspace(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, int32_t height, int32_t width,
                           void* stream) {
   if (!net || !dev_ws) return fail(VY_ERR_INVALID, "null argument");
-  VY_TRY(check_shape(batch, height, width));
+  VY_TRY(vy_check_shape(batch, height, width));
   return bind_plan(net, dev_ws, bytes, batch, height, width, 0, 0, "", stream);
 }
 
@@ -275,8 +275,7 @@ int vy_net_set_keep_activations(vy_net* net, int32_t keep) {
   if (!net) return fail(VY_ERR_INVALID, "net is null");
   if ((keep != 0) != net->keep_activations) {
     net->keep_activations = keep != 0;
-    net->dev_ws = nullptr;  // the plan changed: the workspace has to be sized and bound again
-    net->ws_bytes = 0;
+    net->unbind();
   }
   return 0;
 }
@@ -288,8 +287,7 @@ int vy_net_set_conv_mode(vy_net* net, int32_t mode) {
     return fail(VY_ERR_UNSUPPORTED, "conv mode %d: a window net runs the exact fp32 kernels only", mode);
   if (mode != net->conv_mode) {
     net->conv_mode = mode;
-    net->dev_ws = nullptr;  // the plan changed (the weight images live in the workspace): size and bind again
-    net->ws_bytes = 0;
+    net->unbind();  // (the weight images live in the workspace)
   }
   return 0;
 }
@@ -300,7 +298,7 @@ int vy_net_streamk_state(const vy_net* net, int32_t* enabled, size_t* flags_offs
   if (!net) return fail(VY_ERR_INVALID, "net is null");
   if (!net->dev_ws) return fail(VY_ERR_STATE, "workspace not bound");
   if (enabled) *enabled = net->sk_ok ? 1 : 0;
-  if (flags_offset) *flags_offset = net->sk_off;
+  if (flags_offset) *flags_offset = net->cur.sk_off;
   if (n_flags) *n_flags = VY_SK_FLAGS;
   return 0;
 }
@@ -314,7 +312,7 @@ int vy_net_invalidate_split_weights(vy_net* net) {
 int32_t vy_net_num_anchors(const vy_net* net) {
   if (!net || !net->dev_ws) return 0;
   int n = 0;
-  for (int i = 0; i < 3; ++i) n += 3 * net->planes[net->head_plane[i]].H * net->planes[net->head_plane[i]].W;
+  for (int i = 0; i < 3; ++i) n += 3 * net->plane(net->head_plane[i]).H * net->plane(net->head_plane[i]).W;
   return n;
 }
 
@@ -379,14 +377,14 @@ static int check_video_shape(const vy_net* net, int32_t frames, int32_t clips, i
     return fail(VY_ERR_INVALID, "video plan: frames %d and clips * k = %d x %d must not exceed %d table entries (they travel "
                 "in the kernel arguments)", frames, clips, net->window_k, VY_VIDEO_TABLE_MAX);
   if (net->conv_mode != VY_CONV_EXACT_FP32) return fail(VY_ERR_UNSUPPORTED, "a video plan runs the exact fp32 kernels only");
-  return check_shape(clips, h, w);
+  return vy_check_shape(clips, h, w);
 }
 
 size_t vy_net_video_workspace_bytes(const vy_net* net, int32_t frames, int32_t clips, int32_t ring, int32_t height,
                                     int32_t width) {
   if (need_window(net, "vy_net_video_workspace_bytes") || check_video_shape(net, frames, clips, ring, height, width)) return 0;
-  const_cast<vy_net*>(net)->resolve_cus();
-  return const_cast<vy_net*>(net)->plan(clips, height, width, false, net->keep_activations, frames, ring);
+  net->resolve_cus();
+  return net->plan(clips, height, width, net->keep_activations, frames, ring).total;
 }
 
 int vy_net_bind_video(vy_net* net, void* dev_ws, size_t bytes, int32_t frames, int32_t clips, int32_t ring, int32_t height,
@@ -400,15 +398,15 @@ int vy_net_bind_video(vy_net* net, void* dev_ws, size_t bytes, int32_t frames, i
 // VY_ERR_INVALID unless the `n` entries of a video entry's slot table lie in [lo, ring)
 static int check_slots(const vy_net* net, const char* entry, const int32_t* table, int n, int lo) {
   for (int i = 0; i < n; ++i)
-    if (table[i] < lo || table[i] >= net->video_R)
-      return fail(VY_ERR_INVALID, "%s: entry %d of the slot table is %d, outside [%d, %d)", entry, i, table[i], lo, net->video_R);
+    if (table[i] < lo || table[i] >= net->cur.video_R)
+      return fail(VY_ERR_INVALID, "%s: entry %d of the slot table is %d, outside [%d, %d)", entry, i, table[i], lo, net->cur.video_R);
   return 0;
 }
 
 int vy_net_video_push(vy_net* net, const float* x, const int32_t* slots, void* stream) {
   VY_TRY(need_window(net, "vy_net_video_push"));
   return run_entry(net, x && slots, "vy_net_video_push", stream, [&](hipStream_t s) {
-    VY_TRY(check_slots(net, "vy_net_video_push", slots, net->video_F, -1));
+    VY_TRY(check_slots(net, "vy_net_video_push", slots, net->cur.video_F, -1));
     VY_TRY(net->prepare(s, plain, true));
     VY_TRY(net->run_cells(0, net->n_backbone, x, s, plain));
     return net->ring_push(slots, s, plain);
@@ -419,7 +417,7 @@ int vy_net_video_detect(vy_net* net, const int32_t* table, float* ids, float* sc
                         void* stream) {
   VY_TRY(need_window(net, "vy_net_video_detect"));
   return run_entry(net, table && ids && scores && bboxes, "vy_net_video_detect", stream, [&](hipStream_t s) {
-    VY_TRY(check_slots(net, "vy_net_video_detect", table, net->B * net->window_k, 0));
+    VY_TRY(check_slots(net, "vy_net_video_detect", table, net->cur.B * net->window_k, 0));
     VY_TRY(net->prepare(s, plain, false));
     VY_TRY(net->ring_pool(table, s, plain));
     VY_TRY(net->run_cells(net->n_backbone, (int)net->convs.size(), nullptr, s, plain));
@@ -430,12 +428,12 @@ int vy_net_video_detect(vy_net* net, const int32_t* table, float* ids, float* sc
 int vy_net_video_read_slot(vy_net* net, int32_t slot, float* f0, float* f1, float* f2, void* stream) {
   VY_TRY(need_window(net, "vy_net_video_read_slot"));
   VY_TRY(entry_ready(net, f0 && f1 && f2, "vy_net_video_read_slot"));
-  if (slot < 0 || slot >= net->video_R) return fail(VY_ERR_INVALID, "slot %d outside [0, %d)", slot, net->video_R);
+  if (slot < 0 || slot >= net->cur.video_R) return fail(VY_ERR_INVALID, "slot %d outside [0, %d)", slot, net->cur.video_R);
   RingRoute rr[3];
   net->ring_routes(rr);
   float* const out[3] = {f0, f1, f2};
   for (int i = 0; i < 3; ++i)
-    HIP_TRY(vy_launch_ring_read(rr[i].ring + slot * net->ring_slot_floats, rr[i].H, rr[i].W, rr[i].C, out[i],
+    HIP_TRY(vy_launch_ring_read(rr[i].ring + slot * net->cur.ring_slot_floats, rr[i].H, rr[i].W, rr[i].C, out[i],
                                 static_cast<hipStream_t>(stream)));
   return 0;
 }
@@ -443,8 +441,8 @@ int vy_net_video_read_slot(vy_net* net, int32_t slot, float* f0, float* f1, floa
 int vy_net_read_head(vy_net* net, int32_t i, float* dst_dev, void* stream) {
   if (!net || !dst_dev || i < 0 || i > 2) return fail(VY_ERR_INVALID, "bad argument");
   if (int rc = net->check_ready(true)) return rc;
-  const PlaneT& p = net->planes[net->head_plane[i]];
-  HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(net->head_plane[i]), net->B, p.H, p.W, p.C, 0,
+  const PlaneAt p = net->plane(net->head_plane[i]);
+  HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(net->head_plane[i]), net->cur.B, p.H, p.W, p.C, 0,
                                   3 * (5 + net->num_class), dst_dev, static_cast<hipStream_t>(stream)));
   return 0;
 }
@@ -456,8 +454,8 @@ int vy_net_detect_heads(vy_net* net, const float* head0, const float* head1, con
   hipStream_t s = static_cast<hipStream_t>(stream);
   const float* src[3] = {head0, head1, head2};
   for (int i = 0; i < 3; ++i) {
-    const PlaneT& p = net->planes[net->head_plane[i]];
-    HIP_TRY(vy_launch_nchw_to_plane(src[i], net->B, p.H, p.W, p.C, 0, 3 * (5 + net->num_class),
+    const PlaneAt p = net->plane(net->head_plane[i]);
+    HIP_TRY(vy_launch_nchw_to_plane(src[i], net->cur.B, p.H, p.W, p.C, 0, 3 * (5 + net->num_class),
                                     net->plane_ptr(net->head_plane[i]), s));
   }
   return net->detect_tail(ids, scores, bboxes, keep_idx, s, plain);
@@ -467,23 +465,23 @@ int vy_net_read_activation(vy_net* net, const char* name, float* dst_dev, int32_
                            void* stream) {
   if (!net || !name) return fail(VY_ERR_INVALID, "bad argument");
   if (int rc = net->check_ready(true)) return rc;
-  if (dst_dev && net->planes_shared)
+  if (dst_dev && net->cur.planes_shared)
     return fail(VY_ERR_STATE, "activation planes are recycled in this plan: call vy_net_set_keep_activations(net, 1) "
                 "before sizing / binding the workspace to read intermediate activations");
   if (const int i = vy_pool_tap(net, name); i >= 0) {
     const vy_net::RouteSlot& r = net->routes[i];
-    const PlaneT& p = net->planes[r.plane];
+    const PlaneAt p = net->plane(r.plane);
     if (c) *c = r.C;
     if (h) *h = p.H;
     if (w) *w = p.W;
     if (dst_dev)
-      HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(r.plane), net->B, p.H, p.W, p.C, r.co, r.C, dst_dev,
+      HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(r.plane), net->cur.B, p.H, p.W, p.C, r.co, r.C, dst_dev,
                                       static_cast<hipStream_t>(stream)));
     return 0;
   }
   for (const ConvT& cv : net->convs) {
     if (cv.name != name) continue;
-    const PlaneT& p = net->planes[cv.out_plane];
+    const PlaneAt p = net->plane(cv.out_plane);
     if (c) *c = cv.cout;
     if (h) *h = p.H;
     if (w) *w = p.W;

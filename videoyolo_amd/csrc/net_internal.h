@@ -26,6 +26,8 @@ struct vy_net;
 // per-frame routes and a table (VY_TAKES_BANK)
 enum { VY_TAKES_IMAGES = 0, VY_TAKES_ROUTES = 1, VY_TAKES_BANK = 2 };
 int vy_check_kind(const vy_net* net, int takes, const char* entry);
+// VY_ERR_INVALID unless (batch, h, w) is a shape the planner takes (defined in net.hip)
+int vy_check_shape(int32_t batch, int32_t h, int32_t w);
 
 // the inputs of a *_bank entry: three banks of per-frame routes (n_frames, C, h, w) and the (B, k) table of frames
 struct BankRef {
@@ -65,11 +67,9 @@ struct ParamT {
 };
 
 struct PlaneT {
-  int C = 0;         // channel stride
-  int div = 1;       // spatial = input / div
-  size_t off = 0;    // float offset in workspace (set by plan)
-  int H = 0, W = 0;  // set by plan
-  int fm = 1;        // frames per batch entry: k for the stem and stage planes of a window net (B*k frames), 1 otherwise
+  int C = 0;    // channel stride
+  int div = 1;  // spatial = input / div
+  int fm = 1;   // frames per batch entry: k for the stem and stage planes of a window net (B*k frames), 1 otherwise
 };
 
 struct ConvT {
@@ -83,8 +83,40 @@ struct ConvT {
   int p_bias;                     // -1 for cells
   int64_t scale_off, shift_off;   // folded BN scratch (element offsets), -1 if none
   int is_stem;
-  int64_t wino_off = -1;          // ... of its Winograd-transformed image sets (conv_wino.hip: 3x3 stride-1 cells with cout % 128 == 0), -1: none
-  int64_t split_off = -1;         // conv mode VY_CONV_SPLIT_BF16X3: byte offset of the bf16 weight images in the workspace region, -1: exact kernel
+};
+
+// Where one shape puts the graph in the workspace: everything a bind decides.  vy_net::plan computes one from the graph and
+// the settings and writes nothing; a bind commits it by assignment (vy_net::cur, commit_bind)
+struct NetPlan {
+  int B = 0, H = 0, W = 0;
+  // a video plan (vy_net_bind_video): the stem and stage planes hold video_F single frames, the planes from the
+  // pooled routes on hold B clips, and behind the planes lies a ring of video_R slots of per-frame routes (video.hip).
+  // 0: the clip plan — binding either way switches the net over
+  int video_F = 0, video_R = 0;
+  size_t fold_desc_off = 0, det_scratch_off = 0, sk_off = 0;  // byte offsets in the workspace
+  size_t ck_off = 0, ck_bytes = 0;  // running-sum scratch of the convs whose K is summed in runs (conv_igemm.hip)
+  size_t wsplit_off = 0, planes_off = 0;
+  size_t ring_off = 0;             // the ring of a video plan
+  long long ring_slot_floats = 0;  // floats per slot
+  size_t total = 0;                // bytes of the workspace the plan needs
+  bool planes_shared = false;      // the plan recycles planes (read_activation is then meaningless)
+  struct Plane {
+    int H = 0, W = 0;
+    size_t off = 0;  // float offset in the plane region
+  };
+  // conv mode VY_CONV_SPLIT_BF16X3: byte offsets in the region at wsplit_off of the bf16 weight images (-1: exact kernel)
+  // and of the Winograd-transformed image sets (conv_wino.hip: 3x3 stride-1 cells with cout % 128 == 0; -1: none)
+  struct Conv {
+    int64_t split_off = -1, wino_off = -1;
+  };
+  std::vector<Plane> planes;  // per plane of the graph
+  std::vector<Conv> convs;    // per conv
+};
+
+// a plane of the graph where the committed plan put it (vy_net::plane)
+struct PlaneAt {
+  int C, H, W;
+  size_t off;
 };
 
 // the cells Darknet3D builds with the norm_layer passed to yolo3_darknet53 — the stem and the five stride-2 convs
@@ -115,17 +147,15 @@ struct vy_net {
   int64_t param_elems = 0;           // tensors + scratch
   int64_t tensor_elems = 0;
   std::vector<FoldDesc> folds;
-  // bound state
+  // the graph above is written by build() alone.  Bound state:
   float* dev_params = nullptr;
   unsigned char* dev_ws = nullptr;
   size_t ws_bytes = 0;
-  int B = 0, H = 0, W = 0;
-  size_t fold_desc_off = 0, det_scratch_off = 0, planes_off = 0, sk_off = 0;  // byte offsets in workspace
-  size_t ck_off = 0, ck_bytes = 0;  // running-sum scratch of the convs whose K is summed in runs (conv_igemm.hip)
+  NetPlan cur;           // the committed plan (commit_bind): what every launch reads
+  unsigned commits = 0;  // plans committed so far: a training plan is valid while the one it was carved behind is the last
   bool fold_uploaded = false;
   bool fold_in_stem = false;  // set by prepare(): this sequence's stem launch carries the BatchNorm fold
   bool keep_activations = false;  // vy_net_set_keep_activations: inference planes are not recycled (parity taps)
-  bool planes_shared = false;     // the committed plan recycles planes (read_activation is then meaningless)
   // vy_net_set_conv_mode: VY_CONV_SPLIT_BF16X3 sends the inference launches conv_split.hip can serve through the bf16
   // matrix core (bf16 x 3, six products, fp32 accumulate); their pre-split weight images live in the workspace and are
   // rebuilt by the next forward whenever the parameters may have changed (split_dirty)
@@ -148,12 +178,12 @@ struct vy_net {
   // and checked at every bind against the device that owns the workspace (bind_cus below), so that a C-ABI caller whose
   // current device differs between vy_net_*workspace_bytes and vy_net_bind_* gets an error instead of a plan sized for
   // one chip and bound on another.  Every cost-model choice reads this through ConvArgs::cus.
-  int cus = 0;
-  int resolve_cus() {
+  mutable int cus = 0;
+  int resolve_cus() const {
     if (!cus) cus = vy_cu_count();
     return cus;
   }
-  int bind_cus(const void* ws) {
+  int bind_cus(const void* ws) const {
     const int sized = resolve_cus();
     const int owner = vy_cu_count_of_ptr(ws);
     if (owner && owner != sized)
@@ -162,7 +192,6 @@ struct vy_net {
                   "device at the first vy_net_*workspace_bytes call): size and bind with the same current device", owner, sized);
     return 0;
   }
-  size_t wsplit_off = 0;
   struct VyTrain* train = nullptr;  // training planner state, owned by train.hip
   // vy_net_create_heads: the graph starts at the three route tensors (YOLOV3_noback, yolo3.py:1686-1920) — no stem, no
   // stages; the routes are imported into the planes the backbone's last blocks write in a full net
@@ -183,30 +212,24 @@ struct vy_net {
   bool clip_net() const { return window_k && !heads_only; }
   int frame_routes[3] = {-1, -1, -1};
 
-  // video plan of a window net (vy_net_bind_video): the stem and stage planes hold video_F single frames, the
-  // planes from the pooled routes on hold B clips, and behind the planes lies a ring of video_R slots of per-frame routes
-  // (video.hip).  0: the clip plan (or no plan); every plan(commit) sets them, so binding either way switches the net over
-  int video_F = 0, video_R = 0;
-  size_t ring_off = 0;            // byte offset of the ring in the workspace
-  long long ring_slot_floats = 0;  // floats per slot
-
   // frames a stem / stage plane of a window net holds for `b` clips: b*k of the clip plan, `frames` of a video plan
   static int backbone_frames(const PlaneT& p, int b, int frames) { return frames && p.fm > 1 ? frames : b * p.fm; }
   // frames of the batch a plane holds / a conv runs on (its output plane's: a window net's backbone cells B*k)
-  int plane_batch(int p) const { return backbone_frames(planes[p], B, video_F); }
+  int plane_batch(int p) const { return backbone_frames(planes[p], cur.B, cur.video_F); }
   int conv_batch(const ConvT& c) const { return plane_batch(c.out_plane); }
+  PlaneAt plane(int i) const { return {planes[i].C, cur.planes[i].H, cur.planes[i].W, cur.planes[i].off}; }
   // the pooling launch of a window net, forward (grads == nullptr) or backward (grads: the training gradient planes,
   // same offsets as the activation planes)
   WindowPoolArgs pool_args(float* grads) const {
     WindowPoolArgs a;
     memset(&a, 0, sizeof a);
     a.n = 3;
-    a.B = B;
+    a.B = cur.B;
     a.k = window_k;
     a.join = window_join;
     for (int i = 0; i < 3; ++i) {
-      const PlaneT& fp = planes[frame_routes[i]];
-      const PlaneT& dp = planes[routes[i].plane];
+      const PlaneAt fp = plane(frame_routes[i]);
+      const PlaneAt dp = plane(routes[i].plane);
       PoolRoute& r = a.r[i];
       r.src = plane_ptr(frame_routes[i]);
       r.dst = plane_ptr(routes[i].plane);
@@ -235,10 +258,10 @@ struct vy_net {
   }
   // the three routes of a video plan's launches (video.hip): per-frame planes, ring, pooled planes
   void ring_routes(RingRoute* rr) const {
-    float* ring = reinterpret_cast<float*>(dev_ws + ring_off);
+    float* ring = reinterpret_cast<float*>(dev_ws + cur.ring_off);
     for (int i = 0; i < 3; ++i) {
-      const PlaneT& fp = planes[frame_routes[i]];
-      const PlaneT& dp = planes[routes[i].plane];
+      const PlaneAt fp = plane(frame_routes[i]);
+      const PlaneAt dp = plane(routes[i].plane);
       RingRoute& r = rr[i];
       r.plane = plane_ptr(frame_routes[i]);
       r.ring = ring;
@@ -497,11 +520,16 @@ struct vy_net {
 
   // frames / ring: a video plan (vy_net_bind_video) — `frames` single frames in the stem and stage planes instead of b*k,
   // b clips from the pooled routes on, and `ring` route slots behind the planes; 0, 0: the clip plan
-  size_t plan(int b, int h, int w, bool commit, bool keep_all, int frames = 0, int ring = 0) {
+  NetPlan plan(int b, int h, int w, bool keep_all, int frames = 0, int ring = 0) const {
+    NetPlan p;
+    p.B = b;
+    p.H = h;
+    p.W = w;
+    p.planes_shared = !keep_all;
     size_t off = 0;
-    const size_t fold_off = off;
+    p.fold_desc_off = off;
     off += al(sizeof(FoldDesc) * folds.size());
-    const size_t det_off = off;
+    p.det_scratch_off = off;
     int n_items = 0;
     // a plane's spatial size = ceil(input / div): every stride-2 3x3 pad-1 conv maps n rows to ceil(n / 2), and the
     // x2 upsample is cropped to the route it is concatenated with (slice_like, yolo3.py:1177) — inputs need not be
@@ -509,90 +537,78 @@ struct vy_net {
     auto cdiv = [](int a, int d) { return (a + d - 1) / d; };
     for (int i = 0; i < 3; ++i) n_items += 3 * cdiv(h, planes[head_plane[i]].div) * cdiv(w, planes[head_plane[i]].div);
     off += al(vy_det_scratch_bytes(b, n_items, num_class));
-    const size_t sk_o = off;  // stream-K scratch of the conv launches (conv_igemm.hip): flags first, then the slabs
+    p.sk_off = off;  // stream-K scratch of the conv launches (conv_igemm.hip): flags first, then the slabs
     off += al((size_t)VY_SK_FLAGS * sizeof(unsigned)) + al(VY_SK_PARTIAL_BYTES);
     // parked chains of the convs whose K is summed in runs (vy_conv_k_chunks; conv_igemm.hip `boundary`): runs - 1 tile-shaped
     // slabs per output tile of the conv that needs most
-    const size_t ck_o = off;
-    size_t ck_b = 0;
+    p.ck_off = off;
     for (const ConvT& c : convs) {
       const int runs = c.is_stem ? 1 : vy_conv_runs(c.k * c.k, (c.cin + 31) >> 5);
       if (runs < 2) continue;
       const PlaneT& op = planes[c.out_plane];
       const long long Mo = (long long)backbone_frames(op, b, frames) * cdiv(h, op.div) * cdiv(w, op.div);
-      ck_b = std::max(ck_b, vy_conv_chunk_scratch_bytes(Mo, c.cout, runs));
+      p.ck_bytes = std::max(p.ck_bytes, vy_conv_chunk_scratch_bytes(Mo, c.cout, runs));
     }
-    off += al(ck_b);
-    const size_t wsp_off = off;  // split-fp32 weight images (conv mode VY_CONV_SPLIT_BF16X3 only)
-    for (ConvT& c : convs) {
-      const bool el = split_eligible(c);
-      if (commit) c.split_off = el ? (int64_t)(off - wsp_off) : -1;
-      if (el) off += al(vy_split_weight_bytes(c.cout, c.k * c.k, c.cin));
-      const bool wel = el && c.k == 3 && c.stride == 1 && c.ups == 1 && c.cout % 128 == 0;
-      if (commit) c.wino_off = wel ? (int64_t)(off - wsp_off) : -1;
-      if (wel) off += al(vy_wino_weight_bytes(c.cout, c.cin));
-    }
-    const size_t pl_off = off;
-    size_t fl = 0;
-    const std::vector<int> slot = plane_slots(keep_all);
-    std::vector<size_t> slot_off(planes.size(), 0);
-    for (size_t i = 0; i < planes.size(); ++i) {
-      PlaneT& p = planes[i];
-      const int ph = cdiv(h, p.div), pw = cdiv(w, p.div);
-      if ((size_t)slot[i] == i) {  // owns its storage (owners come first in definition order: see plane_slots)
-        slot_off[i] = fl;
-        fl += ((size_t)backbone_frames(p, b, frames) * (ph + 2) * (pw + 2) * p.C + 63) & ~(size_t)63;
+    off += al(p.ck_bytes);
+    p.wsplit_off = off;  // split-fp32 weight images (conv mode VY_CONV_SPLIT_BF16X3 only)
+    p.convs.resize(convs.size());
+    for (size_t i = 0; i < convs.size(); ++i) {
+      const ConvT& c = convs[i];
+      if (!split_eligible(c)) continue;
+      p.convs[i].split_off = (int64_t)(off - p.wsplit_off);
+      off += al(vy_split_weight_bytes(c.cout, c.k * c.k, c.cin));
+      if (c.k == 3 && c.stride == 1 && c.ups == 1 && c.cout % 128 == 0) {
+        p.convs[i].wino_off = (int64_t)(off - p.wsplit_off);
+        off += al(vy_wino_weight_bytes(c.cout, c.cin));
       }
     }
-    for (size_t i = 0; i < planes.size() && commit; ++i) {
-      PlaneT& p = planes[i];
-      p.H = cdiv(h, p.div);
-      p.W = cdiv(w, p.div);
-      p.off = slot_off[slot[i]];
+    p.planes_off = off;
+    size_t fl = 0;
+    const std::vector<int> slot = plane_slots(keep_all);
+    p.planes.resize(planes.size());
+    for (size_t i = 0; i < planes.size(); ++i) {
+      const PlaneT& g = planes[i];
+      NetPlan::Plane& q = p.planes[i];
+      q.H = cdiv(h, g.div);
+      q.W = cdiv(w, g.div);
+      if ((size_t)slot[i] == i) {  // owns its storage
+        q.off = fl;
+        fl += ((size_t)backbone_frames(g, b, frames) * (q.H + 2) * (q.W + 2) * g.C + 63) & ~(size_t)63;
+      }
     }
+    for (size_t i = 0; i < planes.size(); ++i) p.planes[i].off = p.planes[slot[i]].off;  // (an owner may come later)
     off += fl * sizeof(float);
-    const size_t ring_o = al(off);
-    if (ring > 0) off = ring_o + (size_t)ring * slot_floats(h, w) * sizeof(float);
-    if (commit) {
-      video_F = ring > 0 ? frames : 0;
-      video_R = ring > 0 ? ring : 0;
-      ring_off = ring_o;
-      ring_slot_floats = ring > 0 ? slot_floats(h, w) : 0;
-      planes_shared = !keep_all;
-      fold_desc_off = fold_off;
-      det_scratch_off = det_off;
-      sk_off = sk_o;
-      ck_off = ck_o;
-      ck_bytes = ck_b;
-      wsplit_off = wsp_off;
-      split_dirty = dsplit_dirty = wino_dirty = true;
-      planes_off = pl_off;
-      B = b;
-      H = h;
-      W = w;
+    p.ring_off = al(off);
+    if (ring > 0) {
+      p.video_F = frames;
+      p.video_R = ring;
+      p.ring_slot_floats = slot_floats(h, w);
+      off = p.ring_off + (size_t)ring * p.ring_slot_floats * sizeof(float);
     }
-    return off;
+    p.total = off;
+    return p;
   }
 
-  float* plane_ptr(int i) const { return reinterpret_cast<float*>(dev_ws + planes_off) + planes[i].off; }
+  float* plane_ptr(int i) const { return reinterpret_cast<float*>(dev_ws + cur.planes_off) + cur.planes[i].off; }
 
   // video_ok: the entry also serves a net bound for video (the video entries, the taps); every other entry runs the clip plan
   int check_ready(bool video_ok = false) const {
     if (!dev_params) return fail(VY_ERR_STATE, "parameters not bound (vy_net_bind_params)");
     if (!dev_ws) return fail(VY_ERR_STATE, "workspace not bound (vy_net_bind_workspace)");
-    if (video_F && !video_ok)
+    if (cur.video_F && !video_ok)
       return fail(VY_ERR_STATE, "the net is bound for video (vy_net_bind_video): bind a clip plan again with "
                   "vy_net_bind_workspace / vy_net_bind_train");
     return 0;
   }
 
-  // forward launch of conv `c`: reads plane views, writes `out_plane_ptr` (the activation plane, or
+  // forward launch of conv `ci`: reads plane views, writes `out_plane_ptr` (the activation plane, or
   // the raw-conv "z" plane in training)
-  ConvArgs conv_args(const ConvT& c) const {
+  ConvArgs conv_args(int ci) const {
     ConvArgs a;
     memset(&a, 0, sizeof a);
-    const PlaneT& ip = planes[c.in_plane];
-    const PlaneT& op = planes[c.out_plane];
+    const ConvT& c = convs[ci];
+    const PlaneAt ip = plane(c.in_plane);
+    const PlaneAt op = plane(c.out_plane);
     a.in = plane_ptr(c.in_plane);
     a.w = dev_params + params[c.p_weight].info.offset;
     if (c.p_gamma >= 0) {
@@ -641,8 +657,9 @@ struct vy_net {
     }
     a.leaky = c.leaky;
     a.dgrad = 0;
-    a.w_split = c.split_off >= 0 ? dev_ws + wsplit_off + c.split_off : nullptr;
-    a.w_wino = c.wino_off >= 0 ? dev_ws + wsplit_off + c.wino_off : nullptr;
+    const NetPlan::Conv& im = cur.convs[ci];
+    a.w_split = im.split_off >= 0 ? dev_ws + cur.wsplit_off + im.split_off : nullptr;
+    a.w_wino = im.wino_off >= 0 ? dev_ws + cur.wsplit_off + im.wino_off : nullptr;
     launch_env(a, /*k_runs=*/true, /*splitk=*/true);
     return a;
   }
@@ -657,8 +674,8 @@ struct vy_net {
     a.shift = dev_params + c.shift_off;
     a.out = plane_ptr(c.out_plane);
     a.B = conv_batch(c);
-    a.H = H;
-    a.W = W;
+    a.H = cur.H;
+    a.W = cur.W;
     a.Cout = c.cout;
     a.out_cs = planes[c.out_plane].C;
     a.out_co = c.out_co;
@@ -666,21 +683,30 @@ struct vy_net {
     return a;
   }
 
-  // a plan was just committed for the workspace `ws`: take it, zero the `need` bytes the plan uses (all stream-K flags
-  // down) and probe the device's workgroup placement
-  int commit_bind(void* ws, size_t bytes, size_t need, hipStream_t s) {
+  // `plan` comes into force in the workspace `ws`, of whose `bytes` it (and what a training plan carved behind it) uses
+  // `need`: every image set is stale, the fold table gone; zero the bytes in use (all stream-K flags down) and probe the
+  // device's workgroup placement.  A training plan carved behind an earlier commit is void from here on (bound_train)
+  int commit_bind(NetPlan&& plan, void* ws, size_t bytes, size_t need, hipStream_t s) {
+    cur = std::move(plan);
+    ++commits;
     dev_ws = static_cast<unsigned char*>(ws);
     ws_bytes = bytes;
+    split_dirty = dsplit_dirty = wino_dirty = true;
     fold_uploaded = false;
     HIP_TRY(hipMemsetAsync(ws, 0, need, s));
     sk_dirty = false;
-    sk_ok = vy_sk_verify_topology(reinterpret_cast<unsigned*>(dev_ws + sk_off), s) != 0;
+    sk_ok = vy_sk_verify_topology(reinterpret_cast<unsigned*>(dev_ws + cur.sk_off), s) != 0;
     return 0;
+  }
+  // a setting the plan depends on changed: the workspace has to be sized and bound again
+  void unbind() {
+    dev_ws = nullptr;
+    ws_bytes = 0;
   }
 
   int sk_begin(hipStream_t s) {
     if (sk_dirty && dev_ws) {
-      HIP_TRY(hipMemsetAsync(dev_ws + sk_off, 0, al((size_t)VY_SK_FLAGS * sizeof(unsigned)), s));
+      HIP_TRY(hipMemsetAsync(dev_ws + cur.sk_off, 0, al((size_t)VY_SK_FLAGS * sizeof(unsigned)), s));
       sk_dirty = false;
     }
     return 0;
@@ -697,17 +723,17 @@ struct vy_net {
   void launch_env(ConvArgs& a, bool k_runs, bool splitk) const {
     a.knobs = &knobs;
     a.cus = cus;
-    float* const sk_slabs = reinterpret_cast<float*>(dev_ws + sk_off + al((size_t)VY_SK_FLAGS * sizeof(unsigned)));
+    float* const sk_slabs = reinterpret_cast<float*>(dev_ws + cur.sk_off + al((size_t)VY_SK_FLAGS * sizeof(unsigned)));
     if (k_runs) {
-      a.ck_scratch = ck_bytes ? reinterpret_cast<float*>(dev_ws + ck_off) : nullptr;
-      a.ck_bytes = ck_bytes;
+      a.ck_scratch = cur.ck_bytes ? reinterpret_cast<float*>(dev_ws + cur.ck_off) : nullptr;
+      a.ck_bytes = cur.ck_bytes;
     }
     if (splitk) {
       a.splitk_slabs = sk_slabs;
       a.splitk_bytes = VY_SK_PARTIAL_BYTES;
     }
     if (!sk_ok) return;
-    a.sk_flags = reinterpret_cast<unsigned*>(dev_ws + sk_off);
+    a.sk_flags = reinterpret_cast<unsigned*>(dev_ws + cur.sk_off);
     a.sk_partials = sk_slabs;
     a.sk_bytes = VY_SK_PARTIAL_BYTES;
     a.sk_nflags = VY_SK_FLAGS;
@@ -718,9 +744,9 @@ struct vy_net {
     RouteArgs r;
     memset(&r, 0, sizeof r);
     r.n = 3;
-    r.B = B;
+    r.B = cur.B;
     for (int i = 0; i < 3; ++i) {
-      const PlaneT& p = planes[routes[i].plane];
+      const PlaneAt p = plane(routes[i].plane);
       r.r[i].plane = plane_ptr(routes[i].plane);
       r.r[i].nchw = const_cast<float*>(nchw[i]);
       r.r[i].H = p.H;
@@ -737,7 +763,7 @@ struct vy_net {
     memset(&d, 0, sizeof d);
     int base = 0;
     for (int i = 0; i < 3; ++i) {
-      const PlaneT& p = planes[head_plane[i]];
+      const PlaneAt p = plane(head_plane[i]);
       HeadView& hv = d.head[i];
       hv.pred = plane_ptr(head_plane[i]);
       hv.H = p.H;
@@ -752,7 +778,7 @@ struct vy_net {
       hv.cand_base = base;
       base += num_class * p.H * p.W * 3;
     }
-    d.B = B;
+    d.B = cur.B;
     d.C = num_class;
     d.n_cand = base;
     d.valid_thresh = 0.01f;  // yolo3.py:1199
@@ -777,7 +803,7 @@ struct vy_net {
   // stem_runs: the sequence launches the stem, which then carries the fold if it can (run_cells reads fold_in_stem)
   template <typename Hook>
   int prepare(hipStream_t s, Hook& hook, bool stem_runs) {
-    FoldDesc* fd = reinterpret_cast<FoldDesc*>(dev_ws + fold_desc_off);
+    FoldDesc* fd = reinterpret_cast<FoldDesc*>(dev_ws + cur.fold_desc_off);
     if (!fold_uploaded) {
       HIP_TRY(hipMemcpyAsync(fd, folds.data(), sizeof(FoldDesc) * folds.size(), hipMemcpyHostToDevice, s));
       HIP_TRY(hipStreamSynchronize(s));  // `folds` is pageable host memory; one-time
@@ -786,17 +812,18 @@ struct vy_net {
     // The fold runs EVERY forward (the caller owns the parameter buffer and may have written to it) — inside the stem launch
     // when that has a block per layer (StemArgs), in a launch of its own otherwise
     fold_in_stem = stem_runs && !convs.empty() && convs[0].is_stem && convs[0].scale_off == folds[0].scale &&
-                   vy_stem_can_fold(conv_batch(convs[0]), H, W, (int)folds.size(), cus);
+                   vy_stem_can_fold(conv_batch(convs[0]), cur.H, cur.W, (int)folds.size(), cus);
     if (!fold_in_stem) HOOKED(hook, "bn_fold", 0.0, 0.0, vy_launch_bn_fold(dev_params, fd, (int)folds.size(), 1024, 1e-5f, s));
     if (conv_mode != VY_CONV_EXACT_FP32 && (split_dirty || wino_dirty)) {  // once per parameter change, not per forward
       hook("split_weights", 0.0, 0.0, true);
-      for (const ConvT& c : convs)
-        if (split_dirty && c.split_off >= 0)
-          HIP_TRY(vy_launch_split_weights(dev_params + params[c.p_weight].info.offset, dev_ws + wsplit_off + c.split_off,
-                                          c.cout, c.k * c.k, c.cin, s));
-      for (const ConvT& c : convs)
-        if (wino_dirty && c.wino_off >= 0)
-          HIP_TRY(vy_launch_wino_weights(dev_params + params[c.p_weight].info.offset, dev_ws + wsplit_off + c.wino_off, c.cout,
+      unsigned char* const images = dev_ws + cur.wsplit_off;
+      for (size_t i = 0; i < convs.size(); ++i)
+        if (const ConvT& c = convs[i]; split_dirty && cur.convs[i].split_off >= 0)
+          HIP_TRY(vy_launch_split_weights(dev_params + params[c.p_weight].info.offset, images + cur.convs[i].split_off, c.cout,
+                                          c.k * c.k, c.cin, s));
+      for (size_t i = 0; i < convs.size(); ++i)
+        if (const ConvT& c = convs[i]; wino_dirty && cur.convs[i].wino_off >= 0)
+          HIP_TRY(vy_launch_wino_weights(dev_params + params[c.p_weight].info.offset, images + cur.convs[i].wino_off, c.cout,
                                          c.cin, s));
       hook("split_weights", 0.0, 0.0, false);
       split_dirty = wino_dirty = false;
@@ -819,17 +846,17 @@ struct vy_net {
         const int Bs = a.B;
         if (fold_in_stem) {
           a.fold_params = dev_params;
-          a.fold_descs = reinterpret_cast<FoldDesc*>(dev_ws + fold_desc_off);
+          a.fold_descs = reinterpret_cast<FoldDesc*>(dev_ws + cur.fold_desc_off);
           a.fold_n = (int)folds.size();
           a.fold_stem = 0;
           a.fold_eps = 1e-5f;
         }
-        const double fl = kLabels<Hook> ? 2.0 * Bs * H * W * 27.0 * c.cout : 0.0;
-        const double by = kLabels<Hook> ? 4.0 * Bs * H * W * (3.0 + c.cout) : 0.0;
+        const double fl = kLabels<Hook> ? 2.0 * Bs * a.H * a.W * 27.0 * c.cout : 0.0;
+        const double by = kLabels<Hook> ? 4.0 * Bs * a.H * a.W * (3.0 + c.cout) : 0.0;
         HOOKED(hook, c.name.c_str(), fl, by, vy_launch_stem(a, s));
         continue;
       }
-      const ConvArgs a = conv_args(c);
+      const ConvArgs a = conv_args(ci);
       const ConvKernel kernel = a.w_wino && vy_conv_wino_pays(a) ? kWino : a.w_split && vy_conv_split_pays(a) ? kSplit : kExact;
       if (!kLabels<Hook>) {  // plain forward: no label, no second tile / stream-K query per launch (batch-1 latency path)
         HIP_TRY(launch_conv(kernel, a, s));
@@ -876,12 +903,12 @@ struct vy_net {
       floats += (double)r.r[i].C * r.r[i].H * r.r[i].W;
     }
     ra.n = 3;
-    ra.B = B;
+    ra.B = cur.B;
     ra.k = window_k;
     ra.join = window_join;
     ra.T = bank.n_frames;
-    memcpy(ra.table, bank.table, sizeof(int32_t) * B * window_k);
-    HOOKED(hook, "route_import_pool", 0.0, 4.0 * (window_k + 1) * B * floats, vy_launch_route_import_pool(ra, s));
+    memcpy(ra.table, bank.table, sizeof(int32_t) * cur.B * window_k);
+    HOOKED(hook, "route_import_pool", 0.0, 4.0 * (window_k + 1) * cur.B * floats, vy_launch_route_import_pool(ra, s));
     return 0;
   }
   // full nets, after the last stage cell: the three routes out to the caller's tensors
@@ -903,13 +930,13 @@ struct vy_net {
     memset(&ra, 0, sizeof ra);
     ring_routes(ra.r);
     ra.n = 3;
-    ra.B = B;
+    ra.B = cur.B;
     ra.k = window_k;
     ra.join = window_join;
-    ra.R = video_R;
-    ra.slot_stride = ring_slot_floats;
-    memcpy(ra.table, table, sizeof(int32_t) * B * window_k);
-    HOOKED(hook, "ring_pool", 0.0, 4.0 * (window_k + 1) * B * ring_slot_floats, vy_launch_ring_pool(ra, s));
+    ra.R = cur.video_R;
+    ra.slot_stride = cur.ring_slot_floats;
+    memcpy(ra.table, table, sizeof(int32_t) * cur.B * window_k);
+    HOOKED(hook, "ring_pool", 0.0, 4.0 * (window_k + 1) * cur.B * cur.ring_slot_floats, vy_launch_ring_pool(ra, s));
     return 0;
   }
   // ... and store the routes of the video_F frames the stages just ran on in the slots `slots`
@@ -919,11 +946,11 @@ struct vy_net {
     memset(&ra, 0, sizeof ra);
     ring_routes(ra.r);
     ra.n = 3;
-    ra.F = video_F;
-    ra.R = video_R;
-    ra.slot_stride = ring_slot_floats;
-    memcpy(ra.slot, slots, sizeof(int32_t) * video_F);
-    HOOKED(hook, "ring_push", 0.0, 8.0 * video_F * ring_slot_floats, vy_launch_ring_push(ra, s));
+    ra.F = cur.video_F;
+    ra.R = cur.video_R;
+    ra.slot_stride = cur.ring_slot_floats;
+    memcpy(ra.slot, slots, sizeof(int32_t) * cur.video_F);
+    HOOKED(hook, "ring_push", 0.0, 8.0 * cur.video_F * cur.ring_slot_floats, vy_launch_ring_push(ra, s));
     return 0;
   }
 
@@ -932,10 +959,10 @@ struct vy_net {
   int detect_tail(float* ids, float* scores, float* bboxes, int32_t* keep_idx, hipStream_t s, Hook& hook) {
     const DetArgs d = det_args();
     double dby = 0;
-    for (int i = 0; i < 3; ++i) dby += 4.0 * B * d.head[i].H * d.head[i].W * d.head[i].cs;
+    for (int i = 0; i < 3; ++i) dby += 4.0 * d.B * d.head[i].H * d.head[i].W * d.head[i].cs;
     const bool nms_on = nms_thresh > 0.f && nms_thresh < 1.f;  // yolo3.py:1197; off: the outputs are (B, N*C, .), the detection tensor itself
     HOOKED(hook, "decode_nms", 0.0, dby,
-           nms_on ? vy_launch_detect(d, dev_ws + det_scratch_off, ids, scores, bboxes, keep_idx, s)
+           nms_on ? vy_launch_detect(d, dev_ws + cur.det_scratch_off, ids, scores, bboxes, keep_idx, s)
                   : vy_launch_raw_detections(d, ids, scores, bboxes, keep_idx, s));
     return 0;
   }
@@ -947,7 +974,7 @@ inline int entry_ready(vy_net* net, bool args_ok, const char* video_entry) {
   int rc = 0;
   if (!net || !args_ok) rc = fail(VY_ERR_INVALID, "null argument");
   if (rc == 0) rc = net->check_ready(video_entry != nullptr);
-  if (rc == 0 && video_entry && !net->video_F)
+  if (rc == 0 && video_entry && !net->cur.video_F)
     rc = fail(VY_ERR_STATE, "%s: the net is not bound for video (vy_net_bind_video)", video_entry);
   if (rc && net) net->sk_dirty = true;  // (any error return: see vy_net::sk_dirty)
   return rc;
@@ -965,10 +992,10 @@ int run_entry(vy_net* net, bool args_ok, const char* video_entry, void* stream, 
 // VY_ERR_INVALID unless the bank and the table of a *_bank entry fit the bound plan: B * k table entries (they travel in the
 // kernel arguments), each a frame of the bank.  Before anything is launched
 inline int vy_check_bank(const vy_net* net, const char* entry, const BankRef& bank) {
-  const long long n = (long long)net->B * net->window_k;
+  const long long n = (long long)net->cur.B * net->window_k;
   if (n > VY_ROUTE_TABLE_MAX)
     return fail(VY_ERR_INVALID, "%s: clips * k = %d x %d exceeds %d table entries (they travel in the kernel arguments)", entry,
-                net->B, net->window_k, VY_ROUTE_TABLE_MAX);
+                net->cur.B, net->window_k, VY_ROUTE_TABLE_MAX);
   if (bank.n_frames < 1) return fail(VY_ERR_INVALID, "%s: a bank of %d frames", entry, bank.n_frames);
   for (int i = 0; i < (int)n; ++i)
     if (bank.table[i] < 0 || bank.table[i] >= bank.n_frames)

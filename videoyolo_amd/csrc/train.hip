@@ -30,7 +30,7 @@ struct TrainCell {
   int splits = 1, k_per_split = 32;  // weight-gradient split-K
   size_t tab_off = 0;         // byte offset of its weight-gradient pixel table in the workspace
   // conv mode VY_CONV_SPLIT_BF16X3_TRAIN: byte offset of its weights' DATA-GRADIENT tile images ([k = cout][n = cin]
-  // operand; conv_split.hip) in the region at TrainPlan::dsplit_off, -1: none.  The forward images are the net's.
+  // operand; conv_split.hip) in the region at TrainPlan::dsplit_off, -1: none.  The forward images are the NetPlan's.
   long long dsplit = -1;
   // the split-fp32 routing, decided once from (conv mode, VY_SPLIT_TRAIN): does the forward launch of this cell carry its
   // split images, does its data gradient (the cost model has the last word)
@@ -40,11 +40,14 @@ struct TrainCell {
 
 struct TrainPlan {
   int B = 0, H = 0, W = 0;
+  // vy_net::commits when vy_net_bind_train committed the inference plan these regions lie behind — 0: none; any later
+  // commit (vy_net_bind_workspace, vy_net_bind_video) lays the workspace out anew and voids this plan (bound_train)
+  unsigned behind = 0;
   // regions: byte offsets in the workspace, behind the inference plan
   size_t dsplit_off = 0, g_off = 0, z_off = 0, save_off = 0, coef_off = 0, sums_off = 0, slice_off = 0, part_off = 0;
   size_t slab_off = 0, loss_part_off = 0, loss_off = 0, zero_off = 0, sdesc_off = 0, seg_off = 0, chunk_off = 0, total = 0;
   std::vector<TrainCell> cells;  // per conv
-  // all image sets (forward + data gradient) for the one-launch rebuild (the forward ones are the net's: committed plans only)
+  // all image sets (forward + data gradient) for the one-launch rebuild
   std::vector<SplitDesc> sdesc;
   long long sdesc_total = 0;
   std::vector<SgdSeg> segs;
@@ -164,15 +167,16 @@ static constexpr int train_abl(const vy_net*) { return 0; }
 
 constexpr int kBwdChunk = 64;  // pixels per partial-sum block of the bias-gradient reductions (and the scratch bound)
 
+// the per-parameter options a net starts with
+void default_options(const vy_net& net, VyTrain* t) {
+  t->lr_mult.assign(net.params.size(), 1.0f);
+  t->wd_mult.assign(net.params.size(), 1.0f);
+  t->enabled.resize(net.params.size());
+  for (size_t i = 0; i < net.params.size(); ++i) t->enabled[i] = net.params[i].info.trainable;
+}
+
 VyTrain* get_train(vy_net* net) {
-  if (!net->train) {
-    net->train = new VyTrain();
-    VyTrain* t = net->train;
-    t->lr_mult.assign(net->params.size(), 1.0f);
-    t->wd_mult.assign(net->params.size(), 1.0f);
-    t->enabled.resize(net->params.size());
-    for (size_t i = 0; i < net->params.size(); ++i) t->enabled[i] = net->params[i].info.trainable;
-  }
+  if (!net->train) default_options(*net, net->train = new VyTrain());
   return net->train;
 }
 
@@ -200,9 +204,9 @@ void wgrad_split_k(long long M, long long tiles, long long held, int* splits, in
   *k_per_split = (int)best_k;
 }
 
-// The training regions behind the inference workspace, and everything the step derives from the shape.  Reads the
-// per-parameter options of `opt`, writes nothing but the net's own plan (vy_net::plan, when commit).
-TrainPlan plan_train(vy_net* net, const VyTrain& opt, int b, int h, int w, bool commit) {
+// The training regions behind the inference plan `fwd` (of the same shape, every plane kept: backward reads them all), and
+// everything the step derives from the shape.  Reads the per-parameter options of `opt`; writes nothing.
+TrainPlan plan_train(const vy_net& net, const VyTrain& opt, const NetPlan& fwd, int b, int h, int w) {
   TrainPlan p;
   p.B = b;
   p.H = h;
@@ -210,24 +214,24 @@ TrainPlan plan_train(vy_net* net, const VyTrain& opt, int b, int h, int w, bool 
   struct {  // carves 256-byte aligned regions off the workspace, in call order
     size_t off;
     size_t take(size_t bytes) { return std::exchange(off, off + vy_net::al(bytes)); }
-  } ws{vy_net::al(net->plan(b, h, w, commit, /*keep_all=*/true))};  // backward reads every activation plane
-  const size_t n = net->convs.size();
+  } ws{vy_net::al(fwd.total)};
+  const size_t n = net.convs.size();
   p.cells.resize(n);
   // split-fp32 training mode: the data gradients whose N (= cin) the split kernel has a tile for get their own weight
   // images — whenever VY_SPLIT_TRAIN != 0, the forward-only mode 2 included, which does not launch with them
-  const int st = net->knobs.split_train;  // 0 none, 1 both, 2 forward only, 3 dgrad only
-  const bool images = net->conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && st != 0;
+  const int st = net.knobs.split_train;  // 0 none, 1 both, 2 forward only, 3 dgrad only
+  const bool images = net.conv_mode == VY_CONV_SPLIT_BF16X3_TRAIN && st != 0;
   p.dsplit_off = ws.off;
   for (size_t i = 0; i < n; ++i) {
-    const ConvT& c = net->convs[i];
+    const ConvT& c = net.convs[i];
     TrainCell& cell = p.cells[i];
-    const int div_in = c.is_stem ? 1 : net->planes[c.in_plane].div;
-    cell.B = b * net->planes[c.out_plane].fm;
+    const int div_in = c.is_stem ? 1 : net.planes[c.in_plane].div;
+    cell.B = b * net.planes[c.out_plane].fm;
     cell.Ho = h / div_in / c.stride;
     cell.Wo = w / div_in / c.stride;
     cell.M = (long long)cell.B * cell.Ho * cell.Wo;
     cell.bucket = c.name.rfind("stages.2", 0) == 0 ? 1 : c.name.rfind("stages.1", 0) == 0 ? 2 : c.name.rfind("stages.0", 0) == 0 ? 3 : 0;
-    cell.fwd_split = images && st != 3 && net->split_eligible(c);
+    cell.fwd_split = images && st != 3 && net.split_eligible(c);
     if (images && !c.is_stem && c.cin % 64 == 0) {
       cell.dsplit = (long long)(ws.take(vy_split_weight_dgrad_bytes(c.cout, c.k * c.k, c.cin)) - p.dsplit_off);
       cell.dgrad_split = st != 2;
@@ -235,12 +239,12 @@ TrainPlan plan_train(vy_net* net, const VyTrain& opt, int b, int h, int w, bool 
   }
   // gradient planes mirror the activation planes
   size_t gfl = 0;
-  for (auto& pl : net->planes) gfl += ((size_t)b * pl.fm * (h / pl.div + 2) * (w / pl.div + 2) * pl.C + 63) & ~(size_t)63;
+  for (auto& pl : net.planes) gfl += ((size_t)b * pl.fm * (h / pl.div + 2) * (w / pl.div + 2) * pl.C + 63) & ~(size_t)63;
   p.g_off = ws.take(gfl * sizeof(float));
   // z planes and saved statistics: one per BN conv; the partial-sum and slab scratch: the largest any conv needs
   size_t zfl = 0, sfl = 0, part = 0, slab = 0;
   for (size_t i = 0; i < n; ++i) {
-    const ConvT& c = net->convs[i];
+    const ConvT& c = net.convs[i];
     TrainCell& cell = p.cells[i];
     const long long M = cell.M;
     const size_t chunks = (size_t)((M + kBwdChunk - 1) / kBwdChunk);
@@ -267,7 +271,7 @@ TrainPlan plan_train(vy_net* net, const VyTrain& opt, int b, int h, int w, bool 
       const int Ntot = c.k * c.k * c.cin;
       const int rows = vy_wgrad_tile_rows(c.cout, c.k, c.cin);
       const int tiles = ((c.cout + rows - 1) / rows) * ((Ntot + 127) / 128);
-      wgrad_split_k(M, tiles, 2ll * net->resolve_cus(), &cell.splits, &cell.k_per_split);
+      wgrad_split_k(M, tiles, 2ll * net.resolve_cus(), &cell.splits, &cell.k_per_split);
       slab = std::max(slab, (size_t)cell.splits * c.cout * Ntot);
     }
   }
@@ -280,15 +284,15 @@ TrainPlan plan_train(vy_net* net, const VyTrain& opt, int b, int h, int w, bool 
   p.slab_off = ws.take(slab * sizeof(float));
   int N = 0;
   for (int i = 0; i < 3; ++i) {
-    const int dv = net->planes[net->head_plane[i]].div;
+    const int dv = net.planes[net.head_plane[i]].div;
     N += 3 * (h / dv) * (w / dv);
   }
   p.loss_part_off = ws.take((size_t)vy_loss_blocks_per_image(N) * b * 4 * sizeof(float));
   p.loss_off = ws.take((size_t)4 * b * sizeof(float));
   p.zero_off = ws.take(1024);
   // SGD segment tables
-  for (size_t i = 0; i < net->params.size(); ++i) {
-    const vy_param_info& pi = net->params[i].info;
+  for (size_t i = 0; i < net.params.size(); ++i) {
+    const vy_param_info& pi = net.params[i].info;
     if (!pi.trainable) continue;
     const int32_t si = (int32_t)p.segs.size();
     p.segs.push_back(SgdSeg{pi.offset, pi.size, opt.lr_mult[i], opt.wd_mult[i], opt.enabled[i] ? 1 : 0, 0});
@@ -300,7 +304,7 @@ TrainPlan plan_train(vy_net* net, const VyTrain& opt, int b, int h, int w, bool 
   }
   // weight-gradient pixel tables (wgrad.hip): 8 bytes per output pixel of every conv but the stem
   for (size_t i = 0; i < n; ++i)
-    if (!net->convs[i].is_stem) p.cells[i].tab_off = ws.take(vy_wgrad_table_entries(p.cells[i].M) * 8);
+    if (!net.convs[i].is_stem) p.cells[i].tab_off = ws.take(vy_wgrad_table_entries(p.cells[i].M) * 8);
   p.sdesc_off = ws.take(sizeof(SplitDesc) * 2 * n);
   p.seg_off = ws.take(p.segs.size() * sizeof(SgdSeg));
   p.chunk_off = ws.take(p.chunk_seg.size() * sizeof(int32_t));
@@ -308,11 +312,11 @@ TrainPlan plan_train(vy_net* net, const VyTrain& opt, int b, int h, int w, bool 
   // the image sets and the gradient buckets' parameter ranges
   int64_t lo[4] = {INT64_MAX, INT64_MAX, INT64_MAX, INT64_MAX}, hi[4] = {0, 0, 0, 0};
   for (size_t i = 0; i < n; ++i) {
-    const ConvT& c = net->convs[i];
+    const ConvT& c = net.convs[i];
     const TrainCell& cell = p.cells[i];
-    const long long w_off = net->params[c.p_weight].info.offset;
-    if (c.split_off >= 0) {
-      p.sdesc.push_back(SplitDesc{p.sdesc_total, w_off, (long long)(net->wsplit_off + c.split_off), c.cout, c.k * c.k, c.cin, 0});
+    const long long w_off = net.params[c.p_weight].info.offset;
+    if (fwd.convs[i].split_off >= 0) {
+      p.sdesc.push_back(SplitDesc{p.sdesc_total, w_off, (long long)(fwd.wsplit_off + fwd.convs[i].split_off), c.cout, c.k * c.k, c.cin, 0});
       p.sdesc_total += (long long)c.cout * c.k * c.k * c.cin / 8;
     }
     if (cell.dsplit >= 0) {
@@ -321,7 +325,7 @@ TrainPlan plan_train(vy_net* net, const VyTrain& opt, int b, int h, int w, bool 
     }
     for (int pidx : {c.p_weight, c.p_gamma, c.p_beta, c.p_bias}) {
       if (pidx < 0) continue;
-      const vy_param_info& pi = net->params[pidx].info;
+      const vy_param_info& pi = net.params[pidx].info;
       lo[cell.bucket] = std::min(lo[cell.bucket], pi.offset);
       hi[cell.bucket] = std::max(hi[cell.bucket], pi.offset + ((pi.size + 63) & ~(int64_t)63));
     }
@@ -349,7 +353,7 @@ struct TrainCtx {
   T* at(size_t off) const { return reinterpret_cast<T*>(net->dev_ws + off); }
   const TrainCell& cell(int ci) const { return p.cells[ci]; }
   float* gplanes() const { return at<float>(p.g_off); }
-  float* gplane(int i) const { return gplanes() + net->planes[i].off; }
+  float* gplane(int i) const { return gplanes() + net->cur.planes[i].off; }
   float* zplane(int ci) const { return at<float>(p.z_off) + p.cells[ci].z_off; }
   float* coef() const { return at<float>(p.coef_off); }
   double* sums_global() const { return at<double>(p.sums_off); }
@@ -432,7 +436,7 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
 // prediction conv: bias, no BatchNorm, straight into its plane
 int pred_conv(const TrainCtx& c, int ci) {
   const ConvT& cv = c.net->convs[ci];
-  const ConvArgs a = c.net->conv_args(cv);
+  const ConvArgs a = c.net->conv_args(ci);
   g_labels.note(c.net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
   g_labels.via_exact(a);
   HIP_TRY(vy_launch_conv_igemm(a, c.s));
@@ -455,7 +459,7 @@ int raw_conv(const TrainCtx& c, int ci, const float* x, int* n_part) {
     *n_part = vy_stem_blocks(a.B, a.H, a.W);
     return 0;
   }
-  ConvArgs a = net->conv_args(cv);
+  ConvArgs a = net->conv_args(ci);
   a.scale = a.shift = a.res = nullptr;
   a.leaky = 0;
   a.out = c.zplane(ci);
@@ -652,7 +656,7 @@ int launch_wgrad(const TrainCtx& c, int ci, DzView dz, hipStream_t ws) {
   vy_net* net = c.net;
   const ConvT& cv = net->convs[ci];
   const TrainCell& cell = c.cell(ci);
-  const PlaneT& ip = net->planes[cv.in_plane];
+  const PlaneAt ip = net->plane(cv.in_plane);
   WgradArgs w;
   memset(&w, 0, sizeof w);
   w.dz = dz.p;
@@ -700,8 +704,8 @@ int weight_grad(const TrainCtx& c, int ci, DzView dz, const float* x) {
     sw.dz = dz.p;
     sw.partials = c.partials();
     sw.B = c.cell(ci).B;
-    sw.H = c.net->H;
-    sw.W = c.net->W;
+    sw.H = c.p.H;
+    sw.W = c.p.W;
     HIP_TRY(vy_launch_stem_wgrad(sw, c.s));
     HIP_TRY(vy_launch_reduce_partials(c.partials(), vy_stem_wgrad_blocks(sw.B, sw.H, sw.W), 864, c.sums_local(), c.s));
     HIP_TRY(vy_launch_f64_to_f32(c.sums_local(), c.grad_of(cv.p_weight), 864, c.s));
@@ -721,7 +725,7 @@ BwdDgrad make_dgrad(const TrainCtx& c, int ci, DzView dz, const float* addend, i
   const ConvT& cv = net->convs[ci];
   const TrainCell& cell = c.cell(ci);
   BwdDgrad out;
-  const PlaneT& ip = net->planes[cv.in_plane];
+  const PlaneAt ip = net->plane(cv.in_plane);
   ConvArgs a;
   memset(&a, 0, sizeof a);  // (ntaps = 0: counted below)
   a.in = dz.p;
@@ -864,7 +868,7 @@ int build_wgrad_tables(const TrainCtx& c) {
     const ConvT& cv = net->convs[ci];
     const TrainCell& cell = c.cell((int)ci);
     if (cv.is_stem) continue;
-    const PlaneT& ip = net->planes[cv.in_plane];
+    const PlaneAt ip = net->plane(cv.in_plane);
     const int z_cs = cv.p_gamma >= 0 ? cell.z_cs : net->planes[cv.out_plane].C;
     if (cell.M >= (1ll << 31) - 64) return fail(VY_ERR_UNSUPPORTED, "'%s': 2^31 output pixels or more in one batch", cv.name.c_str());
     // (offsets are relative to each split's first pixel: planes of 4 GiB and more are fine — 608x608 past batch 84)
@@ -896,11 +900,11 @@ int backward_train(const TrainCtx& c, const float* x) {
   return 0;
 }
 
-// VY_ERR_STATE unless vy_net_bind_train bound the gradient buffers — and, same_shape: its plan is the one the workspace
-// is bound with now (the step entries; `hint` completes the message)
+// VY_ERR_STATE unless vy_net_bind_train bound the gradient buffers — and, same_shape: no inference plan was committed
+// since, so its regions still lie behind the plan in force (the step entries; `hint` completes the message)
 int bound_train(const vy_net* net, bool same_shape, const char* hint) {
   const VyTrain* t = net->train;
-  if (!t || !t->grads || (same_shape && (t->plan.B != net->B || t->plan.H != net->H || t->plan.W != net->W)))
+  if (!t || !t->grads || (same_shape && t->plan.behind != net->commits))
     return fail(VY_ERR_STATE, "training workspace not bound%s", hint);
   return 0;
 }
@@ -933,14 +937,14 @@ int train_forward(vy_net* net, const float* x, const float* const* routes, const
   la.weights_t = in.weights_t;
   la.clas_t = in.clas_t;
   la.partials = c.at<float>(c.p.loss_part_off);
-  la.B = net->B;
+  la.B = net->cur.B;
   la.C = net->num_class;
   la.M = in.M;
   la.N = N;
   la.ignore_iou_thresh = c.t->ignore_iou;
   la.label_smooth = c.t->label_smooth;
   HIP_TRY(vy_launch_loss(la, c.s));
-  HIP_TRY(vy_launch_loss_reduce(la.partials, vy_loss_blocks_per_image(N), net->B, in.losses, c.s));
+  HIP_TRY(vy_launch_loss_reduce(la.partials, vy_loss_blocks_per_image(N), net->cur.B, in.losses, c.s));
   c.t->forward_done = true;
   c.t->M = in.M;
   return 0;
@@ -970,7 +974,7 @@ int train_mode_forward(vy_net* net, const float* x, const float* const* routes, 
   ra.scales = out.scales;
   ra.objness = out.objness;
   ra.class_pred = out.class_pred;
-  ra.B = net->B;
+  ra.B = net->cur.B;
   ra.C = net->num_class;
   ra.N = N;
   HIP_TRY(vy_launch_raw_preds(ra, c.s));
@@ -981,6 +985,7 @@ int train_backward(vy_net* net, const float* x, hipStream_t s) {
   VyTrain* t = net->train;
   if (!t || !t->forward_done) return fail(VY_ERR_STATE, "vy_net_train_backward without a recorded forward");
   t->forward_done = false;
+  VY_TRY(bound_train(net, true, " (vy_net_bind_train)"));  // (a bind since the forward: its recording is gone)
   return backward_train(TrainCtx(net, s), x);
 }
 
@@ -999,26 +1004,32 @@ static int check_train_shape(int32_t height, int32_t width) {
 size_t vy_net_train_workspace_bytes(const vy_net* net, int32_t batch, int32_t height, int32_t width) {
   if (!net) return 0;
   if (check_train_shape(height, width)) return 0;
-  if (vy_net_workspace_bytes(net, batch, height, width) == 0) return 0;
-  vy_net* n = const_cast<vy_net*>(net);
-  return plan_train(n, *get_train(n), batch, height, width, false).total;
+  if (vy_check_shape(batch, height, width)) return 0;
+  const NetPlan fwd = net->plan(batch, height, width, /*keep_all=*/true);
+  if (net->train) return plan_train(*net, *net->train, fwd, batch, height, width).total;
+  VyTrain fresh;  // (a query allocates nothing on the net)
+  default_options(*net, &fresh);
+  return plan_train(*net, fresh, fwd, batch, height, width).total;
 }
 
 int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, int32_t height, int32_t width,
                       void* dev_grads, void* dev_momentum, void* stream) {
   if (!net || !dev_ws || !dev_grads || !dev_momentum) return fail(VY_ERR_INVALID, "null argument");
   if (int rc = check_train_shape(height, width)) return rc;
-  if (vy_net_workspace_bytes(net, batch, height, width) == 0) return VY_ERR_INVALID;
+  if (vy_check_shape(batch, height, width)) return VY_ERR_INVALID;
   if (int rc = net->bind_cus(dev_ws)) return rc;
   VyTrain* t = get_train(net);
-  const size_t need = plan_train(net, *t, batch, height, width, false).total;
+  NetPlan fwd = net->plan(batch, height, width, /*keep_all=*/true);
+  TrainPlan plan = plan_train(*net, *t, fwd, batch, height, width);
+  const size_t need = plan.total;
   if (bytes < need) return fail(VY_ERR_INVALID, "training workspace too small: %zu < %zu bytes", bytes, need);
-  t->plan = plan_train(net, *t, batch, height, width, true);
+  t->plan = std::move(plan);
   t->sdesc_uploaded = t->tabs_built = t->seg_uploaded = false;  // (the workspace is zeroed below)
   t->grads = static_cast<float*>(dev_grads);
   t->mom = static_cast<float*>(dev_momentum);
   t->forward_done = false;
-  VY_TRY(net->commit_bind(dev_ws, bytes, need, static_cast<hipStream_t>(stream)));
+  VY_TRY(net->commit_bind(std::move(fwd), dev_ws, bytes, need, static_cast<hipStream_t>(stream)));
+  t->plan.behind = net->commits;
   if (net->knobs.train_side_stream && !t->side) {
     // (The weight-gradient stream at the LOWEST queue priority was measured: +0.4 % on top of the raised issue priority of the
     // BatchNorm passes in a fresh process — and the whole training step 1.55x SLOWER, forward included, in a process that had
@@ -1180,13 +1191,13 @@ int vy_net_read_grad_activation(vy_net* net, const char* name, float* dst_dev, v
   TrainCtx c(net, stream);
   if (const int i = vy_pool_tap(net, name); i >= 0) {
     const vy_net::RouteSlot& r = net->routes[i];
-    const PlaneT& p = net->planes[r.plane];
-    HIP_TRY(vy_launch_plane_to_nchw(c.gplane(r.plane), net->B, p.H, p.W, p.C, r.co, r.C, dst_dev, c.s));
+    const PlaneAt p = net->plane(r.plane);
+    HIP_TRY(vy_launch_plane_to_nchw(c.gplane(r.plane), net->cur.B, p.H, p.W, p.C, r.co, r.C, dst_dev, c.s));
     return 0;
   }
   for (const ConvT& cv : net->convs) {
     if (cv.name != name) continue;
-    const PlaneT& p = net->planes[cv.out_plane];
+    const PlaneAt p = net->plane(cv.out_plane);
     HIP_TRY(vy_launch_plane_to_nchw(c.gplane(cv.out_plane), net->plane_batch(cv.out_plane), p.H, p.W, p.C, cv.out_co,
                                     cv.cout, dst_dev, c.s));
     return 0;
@@ -1221,7 +1232,7 @@ int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* d
         d[2] = d[3] = 1;
         break;
       case VY_TAP_GRAD_PADDED: {
-        const PlaneT& p = net->planes[cv.out_plane];
+        const PlaneAt p = net->plane(cv.out_plane);
         src = c.gplane(cv.out_plane);
         d[2] = p.H + 2;
         d[3] = p.W + 2;
@@ -1231,7 +1242,7 @@ int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* d
       }
       case VY_TAP_INPUT_PADDED: {
         if (cv.is_stem) return fail(VY_ERR_INVALID, "the stem reads the image, not a plane");
-        const PlaneT& p = net->planes[cv.in_plane];
+        const PlaneAt p = net->plane(cv.in_plane);
         src = net->plane_ptr(cv.in_plane);
         d[1] = cv.cin;
         d[2] = p.H + 2;
