@@ -416,6 +416,40 @@ typedef struct vy_train_aug {
 int vy_train_transform(const uint8_t* frames, const vy_train_aug* augs, int32_t batch, int32_t k, float* out,
                        int32_t height, int32_t width, const float* fill3, const float* mean3, const float* std3,
                        void* stream);
+
+/* Mixup in the same launch: gluoncv.data.MixupDetection.__getitem__ (the wrapper train_yolov3.py:227-229, 571-581 puts
+ * round its dataset) blends two images on a zero canvas of the larger height and width, both at the origin, and rounds the
+ * blend back to uint8 before the transform sees it [UPSTREAM-RECALLED: gluoncv is not available here; restated from
+ * memory, DESIGN.md §18].  Here nothing is blended ahead of the launch: a vy_train_mix beside a sample's vy_train_aug names
+ * its two sources and the kernel blends every pixel it reads, before the colour ops:
+ *   l1 = (float)lambd, l2 = (float)(1.0 - lambd)            the subtraction in double, by the caller
+ *   both sources cover the pixel    m = (float)p1 * l1 + (float)p2 * l2     each product rounded to fp32, then added
+ *   only the first                  m = (float)p1 * l1
+ *   only the second                 m = 0.0f + (float)p2 * l2
+ *   neither                         m = 0
+ *   the mixed pixel is (uint8)m, truncated toward zero (not rounded); it cannot leave [0, 255]
+ * Unlike gluoncv, which mixes single images, a clip is mixed frame t with frame t (both sources hold k frames).
+ *
+ * The first source's k frames (h1, w1, 3) lie from byte src_offset of the sample's vy_train_aug, the second's (h2, w2, 3)
+ * from byte src2_offset; the aug's src_h x src_w is the mix canvas, max(h1, h2) x max(w1, w2), and everything else in the
+ * vy_train_aug means what it means for vy_train_transform with the canvas as the source.  src2_offset = -1: no second
+ * source — the sample is read as vy_train_transform reads it (src_h x src_w = h1 x w1; h2, w2, l1 and l2 are not used
+ * but are checked like the others), so a batch may hold mixed and unmixed samples. */
+typedef struct vy_train_mix {
+  int64_t src2_offset;
+  int32_t h1, w1;
+  int32_t h2, w2;
+  float l1, l2;
+} vy_train_mix;
+/* Both descriptors travel in the kernel arguments, 144 + 32 bytes a sample: VY_MIX_CHUNK samples per launch. */
+#define VY_MIX_CHUNK 22
+/* vy_train_transform with a HOST array of `batch` vy_train_mix beside augs.  Every descriptor is checked before anything
+ * is launched: what vy_train_transform checks, and all four extents >= 1, src_h x src_w equal to the larger of the two
+ * extents (to the first's when there is no second source), src2_offset >= 0 or exactly -1, 0 <= l1, l2 <= 1 — else
+ * VY_ERR_INVALID naming the descriptor, and no launch. */
+int vy_train_transform_mix(const uint8_t* frames, const vy_train_aug* augs, const vy_train_mix* mixes, int32_t batch,
+                           int32_t k, float* out, int32_t height, int32_t width, const float* fill3, const float* mean3,
+                           const float* std3, void* stream);
 /* Host-only (no device is touched): include/vy_math.h's vy_lanczos4_weights, the eight Lanczos-4 tap weights the
  * kernel uses for the fractional position x, for checkers. */
 void vy_math_lanczos4(float x, float* w8);

@@ -9,7 +9,12 @@ numpy sources (draws, packing, the copy to the device, both launches) is printed
 With --stats the same child runs a second time under `rocprofv3 --kernel-trace --stats` and the kernel's own mean time
 is added.  The table goes to --out (default profiles/train_transform.txt).
 
-    python tools/train_transform.py [--stats] [--size 416] [--batch 16] [--src 720x1280] [--rounds 3] [--out PATH]
+With --mixup the whole-frame draw is also timed through vy_train_transform_mix, every sample mixed with a
+second source of the same size (each tap reads twice the source bytes: the costliest mix), in the same rounds as the plain
+launches; and from host numpy sources, alternating, the wall time of the mixed path (pack both sources, one copy, the mix
+launch) next to the path it replaces (MixedClip.numpy() on the host, pack, one copy, the plain launch).
+
+    python tools/train_transform.py [--stats] [--mixup] [--size 416] [--batch 16] [--src 720x1280] [--rounds 3] [--out PATH]
 """
 import argparse
 import csv
@@ -95,6 +100,22 @@ def measure(args):
             for interp in range(5):
                 a = dict(d, interp=interp)
                 descs[name, interp] = (_lib.TrainAug * b)(*[t.descriptor(a, i * k * frame_bytes) for i in range(b)])
+        if args.mixup:
+            from videoyolo_amd.transforms import MixedClip
+            # the first sources again, then as many second sources; sample i is mixed with sample b + i
+            src_mix = torch.cat([src, torch.randint(0, 256, (b * k * frame_bytes,), dtype=torch.uint8,
+                                                    generator=torch.Generator().manual_seed(1)).to(dev)])
+            mix_one = _lib.TrainMix * b
+            mixes = mix_one(*[_lib.TrainMix((b + i) * k * frame_bytes, sh, sw, sh, sw, float(np.float32(0.37)), float(np.float32(1.0 - 0.37)))
+                              for i in range(b)])
+
+            def launch_mix(descs):
+                _lib.check(lib.vy_train_transform_mix(ctypes.c_void_p(src_mix.data_ptr()), descs, mixes, b, k,
+                                                      ctypes.c_void_p(x.data_ptr()), s, s, three(t._fill), three(t._mean),
+                                                      three(t._std), stream))
+            for interp in range(5):
+                launch_mix(descs["whole frame", interp])
+            ms_mix = {interp: [] for interp in range(5)}
         launch(descs["whole frame", 1])  # a real input for the step
         for _ in range(args.warmup):
             step()
@@ -106,6 +127,8 @@ def measure(args):
         for _ in range(args.rounds):
             for key in descs:
                 ms[key].append(timed(lambda: launch(descs[key]), args.launches))
+                if args.mixup and key[0] == "whole frame":
+                    ms_mix[key[1]].append(timed(lambda: launch_mix(descs[key]), args.launches))
             step_ms.append(timed(step, args.steps))
         med = lambda v: float(np.median(v))  # noqa: E731
         # t.batch end to end from host numpy sources (information only: the copy of the sources dominates)
@@ -123,6 +146,30 @@ def measure(args):
             "bytes_per_launch": b * k * frame_bytes + b * k * 3 * s * s * 4,
             "transform_ms": {"%s/%s" % (n, INTERP[i]): round(med(v), 4) for (n, i), v in ms.items()},
             "batch_wall_ms_from_host": round(wall, 2)}
+        if args.mixup:
+            host2 = [np.random.default_rng(100 + i).integers(0, 256, (k, sh, sw, 3), dtype=np.uint8) for i in range(b)]
+            whole = [dict(draws["whole frame"], interp=1)] * b
+
+            def wall_ms(make):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                t.transform_frames(make(), whole, device=dev)
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+            in_launch = lambda: [MixedClip(u, v, 0.37) for u, v in zip(host, host2)]  # noqa: E731
+            on_host = lambda: [MixedClip(u, v, 0.37).numpy() for u, v in zip(host, host2)]  # noqa: E731
+            wall_ms(in_launch), wall_ms(on_host)
+            walls = {"in_launch": [], "on_host": []}
+            for _ in range(3):  # alternating
+                walls["in_launch"].append(wall_ms(in_launch))
+                walls["on_host"].append(wall_ms(on_host))
+            out["k"][str(k)]["mixup"] = {
+                "bytes_per_launch": 2 * b * k * frame_bytes + b * k * 3 * s * s * 4,
+                "transform_ms": {INTERP[i]: round(med(v), 4) for i, v in ms_mix.items()},
+                "plain_ms_rounds": {INTERP[i]: [round(u, 4) for u in ms["whole frame", i]] for i in range(5)},
+                "mix_ms_rounds": {INTERP[i]: [round(u, 4) for u in v] for i, v in ms_mix.items()},
+                "wall_ms_in_launch": [round(v, 1) for v in walls["in_launch"]],
+                "wall_ms_blend_on_host": [round(v, 1) for v in walls["on_host"]]}
         del net, tr
     return out
 
@@ -138,13 +185,18 @@ def kernel_stats(argv):
         return {"error": "rocprofv3 run did not finish within %d s" % CHILD_TIMEOUT_S}
     if p.returncode != 0:
         return {"error": "rocprofv3 run failed (%d)" % p.returncode, "tail": p.stdout[-1500:]}
+    found = {}
     for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
         with open(path) as f:
             for r in csv.DictReader(f):
-                if "train_transform_kernel" in (r.get("Name") or r.get("KernelName") or ""):
-                    return {"calls": int(r["Calls"]), "mean_us": round(float(r["AverageNs"]) / 1e3, 2),
-                            "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2), "max_us": round(float(r.get("MaxNs", 0)) / 1e3, 2)}
-    return {"error": "no train_transform_kernel row in the kernel statistics"}
+                name = r.get("Name") or r.get("KernelName") or ""
+                if "train_transform_kernel" in name:  # the mix instantiation carries its argument struct's name
+                    found.setdefault("mix" if "MixArgs" in name else "plain", {
+                        "calls": int(r["Calls"]), "mean_us": round(float(r["AverageNs"]) / 1e3, 2),
+                        "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2), "max_us": round(float(r.get("MaxNs", 0)) / 1e3, 2)})
+    if "plain" not in found:
+        return {"error": "no train_transform_kernel row in the kernel statistics"}
+    return dict(found["plain"], mix=found["mix"]) if "mix" in found else found["plain"]
 
 
 def table(res, stats):
@@ -162,6 +214,17 @@ def table(res, stats):
                                                                         "within" if worst <= 0.02 * r["step_ms"] else "MISSED"))
         lines.append("  t.batch from host numpy sources, wall: %.1f ms (draws, packing, host-to-device copy, both launches)" % (
             r["batch_wall_ms_from_host"]))
+        if "mixup" in r:
+            m = r["mixup"]
+            lines.append("  mixup, whole frame, every sample mixed with a second %dx%d source: %.1f MB moved per launch" % (
+                res["src"][0], res["src"][1], m["bytes_per_launch"] / 1e6))
+            lines.append("  %-28s %10s %12s %10s   %s" % ("mix launch / interp", "ms/batch", "x plain", "GB/s", "rounds: plain | mix"))
+            for name, ms in m["transform_ms"].items():
+                plain = r["transform_ms"]["whole frame/" + name]
+                lines.append("  %-28s %10.4f %12.2f %10.0f   %s | %s" % (name, ms, ms / plain, m["bytes_per_launch"] / ms / 1e6,
+                                                                         m["plain_ms_rounds"][name], m["mix_ms_rounds"][name]))
+            lines.append("  from host numpy sources, linear, wall ms: both sources packed + mix launch %s; MixedClip.numpy() on the "
+                         "host + plain launch %s" % (m["wall_ms_in_launch"], m["wall_ms_blend_on_host"]))
         lines.append("")
     if stats is not None:
         lines.append("rocprofv3 --kernel-trace --stats, train_transform_kernel over both k, both draws and all interps: %s" %
@@ -179,13 +242,14 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--stats", action="store_true")
+    ap.add_argument("--mixup", action="store_true", help="also time vy_train_transform_mix and the host blend it replaces")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_transform.txt"))
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         print(json.dumps(measure(args)))
         return
-    argv = ["--size", str(args.size), "--batch", str(args.batch), "--src", args.src]
+    argv = ["--size", str(args.size), "--batch", str(args.batch), "--src", args.src] + (["--mixup"] if args.mixup else [])
     p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--rounds", str(args.rounds), "--launches",
                         str(args.launches), "--steps", str(args.steps), "--warmup", str(args.warmup)] + argv, cwd=ROOT,
                        stdout=subprocess.PIPE, universal_newlines=True, timeout=CHILD_TIMEOUT_S)  # a hung child ends the tool

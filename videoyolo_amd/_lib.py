@@ -144,9 +144,20 @@ class TrainAug(ctypes.Structure):
                 ("a", _f32 * VY_AUG_MAX_OPS), ("b", _f32 * VY_AUG_MAX_OPS), ("hue", (_f32 * 3) * 3)]
 
 
+VY_MIX_CHUNK = 22
+
+
+class TrainMix(ctypes.Structure):
+    """vy_train_mix (include/vyolo.h): one sample's two sources and mix ratios; src2_offset = -1 for no second source."""
+    _fields_ = [("src2_offset", ctypes.c_int64), ("h1", _i32), ("w1", _i32), ("h2", _i32), ("w2", _i32), ("l1", _f32),
+                ("l2", _f32)]
+
+
 SIGNATURES.update({
     # the training transform (videoyolo_amd/transforms.py, csrc/augment.hip)
     "vy_train_transform": (ctypes.c_int, [_vp, ctypes.POINTER(TrainAug), _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "vy_train_transform_mix": (ctypes.c_int, [_vp, ctypes.POINTER(TrainAug), ctypes.POINTER(TrainMix), _i32, _i32, _vp, _i32,
+                                              _i32, _vp, _vp, _vp, _vp]),
     "vy_math_lanczos4": (None, [_f32, ctypes.POINTER(_f32)]),
 })
 

@@ -25,9 +25,22 @@
 //             a side enlarged: the linear arithmetic with s = floor(d * scale),
 //             f = (float)((d + 1) - (s + 1) * inv_scale), f = f <= 0 ? 0 : f - floor(f)
 //   same size nearest with scale 1, which is a copy
+//
+// Mixup (vy_train_transform_mix) [UPSTREAM-RECALLED: gluoncv.data.MixupDetection.__getitem__, restated from
+// memory].  The MIX instantiation treats src_h x src_w as the mix canvas: two sources of their own extents, both at the
+// canvas origin, and inside the canvas a pixel is read from up to two of them and blended BEFORE the colour ops:
+//   l1 = (float)lambd, l2 = (float)(1.0 - lambd)       (the subtraction in double, on the host)
+//   both cover      m = (float)p1 * l1 + (float)p2 * l2   (each product rounded to fp32, then added)
+//   first only      m = (float)p1 * l1
+//   second only     m = 0.0f + (float)p2 * l2
+//   neither         m = 0
+//   mixed pixel     (uint8)m, truncated toward zero, not rounded; it cannot leave [0, 255]
+// That uint8 value is what the colour step converts to float.  A sample without a second source takes the plain read.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/vyolo.h"
 #include "net_internal.h"
@@ -46,12 +59,64 @@ struct AugArgs {
 
 static_assert(sizeof(vy_train_aug) == 144 && sizeof(AugArgs) <= 4096, "the descriptors must fit the argument segment");
 
+// the mix launch's arguments: the same head, and a vy_train_mix beside every vy_train_aug
+struct MixArgs {
+  const uint8_t* src;
+  float* dst;
+  int n, k, H, W;
+  float fill[3], mean[3], stdv[3];
+  vy_train_aug d[VY_MIX_CHUNK];
+  vy_train_mix m[VY_MIX_CHUNK];
+};
+
+static_assert(sizeof(vy_train_mix) == 32 && sizeof(MixArgs) <= 4096, "the mix descriptors must fit the argument segment");
+
 struct Px {
   float c[3];
 };
 
+// frame t of a sample of the mix launch: the first source's frame, the second's (null for a sample without a second
+// source) and the sample's vy_train_mix.  The plain launch's frame is the bare pointer.
+struct MixFrame {
+  const uint8_t* S;
+  const uint8_t* S2;
+  vy_train_mix m;
+};
+
+// the uint8 pixel (x, y) of the mix canvas as floats: the truncated blend of the sources that cover (x, y); each read
+// stays inside its own source's frame.  A sample without a second source takes the plain read (the canvas is its source).
+__device__ __forceinline__ void mixed_pixel(const vy_train_aug& d, const MixFrame& F, int x, int y, float& r, float& g,
+                                            float& b) {
+  if (F.S2 == nullptr) {  // uniform: the sample's
+    const uint8_t* q = F.S + ((long long)y * d.src_w + x) * 3;
+    r = (float)q[0];
+    g = (float)q[1];
+    b = (float)q[2];
+    return;
+  }
+  const vy_train_mix& m = F.m;
+  r = g = b = 0.0f;
+  if (x < m.w1 && y < m.h1) {
+    const uint8_t* q = F.S + ((long long)y * m.w1 + x) * 3;
+    r = (float)q[0] * m.l1;
+    g = (float)q[1] * m.l1;
+    b = (float)q[2] * m.l1;
+  }
+  if (x < m.w2 && y < m.h2) {
+    const uint8_t* q = F.S2 + ((long long)y * m.w2 + x) * 3;
+    r = r + (float)q[0] * m.l2;
+    g = g + (float)q[1] * m.l2;
+    b = b + (float)q[2] * m.l2;
+  }
+  r = (float)(int)r;  // (uint8)m: truncated toward zero, 0 <= m < 256
+  g = (float)(int)g;
+  b = (float)(int)b;
+}
+
 // the pixel at crop coordinates (cx, cy) of frame `S`: the distorted source inside the paste, the fill outside it
-__device__ __forceinline__ Px fetch(const AugArgs& a, const vy_train_aug& d, const uint8_t* S, int cx, int cy) {
+// (the mix launch: the paste is the mix canvas)
+template <class Args, class Src>
+__device__ __forceinline__ Px fetch(const Args& a, const vy_train_aug& d, Src S, int cx, int cy) {
   const int x = cx + d.crop_x - d.paste_x, y = cy + d.crop_y - d.paste_y;
   Px p;
   if (x < 0 || y < 0 || x >= d.src_w || y >= d.src_h) {
@@ -60,8 +125,18 @@ __device__ __forceinline__ Px fetch(const AugArgs& a, const vy_train_aug& d, con
     p.c[2] = a.fill[2];
     return p;
   }
-  const uint8_t* q = S + ((long long)y * d.src_w + x) * 3;
-  float r = (float)q[0], g = (float)q[1], b = (float)q[2];
+  // MIX is the frame's type, and the plain read stays written out here: through a helper shared with the mix launch the
+  // plain instantiation no longer compiled to the code it was (1.5 - 2.7 % slower on linear and Lanczos-4)
+  constexpr bool MIX = std::is_same<Src, MixFrame>::value;
+  float r, g, b;
+  if constexpr (MIX) {
+    mixed_pixel(d, S, x, y, r, g, b);
+  } else {
+    const uint8_t* q = S + ((long long)y * d.src_w + x) * 3;
+    r = (float)q[0];
+    g = (float)q[1];
+    b = (float)q[2];
+  }
 #pragma unroll
   for (int i = 0; i < VY_AUG_MAX_OPS; ++i) {  // unrolled: constant indices keep the descriptor in registers
     if (i >= d.num_ops) break;
@@ -162,8 +237,8 @@ __device__ __forceinline__ void axis_taps(int d, int ssize, int dsize, int idx[N
   }
 }
 
-template <int MODE, int N>
-__device__ __forceinline__ Px resample(const AugArgs& a, const vy_train_aug& d, const uint8_t* S, int ux, int dy) {
+template <int MODE, int N, class Args, class Src>
+__device__ __forceinline__ Px resample(const Args& a, const vy_train_aug& d, Src S, int ux, int dy) {
   int xi[N], yi[N];
   float xw[N], yw[N];
   axis_taps<MODE, N>(ux, d.crop_w, a.W, xi, xw);
@@ -219,13 +294,27 @@ __device__ __forceinline__ AreaSpan area_span(int d, int ssize, int dsize) {
   return a;
 }
 
-__global__ __launch_bounds__(256) void train_transform_kernel(AugArgs a) {
+__device__ __forceinline__ const uint8_t* frame_of(const AugArgs& a, const vy_train_aug& d, int sample, int t) {
+  return a.src + d.src_offset + (long long)t * d.src_h * d.src_w * 3;
+}
+
+__device__ __forceinline__ MixFrame frame_of(const MixArgs& a, const vy_train_aug& d, int sample, int t) {
+  MixFrame F;
+  F.m = a.m[sample];  // uniform, like d
+  F.S = a.src + d.src_offset + (long long)t * F.m.h1 * F.m.w1 * 3;
+  F.S2 = F.m.src2_offset < 0 ? nullptr : a.src + F.m.src2_offset + (long long)t * F.m.h2 * F.m.w2 * 3;
+  return F;
+}
+
+// Args = AugArgs is the plain transform; Args = MixArgs blends two sources in source_pixel()
+template <class Args>
+__global__ __launch_bounds__(256) void train_transform_kernel(Args a) {
   const int dx = blockIdx.x * 256 + threadIdx.x;
   if (dx >= a.W) return;
   const int dy = blockIdx.y, frame = blockIdx.z;
   const int sample = frame / a.k, t = frame - sample * a.k;
   const vy_train_aug d = a.d[sample];  // uniform: the descriptor sits in scalar registers
-  const uint8_t* S = a.src + d.src_offset + (long long)t * d.src_h * d.src_w * 3;
+  const auto S = frame_of(a, d, sample, t);
   const int ux = d.flip ? a.W - 1 - dx : dx;
   Px v;
   switch (d.interp) {
@@ -297,36 +386,41 @@ int kernel_mode(const vy_train_aug& d, int H, int W) {
   return kAreaLinear;
 }
 
-}  // namespace
+// what is wrong with a descriptor, or null
+const char* invalid(const vy_train_aug& d) {
+  if (d.src_offset < 0) return "negative source offset";
+  if (d.src_h < 1 || d.src_w < 1 || d.canvas_h < 1 || d.canvas_w < 1 || d.crop_h < 1 || d.crop_w < 1) return "a size below 1";
+  if (d.paste_x < 0 || d.paste_y < 0 || (long long)d.paste_x + d.src_w > d.canvas_w ||
+      (long long)d.paste_y + d.src_h > d.canvas_h)
+    return "the paste leaves the canvas";
+  if (d.crop_x < 0 || d.crop_y < 0 || (long long)d.crop_x + d.crop_w > d.canvas_w ||
+      (long long)d.crop_y + d.crop_h > d.canvas_h)
+    return "the crop leaves the canvas";
+  if (d.interp < 0 || d.interp > 4) return "interp outside 0..4";
+  if (d.num_ops < 0 || d.num_ops > VY_AUG_MAX_OPS) return "bad op count";
+  for (int j = 0; j < d.num_ops; ++j)
+    if (d.op[j] < VY_AUG_BRIGHTNESS || d.op[j] > VY_AUG_HUE) return "unknown op code";
+  return nullptr;
+}
 
-extern "C" void vy_math_lanczos4(float x, float* w8) { vy_lanczos4_weights(x, w8); }
-
-extern "C" int vy_train_transform(const uint8_t* frames, const vy_train_aug* augs, int32_t batch, int32_t k, float* out,
-                                  int32_t height, int32_t width, const float* fill3, const float* mean3,
-                                  const float* std3, void* stream) {
-  if (!frames || !augs || !out || !fill3 || !mean3 || !std3 || batch < 1 || k < 1 || height < 1 || width < 1)
-    return fail(VY_ERR_INVALID, "vy_train_transform: bad argument");
-  if (k > 2048) return fail(VY_ERR_INVALID, "vy_train_transform: k above 2048");  // a chunk's frames are the grid's z
-  for (int i = 0; i < batch; ++i) {
-    const vy_train_aug& d = augs[i];
-    const char* why = nullptr;
-    if (d.src_offset < 0) why = "negative source offset";
-    else if (d.src_h < 1 || d.src_w < 1 || d.canvas_h < 1 || d.canvas_w < 1 || d.crop_h < 1 || d.crop_w < 1)
-      why = "a size below 1";
-    else if (d.paste_x < 0 || d.paste_y < 0 || (long long)d.paste_x + d.src_w > d.canvas_w ||
-             (long long)d.paste_y + d.src_h > d.canvas_h)
-      why = "the paste leaves the canvas";
-    else if (d.crop_x < 0 || d.crop_y < 0 || (long long)d.crop_x + d.crop_w > d.canvas_w ||
-             (long long)d.crop_y + d.crop_h > d.canvas_h)
-      why = "the crop leaves the canvas";
-    else if (d.interp < 0 || d.interp > 4) why = "interp outside 0..4";
-    else if (d.num_ops < 0 || d.num_ops > VY_AUG_MAX_OPS) why = "bad op count";
-    else
-      for (int j = 0; j < d.num_ops; ++j)
-        if (d.op[j] < VY_AUG_BRIGHTNESS || d.op[j] > VY_AUG_HUE) why = "unknown op code";
-    if (why) return fail(VY_ERR_INVALID, "vy_train_transform: descriptor %d: %s", i, why);
+// what is wrong with a mix descriptor beside its (valid) vy_train_aug, or null
+const char* invalid(const vy_train_aug& d, const vy_train_mix& m) {
+  if (m.h1 < 1 || m.w1 < 1 || m.h2 < 1 || m.w2 < 1) return "a source extent below 1";
+  if (m.src2_offset < -1) return "negative second source offset";
+  if (!(m.l1 >= 0.0f && m.l1 <= 1.0f) || !(m.l2 >= 0.0f && m.l2 <= 1.0f)) return "a mix ratio outside [0, 1]";
+  if (m.src2_offset < 0) {
+    if (d.src_h != m.h1 || d.src_w != m.w1) return "src_h x src_w is not the first source's extent (no second source)";
+  } else if (d.src_h != std::max(m.h1, m.h2) || d.src_w != std::max(m.w1, m.w2)) {
+    return "src_h x src_w is not the larger of the two extents";
   }
-  AugArgs a;
+  return nullptr;
+}
+
+// the launches of a validated batch, CHUNK samples each (mixes is null for the plain launch)
+template <class Args, int CHUNK>
+int launch_chunks(const uint8_t* frames, const vy_train_aug* augs, const vy_train_mix* mixes, int batch, int k, float* out,
+                  int height, int width, const float* fill3, const float* mean3, const float* std3, void* stream) {
+  Args a;
   a.src = frames;
   a.k = k;
   a.H = height;
@@ -337,17 +431,52 @@ extern "C" int vy_train_transform(const uint8_t* frames, const vy_train_aug* aug
     a.stdv[c] = std3[c];
   }
   const long long per_sample = (long long)k * 3 * height * width;
-  for (int i0 = 0; i0 < batch; i0 += VY_AUG_CHUNK) {
-    a.n = std::min(batch - i0, (int)VY_AUG_CHUNK);
+  for (int i0 = 0; i0 < batch; i0 += CHUNK) {
+    a.n = std::min(batch - i0, CHUNK);
     a.dst = out + (long long)i0 * per_sample;
     for (int i = 0; i < a.n; ++i) {
       a.d[i] = augs[i0 + i];
       a.d[i].interp = kernel_mode(augs[i0 + i], height, width);
+      if constexpr (std::is_same<Args, MixArgs>::value) a.m[i] = mixes[i0 + i];
     }
-    for (int i = a.n; i < VY_AUG_CHUNK; ++i) memset(&a.d[i], 0, sizeof(vy_train_aug));
-    hipLaunchKernelGGL(train_transform_kernel, dim3((width + 255) / 256, height, a.n * k), dim3(256), 0,
+    for (int i = a.n; i < CHUNK; ++i) {
+      memset(&a.d[i], 0, sizeof(vy_train_aug));
+      if constexpr (std::is_same<Args, MixArgs>::value) memset(&a.m[i], 0, sizeof(vy_train_mix));
+    }
+    hipLaunchKernelGGL(train_transform_kernel<Args>, dim3((width + 255) / 256, height, a.n * k), dim3(256), 0,
                        static_cast<hipStream_t>(stream), a);
     HIP_TRY(hipGetLastError());
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" void vy_math_lanczos4(float x, float* w8) { vy_lanczos4_weights(x, w8); }
+
+extern "C" int vy_train_transform(const uint8_t* frames, const vy_train_aug* augs, int32_t batch, int32_t k, float* out,
+                                  int32_t height, int32_t width, const float* fill3, const float* mean3,
+                                  const float* std3, void* stream) {
+  if (!frames || !augs || !out || !fill3 || !mean3 || !std3 || batch < 1 || k < 1 || height < 1 || width < 1)
+    return fail(VY_ERR_INVALID, "vy_train_transform: bad argument");
+  if (k > 2048) return fail(VY_ERR_INVALID, "vy_train_transform: k above 2048");  // a chunk's frames are the grid's z
+  for (int i = 0; i < batch; ++i)
+    if (const char* why = invalid(augs[i])) return fail(VY_ERR_INVALID, "vy_train_transform: descriptor %d: %s", i, why);
+  return launch_chunks<AugArgs, VY_AUG_CHUNK>(frames, augs, nullptr, batch, k, out, height, width, fill3, mean3, std3,
+                                                     stream);
+}
+
+extern "C" int vy_train_transform_mix(const uint8_t* frames, const vy_train_aug* augs, const vy_train_mix* mixes,
+                                      int32_t batch, int32_t k, float* out, int32_t height, int32_t width,
+                                      const float* fill3, const float* mean3, const float* std3, void* stream) {
+  if (!frames || !augs || !mixes || !out || !fill3 || !mean3 || !std3 || batch < 1 || k < 1 || height < 1 || width < 1)
+    return fail(VY_ERR_INVALID, "vy_train_transform_mix: bad argument");
+  for (int i = 0; i < batch; ++i) {
+    const char* why = invalid(augs[i]);
+    if (!why) why = invalid(augs[i], mixes[i]);
+    if (why) return fail(VY_ERR_INVALID, "vy_train_transform_mix: descriptor %d: %s", i, why);
+  }
+  if (k > 2048) return fail(VY_ERR_INVALID, "vy_train_transform_mix: k above 2048");  // a chunk's frames are the grid's z
+  return launch_chunks<MixArgs, VY_MIX_CHUNK>(frames, augs, mixes, batch, k, out, height, width, fill3, mean3, std3,
+                                                    stream);
 }

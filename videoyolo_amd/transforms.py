@@ -8,6 +8,8 @@
   train   YOLO3VideoTrainTransform.__call__  models/definitions/yolo/transforms.py:199-294: the random draws on the
           host in the reference's order from the reference's two generators (`draw`), the frames of a whole batch of
           clips in ONE HIP launch (csrc/augment.hip), the targets through targets.YOLOV3PrefetchTargetGenerator.
+  mixup   gluoncv.data.MixupDetection as train_yolov3.py:227-229, 571-581 uses it: the wrapper's draws on the host
+          (MixupDetection), the two sources unblended (MixedClip), the blend inside the transform's launch.
   after   detect_yolo3.py:226 (clip to the image), :256-265 (drop id < 0 rows, boxes / image size,
           one [id, score, x1, y1, x2, y2] row per detection), :327-330 (the prediction txt line).
 """
@@ -172,6 +174,110 @@ def hue_matrix(alpha):
     return (_ITYIQ @ rot @ _TYIQ).T.astype(np.float32)
 
 
+def _clip4(src, what):
+    """A (k, h, w, 3) uint8 view of a clip or of one (h, w, 3) image (numpy or torch)."""
+    if not hasattr(src, "shape"):
+        src = np.asarray(src)
+    if len(src.shape) == 3:
+        src = src[None]
+    if len(src.shape) != 4 or src.shape[3] != 3:
+        raise ValueError("%s: expected (k, h, w, 3) or (h, w, 3) frames, got %s" % (what, tuple(src.shape)))
+    if str(src.dtype).split(".")[-1] != "uint8":
+        raise TypeError("%s: frames must be uint8 (decoded images), got %s" % (what, src.dtype))
+    return src
+
+
+class MixedClip(object):
+    """Two uint8 clips and the ratio `lambd` of their mixup, NOT blended: what MixupDetection.__getitem__ returns for
+    lambd < 1 and what YOLO3VideoTrainTransform takes wherever it takes a clip.  The blend happens in the transform's
+    launch (vy_train_transform_mix), pixel by pixel as the kernel reads them.
+
+    first, second: (k, h, w, 3) uint8 with the same k (an (h, w, 3) image is a clip of k = 1), numpy or torch, of any two
+    sizes.  Both sit at the origin of a canvas of the larger height and width: ``shape`` is (k, max h, max w, 3).
+    ``l1`` = float32(lambd) weighs the first, ``l2`` = float32(1.0 - lambd) — subtracted in double, then cast — the second.
+    """
+
+    def __init__(self, first, second, lambd):
+        self.first, self.second = _clip4(first, "first source"), _clip4(second, "second source")
+        if self.first.shape[0] != self.second.shape[0]:
+            raise ValueError("a clip of %d frames cannot be mixed with one of %d: frame t is blended with frame t" % (
+                self.first.shape[0], self.second.shape[0]))
+        self.lambd = float(lambd)
+        if not 0.0 <= self.lambd <= 1.0:
+            raise ValueError("lambd must lie in [0, 1], got %r" % (lambd,))
+        self.l1, self.l2 = np.float32(self.lambd), np.float32(1.0 - self.lambd)
+
+    @property
+    def shape(self):
+        a, b = self.first.shape, self.second.shape
+        return (int(a[0]), int(max(a[1], b[1])), int(max(a[2], b[2])), 3)
+
+    def numpy(self):
+        """The mixed clip as gluoncv materialises it, (k, max h, max w, 3) uint8 on the host — the slow path the launch
+        replaces, kept for callers that want the image and as the statement of the arithmetic: a float32 canvas of
+        zeros, ``canvas[:h1, :w1] = p1 * l1``, ``canvas[:h2, :w2] += p2 * l2`` (each product rounded to float32, then
+        added), and astype(uint8), which truncates toward zero."""
+        a, b = [s.cpu().numpy() if hasattr(s, "cpu") else np.asarray(s) for s in (self.first, self.second)]
+        canvas = np.zeros(self.shape, np.float32)
+        canvas[:, :a.shape[1], :a.shape[2]] = a.astype(np.float32) * self.l1
+        canvas[:, :b.shape[1], :b.shape[2]] += b.astype(np.float32) * self.l2
+        return canvas.astype(np.uint8)
+
+
+class MixupDetection(object):
+    """gluoncv.data.MixupDetection, the wrapper the reference puts round its training set (train_yolov3.py:227-229) and
+    switches per epoch (:571-581): ``set_mixup(np.random.beta, 1.5, 1.5)`` turns mixing on, ``set_mixup(None)`` off
+    [UPSTREAM-RECALLED: gluoncv is not available here; restated from memory, DESIGN.md §18].
+
+    ``self[idx]`` draws in gluoncv's order — ``dataset[idx]``; ``lambd = max(0, min(1, mixup(*args)))`` (1 without a
+    mixup callable); for lambd >= 1 nothing more is drawn and the first sample is returned itself, its label with a ratio
+    column of ones; otherwise ``idx2 = choice(delete(arange(len(self)), idx))`` and ``dataset[idx2]`` — and returns
+    (MixedClip, label): the two sources and lambd, unblended, and ``vstack(hstack(label1, lambd), hstack(label2,
+    1 - lambd))``.  Boxes are not moved: both sources sit at the canvas origin.
+
+    rng=None draws idx2 from the global ``np.random``, as gluoncv does; rng=(random.Random, np.random.RandomState), the
+    pair YOLO3VideoTrainTransform takes, draws it from the RandomState (pass that RandomState's ``beta`` as the mixup
+    callable to keep the global generator untouched).
+
+    Two departures from gluoncv, both on purpose.  Clips: gluoncv reads shape[0] as the height and breaks on
+    (k, h, w, 3); here frame t is blended with frame t, both samples must have the same k (ValueError otherwise), and
+    (h, w, 3) is k = 1.  Label columns: a label is (N, 5) [x1, y1, x2, y2, class] or (N, 6) with the reference's
+    ``difficult`` column, and comes back as (N1 + N2, 6) [x1, y1, x2, y2, class, ratio] — ``difficult`` is dropped
+    rather than widening the label to seven columns, which YOLO3VideoTrainTransform.draw refuses."""
+
+    def __init__(self, dataset, mixup=None, *args, rng=None):
+        self._dataset = dataset
+        self._rng = rng
+        self._mixup, self._mixup_args = mixup, args
+
+    def set_mixup(self, mixup=None, *args):
+        self._mixup, self._mixup_args = mixup, args
+
+    def __len__(self):
+        return len(self._dataset)
+
+    @staticmethod
+    def _with_ratio(label, ratio):
+        label = np.asarray(label)
+        if label.ndim != 2 or label.shape[1] not in (5, 6):
+            raise ValueError("labels are (N, 5) [x1, y1, x2, y2, class] or (N, 6) [..., difficult] arrays, got %s" % (
+                label.shape,))
+        return np.hstack((label[:, :5], np.full((label.shape[0], 1), ratio)))
+
+    def __getitem__(self, idx):
+        N = self._rng[1] if self._rng is not None else np.random
+        img1, label1 = self._dataset[idx]
+        lambd = 1
+        if self._mixup is not None:
+            lambd = max(0, min(1, self._mixup(*self._mixup_args)))
+        if lambd >= 1:
+            return img1, self._with_ratio(label1, 1.0)
+        idx2 = N.choice(np.delete(np.arange(len(self)), idx))
+        img2, label2 = self._dataset[idx2]
+        mixed = MixedClip(img1, img2, lambd)
+        return mixed, np.vstack((self._with_ratio(label1, lambd), self._with_ratio(label2, 1. - lambd)))
+
+
 class YOLO3VideoTrainTransform(object):
     """The reference's training transform (models/definitions/yolo/transforms.py:167-294) for k-frame clips.
 
@@ -291,23 +397,42 @@ class YOLO3VideoTrainTransform(object):
 
     # -- the frames -----------------------------------------------------------------------------------------------------
     def transform_frames(self, srcs, augs, device="cuda:0"):
-        """One vy_train_transform launch sequence for a batch: srcs is a list of (k, h, w, 3) uint8 clips (numpy or
-        torch, sizes may differ between samples, k is the same for all), augs their draws -> (B, k, 3, height, width)
-        fp32 on `device`."""
+        """One launch sequence for a batch: srcs is a list of (k, h, w, 3) uint8 clips (numpy or torch, sizes may differ
+        between samples, k is the same for all) or MixedClips, augs their draws (a MixedClip's for its canvas size) ->
+        (B, k, 3, height, width) fp32 on `device`.  Every source, both of a MixedClip, goes into the one packed buffer;
+        the batch goes out through vy_train_transform_mix if any sample is mixed, else through vy_train_transform."""
         import torch
         lib = _lib.load()
         dev = torch.device(device)
-        flat, offs, off = [], [], 0
+        flat, off = [], 0
         k = int(srcs[0].shape[0])
-        for s in srcs:
+
+        def pack(s):
+            nonlocal off
             t = s if isinstance(s, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(s))
             if t.dtype != torch.uint8:
                 raise TypeError("frames must be uint8 (decoded images), got %s" % t.dtype)
             if t.dim() != 4 or t.shape[0] != k or t.shape[3] != 3:
                 raise ValueError("expected (%d,h,w,3) frames, got %s" % (k, tuple(t.shape)))
             flat.append(t.reshape(-1))
-            offs.append(off)
+            at = off
             off += t.numel()
+            return at
+
+        offs, mixes = [], []
+        for s in srcs:
+            m = _lib.TrainMix()
+            if isinstance(s, MixedClip):
+                offs.append(pack(s.first))
+                m.src2_offset = pack(s.second)
+                (m.h1, m.w1), (m.h2, m.w2) = s.first.shape[1:3], s.second.shape[1:3]
+                m.l1, m.l2 = float(s.l1), float(s.l2)
+            else:
+                offs.append(pack(s))
+                m.src2_offset = -1
+                m.h1, m.w1 = m.h2, m.w2 = s.shape[1:3]
+                m.l1, m.l2 = 1.0, 0.0
+            mixes.append(m)
         if len({f.device for f in flat}) == 1 and flat[0].device == dev:
             buf = torch.cat(flat)
         else:  # one buffer on the host, one copy
@@ -317,12 +442,16 @@ class YOLO3VideoTrainTransform(object):
                 raise ValueError("a draw for a %s source was given %s frames" % (a["src"], tuple(s.shape[1:3])))
         descs = (_lib.TrainAug * len(srcs))(*[self.descriptor(a, o) for a, o in zip(augs, offs)])
         out = torch.empty((len(srcs), k, 3, self._height, self._width), dtype=torch.float32, device=dev)
+        tail = (len(srcs), k, ctypes.c_void_p(out.data_ptr()), self._height, self._width,
+                self._fill.ctypes.data_as(ctypes.c_void_p), self._mean.ctypes.data_as(ctypes.c_void_p),
+                self._std.ctypes.data_as(ctypes.c_void_p))
         with torch.cuda.device(dev):
-            _lib.check(lib.vy_train_transform(
-                ctypes.c_void_p(buf.data_ptr()), descs, len(srcs), k, ctypes.c_void_p(out.data_ptr()),
-                self._height, self._width, self._fill.ctypes.data_as(ctypes.c_void_p),
-                self._mean.ctypes.data_as(ctypes.c_void_p), self._std.ctypes.data_as(ctypes.c_void_p),
-                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            if any(isinstance(s, MixedClip) for s in srcs):
+                _lib.check(lib.vy_train_transform_mix(ctypes.c_void_p(buf.data_ptr()), descs,
+                                                      (_lib.TrainMix * len(srcs))(*mixes), *tail, stream))
+            else:
+                _lib.check(lib.vy_train_transform(ctypes.c_void_p(buf.data_ptr()), descs, *tail, stream))
         return out
 
     # -- the targets ----------------------------------------------------------------------------------------------------
@@ -341,7 +470,7 @@ class YOLO3VideoTrainTransform(object):
         return gb, gi, gm
 
     def __call__(self, src, label, device="cuda:0"):
-        """One sample.  src: (k, h, w, 3) or (h, w, 3) uint8.  net=None: the image, (k, 3, H, W) or (3, H, W) fp32 on
+        """One sample.  src: (k, h, w, 3) or (h, w, 3) uint8, or a MixedClip (drawn for its canvas size).  net=None: the image, (k, 3, H, W) or (3, H, W) fp32 on
         `device`.  With a net: (img, objectness, center_targets, scale_targets, weights, class_targets, gt_boxes) as the
         reference returns them — for an array label one set ((N, 1) ... (M, 4)); for a list label stacked per frame,
         (T, N, 1) ... and gt_boxes (T, M, 4), M the longest frame's box count (at most 100), shorter frames padded
@@ -349,8 +478,8 @@ class YOLO3VideoTrainTransform(object):
         ``gt_bboxes_t[:, :max_boxes, :]`` (:294); this returns that slice, since the contract is what the reference's
         call returns."""
         import torch
-        t = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(src))
-        was_three = t.dim() == 3
+        t = src if isinstance(src, (torch.Tensor, MixedClip)) else torch.as_tensor(np.ascontiguousarray(src))
+        was_three = len(t.shape) == 3
         if was_three:
             t = t[None]
         aug, bbox = self.draw(t.shape[1], t.shape[2], label)
@@ -371,7 +500,8 @@ class YOLO3VideoTrainTransform(object):
 
     def batch(self, srcs, labels, device="cuda:0"):
         """A training batch: one draw per sample, the sources packed into one device buffer, ONE vy_train_transform call
-        and ONE vy_prefetch_targets call.  srcs: B clips (k, h, w, 3) uint8 (or (h, w, 3) with k = 1) of any sizes;
+        and ONE vy_prefetch_targets call.  srcs: B clips (k, h, w, 3) uint8 (or (h, w, 3) with k = 1) of any sizes, or
+        MixedClips as MixupDetection returns them (drawn for their canvas size; the call is then vy_train_transform_mix);
         labels: B (N_i, 5+) arrays, one label set per clip.  Returns (x, gt_boxes, objectness, center_targets,
         scale_targets, weights, class_targets): x (B, k, 3, H, W) — (B, 3, H, W) for k = 1 — and the six training
         inputs of net(x, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)."""
@@ -384,10 +514,10 @@ class YOLO3VideoTrainTransform(object):
         for s, label in zip(srcs, labels):
             if isinstance(label, list):
                 raise ValueError("batch() takes one label array per clip (the nets train on one label set per sample)")
-            t = s if isinstance(s, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(s))
-            if t.dim() == 3:
+            t = s if isinstance(s, (torch.Tensor, MixedClip)) else torch.as_tensor(np.ascontiguousarray(s))
+            if len(t.shape) == 3:
                 t = t[None]
-            if t.dim() != 4 or t.shape[0] != self._k:
+            if len(t.shape) != 4 or t.shape[0] != self._k:
                 raise ValueError("expected clips of %d frames, got %s" % (self._k, tuple(t.shape)))
             aug, bbox = self.draw(t.shape[1], t.shape[2], label)
             clips.append(t)
