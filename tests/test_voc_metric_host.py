@@ -111,6 +111,28 @@ def test_host_inputs_leave_the_device_counter_alone():
     assert m._chunks == [] and m._n_pos == {}
 
 
+@pytest.mark.parametrize("rows", [(3, 0, 5), (2, 0, 5)])
+def test_chunks_to_host_gives_every_tensor_back_after_one_copy(rows):
+    """Three chunks, one without rows; 1-, 4- and 8-byte kinds in mixed order with 1-D, 2-D and 3-D shapes.  With 7 rows
+    in all the 4- and 1-byte kinds have byte counts that are no multiple of 8: joined in the given order, the wider kinds
+    after them would sit at unaligned offsets."""
+    import torch
+    g = torch.Generator().manual_seed(0)
+    ints = lambda dt, *shape: torch.randint(-100 if dt.is_signed else 0, 100, shape, generator=g).to(dt)    # noqa: E731
+    chunks = [(ints(torch.int32, n), torch.randn(n, generator=g, dtype=torch.float64), ints(torch.uint8, n, 3),
+               torch.rand(n, generator=g) < 0.5, ints(torch.int64, n), torch.randn((n, 4), generator=g, dtype=torch.float64),
+               ints(torch.int8, n), torch.randn((n, 2, 3), generator=g), ints(torch.uint8, n, 4, 10)) for n in rows]
+    got = metrics._chunks_to_host(chunks)
+    assert isinstance(got, list) and len(got) == 3
+    for c, h in zip(chunks, got):
+        assert isinstance(h, tuple) and len(h) == len(c)
+        for t, a in zip(c, h):
+            want = t.numpy()
+            assert isinstance(a, np.ndarray) and a.dtype == want.dtype and a.shape == want.shape and np.array_equal(a, want)
+            assert a.flags.aligned
+    assert metrics._chunks_to_host([]) == []
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the C entry's argument checks: nothing is launched, no device is needed
 def _call(lib, **over):

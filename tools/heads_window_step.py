@@ -12,16 +12,12 @@ route_import_pool moves, each with its bytes and TB/s.
     python tools/heads_window_step.py [--size 416] [--clips 16] [--k 3] [--steps 20] [--warmup 5] [--rounds 3] [--stats]
 """
 import argparse
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _measure
+
+sys.path.insert(0, _measure.ROOT)
 
 COPY_CALLS = 23  # a count of its own: the copy's row of the kernel statistics is found by it
 CHILD_TIMEOUT_S = 900
@@ -147,21 +143,11 @@ def launch_kernels(args):
 
 
 def kernel_stats(args, bank_frames):
-    out = tempfile.mkdtemp(prefix="heads_window_step_")
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable,
-           os.path.abspath(__file__), "--kernels-child", "--bank-frames", str(bank_frames), "--size", str(args.size), "--clips",
-           str(args.clips), "--k", str(args.k), "--steps", str(args.steps)]
-    try:
-        p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True,
-                           timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        return {"error": "rocprofv3 run did not finish within %d s" % CHILD_TIMEOUT_S}
-    if p.returncode != 0:
-        return {"error": "rocprofv3 run failed (%d)" % p.returncode, "tail": p.stdout[-1500:]}
-    paths = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
-    if not paths:
-        return {"error": "no kernel_stats.csv under %s" % out,
-                "files": sorted(glob.glob(os.path.join(out, "**", "*"), recursive=True))[:20]}
+    found = _measure.kernel_rows(__file__, ["--kernels-child", "--bank-frames", str(bank_frames), "--size", str(args.size),
+                                            "--clips", str(args.clips), "--k", str(args.k), "--steps", str(args.steps)],
+                                 CHILD_TIMEOUT_S, "heads_window_step_")
+    if isinstance(found, dict):
+        return found
     per_frame = 4 * route_floats(args.size)
     pool_bytes = per_frame * args.clips * (args.k + 1)  # k frames read, the pooled route written
     want = {"route_import_pool_kernel<0>": ("route_import_pool_max", pool_bytes),
@@ -171,18 +157,15 @@ def kernel_stats(args, bank_frames):
                  "route_import_pool_kernelILi1E": want["route_import_pool_kernel<1>"],
                  "route_xfer_kernelILb1E": want["route_xfer_kernel<true>"]})
     rows = {"bank_frames": bank_frames, "bank_MB": round(per_frame * bank_frames / 1e6, 1)}
-    for path in paths:
-        with open(path) as f:
-            for r in csv.DictReader(f):
-                kname = r.get("Name") or r.get("KernelName") or ""
-                hit = [v for key, v in want.items() if key in kname.replace(" ", "")]
-                if not hit and int(r["Calls"]) == COPY_CALLS and "elementwise" in kname:
-                    hit = [("float4_copy", pool_bytes)]
-                    rows["float4_copy_kernel"] = kname[:100]
-                for name, by in hit:
-                    us = float(r["AverageNs"]) / 1e3
-                    rows[name] = {"calls": int(r["Calls"]), "mean_us": round(us, 2), "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2),
-                                  "bytes": by, "TB_per_s": round(by / (us * 1e-6) / 1e12, 2)}
+    for r in found:
+        kname = r["name"]
+        hit = [v for key, v in want.items() if key in kname.replace(" ", "")]
+        if not hit and r["calls"] == COPY_CALLS and "elementwise" in kname:
+            hit = [("float4_copy", pool_bytes)]
+            rows["float4_copy_kernel"] = kname[:100]
+        for name, by in hit:
+            rows[name] = dict(_measure.stats_of(r, ("calls", "mean_us", "min_us")), bytes=by,
+                              TB_per_s=round(by / (r["mean_ns"] / 1e3 * 1e-6) / 1e12, 2))
     copy = rows.get("float4_copy", {}).get("TB_per_s")
     if copy:
         for name, v in rows.items():
@@ -208,14 +191,7 @@ def main():
         print(json.dumps(measure(args) if args.child else launch_kernels(args)))
         return
     argv = [a for a in sys.argv[1:] if a != "--stats"]
-    try:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + argv, cwd=ROOT, stdout=subprocess.PIPE,
-                           universal_newlines=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        sys.exit("the measurement did not finish within %d s" % CHILD_TIMEOUT_S)
-    if p.returncode != 0:
-        sys.exit(p.returncode)
-    print(p.stdout.strip().splitlines()[-1])
+    print(json.dumps(_measure.run_child(__file__, ["--child"] + argv, CHILD_TIMEOUT_S)))
     if args.stats:
         for frames in (args.clips * args.k, 3 * args.clips * args.k):
             print(json.dumps(kernel_stats(args, frames)))

@@ -17,16 +17,14 @@ launch) next to the path it replaces (MixedClip.numpy() on the host, pack, one c
     python tools/train_transform.py [--stats] [--mixup] [--size 416] [--batch 16] [--src 720x1280] [--rounds 3] [--out PATH]
 """
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
-import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _measure
+from _measure import ROOT
+
 sys.path.insert(0, ROOT)
 CHILD_TIMEOUT_S = 600  # either child: the measurement, or the same under rocprofv3
 INTERP = ["nearest", "linear", "cubic", "area", "lanczos4"]
@@ -86,14 +84,7 @@ def measure(args):
                 autograd.backward([l[0] + l[1] + l[2] + l[3]])
             tr.step(b)
 
-        def timed(fn, n):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1) / n
+        timed = lambda fn, n: _measure.timed(torch, fn, n)  # noqa: E731
 
         descs = {}
         for name, d in draws.items():
@@ -175,25 +166,14 @@ def measure(args):
 
 
 def kernel_stats(argv):
-    out = tempfile.mkdtemp(prefix="train_transform_")
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable,
-           os.path.abspath(__file__), "--child", "--rounds", "1", "--launches", "3", "--steps", "1", "--warmup", "1"] + argv
-    try:
-        p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True,
-                           timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        return {"error": "rocprofv3 run did not finish within %d s" % CHILD_TIMEOUT_S}
-    if p.returncode != 0:
-        return {"error": "rocprofv3 run failed (%d)" % p.returncode, "tail": p.stdout[-1500:]}
+    rows = _measure.kernel_rows(__file__, ["--child", "--rounds", "1", "--launches", "3", "--steps", "1", "--warmup", "1"] + argv,
+                                CHILD_TIMEOUT_S, "train_transform_")
+    if isinstance(rows, dict):
+        return rows
     found = {}
-    for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
-        with open(path) as f:
-            for r in csv.DictReader(f):
-                name = r.get("Name") or r.get("KernelName") or ""
-                if "train_transform_kernel" in name:  # the mix instantiation carries its argument struct's name
-                    found.setdefault("mix" if "MixArgs" in name else "plain", {
-                        "calls": int(r["Calls"]), "mean_us": round(float(r["AverageNs"]) / 1e3, 2),
-                        "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2), "max_us": round(float(r.get("MaxNs", 0)) / 1e3, 2)})
+    for r in rows:
+        if "train_transform_kernel" in r["name"]:  # the mix instantiation carries its argument struct's name
+            found.setdefault("mix" if "MixArgs" in r["name"] else "plain", _measure.stats_of(r))
     if "plain" not in found:
         return {"error": "no train_transform_kernel row in the kernel statistics"}
     return dict(found["plain"], mix=found["mix"]) if "mix" in found else found["plain"]
@@ -250,12 +230,8 @@ def main():
         print(json.dumps(measure(args)))
         return
     argv = ["--size", str(args.size), "--batch", str(args.batch), "--src", args.src] + (["--mixup"] if args.mixup else [])
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--rounds", str(args.rounds), "--launches",
-                        str(args.launches), "--steps", str(args.steps), "--warmup", str(args.warmup)] + argv, cwd=ROOT,
-                       stdout=subprocess.PIPE, universal_newlines=True, timeout=CHILD_TIMEOUT_S)  # a hung child ends the tool
-    if p.returncode != 0:
-        sys.exit(p.returncode)
-    res = json.loads(p.stdout.strip().splitlines()[-1])
+    res = _measure.run_child(__file__, ["--child", "--rounds", str(args.rounds), "--launches", str(args.launches), "--steps",
+                                        str(args.steps), "--warmup", str(args.warmup)] + argv, CHILD_TIMEOUT_S)
     text = table(res, kernel_stats(argv) if args.stats else None)
     with open(args.out, "w") as f:
         f.write(text)

@@ -15,18 +15,16 @@ other, since the two run on different machines:
     python tools/vid_metric.py --reference /path/to/VideoYOLO [--ref-frames 2000]
 """
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _measure
+from _measure import ROOT
+
 sys.path.insert(0, ROOT)
 CHILD_TIMEOUT_S = 900
 SECTIONS = ["## reference on the CPU", "## device"]
@@ -84,16 +82,6 @@ class _MotionView(object):
 
 
 # ------------------------------------------------------------------------------------------------------- the device section
-def _timed(torch, fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
 def measure(args):
     import torch
     import videoyolo_amd as vy
@@ -122,30 +110,13 @@ def measure(args):
     print("updates warmed up", file=sys.stderr, flush=True)
     if args.updates_only:
         return out
-    net = vy.yolo3_darknet53(ds.classes, pretrained_base=False)
-    net.initialize(init="synthetic", seed=233, obj_bias=-2.0)
-    net.collect_params().reset_ctx(dev)
-    net.set_nms(0.45, 400, 100)
-    upd_ms, det_ms = [], {416: [], 608: []}
-    x = {s: torch.randn((batch, 3, s, s), device=dev) for s in det_ms}
-    for s in det_ms:
-        for _ in range(2):
-            net(x[s])
-    torch.cuda.synchronize()
-    for _ in range(args.rounds):
-        upd_ms.append(_timed(torch, update, args.updates))
-        for s in det_ms:
-            det_ms[s].append(_timed(torch, lambda: net(x[s]), args.steps))
-    t0 = time.perf_counter()
-    for _ in range(args.updates):
-        update()
-    host_ms = (time.perf_counter() - t0) / args.updates * 1e3      # the host's side of a call: nothing waits for the device
-    torch.cuda.synchronize()
+    net = _measure.detect_net(vy, ds.classes, dev)
+    upd_ms, det_ms, host_ms = _measure.update_and_detect(torch, update, net, dev, batch, (416, 608), args)
     out["update"] = {"batch": batch, "rows": rows, "ms": round(med(upd_ms), 4), "ms_rounds": [round(v, 4) for v in upd_ms],
                      "host_ms_per_call": round(host_ms, 3),
                      "detect_ms": {str(s): round(med(v), 3) for s, v in det_ms.items()},
                      "detect_ms_rounds": {str(s): [round(t, 3) for t in v] for s, v in det_ms.items()}}
-    del net, x, dets, metric
+    del net, dets, metric
     print("update and detect steps timed: %s" % json.dumps(out["update"]), file=sys.stderr, flush=True)
 
     # ---- a VID-val-sized set
@@ -185,22 +156,12 @@ def measure(args):
 
 
 def kernel_stats():
-    out = tempfile.mkdtemp(prefix="vid_metric_")
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable,
-           os.path.abspath(__file__), "--child", "--updates-only"]
-    try:
-        p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True,
-                           timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        return {"error": "rocprofv3 run did not finish within %d s" % CHILD_TIMEOUT_S}
-    if p.returncode != 0:
-        return {"error": "rocprofv3 run failed (%d)" % p.returncode, "tail": p.stdout[-1500:]}
-    for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
-        with open(path) as f:
-            for r in csv.DictReader(f):
-                if "vid_match_kernel" in (r.get("Name") or r.get("KernelName") or ""):
-                    return {"calls": int(r["Calls"]), "mean_us": round(float(r["AverageNs"]) / 1e3, 2),
-                            "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2), "max_us": round(float(r.get("MaxNs", 0)) / 1e3, 2)}
+    rows = _measure.kernel_rows(__file__, ["--child", "--updates-only"], CHILD_TIMEOUT_S, "vid_metric_")
+    if isinstance(rows, dict):
+        return rows
+    for r in rows:
+        if "vid_match_kernel" in r["name"]:
+            return _measure.stats_of(r)
     return {"error": "no vid_match_kernel row in the kernel statistics"}
 
 
@@ -305,12 +266,8 @@ def main():
         write_section(args.out, SECTIONS[0], text)
         print(text)
         return
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--frames", str(args.frames), "--rounds",
-                        str(args.rounds), "--updates", str(args.updates), "--steps", str(args.steps)], cwd=ROOT,
-                       stdout=subprocess.PIPE, universal_newlines=True, timeout=CHILD_TIMEOUT_S)  # a hung child ends the tool
-    if p.returncode != 0:
-        sys.exit(p.returncode)
-    res = json.loads(p.stdout.strip().splitlines()[-1])
+    res = _measure.run_child(__file__, ["--child", "--frames", str(args.frames), "--rounds", str(args.rounds), "--updates",
+                                        str(args.updates), "--steps", str(args.steps)], CHILD_TIMEOUT_S)
     text = device_section(res, kernel_stats() if args.stats else None)
     write_section(args.out, SECTIONS[1], text)
     print(text)

@@ -9,16 +9,13 @@ ring_pool rows of its kernel statistics are printed with the bytes each launch m
     python tools/video_step.py [--size 416] [--frames 16] [--k 3] [--step 1] [--join max] [--steps 100] [--warmup 5] [--stats]
 """
 import argparse
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _measure
+
+sys.path.insert(0, _measure.ROOT)
+CHILD_TIMEOUT_S = 900
 
 COPY_TB_S = 6.3  # what a float4 copy reaches on this chip (DESIGN §10): the streaming bar is 0.7 of it
 
@@ -82,26 +79,16 @@ def ring_bytes(args):
 
 
 def kernel_stats(args, video_ms_per_frame):
-    out = tempfile.mkdtemp(prefix="video_step_")
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable,
-           os.path.abspath(__file__), "--child", "--size", str(args.size), "--frames", str(args.frames), "--k", str(args.k),
-           "--step", str(args.step), "--join", args.join, "--steps", "4", "--warmup", "1"]
-    p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
-    if p.returncode != 0:
-        return {"error": "rocprofv3 run failed (%d)" % p.returncode, "tail": p.stdout[-1500:]}
-    paths = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
-    if not paths:
-        return {"error": "no kernel_stats.csv under %s" % out,
-                "files": sorted(glob.glob(os.path.join(out, "**", "*"), recursive=True))[:20]}
+    found = _measure.kernel_rows(__file__, ["--child", "--size", str(args.size), "--frames", str(args.frames), "--k", str(args.k),
+                                            "--step", str(args.step), "--join", args.join, "--steps", "4", "--warmup", "1"],
+                                 CHILD_TIMEOUT_S, "video_step_")
+    if isinstance(found, dict):
+        return found
     rows = {}
-    for path in paths:
-        with open(path) as f:
-            for r in csv.DictReader(f):
-                kname = r.get("Name") or r.get("KernelName") or ""
-                for name in ("ring_push", "ring_pool"):
-                    if name in kname:
-                        rows[name] = {"calls": int(r["Calls"]), "mean_us": round(float(r["AverageNs"]) / 1e3, 2),
-                                      "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2)}
+    for r in found:
+        for name in ("ring_push", "ring_pool"):
+            if name in r["name"]:
+                rows[name] = _measure.stats_of(r, ("calls", "mean_us", "min_us"))
     push, pool = ring_bytes(args)
     per_round_us = 0.0
     for name, by in (("ring_push", push), ("ring_pool", pool)):
@@ -131,14 +118,10 @@ def main():
         print(json.dumps(measure(args)))
         return
     argv = [a for a in sys.argv[1:] if a != "--stats"]
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + argv, cwd=ROOT,
-                       stdout=subprocess.PIPE, universal_newlines=True)
-    if p.returncode != 0:
-        sys.exit(p.returncode)
-    line = p.stdout.strip().splitlines()[-1]
-    print(line)
+    res = _measure.run_child(__file__, ["--child"] + argv, CHILD_TIMEOUT_S)
+    print(json.dumps(res))
     if args.stats:
-        print(json.dumps(kernel_stats(args, json.loads(line).get("video_ms_per_frame"))))
+        print(json.dumps(kernel_stats(args, res.get("video_ms_per_frame"))))
 
 
 if __name__ == "__main__":

@@ -13,18 +13,16 @@ With --stats a second child runs such updates under `rocprofv3 --kernel-trace --
     python tools/voc_metric.py [--stats] [--images 5000] [--out PATH]
 """
 import argparse
-import csv
-import glob
 import json
 import os
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _measure
+from _measure import ROOT
+
 sys.path.insert(0, ROOT)
 CHILD_TIMEOUT_S = 600
 N_CLS = 20
@@ -56,16 +54,6 @@ def synthetic(seed, images, rows=100, n_gt=8, size=416):
             gd.astype(f)[:, :, None])
 
 
-def _timed(torch, fn, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
 def measure(args):
     import torch
     import videoyolo_amd as vy
@@ -95,26 +83,9 @@ def measure(args):
     print("updates warmed up", file=sys.stderr, flush=True)
     if args.updates_only:
         return out
-    net = vy.yolo3_darknet53(classes, pretrained_base=False)
-    net.initialize(init="synthetic", seed=233, obj_bias=-2.0)
-    net.collect_params().reset_ctx(dev)
-    net.set_nms(0.45, 400, 100)
-    upd_ms, det_ms = [], {416: [], 608: []}
-    x = {s: torch.randn((batch, 3, s, s), device=dev) for s in det_ms}
-    for s in det_ms:
-        for _ in range(2):
-            net(x[s])
-    torch.cuda.synchronize()
-    for _ in range(args.rounds):
-        upd_ms.append(_timed(torch, update, args.updates))
-        for s in det_ms:
-            det_ms[s].append(_timed(torch, lambda: net(x[s]), args.steps))
-    t0 = time.perf_counter()
-    for _ in range(args.updates):
-        update()
-    call_ms = (time.perf_counter() - t0) / args.updates * 1e3      # the host's side of a call: nothing waits for the device
-    torch.cuda.synchronize()
-    del net, x
+    net = _measure.detect_net(vy, classes, dev)
+    upd_ms, det_ms, call_ms = _measure.update_and_detect(torch, update, net, dev, batch, (416, 608), args)
+    del net
 
     # ---- (c) the host path on the same device tensors: copy, then numpy
     host = VOCMApMetric(class_names=classes)
@@ -160,22 +131,12 @@ def _equal(a, b):
 
 
 def kernel_stats():
-    out = tempfile.mkdtemp(prefix="voc_metric_")
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable,
-           os.path.abspath(__file__), "--child", "--updates-only"]
-    try:
-        p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True,
-                           timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        return {"error": "rocprofv3 run did not finish within %d s" % CHILD_TIMEOUT_S}
-    if p.returncode != 0:
-        return {"error": "rocprofv3 run failed (%d)" % p.returncode, "tail": p.stdout[-1500:]}
-    for path in glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True):
-        with open(path) as f:
-            for r in csv.DictReader(f):
-                if "voc_match_kernel" in (r.get("Name") or r.get("KernelName") or ""):
-                    return {"calls": int(r["Calls"]), "mean_us": round(float(r["AverageNs"]) / 1e3, 2),
-                            "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2), "max_us": round(float(r.get("MaxNs", 0)) / 1e3, 2)}
+    rows = _measure.kernel_rows(__file__, ["--child", "--updates-only"], CHILD_TIMEOUT_S, "voc_metric_")
+    if isinstance(rows, dict):
+        return rows
+    for r in rows:
+        if "voc_match_kernel" in r["name"]:
+            return _measure.stats_of(r)
     return {"error": "no voc_match_kernel row in the kernel statistics"}
 
 
@@ -223,12 +184,8 @@ def main():
     if args.child:
         print(json.dumps(measure(args)))
         return
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--images", str(args.images), "--rounds",
-                        str(args.rounds), "--updates", str(args.updates), "--steps", str(args.steps)], cwd=ROOT,
-                       stdout=subprocess.PIPE, universal_newlines=True, timeout=CHILD_TIMEOUT_S)  # a hung child ends the tool
-    if p.returncode != 0:
-        sys.exit(p.returncode)
-    res = json.loads(p.stdout.strip().splitlines()[-1])
+    res = _measure.run_child(__file__, ["--child", "--images", str(args.images), "--rounds", str(args.rounds), "--updates",
+                                        str(args.updates), "--steps", str(args.steps)], CHILD_TIMEOUT_S)
     text = report(res, kernel_stats() if args.stats else None)
     with open(args.out, "w") as f:
         f.write(text)

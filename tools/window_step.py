@@ -7,16 +7,13 @@ are printed with the bytes each launch moves.
     python tools/window_step.py [--size 416] [--clips 16] [--k 3] [--join max] [--steps 20] [--warmup 5] [--stats]
 """
 import argparse
-import csv
-import glob
 import json
-import os
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _measure
+
+sys.path.insert(0, _measure.ROOT)
+CHILD_TIMEOUT_S = 900
 
 
 def measure(args):
@@ -85,26 +82,14 @@ def pool_bytes(args):
 
 
 def kernel_stats(args):
-    out = tempfile.mkdtemp(prefix="window_step_")
-    cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable,
-           os.path.abspath(__file__), "--child", "--size", str(args.size), "--clips", str(args.clips), "--k", str(args.k),
-           "--join", args.join, "--steps", "2", "--warmup", "1"]
-    p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
-    if p.returncode != 0:
-        return {"error": "rocprofv3 run failed (%d)" % p.returncode, "tail": p.stdout[-1500:]}
+    found = _measure.kernel_rows(__file__, ["--child", "--size", str(args.size), "--clips", str(args.clips), "--k", str(args.k),
+                                            "--join", args.join, "--steps", "2", "--warmup", "1"], CHILD_TIMEOUT_S, "window_step_")
+    if isinstance(found, dict):
+        return found
     rows = {}
-    paths = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
-    if not paths:
-        return {"error": "no kernel_stats.csv under %s" % out,
-                "files": sorted(glob.glob(os.path.join(out, "**", "*"), recursive=True))[:20]}
-    for path in paths:
-        with open(path) as f:
-            for r in csv.DictReader(f):
-                kname = r.get("Name") or r.get("KernelName") or ""
-                if "window_pool" in kname:
-                    name = "window_pool_bwd" if "bwd" in kname else "window_pool"
-                    rows[name] = {"calls": int(r["Calls"]), "mean_us": round(float(r["AverageNs"]) / 1e3, 2),
-                                  "min_us": round(float(r.get("MinNs", 0)) / 1e3, 2)}
+    for r in found:
+        if "window_pool" in r["name"]:
+            rows["window_pool_bwd" if "bwd" in r["name"] else "window_pool"] = _measure.stats_of(r, ("calls", "mean_us", "min_us"))
     fwd, bwd = pool_bytes(args)
     for name, by in (("window_pool", fwd), ("window_pool_bwd", bwd)):
         if name in rows:
@@ -128,11 +113,7 @@ def main():
         print(json.dumps(measure(args)))
         return
     argv = [a for a in sys.argv[1:] if a != "--stats"]
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + argv, cwd=ROOT,
-                       stdout=subprocess.PIPE, universal_newlines=True)
-    if p.returncode != 0:
-        sys.exit(p.returncode)
-    print(p.stdout.strip().splitlines()[-1])
+    print(json.dumps(_measure.run_child(__file__, ["--child"] + argv, CHILD_TIMEOUT_S)))
     if args.stats:
         print(json.dumps(kernel_stats(args)))
 

@@ -17,6 +17,8 @@ along the batch axis like utils/general.py:6-17 ``as_numpy``).  float32 tensors 
 Further down: the ImageNet-VID motion / area mAP (``VIDDetectionMetric``) and the COCO detection metric
 (``COCODetectionMetric``), each with its matching rule stated on the host and applied on the device the same way.
 """
+import ctypes
+
 import numpy as np
 
 
@@ -88,13 +90,62 @@ def voc_match_host(boxes, labels, scores, gt_boxes, gt_labels, gt_difficults, io
     return (flags, best) if return_best else flags
 
 
-def _itemsize(dtype):
-    return np.dtype(dtype).itemsize
-
-
 def _is_gpu_f32(t):
     import torch
     return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+
+
+# what the three device paths below share: a list of per-device tensors joined along the batch on the first one's device
+def _gather(x):
+    if isinstance(x, (list, tuple)) and len(x) and all(hasattr(t, "is_cuda") for t in x):
+        import torch
+        return torch.cat([t.to(x[0].device) for t in x], 0)
+    return x
+
+
+def _upload(cache, dev, **arrays):
+    """The named numpy arrays as tensors on dev, once per device (cache); an empty one padded to one element: a valid pointer."""
+    t = cache.get(dev)
+    if t is None:
+        import torch
+        pad = lambda a: a if a.size else np.zeros((1,) + a.shape[1:], a.dtype)  # noqa: E731
+        t = cache[dev] = {n: torch.from_numpy(pad(a)).to(dev) for n, a in arrays.items()}
+    return t
+
+
+# ctypes arguments of the vy_*_match entries: a device tensor's pointer, a host array's, a device's current stream
+def _devp(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _hostp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _streamp(dev):
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _chunks_to_host(chunks):
+    """``chunks``: one tuple of tensors per update, the same kinds at each position.  Returns the same structure as numpy
+    arrays of the tensors' shapes, after ONE copy to the host: every tensor goes to the first chunk's device and is viewed
+    as bytes, the bytes are joined kind by kind and split back on the host."""
+    if not chunks:
+        return []
+    import torch
+    dev = chunks[0][0].device
+    # kind by kind, the widest item size first: every host view below is aligned
+    kinds = sorted(range(len(chunks[0])), key=lambda k: -chunks[0][k].element_size())
+    raw = torch.cat([torch.cat([c[k].to(dev).reshape(-1) for c in chunks]).view(torch.uint8) for k in kinds]).cpu().numpy()
+    host, at = [[None] * len(c) for c in chunks], 0
+    for k in kinds:
+        dtype = torch.empty(0, dtype=chunks[0][k].dtype).numpy().dtype
+        for i, c in enumerate(chunks):
+            size = c[k].numel() * dtype.itemsize
+            host[i][k] = raw[at:at + size].view(dtype).reshape(tuple(c[k].shape))
+            at += size
+    return [tuple(h) for h in host]
 
 
 class VOCMApMetric(object):
@@ -182,8 +233,7 @@ class VOCMApMetric(object):
         cm = self.class_map
         if not (cm is None or isinstance(cm, (list, tuple, np.ndarray))):
             return False
-        args = [VIDDetectionMetric._gather(x) for x in (pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels,
-                                                        gt_difficults)]
+        args = [_gather(x) for x in (pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults)]
         if not all(hasattr(x, "is_cuda") for x in args[:5]):
             return False
         import torch
@@ -205,7 +255,6 @@ class VOCMApMetric(object):
             return False
         if batch == 0:
             return True
-        import ctypes
         gl = gl.reshape(batch, n_gt)
         if cm is None:
             mapped = torch.where(gl >= 0, gl.to(torch.int32), -1)
@@ -229,11 +278,11 @@ class VOCMApMetric(object):
             best = torch.empty((batch, rows), dtype=torch.int32, device=dev)
             flags = torch.empty((batch, rows), dtype=torch.int8, device=dev)
             spare = best                                              # a valid address for arrays without elements
-            devp = lambda t: ctypes.c_void_p((t if t.numel() else spare).data_ptr())     # noqa: E731
+            devp = lambda t: _devp(t if t.numel() else spare)         # noqa: E731
             with torch.cuda.device(dev):
                 _lib.check(lib.vy_voc_match(batch, rows, n_gt, devp(pb), devp(pl), devp(ps), devp(gb), devp(mapped),
                                             None if diff is None else devp(diff), float(self.iou_thresh), devp(best),
-                                            devp(flags), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                            devp(flags), _streamp(dev)))
             self.device_updates += 1
         else:
             flags = torch.empty((batch, 0), dtype=torch.int8, device=dev)
@@ -248,19 +297,9 @@ class VOCMApMetric(object):
             return
         import torch
         chunks, self._chunks = self._chunks, []
-        dev = chunks[0][0].device
-        kinds = (np.float32, np.float32, np.int32, np.int8, np.uint8)    # labels, scores, gt labels, flags, gt difficults
-        chunks = [c if c[4] is not None else c[:4] + (torch.zeros_like(c[2], dtype=torch.uint8), c[5]) for c in chunks]
-        # kind by kind, the 4-byte kinds first: every host view below is aligned
-        raw = torch.cat([torch.cat([c[k].to(dev).reshape(-1) for c in chunks]).view(torch.uint8) for k in range(5)]).cpu().numpy()
-        host, at = {}, 0
-        for k in range(5):
-            for i, c in enumerate(chunks):
-                size = c[k].numel() * _itemsize(kinds[k])
-                host[k, i] = raw[at:at + size].view(kinds[k])
-                at += size
-        for i, c in enumerate(chunks):
-            labels, scores, glabels, flags, gdiff = (host[k, i] for k in range(5))
+        # labels, scores, gt labels, flags, gt difficults (none given: none is difficult)
+        host = _chunks_to_host([c[:4] + (torch.zeros_like(c[2], dtype=torch.uint8) if c[4] is None else c[4],) for c in chunks])
+        for c, (labels, scores, glabels, flags, gdiff) in zip(chunks, host):
             det = np.flatnonzero(flags != -2)
             dl = labels[det].astype(int)
             order = np.lexsort((-scores[det].astype(np.float64), det // max(c[5], 1), dl))   # class, image, score
@@ -529,16 +568,6 @@ class VIDDetectionMetric(object):
                 ig = ig_m | (area < self._ar[a, 0]) | (area > self._ar[a, 1])
                 self._npos[m * n_a + a] = base - np.bincount(self._gt_label[ig], minlength=n_pos)
 
-    def _tables_on(self, dev):
-        t = self._device_tables.get(dev)
-        if t is None:
-            import torch
-            pad = lambda a: a if a.size else np.zeros((1,) + a.shape[1:], a.dtype)  # noqa: E731
-            t = [torch.from_numpy(pad(a)).to(dev) for a in (self._gt_box, self._gt_label, self._gt_thr, self._gt_motion,
-                                                             self._gt_nig)]
-            self._device_tables[dev] = t
-        return t
-
     def reset(self):
         self._chunks = []     # per update: (rows, labels, scores, tp, fp), numpy or device tensors
         self._seen = set()
@@ -562,17 +591,10 @@ class VIDDetectionMetric(object):
             rows.append(self._row[s])
         return sids, np.asarray(rows, np.int64)
 
-    @staticmethod
-    def _gather(x):
-        if isinstance(x, (list, tuple)) and len(x) and all(hasattr(t, "is_cuda") for t in x):
-            import torch
-            return torch.cat([t.to(x[0].device) for t in x], 0)
-        return x
-
     def update(self, pred_bboxes, pred_labels, pred_scores, gt_bboxes=None, gt_ids=None, gt_difficults=None, sid=None):
         """pred_bboxes (B, N, 4), pred_labels and pred_scores (B, N) or (B, N, 1): numpy, torch, or lists of them (one per
         device, joined along the batch).  Rows with label < 0 or score < conf_score_thresh are dropped."""
-        pb, pl, ps = (self._gather(x) for x in (pred_bboxes, pred_labels, pred_scores))
+        pb, pl, ps = (_gather(x) for x in (pred_bboxes, pred_labels, pred_scores))
         on_device = all(getattr(x, "is_cuda", False) for x in (pb, pl, ps))
         if not on_device:
             pb, pl, ps = (np.asarray(_to_numpy(x)) for x in (pb, pl, ps))
@@ -600,7 +622,6 @@ class VIDDetectionMetric(object):
         return tuple(np.concatenate(o) for o in out)
 
     def _update_device(self, pb, pl, ps, rows):
-        import ctypes
         import torch
         from . import _lib
         lib = _lib.load()
@@ -618,17 +639,16 @@ class VIDDetectionMetric(object):
         fp = torch.empty((batch * n, n_s), dtype=torch.float64, device=dev)
         flag_bytes = int((self._gt_off[rows + 1] - self._gt_off[rows]).sum()) * n_s
         flags = torch.empty(max(flag_bytes, 1), dtype=torch.uint8, device=dev)
-        gt_box, gt_label, gt_thr, gt_motion, gt_nig = self._tables_on(dev)
+        t = _upload(self._device_tables, dev, box=self._gt_box, label=self._gt_label, thr=self._gt_thr,
+                    motion=self._gt_motion, nig=self._gt_nig)
         det_off = np.arange(batch + 1, dtype=np.int64) * n
         gt_frame = rows.astype(np.int32)
-        host = lambda a: a.ctypes.data_as(ctypes.c_void_p)    # noqa: E731
-        devp = lambda t: ctypes.c_void_p(t.data_ptr())        # noqa: E731
         with torch.cuda.device(dev):
             _lib.check(lib.vy_vid_match(
-                batch, host(det_off), devp(box), devp(label), devp(score), self._conf_score_thresh, host(gt_frame),
-                len(self._ids), host(self._gt_off), devp(gt_box), devp(gt_label), devp(gt_thr), devp(gt_motion), devp(gt_nig),
-                len(self._mr), host(self._mr), len(self._ar), host(self._ar), host(self._empty_weight), devp(flags),
-                flag_bytes, devp(tp), devp(fp), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                batch, _hostp(det_off), _devp(box), _devp(label), _devp(score), self._conf_score_thresh, _hostp(gt_frame),
+                len(self._ids), _hostp(self._gt_off), _devp(t['box']), _devp(t['label']), _devp(t['thr']), _devp(t['motion']),
+                _devp(t['nig']), len(self._mr), _hostp(self._mr), len(self._ar), _hostp(self._ar),
+                _hostp(self._empty_weight), _devp(flags), flag_bytes, _devp(tp), _devp(fp), _streamp(dev)))
         return np.repeat(rows, n), label.reshape(-1), score.reshape(-1), tp, fp
 
     # ------------------------------------------------------------------ evaluation
@@ -641,9 +661,10 @@ class VIDDetectionMetric(object):
         dev_chunks = [c for c in self._chunks if not isinstance(c[3], np.ndarray)]
         if dev_chunks:
             import torch
-            joined = [torch.cat([c[k].to(dev_chunks[0][3].device) for c in dev_chunks], 0).cpu().numpy() for k in range(1, 5)]
-            label, score = joined[0], joined[1]
-            keep = np.flatnonzero((label >= 0) & (score >= self._conf_score_thresh))
+            dev = dev_chunks[0][3].device
+            # joined on the device first: thousands of chunks cost more to split on the host than they cost to join there
+            joined = _chunks_to_host([tuple(torch.cat([c[k].to(dev) for c in dev_chunks], 0) for k in range(1, 5))])[0]
+            keep = np.flatnonzero((joined[0] >= 0) & (joined[1] >= self._conf_score_thresh))
             parts[0].append(np.concatenate([c[0] for c in dev_chunks])[keep])
             for k in range(4):
                 parts[k + 1].append(joined[k][keep])
@@ -993,16 +1014,9 @@ class COCODetectionMetric(object):
         return self._scales
 
     def _tables_on(self, dev):
-        t = self._device_tables.get(dev)
-        if t is None:
-            import torch
-            pad = lambda a: a if a.size else np.zeros((1,) + a.shape[1:], a.dtype)  # noqa: E731
-            names = ('_gt_xywh', '_gt_cat', '_gt_area', '_gt_crowd', '_gt_id', '_lut_json', '_lut_k', '_lut_has')
-            t = {n: torch.from_numpy(pad(getattr(self, n))).to(dev) for n in names}
-            if self._data_shape is not None:
-                t['scale'] = torch.from_numpy(pad(self._scale_table())).to(dev)
-            self._device_tables[dev] = t
-        return t
+        names = ('_gt_xywh', '_gt_cat', '_gt_area', '_gt_crowd', '_gt_id', '_lut_json', '_lut_k', '_lut_has')
+        scale = {} if self._data_shape is None else {'scale': self._scale_table()}
+        return _upload(self._device_tables, dev, **{n: getattr(self, n) for n in names}, **scale)
 
     def reset(self):
         self._current_id = 0
@@ -1037,7 +1051,7 @@ class COCODetectionMetric(object):
         (one per device, joined along the batch).  Further positional arguments are accepted and ignored, as in the
         reference; ``sid=`` names the images."""
         sid = kwargs.pop('sid', None)
-        pb, pl, ps = (VIDDetectionMetric._gather(x) for x in (pred_bboxes, pred_labels, pred_scores))
+        pb, pl, ps = (_gather(x) for x in (pred_bboxes, pred_labels, pred_scores))
         on_device = all(hasattr(x, "is_cuda") and _is_gpu_f32(x) for x in (pb, pl, ps)) and \
             pb.device == pl.device == ps.device
         if not on_device:
@@ -1086,7 +1100,6 @@ class COCODetectionMetric(object):
         return rows, cat, score, rank, flags, keep, file_cat, xywh
 
     def _update_device(self, pb, pl, ps, rows):
-        import ctypes
         import torch
         from . import _lib
         lib = _lib.load()
@@ -1122,41 +1135,27 @@ class COCODetectionMetric(object):
         taken_bytes = int((self._gt_off[rows + 1] - self._gt_off[rows]).sum()) * n_a * n_t
         taken = torch.empty(max(taken_bytes, 1), dtype=torch.uint8, device=dev)
         gt_image = rows.astype(np.int32)
-        host = lambda a: a.ctypes.data_as(ctypes.c_void_p)    # noqa: E731
-        devp = lambda x: ctypes.c_void_p(x.data_ptr())        # noqa: E731
         with torch.cuda.device(dev):
             _lib.check(lib.vy_coco_match(
-                batch, n, devp(xywh), devp(cat), devp(score), host(gt_image), len(self._eval_ids), host(self._gt_off),
-                devp(t['_gt_xywh']), devp(t['_gt_cat']), devp(t['_gt_area']), devp(t['_gt_crowd']), devp(t['_gt_id']),
-                n_t, host(self._thr), n_a, host(np.ascontiguousarray(self._ar)), self._max_dets[-1], devp(taken), taken_bytes,
-                devp(rank), devp(flags), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                batch, n, _devp(xywh), _devp(cat), _devp(score), _hostp(gt_image), len(self._eval_ids), _hostp(self._gt_off),
+                _devp(t['_gt_xywh']), _devp(t['_gt_cat']), _devp(t['_gt_area']), _devp(t['_gt_crowd']), _devp(t['_gt_id']), n_t,
+                _hostp(self._thr), n_a, _hostp(np.ascontiguousarray(self._ar)), self._max_dets[-1], _devp(taken), taken_bytes,
+                _devp(rank), _devp(flags), _streamp(dev)))
         self.device_updates += 1
         return rows, cat, score, rank, flags, keep, file_cat, xywh
 
     # ------------------------------------------------------------------ evaluation
     def _fold(self, with_boxes):
         """Every row so far, update after update: image row, category index, score, rank, flags (and kept, file category,
-        xywh for the results file) as numpy arrays.  Device results are copied here, once per kind."""
+        xywh for the results file) as numpy arrays.  Device results are copied here, once."""
         n_a, n_t = len(self._ar), len(self._thr)
         kinds = range(1, 8 if with_boxes else 5)
-        parts = {k: [None] * len(self._chunks) for k in kinds}
         dev_chunks = [i for i, c in enumerate(self._chunks) if not isinstance(c[1], np.ndarray)]
-        if dev_chunks:
-            import torch
-            dev = self._chunks[dev_chunks[0]][1].device
-            for k in kinds:
-                tail = (4,) if k == 7 else (n_a, n_t) if k == 4 else ()
-                joined = torch.cat([self._chunks[i][k].to(dev).reshape((-1,) + tail) for i in dev_chunks], 0).cpu().numpy()
-                at = 0
-                for i in dev_chunks:
-                    size = self._chunks[i][1].numel()
-                    parts[k][i] = joined[at:at + size]
-                    at += size
-        for i, c in enumerate(self._chunks):
-            if isinstance(c[1], np.ndarray):
-                for k in kinds:
-                    tail = (4,) if k == 7 else (n_a, n_t) if k == 4 else ()
-                    parts[k][i] = c[k].reshape((-1,) + tail)
+        host = dict(zip(dev_chunks, _chunks_to_host([tuple(self._chunks[i][k] for k in kinds) for i in dev_chunks])))
+        parts = {}
+        for k in kinds:
+            tail = (4,) if k == 7 else (n_a, n_t) if k == 4 else ()
+            parts[k] = [(host[i][k - 1] if i in host else c[k]).reshape((-1,) + tail) for i, c in enumerate(self._chunks)]
         empty = {1: np.zeros(0, np.int32), 2: np.zeros(0, np.float64), 3: np.zeros(0, np.int32),
                  4: np.zeros((0, n_a, n_t), np.uint8), 5: np.zeros(0, bool), 6: np.zeros(0, np.int64),
                  7: np.zeros((0, 4), np.float64)}
