@@ -100,6 +100,26 @@ int vy_net_create_window(int32_t num_class, int32_t k, int32_t join, vy_net** ou
 int vy_net_create_heads_window(int32_t num_class, int32_t k, int32_t join, vy_net** out);
 /* k and join of a window net (of either kind); k = 0 for any other net. */
 int vy_net_window(const vy_net* net, int32_t* k, int32_t* join);
+/* yolo3_darknet53(classes, new_model=True, hierarchical=[3,..,1], h_join_type='max') — HDarknet, h_darknet.py:103-188: a
+ * detector over clips of T = 3^n_pools frames that pools INSIDE the backbone.  x is (batch, T, 3, h, w), frame t of clip b
+ * is frame b * T + t.  The stem runs per frame; in front of each of the first n_pools stride-2 convs (after features[0],
+ * [1:3], [3:6], [6:15]) consecutive triples of frames are reduced with an element-wise max (hier.hip: strict > in frame
+ * order; backward writes the full gradient to every tied frame), so the cells between pool i - 1 and pool i run on
+ * batch * 3^(n_pools - i) frames and everything behind the last pool on the batch clips, as a single-frame net would.
+ * n_pools 1 .. 4, anything else VY_ERR_INVALID.  With four pools the fourth pooled plane is route 0 itself.  The max has
+ * no parameters: the parameter table and the conv list are vy_net_create's, name for name, offset for offset and in the
+ * same order.  `batch` counts clips in sizing, binding and every entry.  vy_net_forward_infer, vy_net_profile_infer
+ * (launches "hpool.<i>") and the training entries work on it; vy_net_forward_features, the *_routes / *_bank entries and
+ * the video entries fail with VY_ERR_STATE, the split conv modes with VY_ERR_UNSUPPORTED.  Taps: vy_net_read_activation,
+ * vy_net_read_grad_activation and vy_net_read_train_tap (VY_TAP_GRAD_PADDED: the pooled plane's gradient,
+ * VY_TAP_INPUT_PADDED: the pre-pool plane) take "hpool.0" .. "hpool.<n_pools - 1>"; every tap has batch *
+ * vy_net_tap_frames frames. */
+int vy_net_create_hier(int32_t num_class, int32_t n_pools, vy_net** out);
+/* pools and frames per clip (3^n_pools) of a hierarchical net; 0 and 1 for any other net. */
+int vy_net_hier(const vy_net* net, int32_t* n_pools, int32_t* frames);
+/* frames per batch entry of the tap `name` (a cell, "pool.<i>" or "hpool.<i>") of any net: its leading dimension in a plan
+ * bound for `batch` is batch * frames (a video plan aside).  VY_ERR_INVALID: no such tap. */
+int vy_net_tap_frames(const vy_net* net, const char* name, int32_t* frames);
 void vy_net_destroy(vy_net* net);
 
 /* net.set_nms(nms_thresh, nms_topk, post_nms) — yolo3.py:1208-1228.

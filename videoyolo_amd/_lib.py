@@ -115,6 +115,10 @@ SIGNATURES.update({
     # k-frame clip nets (yolo3_darknet53 with k > 1, early join)
     "vy_net_create_window": (ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(_vp)]),
     "vy_net_window": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    # hierarchical nets: frames max-pooled by threes inside the backbone (yolo3_darknet53 with new_model / hierarchical)
+    "vy_net_create_hier": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(_vp)]),
+    "vy_net_hier": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "vy_net_tap_frames": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.POINTER(_i32)]),
     # windowed heads-only nets: a bank of stored per-frame routes and a (B, k) table (yolo3_no_backbone with k > 1)
     "vy_net_create_heads_window": (ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(_vp)]),
     "vy_net_forward_infer_bank": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, ctypes.POINTER(_i32), _vp, _vp, _vp, _vp, _vp]),

@@ -234,6 +234,27 @@ hipError_t vy_launch_window_pool(const WindowPoolArgs& a, hipStream_t s);
 // backward: gsrc = gdst / k (mean), gdst where src == dst and 0 elsewhere (max)
 hipError_t vy_launch_window_pool_bwd(const WindowPoolArgs& a, hipStream_t s);
 
+// ---- temporal pooling inside the backbone of a hierarchical net (hier.hip): the max over consecutive triples of frames of
+// one plane (3 * frames frames, channel stride s_cs, the C channels at channel 0) into channels [d_co, d_co + C) of a plane
+// of `frames` frames.  Both planes have the same H x W and a zero border, which is never written.  C a power of two >= 4;
+// s_cs, d_cs and d_co multiples of 4.  One plane per launch.
+struct HierPoolArgs {
+  const float* src;    // pre-pool plane (read)
+  float* dst;          // pooled plane (forward: written; backward: read)
+  float* gsrc;         // backward: gradient plane of src (written: overwrite, interior only)
+  const float* gdst;   // backward: gradient plane of dst (read)
+  int frames;          // pooled frames
+  int H, W, C, s_cs, d_cs, d_co;
+  // filled by the launcher
+  int c4_shift;            // log2(C / 4)
+  unsigned row_items;      // W * C / 4 lanes per row
+  long long frame_pixels;  // (H + 2) * (W + 2)
+};
+// forward: dst frame n = max of src frames 3n, 3n + 1, 3n + 2 (strict >, in frame order)
+hipError_t vy_launch_hier_pool(const HierPoolArgs& a, hipStream_t s);
+// backward: gsrc frame 3n + t = gdst frame n where src == dst, +0 elsewhere
+hipError_t vy_launch_hier_pool_bwd(const HierPoolArgs& a, hipStream_t s);
+
 // ---- per-frame route ring of a video plan (video.hip): the three routes of single frames, kept in R slots and pooled by
 // window.  A slot is the three routes back to back, tight NHWC without borders (only ring_pool and the test tap read it):
 // route i of slot s starts at ring + s * slot_stride (+ the sizes of the routes before it).  Frame -> slot and clip -> slots

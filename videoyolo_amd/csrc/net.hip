@@ -52,15 +52,23 @@ static int refuse_window(const vy_net* net, const char* entry) {
                 entry);
   return 0;
 }
+// VY_ERR_STATE for a hierarchical net (vy_net_create_hier) at an entry point that does not serve one
+static int refuse_hier(const vy_net* net, const char* entry) {
+  if (net && net->hier_n)
+    return fail(VY_ERR_STATE, "%s does not take a hierarchical net (vy_net_create_hier): use vy_net_create for single frames",
+                entry);
+  return 0;
+}
 
-// the three constructors: the checks they share, and the net itself (k = 0: not a window net)
+// the constructors: the checks they share, and the net itself (k = 0: not a window net)
 static int check_create(int32_t num_class, vy_net** out) {
   if (!out) return fail(VY_ERR_INVALID, "out is null");
   if (num_class < 1 || num_class > 1000) return fail(VY_ERR_INVALID, "num_class %d out of range", num_class);
   return 0;
 }
-static vy_net* create(int32_t num_class, bool heads_only, int32_t k, int32_t join) {
+static vy_net* create(int32_t num_class, bool heads_only, int32_t k, int32_t join, int32_t hier_n = 0) {
   vy_net* n = new vy_net();
+  n->hier_n = hier_n;
   n->num_class = num_class;
   n->knobs = vy_knobs_read();
   n->heads_only = heads_only;
@@ -79,7 +87,7 @@ template <typename Hook>
 static int infer_sequence(vy_net* net, const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
                           hipStream_t s, Hook& hook) {
   VY_TRY(net->prepare(s, hook, true));
-  VY_TRY(net->run_cells(0, net->n_backbone, x, s, hook));
+  VY_TRY(net->run_backbone(x, s, hook));
   if (net->clip_net()) VY_TRY(net->window_pool(s, hook));
   VY_TRY(net->run_cells(net->n_backbone, (int)net->convs.size(), nullptr, s, hook));
   return net->detect_tail(ids, scores, bboxes, keep_idx, s, hook);
@@ -127,6 +135,39 @@ int vy_net_window(const vy_net* net, int32_t* k, int32_t* join) {
   if (k) *k = net->window_k;
   if (join) *join = net->window_k ? net->window_join : 0;
   return 0;
+}
+
+int vy_net_create_hier(int32_t num_class, int32_t n_pools, vy_net** out) {
+  VY_TRY(check_create(num_class, out));
+  if (n_pools < 1 || n_pools > 4)
+    return fail(VY_ERR_INVALID, "n_pools = %d: a hierarchical net pools 1 ... 4 times (0: vy_net_create)", n_pools);
+  *out = create(num_class, false, 0, 0, n_pools);
+  return 0;
+}
+
+int vy_net_hier(const vy_net* net, int32_t* n_pools, int32_t* frames) {
+  if (!net) return fail(VY_ERR_INVALID, "net is null");
+  if (n_pools) *n_pools = net->hier_n;
+  if (frames) *frames = net->hier_frames();
+  return 0;
+}
+
+int vy_net_tap_frames(const vy_net* net, const char* name, int32_t* frames) {
+  if (!net || !name || !frames) return fail(VY_ERR_INVALID, "null argument");
+  if (const int i = vy_hpool_tap(net, name); i >= 0) {
+    *frames = net->planes[net->hpools[i].dst].fm;
+    return 0;
+  }
+  if (vy_pool_tap(net, name) >= 0) {
+    *frames = 1;
+    return 0;
+  }
+  for (const ConvT& cv : net->convs)
+    if (cv.name == name) {
+      *frames = net->planes[cv.out_plane].fm;
+      return 0;
+    }
+  return fail(VY_ERR_INVALID, "no cell named '%s'", name);
 }
 
 void vy_net_destroy(vy_net* net) {
@@ -285,6 +326,8 @@ int vy_net_set_conv_mode(vy_net* net, int32_t mode) {
   if (mode < VY_CONV_EXACT_FP32 || mode > VY_CONV_SPLIT_BF16X3_TRAIN) return fail(VY_ERR_INVALID, "conv mode %d", mode);
   if (net->clip_net() && mode != VY_CONV_EXACT_FP32)
     return fail(VY_ERR_UNSUPPORTED, "conv mode %d: a window net runs the exact fp32 kernels only", mode);
+  if (net->hier_n && mode != VY_CONV_EXACT_FP32)
+    return fail(VY_ERR_UNSUPPORTED, "conv mode %d: a hierarchical net runs the exact fp32 kernels only", mode);
   if (mode != net->conv_mode) {
     net->conv_mode = mode;
     net->unbind();  // (the weight images live in the workspace)
@@ -327,6 +370,7 @@ int vy_net_forward_infer(vy_net* net, const float* x, float* ids, float* scores,
 int vy_net_forward_features(vy_net* net, const float* x, float* f0, float* f1, float* f2, void* stream) {
   VY_TRY(vy_check_kind(net, false, "vy_net_forward_features"));
   VY_TRY(refuse_window(net, "vy_net_forward_features"));
+  VY_TRY(refuse_hier(net, "vy_net_forward_features"));
   return run_entry(net, x && f0 && f1 && f2, nullptr, stream, [&](hipStream_t s) {
     const float* const out[3] = {f0, f1, f2};
     VY_TRY(net->prepare(s, plain, true));
@@ -468,6 +512,17 @@ int vy_net_read_activation(vy_net* net, const char* name, float* dst_dev, int32_
   if (dst_dev && net->cur.planes_shared)
     return fail(VY_ERR_STATE, "activation planes are recycled in this plan: call vy_net_set_keep_activations(net, 1) "
                 "before sizing / binding the workspace to read intermediate activations");
+  if (const int i = vy_hpool_tap(net, name); i >= 0) {
+    const vy_net::HierPool& hp = net->hpools[i];
+    const PlaneAt p = net->plane(hp.dst);
+    if (c) *c = hp.C;
+    if (h) *h = p.H;
+    if (w) *w = p.W;
+    if (dst_dev)
+      HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(hp.dst), net->plane_batch(hp.dst), p.H, p.W, p.C, hp.dst_co, hp.C, dst_dev,
+                                      static_cast<hipStream_t>(stream)));
+    return 0;
+  }
   if (const int i = vy_pool_tap(net, name); i >= 0) {
     const vy_net::RouteSlot& r = net->routes[i];
     const PlaneAt p = net->plane(r.plane);

@@ -69,7 +69,9 @@ struct ParamT {
 struct PlaneT {
   int C = 0;    // channel stride
   int div = 1;  // spatial = input / div
-  int fm = 1;   // frames per batch entry: k for the stem and stage planes of a window net (B*k frames), 1 otherwise
+  // frames per batch entry: k for the stem and stage planes of a window net (B*k frames); 3^(pools still ahead) for the
+  // backbone planes of a hierarchical net; 1 otherwise
+  int fm = 1;
 };
 
 struct ConvT {
@@ -211,6 +213,41 @@ struct vy_net {
   // the B*k-frame backbone of a window net keys on clip_net()
   bool clip_net() const { return window_k && !heads_only; }
   int frame_routes[3] = {-1, -1, -1};
+  // vy_net_create_hier: a hierarchical net (HDarknet, h_join_type 'max'; hier.hip).  A clip of 3^hier_n frames goes through
+  // the stem per frame; in front of each of the first hier_n stride-2 convs the frames are max-pooled by threes into a
+  // plane of a third of the frames, which that conv reads.  From the last pool on it is the single-frame net on B clips.
+  // The conv list and the parameter table are the single-frame net's; only planes and their fm differ
+  int hier_n = 0;  // pools, 1..4; 0: not a hierarchical net
+  struct HierPool {
+    int src, dst, dst_co, C;  // pre-pool plane (its C channels at 0) -> channels [dst_co, dst_co + C) of the pooled plane
+    int conv;                 // the stride-2 conv that reads the pooled plane: the pool runs in front of it
+  };
+  std::vector<HierPool> hpools;
+  int hier_frames() const {
+    int f = 1;
+    for (int i = 0; i < hier_n; ++i) f *= 3;
+    return f;
+  }
+  // one pool launch, forward (grads == nullptr) or backward (grads: the training gradient planes)
+  HierPoolArgs hier_args(const HierPool& hp, float* grads) const {
+    HierPoolArgs a;
+    memset(&a, 0, sizeof a);
+    const PlaneAt sp = plane(hp.src), dp = plane(hp.dst);
+    a.src = plane_ptr(hp.src);
+    a.dst = plane_ptr(hp.dst);
+    if (grads) {
+      a.gsrc = grads + sp.off;
+      a.gdst = grads + dp.off;
+    }
+    a.frames = plane_batch(hp.dst);
+    a.H = dp.H;
+    a.W = dp.W;
+    a.C = hp.C;
+    a.s_cs = sp.C;
+    a.d_cs = dp.C;
+    a.d_co = hp.dst_co;
+    return a;
+  }
 
   // frames a stem / stage plane of a window net holds for `b` clips: b*k of the clip plan, `frames` of a video plan
   static int backbone_frames(const PlaneT& p, int b, int frames) { return frames && p.fm > 1 ? frames : b * p.fm; }
@@ -360,12 +397,29 @@ struct vy_net {
     };
     routes[0] = {cat2, 128, 256};
     routes[1] = {cat1, 256, 512};
-    const int bfm = clip_net() ? window_k : 1;  // frames per batch entry of the backbone planes
+    int bfm = clip_net() ? window_k : hier_frames();  // frames per batch entry of the backbone planes (falls at a hier pool)
     int cur = add_plane(heads_only ? 1024 : 32, heads_only ? 32 : 1, bfm), cur_co = 0;
     if (!heads_only) add_conv(feat_name(feat++), -1, 0, 3, cur, 0, 32, 3, 1, true, 1);
     int div = 1;
     for (int st = 0; st < 5 && !heads_only; ++st) {
       const int ch = chans[st + 1];
+      if (st < hier_n) {  // pool point: the frames of `cur` by threes into a plane that this stage's stride-2 conv reads
+        bfm /= 3;
+        HierPool hp;
+        hp.src = cur;
+        hp.C = chans[st];
+        hp.conv = (int)convs.size();
+        if (st == 3) {  // the fourth pooled plane is route 0: straight into the place a single-frame backbone writes it
+          hp.dst = cat2;
+          hp.dst_co = 128;
+        } else {
+          hp.dst = add_plane(chans[st], div, bfm);
+          hp.dst_co = 0;
+        }
+        hpools.push_back(hp);
+        cur = hp.dst;
+        cur_co = hp.dst_co;
+      }
       div *= 2;
       int nxt = add_plane(ch, div, bfm);
       add_conv(feat_name(feat++), cur, cur_co, chans[st], nxt, 0, ch, 3, 2, true, 1);
@@ -381,7 +435,7 @@ struct vy_net {
         if (clip_net() && (feat - 1 == 14 || feat - 1 == 23)) {
           outp = add_plane(ch, div, bfm);
           frame_routes[feat - 1 == 14 ? 0 : 1] = outp;
-        } else if (feat - 1 == 14) {
+        } else if (feat - 1 == 14 && hier_n < 4) {  // (four pools: route 0 is pooled into cat2 out of a plane of its own)
           outp = cat2;
           outco = 128;
         } else if (feat - 1 == 23) {
@@ -491,6 +545,10 @@ struct vy_net {
       for (int i = 0; i < 3; ++i) def[routes[i].plane] = -1;
     if (clip_net())  // ... and window_pool reads the per-frame routes after the last stage cell
       for (int i = 0; i < 3; ++i) last[frame_routes[i]] = kLive;
+    for (const HierPool& hp : hpools) {  // a pool runs in front of its conv: it writes dst, and src stays live up to it
+      def[hp.dst] = std::min(def[hp.dst], hp.conv);
+      last[hp.src] = std::max(last[hp.src], hp.conv);
+    }
     std::vector<int> order(np);
     for (int i = 0; i < np; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return def[a] < def[b]; });
@@ -923,6 +981,26 @@ struct vy_net {
     HOOKED(hook, "window_pool", 0.0, 0.0, vy_launch_window_pool(pool_args(nullptr), s));
     return 0;
   }
+  // hierarchical nets: pool `i`, in front of the conv that reads the pooled plane
+  template <typename Hook>
+  int hier_pool(int i, hipStream_t s, Hook& hook) {
+    const HierPoolArgs a = hier_args(hpools[i], nullptr);
+    char nm[16];
+    snprintf(nm, sizeof nm, "hpool.%d", i);
+    HOOKED(hook, nm, 0.0, 16.0 * a.frames * a.H * a.W * a.C, vy_launch_hier_pool(a, s));
+    return 0;
+  }
+  // the backbone: the stem and stage cells, with the pools of a hierarchical net between the groups they separate
+  template <typename Hook>
+  int run_backbone(const float* x, hipStream_t s, Hook& hook) {
+    int first = 0;
+    for (int i = 0; i < (int)hpools.size(); ++i) {
+      VY_TRY(run_cells(first, hpools[i].conv, x, s, hook));
+      VY_TRY(hier_pool(i, s, hook));
+      first = hpools[i].conv;
+    }
+    return run_cells(first, n_backbone, x, s, hook);
+  }
   // video plans (the caller has checked the tables): pool the B clips of `table` out of the ring ...
   template <typename Hook>
   int ring_pool(const int32_t* table, hipStream_t s, Hook& hook) {
@@ -1001,6 +1079,12 @@ inline int vy_check_bank(const vy_net* net, const char* entry, const BankRef& ba
     if (bank.table[i] < 0 || bank.table[i] >= bank.n_frames)
       return fail(VY_ERR_INVALID, "%s: entry %d of the table is %d, outside [0, %d)", entry, i, bank.table[i], bank.n_frames);
   return 0;
+}
+
+// the pooled plane `name` = "hpool.<i>" of a hierarchical net (the taps): its index, or -1
+inline int vy_hpool_tap(const vy_net* net, const char* name) {
+  if (strncmp(name, "hpool.", 6) != 0 || name[6] < '0' || name[6] >= '0' + net->hier_n || name[7]) return -1;
+  return name[6] - '0';
 }
 
 // the pooled route `name` = "pool.<i>" of a window net (the taps of vy_net_read_activation / read_grad_activation): 0..2, or -1

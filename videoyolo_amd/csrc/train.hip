@@ -556,7 +556,13 @@ int forward_train(const TrainCtx& c, const float* x, const float* const* routes,
   VY_TRY(refresh_split_images(c));
   if (routes) VY_TRY(net->route_import(routes, c.s, plain));
   if (bank) VY_TRY(net->import_pool(*bank, c.s, plain));
-  VY_TRY(train_cells(c, 0, net->n_backbone, x));
+  int first = 0;
+  for (int i = 0; i < (int)net->hpools.size(); ++i) {  // a hierarchical net: the pool in front of the conv that reads it
+    VY_TRY(train_cells(c, first, net->hpools[i].conv, x));
+    VY_TRY(net->hier_pool(i, c.s, plain));
+    first = net->hpools[i].conv;
+  }
+  VY_TRY(train_cells(c, first, net->n_backbone, x));
   if (net->clip_net()) VY_TRY(net->window_pool(c.s, plain));  // the stages are done: pool the routes
   return train_cells(c, net->n_backbone, (int)net->convs.size(), nullptr);
 }
@@ -856,6 +862,16 @@ int backward_cells(const TrainCtx& c, BwdState& st, int first, int last, const f
       VY_TRY(bn_backward(c, ci, st, &dz));
     VY_TRY(weight_grad(c, ci, dz, x));
     if (!cv.is_stem) VY_TRY(data_grad(c, ci, dz, st));  // (no gradient w.r.t. the image)
+    for (const vy_net::HierPool& hp : c.net->hpools) {
+      if (hp.conv != ci) continue;
+      // a hierarchical net: this conv read a pooled plane, whose gradient is final now (route 0 of a four-pool net: the
+      // stride-8 head's contribution and this conv's, summed by data_grad).  hier_pool_bwd writes the pre-pool plane's
+      // gradient, which the producer in front reads as its output gradient
+      if (st.covered(hp.dst, hp.dst_co, hp.dst_co + hp.C) != 1)
+        return fail(VY_ERR_STATE, "internal: gradient of the pooled plane in front of '%s' was never produced", cv.name.c_str());
+      HIP_TRY(vy_launch_hier_pool_bwd(c.net->hier_args(hp, c.gplanes()), c.s));
+      st.touched[hp.src].push_back({0, hp.C});
+    }
     if (ci == 0 || c.cell(ci - 1).bucket != c.cell(ci).bucket) VY_TRY(emit_bucket(c, c.cell(ci).bucket));
   }
   return 0;
@@ -1189,6 +1205,12 @@ int vy_net_read_grad_activation(vy_net* net, const char* name, float* dst_dev, v
   VY_TRY(net->check_ready());
   VY_TRY(bound_train(net, false, ""));
   TrainCtx c(net, stream);
+  if (const int i = vy_hpool_tap(net, name); i >= 0) {
+    const vy_net::HierPool& hp = net->hpools[i];
+    const PlaneAt p = net->plane(hp.dst);
+    HIP_TRY(vy_launch_plane_to_nchw(c.gplane(hp.dst), net->plane_batch(hp.dst), p.H, p.W, p.C, hp.dst_co, hp.C, dst_dev, c.s));
+    return 0;
+  }
   if (const int i = vy_pool_tap(net, name); i >= 0) {
     const vy_net::RouteSlot& r = net->routes[i];
     const PlaneAt p = net->plane(r.plane);
@@ -1210,6 +1232,20 @@ int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* d
   VY_TRY(net->check_ready());
   VY_TRY(bound_train(net, false, ""));
   TrainCtx c(net, stream);
+  if (const int i = vy_hpool_tap(net, name); i >= 0) {  // a pooled plane: its gradient, or the pre-pool plane it was made of
+    const vy_net::HierPool& hp = net->hpools[i];
+    if (which != VY_TAP_GRAD_PADDED && which != VY_TAP_INPUT_PADDED)
+      return fail(VY_ERR_INVALID, "'%s' has the taps VY_TAP_GRAD_PADDED and VY_TAP_INPUT_PADDED only", name);
+    const bool grad = which == VY_TAP_GRAD_PADDED;
+    const int pl = grad ? hp.dst : hp.src;
+    const PlaneAt p = net->plane(pl);
+    const int32_t d[4] = {net->plane_batch(pl), hp.C, p.H + 2, p.W + 2};
+    if (dims) memcpy(dims, d, sizeof d);
+    if (dst_dev)
+      HIP_TRY(vy_launch_padded_plane_to_nchw(grad ? c.gplane(pl) : net->plane_ptr(pl), d[0], d[2], d[3], p.C, grad ? hp.dst_co : 0,
+                                             hp.C, dst_dev, c.s));
+    return 0;
+  }
   for (int ci = 0; ci < (int)net->convs.size(); ++ci) {
     const ConvT& cv = net->convs[ci];
     if (cv.name != name) continue;

@@ -1203,6 +1203,120 @@ class YOLOV3Window(YOLOV3):
     extract_features = detect_two_streams = profile = _not_windowed
 
 
+def hier_pools(hierarchical):
+    """Pools of a valid ``hierarchical`` list — a run of 3s followed by 1s, five entries, the last one 1 (h_darknet.py:
+    103-188: the regrouping is hard-wired to 3 and the routes need a squeezed time axis) — or None."""
+    try:
+        h = [int(v) for v in hierarchical]
+    except (TypeError, ValueError):
+        return None
+    n = next((i for i, v in enumerate(h) if v != 3), len(h))
+    if len(h) != 5 or not 1 <= n <= 4 or any(v != 1 for v in h[n:]):
+        return None
+    return n
+
+
+class YOLOV3Hier(YOLOV3):
+    """``yolo3_darknet53(classes, new_model=True, hierarchical=[3,3,1,1,1], h_join_type='max')``: ``YOLOV3TB`` over
+    ``HDarknet`` (h_darknet.py:103-188), a detector over clips of ``T = 3 ** n`` frames, n the number of leading 3s.  Input
+    is ``(B, T, 3, H, W)``, frame t of clip b is frame ``b * T + t``.  The stem runs per frame; in front of each of the first
+    n stride-2 convs consecutive triples of frames are reduced with an element-wise max, so each group of cells runs on a
+    third of the frames of the one before it, and from the last pool on it is the single-frame net on the B clips.  Targets,
+    losses and detections are per clip; BatchNorm normalises over the frames a cell runs on.  The max has no parameters:
+    the keys are the single-frame net's and a single-frame file loads as is.  ``load_parameters`` / ``set_parameters``
+    also accept the reference's ``new_model`` spelling of the backbone, ``d_model.features.N.<rest>``, N counting the 29
+    feature cells across ``stages.0/1/2`` in order [UPSTREAM-RECALLED: no such file was at hand to verify it]."""
+
+    _ONE_RANK = "a hierarchical net (yolo3_darknet53 with hierarchical=...)"
+    _FEATURES_RE = re.compile(r"^d_model\.features\.(\d+)\.")
+
+    def __init__(self, classes, *args, hierarchical=(3, 1, 1, 1, 1), **kwargs):
+        n = hier_pools(hierarchical)
+        if n is None:
+            raise ValueError("hierarchical net: hierarchical must be a run of 3s followed by 1s, five entries, the last "
+                             "one 1 (got %r)" % (hierarchical,))
+        self._hier, self._pools = tuple(int(v) for v in hierarchical), n
+        super().__init__(classes, *args, **kwargs)
+        self.two_stream_batch = 0
+
+    @property
+    def hierarchical(self):
+        return list(self._hier)
+
+    @property
+    def frames(self):
+        return 3 ** self._pools
+
+    h_join_type = "max"
+
+    def _create_handle(self, num_class, out):
+        return self._lib.vy_net_create_hier(num_class, self._pools, out)
+
+    def _ctor_kwargs(self):
+        return dict(hierarchical=self._hier)
+
+    @classmethod
+    def _key(cls, name):
+        m = cls._FEATURES_RE.match(name)
+        if not m:
+            return name
+        f = int(m.group(1))
+        if f >= 29:
+            return name
+        si = 0 if f < 15 else (1 if f < 24 else 2)
+        return "stages.%d.%d.%s" % (si, f - (0, 15, 24)[si], name[m.end():])
+
+    def _bhw(self, x):
+        return x.shape[0], x.shape[3], x.shape[4]
+
+    def _tap_batch(self, name):
+        fm = ctypes.c_int32(0)
+        _lib.check(self._lib.vy_net_tap_frames(self._h, name.encode(), ctypes.byref(fm)))
+        return self._plan[0] * fm.value
+
+    def set_parameters(self, arrays, allow_missing=False, ignore_extra=False):
+        """As ``YOLOV3.set_parameters``; backbone keys may also come as ``d_model.features.N.<rest>``."""
+        super().set_parameters(OrderedDict((self._key(k), v) for k, v in arrays.items()), allow_missing=allow_missing,
+                               ignore_extra=ignore_extra)
+
+    def _as_input(self, x):
+        shape = tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
+        if len(shape) != 5 or shape[1] != self.frames or shape[2] != 3:
+            raise ValueError("a hierarchical net %r takes (B, T, 3, H, W) clips with T = %d, got %s"
+                             % (self.hierarchical, self.frames, shape))
+        torch = _torch()
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x, np.float32))
+        return super()._as_input(x.reshape((-1,) + shape[2:])).view(shape)
+
+    def set_conv_mode(self, mode="exact"):
+        if mode != "exact":
+            raise NotImplementedError("conv mode %r: a hierarchical net runs the exact fp32 kernels only" % (mode,))
+        super().set_conv_mode(mode)
+
+    def profile(self, x):
+        """As ``YOLOV3.profile``, for a ``(B, T, 3, H, W)`` batch of clips; the pools are the launches ``hpool.<i>``."""
+        torch = _torch()
+        x = self._as_input(x)
+        b, h, w = self._bhw(x)
+        with torch.cuda.device(self._device):
+            self._ensure_plan(b, h, w)
+            outs = self._detect_outputs(b, self._out_rows(), keep=False)
+            cap = 256
+            stats = (_lib.LaunchStat * cap)()
+            n = ctypes.c_int32(cap)
+            _lib.check(self._lib.vy_net_profile_infer(self._h, *_ptrs((x,) + outs[:3]), stats, ctypes.byref(n),
+                                                      self._stream()))
+        return [(stats[i].name.decode(), float(stats[i].ms), float(stats[i].flops), float(stats[i].bytes))
+                for i in range(n.value)]
+
+    def _not_hierarchical(self, *args, **kwargs):
+        raise NotImplementedError("not available on a hierarchical net (yolo3_darknet53 with hierarchical=...): use a "
+                                  "single-frame net")
+
+    extract_features = detect_two_streams = _not_hierarchical
+
+
 class YOLOV3NoBackboneWindow(YOLOV3NoBackbone):
     """``yolo3_no_backbone(classes, k=k, k_join_type=..., k_join_pos='early')``: the head half of ``YOLOV3Window``, for the
     reference's ``--features_dir --window k`` workflow (datasets/imgnetvid.py:146-174 stacks the k frames' saved routes
@@ -1391,20 +1505,29 @@ def yolo3_darknet53(classes, pretrained_base=True, norm_layer=BatchNorm, norm_kw
                     t_out=False, **kwargs):
     """Drop-in for models/definitions/yolo/wrappers.py:9-110 on the default (k=1) branch and on the early-join window
     branch: ``k >= 2`` with ``k_join_type`` 'max' or 'mean' and ``k_join_pos='early'`` returns a ``YOLOV3Window``.
+    ``new_model=True`` with ``hierarchical`` a run of 3s followed by 1s (``[3,1,1,1,1]`` ... ``[3,3,3,3,1]``) and
+    ``h_join_type='max'`` — all three together, wrappers.py:40-44 — returns a ``YOLOV3Hier``.
 
     Only the arguments that select those paths are honoured; any other temporal / two-stream / hierarchical option
-    raises NotImplementedError (out of scope).
+    (``new_model`` alone, a hierarchical list without it, ``h_join_type`` None or 'conv', any other list) raises
+    NotImplementedError naming it (out of scope).
     ``pretrained_base=True`` cannot be honoured offline (gluoncv model zoo download,
     three_darknet.py:262): it warns and leaves the backbone to ``initialize()`` / ``load_parameters``.
     """
     window = k not in (None, 1) and int(k) >= 2 and k_join_type in YOLOV3Window._JOINS and k_join_pos == 'early'
+    hier_listed = any(str(h) != '1' for h in hierarchical)
+    pools = hier_pools(hierarchical) if hier_listed else None
+    hier = bool(new_model) and pools is not None and h_join_type == 'max' and not window and k in (None, 1)
     unsupported = {
         "k": k not in (None, 1) and not window, "k_join_type": k_join_type is not None and not window,
         "k_join_pos": k_join_pos is not None and not window,
         "block_conv_type": str(block_conv_type) != '2', "rnn_pos": rnn_pos is not None,
         "corr_pos": corr_pos is not None, "corr_d": corr_d is not None, "motion_stream": motion_stream is not None,
-        "add_type": add_type is not None, "agnostic": bool(agnostic), "new_model": bool(new_model),
-        "hierarchical": any(int(h) != 1 for h in hierarchical), "h_join_type": h_join_type is not None,
+        "add_type": add_type is not None, "agnostic": bool(agnostic),
+        # new_model + hierarchical + h_join_type='max' together are the door to the hierarchical net
+        "new_model": bool(new_model) and not hier_listed,
+        "hierarchical": hier_listed and (pools is None or not new_model or (h_join_type == 'max' and not hier)),
+        "h_join_type": (h_join_type != 'max') if hier_listed else h_join_type is not None,
         "temporal": bool(temporal), "t_out": bool(t_out)}
     bad = [n for n, v in unsupported.items() if v]
     if bad:
@@ -1415,6 +1538,8 @@ def yolo3_darknet53(classes, pretrained_base=True, norm_layer=BatchNorm, norm_kw
     if window:
         net = YOLOV3Window(classes, norm_layer=norm_layer, norm_kwargs=norm_kwargs, k=int(k), k_join_type=k_join_type,
                            **kwargs)
+    elif hier:
+        net = YOLOV3Hier(classes, norm_layer=norm_layer, norm_kwargs=norm_kwargs, hierarchical=hierarchical, **kwargs)
     else:
         net = YOLOV3(classes, norm_layer=norm_layer, norm_kwargs=norm_kwargs, **kwargs)
     if pretrained_base:
