@@ -13,6 +13,11 @@ the bound never fails a correct kernel).  Forward convolutions (pinned summation
 BatchNorm forward apply are bit-exact; the batch statistics are within 1 ulp of their float64 value rounded the way
 the finalize rounds it.
 
+A SyncBatchNorm cell's statistics are those of the global batch: the other ranks' contribution to the all-reduce is one
+more input of the cell (`peer`, `world` of stats64 / check_stats / check_running / bn_backward64 / check_bn_backward;
+check_sync_sums for the sums the exchange is handed; sync_peer constructs a peer).  Without a peer every check is the
+per-device one, bit for bit.
+
 The graph walked here mirrors OracleYolo3Train.forward_raw / backward: routes, concat order (the upsampled
 transition first), x2 transition gradients summed over 2x2, residual skips, planes with several consumers.
 
@@ -28,9 +33,12 @@ U = 2.0 ** -24
 F32 = np.float32
 
 
-def gamma(n):
+U64 = 2.0 ** -53
+
+
+def gamma(n, u=U):
     n = np.asarray(n, np.float64)
-    return n * U / (1.0 - n * U)
+    return n * u / (1.0 - n * u)
 
 
 class Result:
@@ -38,6 +46,7 @@ class Result:
         self.kind, self.name, self.ratio, self.headroom = kind, name, float(ratio), float(headroom)
         self.err_max, self.want_max = float(err_max), float(want_max)
         self.detail = detail
+        self.extra = {}  # conditions on the inputs a check found on the way (not part of the verdict)
 
     @property
     def ok(self):
@@ -61,14 +70,15 @@ class Result:
                                                                   (" " + self.detail) if self.detail else "")
 
 
-def _bounded(kind, name, got, want, absum, n, detail=""):
-    """got (fp32) vs want (float64) elementwise, bar gamma_n * absum (n scalar or per element)."""
+def _bounded(kind, name, got, want, absum, n, detail="", u=U):
+    """got (fp32) vs want (float64) elementwise, bar gamma_n * absum (n scalar or per element; u: the unit roundoff of
+    the accumulation, 2^-24 unless the device sums in double)."""
     got = np.asarray(got, np.float64)
     err = np.abs(got - want)
-    bound = gamma(n) * absum
+    bound = gamma(n, u) * absum
     with np.errstate(divide="ignore", invalid="ignore"):
         r = np.where(err == 0, 0.0, err / bound)
-        h = np.where(err == 0, 0.0, err / (U * np.sqrt(n) * absum))
+        h = np.where(err == 0, 0.0, err / (u * np.sqrt(n) * absum))
     return Result(kind, name, r.max(initial=0.0), h.max(initial=0.0), err.max(initial=0.0),
                   np.abs(want).max(initial=0.0), detail)
 
@@ -277,13 +287,24 @@ def check_forward_conv(name, a, w, stride, z_got):
     return _exact("forward conv", name, z_got, O.conv2d(a, w, stride, k // 2))
 
 
-def check_stats(name, z, mean_got, invstd_got, gamma_p, beta_p, scale_got, shift_got, eps=1e-5):
-    """saved mean / invstd within 1 ulp of the float64 statistics rounded in the finalize's form; scale / shift as the
-    finalize forms them from those"""
+def stats64(z, peer=None, world=1):
+    """(mean, biased variance, count) of a cell in float64: the sums of the tapped z, plus — SyncBatchNorm — the peer
+    ranks' [2][C] contribution to the all-reduce (an exact input of the cell, as recorded), over world * n samples"""
     z64 = z.astype(np.float64)
     n = z.shape[0] * z.shape[2] * z.shape[3]
-    mean = z64.sum(axis=(0, 2, 3)) / n
-    var = np.maximum((z64 * z64).sum(axis=(0, 2, 3)) / n - mean * mean, 0.0)
+    s1, s2 = z64.sum(axis=(0, 2, 3)), (z64 * z64).sum(axis=(0, 2, 3))
+    if peer is not None:
+        s1, s2 = s1 + peer[0], s2 + peer[1]
+    n = n * world
+    mean = s1 / n
+    return mean, np.maximum(s2 / n - mean * mean, 0.0), n
+
+
+def check_stats(name, z, mean_got, invstd_got, gamma_p, beta_p, scale_got, shift_got, eps=1e-5, peer=None, world=1):
+    """saved mean / invstd within 1 ulp of the float64 statistics rounded in the finalize's form; scale / shift as the
+    finalize forms them from those.  peer, world: a synchronised cell's statistics are those of the global batch
+    (stats64)"""
+    mean, var, _ = stats64(z, peer, world)
     mf, vf = mean.astype(F32), var.astype(F32)
     inv = (F32(1.0) / np.sqrt(vf + F32(eps))).astype(F32)
     e_m = np.abs(mean_got.astype(np.float64) - mf) / np.spacing(np.abs(mf)).astype(np.float64)
@@ -307,9 +328,113 @@ def check_apply(name, z, scale, shift, out_got, res=None, ups=1):
     return _exact("forward apply", name, out_got, v)
 
 
-def bn_backward64(z, g_out, bn, gamma_p, ups):
+def sync_cells(cells):
+    """names of the SyncBatchNorm cells of a graph, in forward order: the stem and the five stride-2 convs of the stages
+    (is_sync_layer, csrc/net_internal.h) — the statistics exchange runs for them in this order forward, reversed
+    backward"""
+    return [c["name"] for c in cells if c.get("bn") and c["name"].startswith("stages.") and ".body." not in c["name"]]
+
+
+def sync_peer(index, local, n, world, forward, seed=0):
+    """The constructed peer of one statistics exchange: what the other world - 1 ranks add to the [2][C] sums `local`
+    (float64) of a rank with n samples, drawn from a generator keyed by (seed, index of the call in the step).
+    Forward: the sums of (world - 1) n samples whose per-channel mean is the local mean shifted by +-[0.25, 1] local
+    standard deviations and whose variance is the local variance times 2^[-1, 1] — the global variance stays positive
+    and every channel's global mean differs from the local one (the variance too, but for a chance cancellation of the
+    two shifts; tests/test_train_cells64_sensitivity.py holds both at the counts the GPU test uses).  Backward: a per-channel multiple in [-1, 2] of the
+    local sum plus an offset of +-[0.25, 1] times the call's largest |local sum| (never zero), times world - 1.
+    world = 1: zeros, the all-reduce over one rank."""
+    local = np.asarray(local, np.float64)
+    C = local.shape[1]
+    if world == 1:
+        return np.zeros_like(local)
+    rng = np.random.default_rng([seed, index])
+    sign = lambda shape: rng.choice([-1.0, 1.0], shape)  # noqa: E731
+    m = float((world - 1) * n)
+    if forward:
+        mu = local[0] / n
+        var = np.maximum(local[1] / n - mu * mu, 0.0)
+        mp = mu + rng.uniform(0.25, 1.0, C) * sign(C) * np.sqrt(var)
+        vp = var * 2.0 ** rng.uniform(-1.0, 1.0, C)
+        return np.stack([m * mp, m * (vp + mp * mp)])
+    a = rng.uniform(-1.0, 2.0, (2, C))
+    b = rng.uniform(0.25, 1.0, (2, C)) * sign((2, C))
+    return (world - 1) * (a * local + b * np.abs(local).max())
+
+
+def _fsum_channels(a):
+    """per-channel sums of (B, C, H, W) float64 values, correctly rounded (math.fsum)"""
+    import math
+    rows = np.ascontiguousarray(a.transpose(1, 0, 2, 3)).reshape(a.shape[1], -1)
+    return np.array([math.fsum(r) for r in rows], np.float64)
+
+
+def check_sync_sums(name, local_got, z=None, bwd=None, rows_per_chunk=None):
+    """The [2][C] double sums a synchronised cell hands to the all-reduce (reduce_partials_kernel's output, as the
+    callback received it), against the sums of the cell's own tensors.
+
+    Forward (z: the tapped z): [sum z, sum z^2].  Every term is exact in double (z is fp32, z^2 has 48 significant
+    bits) and every add on the device is a double add: the conv epilogue sums a tile's rows per thread, across the two
+    half-waves and across the tile's waves; the stem sums its block's rows; reduce_partials_kernel<double> adds the
+    per-tile rows in 32 row groups and the groups in order.  The tile shape depends on the launch form, but whatever it
+    is the whole is one summation tree over the cell's n local samples, so
+        |got - want| <= gamma_n(2^-53) sum|terms|,
+    n - 1 adds on the device plus the one rounding of the reference, which is the correctly rounded sum (math.fsum).
+
+    Backward (bwd: bn_backward64's dict; rows_per_chunk: the plan's): [sum dy, sum dy xhat].  bn_bwd_reduce_kernel sums
+    one chunk of rows_per_chunk image rows of W pixels per channel in fp32 (two accumulator sets per lane, the lanes in a
+    fixed tree: a tree of depth <= rows_per_chunk W - 1), each term rounded on the way: the slope product 0.1f da (1,
+    and 0.1f is 0.1 (1 + 0.25 u)), xhat = (z - mean) invstd (2; the product dy xhat enters through an fma); the x2
+    transitions' 2x2 sum (2) never meets a synchronised cell but is covered.  The chunk partials are then added as
+    doubles (reduce_partials_kernel<float>: 2^-53 per add, under one more u).  So
+        |got - want| <= gamma_d sum|terms|,  d = rows_per_chunk W + 8,
+    the bar dgamma / dbeta are held to (check_bn_backward), here on the sums before their cast to fp32."""
+    local_got = np.asarray(local_got, np.float64)
+    if z is not None:
+        z64 = z.astype(np.float64)
+        n = z.shape[0] * z.shape[2] * z.shape[3]
+        sq = z64 * z64
+        want = np.stack([_fsum_channels(z64), _fsum_channels(sq)])
+        absum = np.stack([np.abs(z64).sum(axis=(0, 2, 3)), sq.sum(axis=(0, 2, 3))])
+        return _bounded("sync sums forward", name, local_got, want, absum, n, u=U64)
+    d = rows_per_chunk * bwd["dz"].shape[3] + 8
+    return _bounded("sync sums backward", name, local_got, np.stack([bwd["dbeta"], bwd["dgamma"]]),
+                    np.stack([bwd["s1"], bwd["s2"]]), d)
+
+
+def check_running(name, z, mean_got, before, after, peer=None, world=1, unbiased=False, momentum=0.9):
+    """running_mean / running_var ([2][C] fp32, `before` and `after` the step) in bn_finalize_channel's fp32 operation
+    order, r' = r * momentum + s * (1.0f - momentum), every operation rounded (-ffp-contract=off).
+    The mean takes s = the saved mean: bit-equal given the saved mean the device holds.  The variance takes s = the fp32
+    variance, times — running_var_unbiased — (float)(N / max(N - 1, 1)) with N = world n formed in double; the fp32
+    variance is not saved, the statistics check allows it 1 ulp around the float64 variance of the global batch rounded
+    once, so the result must be bit-equal to the formula at that value or at one of its two fp32 neighbours.  The ratio
+    is the distance in ulp of the variance that matched (0 or 1; inf: none did, or the mean differs)."""
+    _, var, N = stats64(z, peer, world)
+    mom = F32(momentum)
+    om = F32(1.0) - mom
+    want_m = ((before[0] * mom).astype(F32) + (mean_got.astype(F32) * om).astype(F32)).astype(F32)
+    bad_m = int(np.count_nonzero(want_m != after[0]))
+    vf = var.astype(F32)
+    fac = F32(np.float64(N) / max(np.float64(N) - 1.0, 1.0)) if unbiased else None
+    ulps = np.full(vf.shape, np.inf)
+    for dist, v in ((1, np.nextafter(vf, F32(np.inf))), (1, np.nextafter(vf, F32(-np.inf))), (0, vf)):
+        rv = (v * fac).astype(F32) if unbiased else v
+        r = ((before[1] * mom).astype(F32) + (rv * om).astype(F32)).astype(F32)
+        ulps = np.where(r == after[1], dist, ulps)
+    bad_v = int(np.count_nonzero(np.isinf(ulps)))
+    ratio = np.inf if bad_m or bad_v else float(ulps.max(initial=0.0))
+    detail = "%d means, %d variances differ" % (bad_m, bad_v) if bad_m or bad_v else "variance at %d ulp" % ratio
+    err = max(np.abs(want_m.astype(np.float64) - after[0]).max(initial=0.0), 0.0)
+    return Result("running stats", name, ratio, ratio, err, np.abs(want_m).max(initial=0.0), detail)
+
+
+def bn_backward64(z, g_out, bn, gamma_p, ups, peer=None, world=1):
     """float64 BN + leaky backward from the tapped z, output gradient (interior, at the stored resolution) and
-    [mean, invstd, scale, shift]: dict of the references and their absolute-value sums"""
+    [mean, invstd, scale, shift]: dict of the references and their absolute-value sums.  peer, world (a synchronised
+    cell): dbeta / dgamma stay the LOCAL sums; the coefficients c2, c3 of dz are (local + peer) / (world n), the means
+    over the global batch; dz_local is dz with the local-only coefficients (what a kernel that missed the exchange
+    would give)."""
     mean, inv, sc, sh = [bn[i].astype(np.float64).reshape(1, -1, 1, 1) for i in range(4)]
     z64 = z.astype(np.float64)
     g = g_out.astype(np.float64)
@@ -327,25 +452,57 @@ def bn_backward64(z, g_out, bn, gamma_p, ups):
     dbeta, s1 = dy.sum(axis=(0, 2, 3)), dy_abs.sum(axis=(0, 2, 3))
     dgamma, s2 = (dy * xh).sum(axis=(0, 2, 3)), (dy_abs * np.abs(xh)).sum(axis=(0, 2, 3))
     c1 = gamma_p.astype(np.float64).reshape(1, -1, 1, 1) * inv
-    c2, c3 = (dbeta / n).reshape(1, -1, 1, 1), (dgamma / n).reshape(1, -1, 1, 1)
+    N = n * world
+    g1, g2 = (dbeta, dgamma) if peer is None else (dbeta + peer[0], dgamma + peer[1])
+    c2, c3 = (g1 / N).reshape(1, -1, 1, 1), (g2 / N).reshape(1, -1, 1, 1)
     dz = c1 * (dy - c2 - xh * c3)
-    return dict(dbeta=dbeta, s1=s1, dgamma=dgamma, s2=s2, dz=dz, c1=c1, c2=c2, c3=c3, dy_abs=dy_abs, xh=xh, n=n)
+    r = dict(dbeta=dbeta, s1=s1, dgamma=dgamma, s2=s2, dz=dz, c1=c1, c2=c2, c3=c3, dy_abs=dy_abs, xh=xh, n=n, N=N)
+    if peer is not None:
+        r["dz_local"] = c1 * (dy - (dbeta / n).reshape(1, -1, 1, 1) - xh * (dgamma / n).reshape(1, -1, 1, 1))
+    return r
 
 
-def check_bn_backward(name, z, g_out, bn, gamma_p, ups, rows_per_chunk, dgamma_got, dbeta_got, dz_got):
+def check_bn_backward(name, z, g_out, bn, gamma_p, ups, rows_per_chunk, dgamma_got, dbeta_got, dz_got, peer=None,
+                      world=1, local_got=None):
     """dgamma / dbeta: fp32 partial sums over one chunk of rows_per_chunk image rows (then float64), each term rounded
-    a few times on the way (2x2 sum, slope, xhat); dz = c1 ((dy - c2) - xhat c3) from the fp32 coefficients"""
-    r = bn_backward64(z, g_out, bn, gamma_p, ups)
+    a few times on the way (2x2 sum, slope, xhat); dz = c1 ((dy - c2) - xhat c3) from the fp32 coefficients.
+
+    A synchronised cell (peer: the recorded [2][C] contribution of the other ranks, world: their number plus one):
+    dgamma / dbeta are the LOCAL sums, to the same bar (the gradients are all-reduced later with every other one).  The
+    coefficients are the global means: the device forms c2 = fl32((L^ + P) / N), N = world n, from its own local sum L^
+    and the peer P.  P is an input, exact on both sides, and |L^ - L| <= gamma_d s1 (check_sync_sums), so
+        |c2_dev - c2| <= gamma_d s1 / N + (u + 2 u64) |c2|
+    (the double add and divide, u64 = 2^-53 each, then the cast): only the local partial sums' rounding enters, divided
+    by the GLOBAL count; the same for c3 with s2.  These are e2, e3 below; with world = 1 and no peer they are the
+    per-device terms unchanged.  local_got (the [2][C] sums the callback received) adds check_sync_sums' backward
+    Result.  The dz Result of a cell with a peer carries extra["local_only_differs"]: whether dz_local is more than
+    TWICE the bar away from dz in some element of EVERY channel of this block, so that a device that used local coefficients (within one bar
+    of dz_local) could not pass."""
+    r = bn_backward64(z, g_out, bn, gamma_p, ups, peer, world)
     d = rows_per_chunk * z.shape[3] + 8
     out = [_bounded("bn backward dbeta", name, dbeta_got, r["dbeta"], r["s1"], d),
            _bounded("bn backward dgamma", name, dgamma_got, r["dgamma"], r["s2"], d)]
-    e2 = gamma(d) * r["s1"].reshape(1, -1, 1, 1) / r["n"] + U * np.abs(r["c2"])
-    e3 = gamma(d) * r["s2"].reshape(1, -1, 1, 1) / r["n"] + U * np.abs(r["c3"])
+    if local_got is not None:
+        out.append(check_sync_sums(name, local_got, bwd=r, rows_per_chunk=rows_per_chunk))
+    uc = U if peer is None else U + 2 * U64
+    e2 = gamma(d) * r["s1"].reshape(1, -1, 1, 1) / r["N"] + uc * np.abs(r["c2"])
+    e3 = gamma(d) * r["s2"].reshape(1, -1, 1, 1) / r["N"] + uc * np.abs(r["c3"])
     absum = r["dy_abs"] + np.abs(r["c2"]) + np.abs(r["xh"] * r["c3"])
     # bar = |c1| (e2 + |xhat| e3 + gamma_10 absum), written as gamma_10 * S_eff for _bounded
     s_eff = np.abs(r["c1"]) * ((e2 + np.abs(r["xh"]) * e3) / gamma(10) + absum)
     out.append(_bounded("bn backward dz", name, dz_got, r["dz"], s_eff, 10))
+    if peer is not None:
+        far = np.abs(r["dz_local"] - r["dz"]) > 2 * gamma(10) * s_eff
+        out[-1].extra["local_only_differs"] = bool(far.any(axis=(0, 2, 3)).all())
     return out
+
+
+def local_mean_differs(z, peer, world):
+    """per channel: does the fp32 mean of the local samples alone lie more than 1 ulp from the fp32 global mean (so that
+    a finalize that missed the exchange, or the count, fails check_stats)?"""
+    lm = stats64(z)[0].astype(F32)
+    gm = stats64(z, peer, world)[0].astype(F32)
+    return np.abs(lm.astype(np.float64) - gm) > np.spacing(np.abs(gm)).astype(np.float64)
 
 
 def wgrad64(dz, a, k, stride, sel):

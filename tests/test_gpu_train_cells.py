@@ -142,9 +142,18 @@ def _sel(B, fm):
     return sorted(set(range(fm)) | set(range((B - 1) * fm, B * fm)))
 
 
-def _walk(st, split=None):
+def _walk(st, split=None, only=None):
     """Every check of one recorded step `st` (a builder's dict) -> (results, pool counts {route: (wins, ties, clips counted)}).
     The loss census (R.loss_census) of the step is left in st["census"].
+
+    st["sync"] (tests/test_gpu_syncbn_cells.py): the step ran with a SyncBatchNorm statistics callback — dict(world,
+    calls=[dict(local, peer)] in call order, before / after={cell: [2][C] running statistics}, unbiased).  The
+    synchronised cells (R.sync_cells) are then checked against the statistics of the global batch: check_stats and
+    check_bn_backward with the recorded peer, check_sync_sums on what the callback received, check_running; what each
+    block's inputs could tell apart is left in st["sync"]["nonvacuous"][cell].
+
+    only: a set of cell names — the BatchNorm-side checks (borders, statistics, apply, BN backward) of those cells
+    alone; no convolution, gradient-plane or loss check runs.
 
     split (tests/test_gpu_split_cells.py): the launches of the step that ran on the split-fp32 kernels, from its label
     log — dict(fwd={cell: k-split}, dgrad={cell: k-split}, wgrad={cell: splits}).  For those launches three checks are
@@ -171,7 +180,17 @@ def _walk(st, split=None):
         """forward value of a producer: a cell's or pool node's output, or the caller's route"""
         return st["routes"][name] if name in st.get("routes", {}) else _host(net.read_activation(name))
 
+    sync, sync_at = st.get("sync"), {}
+    if sync:  # the statistics exchanges of the step: forward in cell order, backward reversed; [2][C] doubles each
+        names = R.sync_cells(cells)
+        counts = [2 * by_name[n]["cout"] for n in names]
+        assert [q["local"].size for q in sync["calls"]] == counts + counts[::-1], [q["local"].size for q in sync["calls"]]
+        sync_at = {n: (sync["calls"][i], sync["calls"][2 * len(names) - 1 - i]) for i, n in enumerate(names)}
+        sync["nonvacuous"] = {}
+
     for c in cells:
+        if only is not None and (R.is_pool(c) or c["name"] not in only or not c["bn"]):
+            continue
         if R.is_pool(c):  # pool forward on the device's own per-frame route, whole batch
             frames = act(c["src"][0])
             assert frames.shape[0] == B * k, (c["name"], frames.shape)
@@ -186,7 +205,9 @@ def _walk(st, split=None):
         res.append(R.border_zero("borders", name + " grad", g_pad))
         g = R.interior(g_pad)
         del g_pad
-        if c["src"] == ["image"]:
+        if only is not None:
+            a = None
+        elif c["src"] == ["image"]:
             a = st["frames"]
         else:
             a_pad = tap(name, "input")
@@ -201,7 +222,7 @@ def _walk(st, split=None):
                     off += src.shape[1]
                 else:
                     off += by_name[p]["cout"]
-        assert a.shape[0] == B * c["fm"], (name, a.shape)
+        assert only is not None or a.shape[0] == B * c["fm"], (name, a.shape)
         wname = name + (".0.weight" if c["bn"] else ".weight")
         w = params[wname]
         plan = net.train_conv_plan(name)
@@ -227,7 +248,9 @@ def _walk(st, split=None):
         gam, bet = params[name + ".1.gamma"], params[name + ".1.beta"]
         out = _host(net.read_activation(name))
         skip = _host(net.read_activation(c["skip"])) if c["skip"] else None
-        if name in split["fwd"]:  # the raw conv on conv_split_kernel: no epilogue, per-tile statistics, never k-split
+        if only is not None:
+            pass
+        elif name in split["fwd"]:  # the raw conv on conv_split_kernel: no epilogue, per-tile statistics, never k-split
             ch = S.sample_channels(c["cout"], name, z[sel_img][:, 0].size)
             a_s = np.ascontiguousarray(a[sel_img])
             res += S.check_split("split forward conv", name, z[sel_img][:, ch], S.six_parts(a_s, w[ch], s, kk // 2),
@@ -240,21 +263,39 @@ def _walk(st, split=None):
         parts = {}
         for lo, hi in _blocks(c["cout"], per * c["ups"] ** 2):
             cs = slice(lo, hi)
+            kw_f, kw_b = {}, {}
+            if name in sync_at:  # the statistics of the global batch: the recorded peer is an input of the cell
+                fwd, bwd = sync_at[name]
+                kw_f = dict(peer=fwd["peer"][:, cs], world=sync["world"])
+                kw_b = dict(peer=bwd["peer"][:, cs], world=sync["world"], local_got=bwd["local"][:, cs])
+                parts.setdefault("sync", []).append(R.check_sync_sums(name, fwd["local"][:, cs], z=z[:, cs]))
+                parts.setdefault("running", []).append(R.check_running(
+                    name, z[:, cs], bn[0, cs], sync["before"][name][:, cs], sync["after"][name][:, cs],
+                    unbiased=sync["unbiased"], **kw_f))
+                sync["nonvacuous"].setdefault(name, []).append(
+                    dict(mean=bool(R.local_mean_differs(z[:, cs], **kw_f).all())))
             parts.setdefault("stats", []).append(R.check_stats(name, z[:, cs], bn[0, cs], bn[1, cs], gam[cs], bet[cs],
-                                                              bn[2, cs], bn[3, cs]))
+                                                              bn[2, cs], bn[3, cs], **kw_f))
             parts.setdefault("apply", []).append(R.check_apply(
                 name, z[:, cs], bn[2, cs], bn[3, cs], out[:, cs], None if skip is None else skip[:, cs], c["ups"]))
             for r in R.check_bn_backward(name, z[:, cs], g[:, cs], bn[:, cs], gam[cs], c["ups"], plan[2], dgam[cs],
-                                         dbet[cs], dz[:, cs]):
+                                         dbet[cs], dz[:, cs], **kw_b):
                 parts.setdefault(r.kind, []).append(r)
+                if "local_only_differs" in r.extra:
+                    sync["nonvacuous"][name][-1]["dz"] = r.extra["local_only_differs"]
         res += [R.Result.merge(p) for p in parts.values()]
         del out, skip, z
+        if only is not None:
+            continue
         if c["src"] == ["image"]:
             res.append(R.check_wgrad(name, dz, a, kk, s, list(range(c["cout"])), grad(wname), plan[0], plan[1],
                                      kind="stem weight gradient"))
         else:
             res += wgrad_check(dz)
         del dz, a
+
+    if only is not None:
+        return res, pools
 
     # data gradients: every producer's gradient plane, first and last clip
     for c in cells:

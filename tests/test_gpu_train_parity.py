@@ -239,7 +239,12 @@ def test_syncbn_plumbing_with_simulated_ranks():
     """SyncBatchNorm path on one GPU: the statistics callback is driven with a stand-in for the RCCL
     all-reduce that doubles the [2][C] sums, i.e. two ranks holding the same frames.  Batch mean and
     variance are then unchanged, so losses and gradients must equal the per-device-BN run exactly;
-    the callback must fire for the 6 SyncBN layers, forward and backward (12 calls)."""
+    the callback must fire for the 6 SyncBN layers, forward and backward (12 calls).
+
+    What doubling cannot tell apart: the peer holds the same frames, so the global mean, variance and backward means
+    equal the local ones.  A finalize that took the backward coefficients from the local sums over the local count, or
+    the running statistics from local values, would pass this test bit for bit.  That is held, cell by cell against
+    float64 and with a constructed peer whose statistics differ in every channel, by tests/test_gpu_syncbn_cells.py."""
     import torch
     import videoyolo_amd as vy
     from videoyolo_amd import _lib, autograd

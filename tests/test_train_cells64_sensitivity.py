@@ -14,6 +14,11 @@ Two more planted bugs are the ways a broken stream-K hand-off would show: a data
 32-channel k-step of one tap on one 64x64 tile (check_dgrad), and one tile's rows missing from the per-tile statistics
 sums (check_stats).
 
+The SyncBatchNorm statistics exchange: a toy synchronised cell in the device's blocked order (per-tile double sums,
+fp32 chunk partials, the 32-group ordered reduce in 32-column blocks, a "callback" that adds R.sync_peer's peer, the count
+times the world size, the fp32 finalize with running statistics) passes check_sync_sums / check_stats / check_running /
+check_bn_backward at world 3, 2 and 1; eight planted exchange bugs must each fail the check they belong to.
+
 The two ends of the step get the same treatment: loss_kernel + loss_reduce_kernel, raw_preds_kernel and sgd_kernel are
 restated in fp32 numpy (vy_math's exp / log, the 256-lane butterfly, the blocks summed in double; four momentum steps
 with a multiplier change) and must pass check_losses / check_head_grad / check_raw_preds / SgdRef; nine loss faults, one
@@ -250,6 +255,189 @@ def test_a_broken_stream_k_hand_off_fails_its_check(mut):
     assert bad == ["data gradient" if mut.startswith("dgrad") else "forward stats"], (mut, res)
     old = [r.old_bar_ok for r in res if not r.ok]
     print("%s: fails %s; the 2e-3-of-max bar %s" % (mut, bad, "MISSES it" if all(old) else "catches it"))
+
+
+# ---------------------------------------------------------------- the SyncBatchNorm statistics exchange
+# A synchronised cell in the device's blocked order: per-tile double sums (forward) or fp32 chunk partials (backward),
+# the ordered reduce of the partial rows (32 row groups, 32-column blocks) into the local [2][C] sums, the exchange (the
+# peer of R.sync_peer added by the "callback"), the count times the world size, the finalize in fp32.
+def dev_reduce_partials(parts, drop_last_block=False):
+    """reduce_partials_kernel: row group r adds rows r, r + 32, ... in order, then the 32 group sums in order"""
+    p = np.asarray(parts, np.float64)
+    groups = np.zeros((32, p.shape[1]))
+    for t in range(p.shape[0]):
+        groups[t % 32] += p[t]
+    out = np.zeros(p.shape[1])
+    for r in range(32):
+        out += groups[r]
+    if drop_last_block:  # the last block of 32 columns never launched: its sums keep what the buffer held
+        out[(p.shape[1] - 1) // 32 * 32:] = 0.0
+    return out
+
+
+def dev_sync_stats(z, gam, bet, before, exchange, world, unbiased, mut=None):
+    """-> (bn [4][C], running statistics after [2][C]).  exchange(local [2C] doubles) -> the global sums."""
+    B, C, H, W = z.shape
+    n = B * H * W
+    rows = z.transpose(0, 2, 3, 1).reshape(n, C).astype(np.float64)
+    parts = np.stack([np.concatenate([rows[i:i + 64].sum(0), (rows[i:i + 64] ** 2).sum(0)]) for i in range(0, n, 64)])
+    local = dev_reduce_partials(parts, mut == "last_32_column_block_of_the_reduce_missing")
+    glob = exchange(local)
+    count = float(n if mut == "count_not_multiplied_by_world" else n * world)
+
+    def stats(sums, cnt):
+        mean = sums[:C] / cnt
+        return mean.astype(F32), np.maximum(sums[C:] / cnt - mean * mean, 0).astype(F32)
+
+    mf, vf = stats(glob, count)
+    inv = (F32(1) / np.sqrt(vf + F32(1e-5))).astype(F32)
+    sc = (gam * inv).astype(F32)
+    rm, rv = stats(local, float(n)) if mut == "running_statistics_from_the_local_batch" else (mf, vf)
+    if unbiased:
+        cnt = float(n) if mut == "unbiased_factor_from_the_local_count" else count
+        rv = (rv * F32(cnt / max(cnt - 1.0, 1.0))).astype(F32)
+    mom = F32(0.9)
+    om = F32(1) - mom
+    after = np.stack([((before[0] * mom).astype(F32) + (rm * om).astype(F32)).astype(F32),
+                      ((before[1] * mom).astype(F32) + (rv * om).astype(F32)).astype(F32)])
+    return np.stack([mf, inv, sc, R.fmaf(-mf, sc, bet)]), after
+
+
+def dev_sync_bn_bwd(z, g, bn, gam, rpc, exchange, world, mut=None):
+    """-> (dgamma, dbeta, dz): fp32 partial rows over chunks of rpc image rows, the ordered reduce, the exchange, then
+    dgamma / dbeta from the local sums and the coefficients of dz from the global sums over the global count"""
+    mu, inv, sc, sh = [bn[i].reshape(1, -1, 1, 1) for i in range(4)]
+    dy = np.where(R.fmaf(z, sc, sh) > 0, g, F32(0.1) * g).astype(F32)
+    xh = ((z - mu) * inv).astype(F32)
+    B, C, H, W = z.shape
+    n = B * H * W
+    rows_dy = dy.transpose(0, 2, 1, 3).reshape(B * H, C, W)
+    rows_p = (dy * xh).astype(F32).transpose(0, 2, 1, 3).reshape(B * H, C, W)
+    parts = np.stack([np.concatenate([rows_dy[r0:r0 + rpc].sum(axis=(0, 2), dtype=F32),
+                                      rows_p[r0:r0 + rpc].sum(axis=(0, 2), dtype=F32)]) for r0 in range(0, B * H, rpc)])
+    local = dev_reduce_partials(parts, mut == "last_32_column_block_of_the_reduce_missing")
+    glob = exchange(local)
+    count = float(n if mut == "count_not_multiplied_by_world" else n * world)
+    own = glob if mut == "dgamma_dbeta_from_the_global_sums" else local
+    coef, cnt = (local, float(n)) if mut == "backward_coefficients_from_the_local_sums" else (glob, count)
+    c1 = (gam * inv[0, :, 0, 0]).astype(F32).reshape(1, -1, 1, 1)
+    c2 = (coef[:C] / cnt).astype(F32).reshape(1, -1, 1, 1)
+    c3 = (coef[C:] / cnt).astype(F32).reshape(1, -1, 1, 1)
+    dz = (c1 * ((dy - c2) - xh * c3)).astype(F32)
+    return own[C:].astype(F32), own[:C].astype(F32), dz
+
+
+SYNC_MUTATIONS = ["count_not_multiplied_by_world", "backward_coefficients_from_the_local_sums",
+                  "dgamma_dbeta_from_the_global_sums", "running_statistics_from_the_local_batch",
+                  "unbiased_factor_from_the_local_count", "exchange_covers_the_first_C_doubles_only",
+                  "last_32_column_block_of_the_reduce_missing", "forward_peer_added_twice"]
+
+
+def _run_sync(mut=None, world=3, unbiased=True):
+    rng = np.random.default_rng(23)
+    r = lambda *s: rng.standard_normal(s).astype(F32)  # noqa: E731
+    B, C, S, rpc = 3, 48, 24, 5            # 2C = 96 columns: three 32-column blocks; 1728 samples: 27 tiles, 15 chunks
+    z, g = (0.5 + 1.5 * r(B, C, S, S)).astype(F32), r(B, C, S, S)
+    gam, bet = (1 + 0.2 * r(C)).astype(F32), (0.3 * r(C)).astype(F32)
+    before = np.stack([0.2 * r(C), (1 + 0.3 * np.abs(r(C))).astype(F32)])
+    n = B * S * S
+    calls = []
+
+    def exchange(local):
+        """the statistics callback: records what it is handed and the peer it adds"""
+        i = len(calls)
+        peer = R.sync_peer(i, local.reshape(2, C), n, world, forward=i == 0, seed=1)
+        calls.append(dict(local=local.reshape(2, C).copy(), peer=peer))
+        add = peer.reshape(-1).copy()
+        if mut == "exchange_covers_the_first_C_doubles_only":
+            add[C:] = 0.0
+        glob = local + add
+        if mut == "forward_peer_added_twice" and i == 0:  # the callback's result accumulated onto the local sums as well
+            glob = glob + add
+        return glob
+
+    bn, after = dev_sync_stats(z, gam, bet, before, exchange, world, unbiased, mut)
+    fwd = calls[0]
+    kw = dict(peer=fwd["peer"], world=world)
+    res = [R.check_sync_sums("sync cell", fwd["local"], z=z),
+           R.check_stats("sync cell", z, bn[0], bn[1], gam, bet, bn[2], bn[3], **kw),
+           R.check_running("sync cell", z, bn[0], before, after, unbiased=unbiased, **kw)]
+    out = R.leaky(R.fmaf(z, bn[2].reshape(1, -1, 1, 1), bn[3].reshape(1, -1, 1, 1)))
+    res.append(R.check_apply("sync cell", z, bn[2], bn[3], out))
+    dg, db, dz = dev_sync_bn_bwd(z, g, bn, gam, rpc, exchange, world, mut)
+    bwd = calls[1]
+    res += R.check_bn_backward("sync cell", z, g, bn, gam, 1, rpc, dg, db, dz, peer=bwd["peer"], world=world,
+                               local_got=bwd["local"])
+    told_apart = (bool(R.local_mean_differs(z, **kw).all()), res[-1].extra.get("local_only_differs"))
+    return res, told_apart
+
+
+@pytest.mark.parametrize("world,unbiased", [(3, True), (2, False), (1, False)])
+def test_blocked_sync_device_passes_every_check(world, unbiased):
+    res, told_apart = _run_sync(None, world, unbiased)
+    bad = [r for r in res if not r.ok]
+    assert not bad, bad
+    assert {r.kind for r in res} == {"sync sums forward", "forward stats", "running stats", "forward apply",
+                                     "bn backward dbeta", "bn backward dgamma", "sync sums backward", "bn backward dz"}
+    for r in res:
+        print(r)
+    # the inputs tell a kernel that missed the exchange from a right one — unless there is no peer (world 1)
+    assert told_apart == (world > 1, world > 1), told_apart
+    assert all(r.headroom < 50 for r in res)
+
+
+def test_sync_references_without_a_peer_are_the_per_device_ones():
+    """peer=None, world=1: check_stats / check_bn_backward give the per-device Results bit for bit (a zero peer too)"""
+    c = _case()
+    bn = dev_stats(c["z"], c["gam"], c["bet"])
+    dg, db, dz = dev_bn_bwd(c["z"], c["g"], bn, c["gam"], 1, 5)
+    zero = np.zeros((2, c["C"]))
+    a = [R.check_stats("cell3", c["z"], bn[0], bn[1], c["gam"], c["bet"], bn[2], bn[3])]
+    a += R.check_bn_backward("cell3", c["z"], c["g"], bn, c["gam"], 1, 5, dg, db, dz)
+    b = [R.check_stats("cell3", c["z"], bn[0], bn[1], c["gam"], c["bet"], bn[2], bn[3], peer=zero, world=1)]
+    b += R.check_bn_backward("cell3", c["z"], c["g"], bn, c["gam"], 1, 5, dg, db, dz, peer=zero, world=1)
+    assert [(r.kind, r.ratio, r.headroom, r.err_max) for r in a][:3] == [(r.kind, r.ratio, r.headroom, r.err_max) for r in b][:3]
+    assert a[3].err_max == b[3].err_max and abs(a[3].ratio / b[3].ratio - 1) < 1e-8   # (dz: the bar gains 2 u64 |c|)
+
+
+@pytest.mark.parametrize("n,world", [(4, 3), (8, 2), (4096, 2)])
+def test_constructed_peer_moves_every_channel(n, world):
+    """R.sync_peer at the sample counts of tests/test_gpu_syncbn_cells.py's deepest cells (4 and 8 local samples) and a
+    large one, for every call index of a step: the global variance stays positive, the fp32 global mean is more than
+    1 ulp from the local one and the variance moves in every channel, the backward peer is nonzero in every entry and
+    changes with the call index; world 1 gives a zero peer."""
+    C = 1024
+    for index in range(12):
+        z = (0.3 + np.random.default_rng(100 + index).standard_normal((n, C, 1, 1))).astype(F32)
+        z64 = z.astype(np.float64)
+        local = np.stack([z64.sum(axis=(0, 2, 3)), (z64 * z64).sum(axis=(0, 2, 3))])
+        fwd = R.sync_peer(index, local, n, world, forward=True, seed=3)
+        mean, var, count = R.stats64(z, fwd, world)
+        assert count == n * world and (var > 0).all() and R.local_mean_differs(z, fwd, world).all()
+        lvar = R.stats64(z)[1]   # (the two shifts can nearly cancel in a channel: the bar is what check_stats resolves)
+        assert (np.abs(var - lvar) > 4 * np.spacing(lvar.astype(F32)).astype(np.float64)).all()
+        bwd = R.sync_peer(index, local, n, world, forward=False, seed=3)
+        assert np.abs(bwd).min() > 0
+        assert not np.array_equal(bwd, R.sync_peer(index + 1, local, n, world, forward=False, seed=3))
+        assert not R.sync_peer(index, local, n, 1, forward=True, seed=3).any()
+
+
+@pytest.mark.parametrize("mut", SYNC_MUTATIONS)
+def test_every_sync_mutation_fails_a_check(mut):
+    res, _ = _run_sync(mut)
+    bad = [r for r in res if not r.ok]
+    assert bad, "mutation %s passed every check" % mut
+    want = {"count_not_multiplied_by_world": "forward stats", "backward_coefficients_from_the_local_sums": "bn backward dz",
+            "dgamma_dbeta_from_the_global_sums": "bn backward dgamma", "running_statistics_from_the_local_batch": "running stats",
+            "unbiased_factor_from_the_local_count": "running stats", "exchange_covers_the_first_C_doubles_only": "forward stats",
+            "last_32_column_block_of_the_reduce_missing": "sync sums forward", "forward_peer_added_twice": "forward stats"}
+    assert want[mut] in {r.kind for r in bad}, (mut, bad)
+    if mut in ("backward_coefficients_from_the_local_sums", "dgamma_dbeta_from_the_global_sums",
+               "running_statistics_from_the_local_batch", "unbiased_factor_from_the_local_count"):
+        assert {r.kind for r in bad} <= {want[mut], "bn backward dbeta"}, (mut, bad)   # nothing else moves
+    old = [r.old_bar_ok for r in bad if r.kind != "running stats"]
+    verdict = "is not applicable" if not old else ("MISSES it" if all(old) else "catches it")
+    print("%s: fails %s; the 2e-3-of-max bar %s" % (mut, sorted(set(r.kind for r in bad)), verdict))
 
 
 # ---------------------------------------------------------------- the toy window step
