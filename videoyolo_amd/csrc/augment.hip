@@ -39,11 +39,13 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
+#include <algorithm>
 #include <type_traits>
 
-#include "../../include/vyolo.h"
-#include "net_internal.h"
+#include "../../include/vy_math.h"
+#include "vy_support.h"
 
 namespace {
 

@@ -30,8 +30,9 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "../../include/vyolo.h"
-#include "net_internal.h"
+#include <algorithm>
+
+#include "vy_support.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // conv_device.h — device-side helpers shared by the implicit-GEMM conv kernels (conv_igemm.hip, conv_split.hip,
-// conv_wino.hip) and the split-fp32 weight gradient (wgrad_split.hip).
+// conv_wino.hip) and the weight gradients (wgrad.hip, wgrad_split.hip).
 #pragma once
 #include "kernels.h"
 
@@ -67,5 +67,18 @@ __device__ __forceinline__ void lds_barrier() {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #endif
+}
+
+// The weight gradients' view of output pixel p of a conv (wgrad.hip, the pixel table): the byte offset of its dz vector
+// inside the dz plane and of its (stride-scaled) centre pixel inside the input plane, both zero-bordered
+struct WgradPix {
+  unsigned long long zo, ao;
+};
+__device__ __forceinline__ WgradPix wgrad_pixel_offsets(int p, int Ho, int Wo, int z_cs, int a_Hp, int a_Wp, int a_cs, int stride) {
+  const int x = p % Wo, t = p / Wo, y = t % Ho, b = t / Ho;
+  WgradPix o;
+  o.zo = ((unsigned long long)(b * (Ho + 2) + y + 1) * (Wo + 2) + x + 1) * z_cs * 4ull;
+  o.ao = ((unsigned long long)(b * a_Hp + y * stride + 1) * a_Wp + x * stride + 1) * a_cs * 4ull;
+  return o;
 }
 

@@ -26,37 +26,10 @@ int vy_fail(int code, const char* fmt, ...) {
 }
 #define fail vy_fail
 
-int vy_check_kind(const vy_net* net, int takes, const char* entry) {
-  if (!net) return 0;  // (the entry's own argument check reports it)
-  const int kind = !net->heads_only ? VY_TAKES_IMAGES : net->window_k ? VY_TAKES_BANK : VY_TAKES_ROUTES;
-  if (kind == takes) return 0;
-  static const char* const what[3] = {"takes an image batch", "takes the route tensors of single frames",
-                                      "takes a bank of per-frame routes and a table"};
-  static const char* const is[3] = {"a full net (vy_net_create / vy_net_create_window)",
-                                    "a heads-only net (vy_net_create_heads), use the *_routes entry points",
-                                    "a windowed heads-only net (vy_net_create_heads_window), use the *_bank entry points"};
-  return fail(VY_ERR_STATE, "%s %s: this is %s", entry, what[takes], is[kind]);
-}
-
 int vy_check_shape(int32_t batch, int32_t h, int32_t w) {
   if (batch < 1) return fail(VY_ERR_INVALID, "batch %d < 1", batch);
   if (h < 32 || w < 32 || h > 4096 || w > 4096)
     return fail(VY_ERR_INVALID, "input %dx%d: height and width must lie in [32, 4096]", h, w);
-  return 0;
-}
-
-// VY_ERR_STATE for a window net (vy_net_create_window) at an entry point that does not serve one
-static int refuse_window(const vy_net* net, const char* entry) {
-  if (net && net->clip_net())
-    return fail(VY_ERR_STATE, "%s does not take a window net (vy_net_create_window): use vy_net_create for single frames",
-                entry);
-  return 0;
-}
-// VY_ERR_STATE for a hierarchical net (vy_net_create_hier) at an entry point that does not serve one
-static int refuse_hier(const vy_net* net, const char* entry) {
-  if (net && net->hier_n)
-    return fail(VY_ERR_STATE, "%s does not take a hierarchical net (vy_net_create_hier): use vy_net_create for single frames",
-                entry);
   return 0;
 }
 
@@ -154,20 +127,10 @@ int vy_net_hier(const vy_net* net, int32_t* n_pools, int32_t* frames) {
 
 int vy_net_tap_frames(const vy_net* net, const char* name, int32_t* frames) {
   if (!net || !name || !frames) return fail(VY_ERR_INVALID, "null argument");
-  if (const int i = vy_hpool_tap(net, name); i >= 0) {
-    *frames = net->planes[net->hpools[i].dst].fm;
-    return 0;
-  }
-  if (vy_pool_tap(net, name) >= 0) {
-    *frames = 1;
-    return 0;
-  }
-  for (const ConvT& cv : net->convs)
-    if (cv.name == name) {
-      *frames = net->planes[cv.out_plane].fm;
-      return 0;
-    }
-  return fail(VY_ERR_INVALID, "no cell named '%s'", name);
+  TapRef t;
+  VY_TRY(vy_resolve_tap(net, name, &t));
+  *frames = net->planes[t.plane].fm;  // (a pooled route's plane: 1)
+  return 0;
 }
 
 void vy_net_destroy(vy_net* net) {
@@ -238,18 +201,6 @@ int vy_net_bind_params(vy_net* net, void* dev_params) {
   net->dev_params = static_cast<float*>(dev_params);
   net->split_dirty = net->dsplit_dirty = net->wino_dirty = true;
   return 0;
-}
-
-// OIHW (reference) <-> O,kh,kw,I (device)
-static void pack_oihw(const float* src, float* dst, int O, int I, int k) {
-  for (int o = 0; o < O; ++o)
-    for (int i = 0; i < I; ++i)
-      for (int t = 0; t < k * k; ++t) dst[((size_t)o * k * k + t) * I + i] = src[((size_t)o * I + i) * k * k + t];
-}
-static void unpack_oihw(const float* src, float* dst, int O, int I, int k) {
-  for (int o = 0; o < O; ++o)
-    for (int i = 0; i < I; ++i)
-      for (int t = 0; t < k * k; ++t) dst[((size_t)o * I + i) * k * k + t] = src[((size_t)o * k * k + t) * I + i];
 }
 
 int vy_net_param_set(vy_net* net, int32_t i, const float* host_src, void* stream) {
@@ -324,10 +275,9 @@ int vy_net_set_keep_activations(vy_net* net, int32_t keep) {
 int vy_net_set_conv_mode(vy_net* net, int32_t mode) {
   if (!net) return fail(VY_ERR_INVALID, "net is null");
   if (mode < VY_CONV_EXACT_FP32 || mode > VY_CONV_SPLIT_BF16X3_TRAIN) return fail(VY_ERR_INVALID, "conv mode %d", mode);
-  if (net->clip_net() && mode != VY_CONV_EXACT_FP32)
-    return fail(VY_ERR_UNSUPPORTED, "conv mode %d: a window net runs the exact fp32 kernels only", mode);
-  if (net->hier_n && mode != VY_CONV_EXACT_FP32)
-    return fail(VY_ERR_UNSUPPORTED, "conv mode %d: a hierarchical net runs the exact fp32 kernels only", mode);
+  if (const VyKind kind = net->kind(); (kind == VY_WINDOW || kind == VY_HIER) && mode != VY_CONV_EXACT_FP32)
+    return fail(VY_ERR_UNSUPPORTED, "conv mode %d: a %s net runs the exact fp32 kernels only", mode,
+                kind == VY_WINDOW ? "window" : "hierarchical");
   if (mode != net->conv_mode) {
     net->conv_mode = mode;
     net->unbind();  // (the weight images live in the workspace)
@@ -361,16 +311,14 @@ int32_t vy_net_num_anchors(const vy_net* net) {
 
 int vy_net_forward_infer(vy_net* net, const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
                          void* stream) {
-  VY_TRY(vy_check_kind(net, false, "vy_net_forward_infer"));
+  VY_TRY(vy_serves(net, "vy_net_forward_infer", VY_FULL | VY_WINDOW | VY_HIER));
   return run_entry(net, x && ids && scores && bboxes, nullptr, stream, [&](hipStream_t s) {
     return infer_sequence(net, x, ids, scores, bboxes, keep_idx, s, plain);
   });
 }
 
 int vy_net_forward_features(vy_net* net, const float* x, float* f0, float* f1, float* f2, void* stream) {
-  VY_TRY(vy_check_kind(net, false, "vy_net_forward_features"));
-  VY_TRY(refuse_window(net, "vy_net_forward_features"));
-  VY_TRY(refuse_hier(net, "vy_net_forward_features"));
+  VY_TRY(vy_serves(net, "vy_net_forward_features", VY_FULL));
   return run_entry(net, x && f0 && f1 && f2, nullptr, stream, [&](hipStream_t s) {
     const float* const out[3] = {f0, f1, f2};
     VY_TRY(net->prepare(s, plain, true));
@@ -381,7 +329,7 @@ int vy_net_forward_features(vy_net* net, const float* x, float* f0, float* f1, f
 
 int vy_net_forward_infer_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* ids, float* scores,
                                 float* bboxes, int32_t* keep_idx, void* stream) {
-  VY_TRY(vy_check_kind(net, true, "vy_net_forward_infer_routes"));
+  VY_TRY(vy_serves(net, "vy_net_forward_infer_routes", VY_HEADS));
   return run_entry(net, f0 && f1 && f2 && ids && scores && bboxes, nullptr, stream, [&](hipStream_t s) {
     const float* const in[3] = {f0, f1, f2};
     VY_TRY(net->prepare(s, plain, false));
@@ -394,7 +342,7 @@ int vy_net_forward_infer_routes(vy_net* net, const float* f0, const float* f1, c
 int vy_net_forward_infer_bank(vy_net* net, const float* f0, const float* f1, const float* f2, int32_t n_frames,
                               const int32_t* table, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
                               void* stream) {
-  VY_TRY(vy_check_kind(net, VY_TAKES_BANK, "vy_net_forward_infer_bank"));
+  VY_TRY(vy_serves(net, "vy_net_forward_infer_bank", VY_HEADS_WINDOW));
   const BankRef bank{{f0, f1, f2}, n_frames, table};
   return run_entry(net, bank.ok() && ids && scores && bboxes, nullptr, stream, [&](hipStream_t s) {
     VY_TRY(vy_check_bank(net, "vy_net_forward_infer_bank", bank));
@@ -406,14 +354,6 @@ int vy_net_forward_infer_bank(vy_net* net, const float* f0, const float* f1, con
 }
 
 // ---- video plans
-// VY_ERR_STATE unless `net` is a window net: the video entries serve nothing else
-static int need_window(const vy_net* net, const char* entry) {
-  if (!net) return fail(VY_ERR_INVALID, "net is null");
-  if (!net->clip_net())
-    return fail(VY_ERR_STATE, "%s takes a window net (vy_net_create_window): this net has no temporal window", entry);
-  return 0;
-}
-
 static int check_video_shape(const vy_net* net, int32_t frames, int32_t clips, int32_t ring, int32_t h, int32_t w) {
   if (frames < 1 || clips < 1 || ring < 1)
     return fail(VY_ERR_INVALID, "video plan: frames %d, clips %d, ring %d must all be >= 1", frames, clips, ring);
@@ -426,14 +366,14 @@ static int check_video_shape(const vy_net* net, int32_t frames, int32_t clips, i
 
 size_t vy_net_video_workspace_bytes(const vy_net* net, int32_t frames, int32_t clips, int32_t ring, int32_t height,
                                     int32_t width) {
-  if (need_window(net, "vy_net_video_workspace_bytes") || check_video_shape(net, frames, clips, ring, height, width)) return 0;
+  if (vy_serves(net, "vy_net_video_workspace_bytes", VY_WINDOW) || check_video_shape(net, frames, clips, ring, height, width)) return 0;
   net->resolve_cus();
   return net->plan(clips, height, width, net->keep_activations, frames, ring).total;
 }
 
 int vy_net_bind_video(vy_net* net, void* dev_ws, size_t bytes, int32_t frames, int32_t clips, int32_t ring, int32_t height,
                       int32_t width, void* stream) {
-  VY_TRY(need_window(net, "vy_net_bind_video"));
+  VY_TRY(vy_serves(net, "vy_net_bind_video", VY_WINDOW));
   if (!dev_ws) return fail(VY_ERR_INVALID, "null argument");
   VY_TRY(check_video_shape(net, frames, clips, ring, height, width));
   return bind_plan(net, dev_ws, bytes, clips, height, width, frames, ring, "video ", stream);
@@ -448,7 +388,7 @@ static int check_slots(const vy_net* net, const char* entry, const int32_t* tabl
 }
 
 int vy_net_video_push(vy_net* net, const float* x, const int32_t* slots, void* stream) {
-  VY_TRY(need_window(net, "vy_net_video_push"));
+  VY_TRY(vy_serves(net, "vy_net_video_push", VY_WINDOW));
   return run_entry(net, x && slots, "vy_net_video_push", stream, [&](hipStream_t s) {
     VY_TRY(check_slots(net, "vy_net_video_push", slots, net->cur.video_F, -1));
     VY_TRY(net->prepare(s, plain, true));
@@ -459,7 +399,7 @@ int vy_net_video_push(vy_net* net, const float* x, const int32_t* slots, void* s
 
 int vy_net_video_detect(vy_net* net, const int32_t* table, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
                         void* stream) {
-  VY_TRY(need_window(net, "vy_net_video_detect"));
+  VY_TRY(vy_serves(net, "vy_net_video_detect", VY_WINDOW));
   return run_entry(net, table && ids && scores && bboxes, "vy_net_video_detect", stream, [&](hipStream_t s) {
     VY_TRY(check_slots(net, "vy_net_video_detect", table, net->cur.B * net->window_k, 0));
     VY_TRY(net->prepare(s, plain, false));
@@ -470,7 +410,7 @@ int vy_net_video_detect(vy_net* net, const int32_t* table, float* ids, float* sc
 }
 
 int vy_net_video_read_slot(vy_net* net, int32_t slot, float* f0, float* f1, float* f2, void* stream) {
-  VY_TRY(need_window(net, "vy_net_video_read_slot"));
+  VY_TRY(vy_serves(net, "vy_net_video_read_slot", VY_WINDOW));
   VY_TRY(entry_ready(net, f0 && f1 && f2, "vy_net_video_read_slot"));
   if (slot < 0 || slot >= net->cur.video_R) return fail(VY_ERR_INVALID, "slot %d outside [0, %d)", slot, net->cur.video_R);
   RingRoute rr[3];
@@ -512,47 +452,19 @@ int vy_net_read_activation(vy_net* net, const char* name, float* dst_dev, int32_
   if (dst_dev && net->cur.planes_shared)
     return fail(VY_ERR_STATE, "activation planes are recycled in this plan: call vy_net_set_keep_activations(net, 1) "
                 "before sizing / binding the workspace to read intermediate activations");
-  if (const int i = vy_hpool_tap(net, name); i >= 0) {
-    const vy_net::HierPool& hp = net->hpools[i];
-    const PlaneAt p = net->plane(hp.dst);
-    if (c) *c = hp.C;
-    if (h) *h = p.H;
-    if (w) *w = p.W;
-    if (dst_dev)
-      HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(hp.dst), net->plane_batch(hp.dst), p.H, p.W, p.C, hp.dst_co, hp.C, dst_dev,
-                                      static_cast<hipStream_t>(stream)));
-    return 0;
-  }
-  if (const int i = vy_pool_tap(net, name); i >= 0) {
-    const vy_net::RouteSlot& r = net->routes[i];
-    const PlaneAt p = net->plane(r.plane);
-    if (c) *c = r.C;
-    if (h) *h = p.H;
-    if (w) *w = p.W;
-    if (dst_dev)
-      HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(r.plane), net->cur.B, p.H, p.W, p.C, r.co, r.C, dst_dev,
-                                      static_cast<hipStream_t>(stream)));
-    return 0;
-  }
-  for (const ConvT& cv : net->convs) {
-    if (cv.name != name) continue;
-    const PlaneAt p = net->plane(cv.out_plane);
-    if (c) *c = cv.cout;
-    if (h) *h = p.H;
-    if (w) *w = p.W;
-    if (dst_dev)
-      HIP_TRY(vy_launch_plane_to_nchw(net->plane_ptr(cv.out_plane), net->plane_batch(cv.out_plane), p.H, p.W, p.C, cv.out_co,
-                                      cv.cout, dst_dev, static_cast<hipStream_t>(stream)));
-    return 0;
-  }
-  return fail(VY_ERR_INVALID, "no cell named '%s'", name);
+  TapRef t;
+  VY_TRY(vy_resolve_tap(net, name, &t));
+  if (c) *c = t.C;
+  if (h) *h = net->plane(t.plane).H;
+  if (w) *w = net->plane(t.plane).W;
+  if (dst_dev) HIP_TRY(vy_tap_to_nchw(net, t, nullptr, dst_dev, static_cast<hipStream_t>(stream)));
+  return 0;
 }
 
 int vy_net_profile_infer(vy_net* net, const float* x, float* ids, float* scores, float* bboxes,
                          vy_launch_stat* stats, int32_t* n, void* stream) {
-  if (int rc = vy_check_kind(net, false, "vy_net_profile_infer")) return rc;
-  if (int rc = refuse_window(net, "vy_net_profile_infer")) return rc;
-  if (!net || !stats || !n) return fail(VY_ERR_INVALID, "null argument");
+  VY_TRY(vy_serves(net, "vy_net_profile_infer", VY_FULL | VY_HIER));
+  if (!stats || !n) return fail(VY_ERR_INVALID, "null argument");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int cap = *n;
   std::vector<hipEvent_t> ev0, ev1;

@@ -12,22 +12,32 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/vyolo.h"
+#include "vy_support.h"
 #include "kernels.h"
 #include "../../include/vy_math.h"
 
-// error channel (defined in net.hip)
-int vy_fail(int code, const char* fmt, ...);
-#define fail vy_fail
-
-struct vy_net;
-// VY_ERR_STATE unless `net` is of the kind the entry point serves (defined in net.hip): a full net takes images (false /
-// VY_TAKES_IMAGES), a heads-only net its three routes (true / VY_TAKES_ROUTES), a windowed heads-only net a bank of
-// per-frame routes and a table (VY_TAKES_BANK)
-enum { VY_TAKES_IMAGES = 0, VY_TAKES_ROUTES = 1, VY_TAKES_BANK = 2 };
-int vy_check_kind(const vy_net* net, int takes, const char* entry);
 // VY_ERR_INVALID unless (batch, h, w) is a shape the planner takes (defined in net.hip)
 int vy_check_shape(int32_t batch, int32_t h, int32_t w);
+
+// The kind of a net (vy_net::kind), one bit each so that an entry point states the kinds it serves as a set (vy_serves)
+enum VyKind : unsigned {
+  VY_FULL = 1,           // vy_net_create: single frames
+  VY_HEADS = 2,          // vy_net_create_heads: the heads on the three routes of single frames
+  VY_WINDOW = 4,         // vy_net_create_window: clips of k frames, the routes pooled over each clip
+  VY_HEADS_WINDOW = 8,   // vy_net_create_heads_window: the heads on windows of a bank of per-frame routes
+  VY_HIER = 16,          // vy_net_create_hier: clips of 3^n frames pooled by threes inside the backbone
+};
+// OIHW (reference) <-> O,kh,kw,I (device): the host copy of a conv weight or of its gradient
+inline void pack_oihw(const float* src, float* dst, int O, int I, int k) {
+  for (int o = 0; o < O; ++o)
+    for (int i = 0; i < I; ++i)
+      for (int t = 0; t < k * k; ++t) dst[((size_t)o * k * k + t) * I + i] = src[((size_t)o * I + i) * k * k + t];
+}
+inline void unpack_oihw(const float* src, float* dst, int O, int I, int k) {
+  for (int o = 0; o < O; ++o)
+    for (int i = 0; i < I; ++i)
+      for (int t = 0; t < k * k; ++t) dst[((size_t)o * I + i) * k * k + t] = src[((size_t)o * k * k + t) * I + i];
+}
 
 // the inputs of a *_bank entry: three banks of per-frame routes (n_frames, C, h, w) and the (B, k) table of frames
 struct BankRef {
@@ -36,18 +46,6 @@ struct BankRef {
   const int32_t* table;
   bool ok() const { return f[0] && f[1] && f[2] && table; }
 };
-
-#define HIP_TRY(expr)                                                                  \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess) return fail(VY_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-// a step's error ends the sequence it is part of
-#define VY_TRY(expr)                 \
-  do {                               \
-    if (int rc_ = (expr)) return rc_; \
-  } while (0)
 
 // hook before, launch, hook after
 #define HOOKED(hook, name, fl, by, launch) \
@@ -227,6 +225,11 @@ struct vy_net {
     int f = 1;
     for (int i = 0; i < hier_n; ++i) f *= 3;
     return f;
+  }
+  // what the three fields above make of this net: the one place that says so (build() and the planner read the fields)
+  VyKind kind() const {
+    if (heads_only) return window_k ? VY_HEADS_WINDOW : VY_HEADS;
+    return window_k ? VY_WINDOW : hier_n ? VY_HIER : VY_FULL;
   }
   // one pool launch, forward (grads == nullptr) or backward (grads: the training gradient planes)
   HierPoolArgs hier_args(const HierPool& hp, float* grads) const {
@@ -1046,6 +1049,31 @@ struct vy_net {
   }
 };
 
+// ---- the first line of every entry point that serves some kinds of net and not others: `kinds` is the set it serves.
+// VY_ERR_STATE for a net of another kind (VY_ERR_INVALID for none), before any argument is looked at
+inline int vy_serves(const vy_net* net, const char* entry, unsigned kinds) {
+  static const struct {
+    const char *name, *is;
+  } k[5] = {{"full", "a full net (vy_net_create), which the entry points that take an image batch serve"},
+            {"heads-only", "a heads-only net (vy_net_create_heads), which the *_routes entry points serve"},
+            {"window", "a window net (vy_net_create_window), which vy_net_forward_infer, vy_net_train_*forward / _backward and "
+                       "vy_net_video_* serve"},
+            {"windowed heads-only", "a windowed heads-only net (vy_net_create_heads_window), which the *_bank entry points and "
+                                    "vy_net_train_backward_routes serve"},
+            {"hierarchical", "a hierarchical net (vy_net_create_hier), which vy_net_forward_infer, vy_net_profile_infer and "
+                             "vy_net_train_*forward / _backward serve"}};
+  if (!net) return fail(VY_ERR_INVALID, "%s: net is null", entry);
+  const unsigned kind = net->kind();
+  if (kind & kinds) return 0;
+  std::string served;
+  const char* is = "";
+  for (int i = 0; i < 5; ++i) {
+    if (kinds & (1u << i)) served += (served.empty() ? "" : " / ") + std::string(k[i].name);
+    if (kind == (1u << i)) is = k[i].is;
+  }
+  return fail(VY_ERR_STATE, "%s serves a %s net: this is %s", entry, served.c_str(), is);
+}
+
 // ---- the frame of every entry point that launches a sequence of steps, inference (net.hip) and training (train.hip)
 // The frame's checks, before anything is launched: arguments, bound, and for a video entry (named) bound for video
 inline int entry_ready(vy_net* net, bool args_ok, const char* video_entry) {
@@ -1081,14 +1109,40 @@ inline int vy_check_bank(const vy_net* net, const char* entry, const BankRef& ba
   return 0;
 }
 
-// the pooled plane `name` = "hpool.<i>" of a hierarchical net (the taps): its index, or -1
-inline int vy_hpool_tap(const vy_net* net, const char* name) {
-  if (strncmp(name, "hpool.", 6) != 0 || name[6] < '0' || name[6] >= '0' + net->hier_n || name[7]) return -1;
-  return name[6] - '0';
+// ---- what a tap name means, for every entry that takes one (vy_net_tap_frames, vy_net_read_activation; train.hip:
+// vy_net_read_grad_activation, vy_net_read_train_tap): channels [co, co + C) of `plane`.  A cell's name is its output
+// (conv: its index); "hpool.<i>" the plane pool i of a hierarchical net writes (hpool: i); "pool.<i>" pooled route i of
+// either window kind.  The frames the tap holds are the plane's, whatever it names: planes[plane].fm per batch entry,
+// plane_batch(plane) in the bound plan
+struct TapRef {
+  int plane, co, C;
+  int conv, hpool;  // -1: not a cell / not a pooled plane of a hierarchical net
+};
+// VY_ERR_INVALID if the net has no such tap
+inline int vy_resolve_tap(const vy_net* net, const char* name, TapRef* t) {
+  auto index = [name](const char* prefix, int n) {  // name = prefix + one digit below n: the digit, else -1
+    const size_t len = strlen(prefix);
+    return strncmp(name, prefix, len) == 0 && name[len] >= '0' && name[len] < '0' + n && !name[len + 1] ? name[len] - '0' : -1;
+  };
+  if (const int i = index("hpool.", net->hier_n); i >= 0) {
+    const vy_net::HierPool& hp = net->hpools[i];
+    *t = {hp.dst, hp.dst_co, hp.C, -1, i};
+    return 0;
+  }
+  if (const int i = index("pool.", net->window_k ? 3 : 0); i >= 0) {
+    *t = {net->routes[i].plane, net->routes[i].co, net->routes[i].C, -1, -1};
+    return 0;
+  }
+  for (int ci = 0; ci < (int)net->convs.size(); ++ci)
+    if (const ConvT& cv = net->convs[ci]; cv.name == name) {
+      *t = {cv.out_plane, cv.out_co, cv.cout, ci, -1};
+      return 0;
+    }
+  return fail(VY_ERR_INVALID, "no cell named '%s'", name);
 }
-
-// the pooled route `name` = "pool.<i>" of a window net (the taps of vy_net_read_activation / read_grad_activation): 0..2, or -1
-inline int vy_pool_tap(const vy_net* net, const char* name) {
-  if (!net->window_k || strncmp(name, "pool.", 5) != 0 || name[5] < '0' || name[5] > '2' || name[6]) return -1;
-  return name[5] - '0';
+// the tap, out of the activation planes or (`grads`: their base, same offsets) the gradient planes, as dense NCHW
+inline hipError_t vy_tap_to_nchw(const vy_net* net, const TapRef& t, float* grads, float* dst_dev, hipStream_t s) {
+  const PlaneAt p = net->plane(t.plane);
+  return vy_launch_plane_to_nchw(grads ? grads + p.off : net->plane_ptr(t.plane), net->plane_batch(t.plane), p.H, p.W, p.C,
+                                 t.co, t.C, dst_dev, s);
 }

@@ -9,7 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/vyolo.h"
-#include "net_internal.h"
+#include "vy_support.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -24,7 +24,7 @@
 
 #include "../../include/vy_math.h"
 #include "../../include/vyolo.h"
-#include "net_internal.h"
+#include "vy_support.h"
 
 namespace {
 

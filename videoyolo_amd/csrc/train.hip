@@ -1069,7 +1069,7 @@ int vy_net_set_train_options(vy_net* net, float ignore_iou_thresh, int32_t label
 int vy_net_train_forward(vy_net* net, const float* x, const float* gt_boxes, int32_t M, const float* obj_t,
                          const float* centers_t, const float* scales_t, const float* weights_t,
                          const float* clas_t, float* losses, void* stream) {
-  VY_TRY(vy_check_kind(net, false, "vy_net_train_forward"));
+  VY_TRY(vy_serves(net, "vy_net_train_forward", VY_FULL | VY_WINDOW | VY_HIER));
 #ifdef VY_TRAIN_ABL_BUILD
   ++g_abl_forwards;
 #endif
@@ -1080,7 +1080,7 @@ int vy_net_train_forward(vy_net* net, const float* x, const float* gt_boxes, int
 int vy_net_train_forward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, const float* gt_boxes,
                                 int32_t M, const float* obj_t, const float* centers_t, const float* scales_t,
                                 const float* weights_t, const float* clas_t, float* losses, void* stream) {
-  VY_TRY(vy_check_kind(net, true, "vy_net_train_forward_routes"));
+  VY_TRY(vy_serves(net, "vy_net_train_forward_routes", VY_HEADS));
   const float* const routes[3] = {f0, f1, f2};
   const LossInputs in{gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t, M, losses};
   return run_entry(net, f0 && f1 && f2 && in.ok(), nullptr, stream,
@@ -1089,14 +1089,14 @@ int vy_net_train_forward_routes(vy_net* net, const float* f0, const float* f1, c
 
 int vy_net_train_mode_forward(vy_net* net, const float* x, float* box_preds, float* centers, float* scales,
                               float* objness, float* class_pred, void* stream) {
-  VY_TRY(vy_check_kind(net, false, "vy_net_train_mode_forward"));
+  VY_TRY(vy_serves(net, "vy_net_train_mode_forward", VY_FULL | VY_WINDOW | VY_HIER));
   const RawOutputs out{box_preds, centers, scales, objness, class_pred};
   return run_entry(net, x && out.ok(), nullptr, stream, [&](hipStream_t s) { return train_mode_forward(net, x, nullptr, out, s); });
 }
 
 int vy_net_train_mode_forward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, float* box_preds,
                                      float* centers, float* scales, float* objness, float* class_pred, void* stream) {
-  VY_TRY(vy_check_kind(net, true, "vy_net_train_mode_forward_routes"));
+  VY_TRY(vy_serves(net, "vy_net_train_mode_forward_routes", VY_HEADS));
   const float* const routes[3] = {f0, f1, f2};
   const RawOutputs out{box_preds, centers, scales, objness, class_pred};
   return run_entry(net, f0 && f1 && f2 && out.ok(), nullptr, stream,
@@ -1107,7 +1107,7 @@ int vy_net_train_forward_bank(vy_net* net, const float* f0, const float* f1, con
                               const int32_t* table, const float* gt_boxes, int32_t M, const float* obj_t,
                               const float* centers_t, const float* scales_t, const float* weights_t, const float* clas_t,
                               float* losses, void* stream) {
-  VY_TRY(vy_check_kind(net, VY_TAKES_BANK, "vy_net_train_forward_bank"));
+  VY_TRY(vy_serves(net, "vy_net_train_forward_bank", VY_HEADS_WINDOW));
   const BankRef bank{{f0, f1, f2}, n_frames, table};
   const LossInputs in{gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t, M, losses};
   return run_entry(net, bank.ok() && in.ok(), nullptr, stream, [&](hipStream_t s) {
@@ -1119,7 +1119,7 @@ int vy_net_train_forward_bank(vy_net* net, const float* f0, const float* f1, con
 int vy_net_train_mode_forward_bank(vy_net* net, const float* f0, const float* f1, const float* f2, int32_t n_frames,
                                    const int32_t* table, float* box_preds, float* centers, float* scales, float* objness,
                                    float* class_pred, void* stream) {
-  VY_TRY(vy_check_kind(net, VY_TAKES_BANK, "vy_net_train_mode_forward_bank"));
+  VY_TRY(vy_serves(net, "vy_net_train_mode_forward_bank", VY_HEADS_WINDOW));
   const BankRef bank{{f0, f1, f2}, n_frames, table};
   const RawOutputs out{box_preds, centers, scales, objness, class_pred};
   return run_entry(net, bank.ok() && out.ok(), nullptr, stream, [&](hipStream_t s) {
@@ -1129,16 +1129,16 @@ int vy_net_train_mode_forward_bank(vy_net* net, const float* f0, const float* f1
 }
 
 int vy_net_train_backward(vy_net* net, const float* x, void* stream) {
-  VY_TRY(vy_check_kind(net, false, "vy_net_train_backward"));
+  VY_TRY(vy_serves(net, "vy_net_train_backward", VY_FULL | VY_WINDOW | VY_HIER));
   return run_entry(net, x != nullptr, nullptr, stream, [&](hipStream_t s) { return train_backward(net, x, s); });
 }
 
 int vy_net_train_backward_routes(vy_net* net, const float* f0, const float* f1, const float* f2, void* stream) {
   // (nothing is read from the routes: see data_grad — so a windowed heads-only net, whose forward read a bank, is served
   // too, and may pass NULL)
-  const bool windowed = net && net->heads_only && net->window_k;
-  if (!windowed) VY_TRY(vy_check_kind(net, VY_TAKES_ROUTES, "vy_net_train_backward_routes"));
-  return run_entry(net, windowed || (f0 && f1 && f2), nullptr, stream, [&](hipStream_t s) { return train_backward(net, nullptr, s); });
+  VY_TRY(vy_serves(net, "vy_net_train_backward_routes", VY_HEADS | VY_HEADS_WINDOW));
+  return run_entry(net, net->kind() == VY_HEADS_WINDOW || (f0 && f1 && f2), nullptr, stream,
+                   [&](hipStream_t s) { return train_backward(net, nullptr, s); });
 }
 
 int vy_net_param_set_opt(vy_net* net, int32_t i, float lr_mult, float wd_mult, int32_t enabled) {
@@ -1190,10 +1190,7 @@ int vy_net_grad_get(vy_net* net, int32_t i, float* host_dst, void* stream) {
   HIP_TRY(hipMemcpyAsync(tmp.data(), net->train->grads + pi.offset, sizeof(float) * pi.size, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (pi.ndim == 4) {
-    const int O = pi.shape[0], I = pi.shape[1], kk = pi.shape[2] * pi.shape[3];
-    for (int o = 0; o < O; ++o)
-      for (int ii = 0; ii < I; ++ii)
-        for (int tt = 0; tt < kk; ++tt) host_dst[((size_t)o * I + ii) * kk + tt] = tmp[((size_t)o * kk + tt) * I + ii];
+    unpack_oihw(tmp.data(), host_dst, pi.shape[0], pi.shape[1], pi.shape[2]);
   } else {
     memcpy(host_dst, tmp.data(), sizeof(float) * pi.size);
   }
@@ -1205,26 +1202,10 @@ int vy_net_read_grad_activation(vy_net* net, const char* name, float* dst_dev, v
   VY_TRY(net->check_ready());
   VY_TRY(bound_train(net, false, ""));
   TrainCtx c(net, stream);
-  if (const int i = vy_hpool_tap(net, name); i >= 0) {
-    const vy_net::HierPool& hp = net->hpools[i];
-    const PlaneAt p = net->plane(hp.dst);
-    HIP_TRY(vy_launch_plane_to_nchw(c.gplane(hp.dst), net->plane_batch(hp.dst), p.H, p.W, p.C, hp.dst_co, hp.C, dst_dev, c.s));
-    return 0;
-  }
-  if (const int i = vy_pool_tap(net, name); i >= 0) {
-    const vy_net::RouteSlot& r = net->routes[i];
-    const PlaneAt p = net->plane(r.plane);
-    HIP_TRY(vy_launch_plane_to_nchw(c.gplane(r.plane), net->cur.B, p.H, p.W, p.C, r.co, r.C, dst_dev, c.s));
-    return 0;
-  }
-  for (const ConvT& cv : net->convs) {
-    if (cv.name != name) continue;
-    const PlaneAt p = net->plane(cv.out_plane);
-    HIP_TRY(vy_launch_plane_to_nchw(c.gplane(cv.out_plane), net->plane_batch(cv.out_plane), p.H, p.W, p.C, cv.out_co,
-                                    cv.cout, dst_dev, c.s));
-    return 0;
-  }
-  return fail(VY_ERR_INVALID, "no cell named '%s'", name);
+  TapRef t;
+  VY_TRY(vy_resolve_tap(net, name, &t));
+  HIP_TRY(vy_tap_to_nchw(net, t, c.gplanes(), dst_dev, c.s));
+  return 0;
 }
 
 int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* dst_dev, int32_t* dims, void* stream) {
@@ -1232,8 +1213,10 @@ int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* d
   VY_TRY(net->check_ready());
   VY_TRY(bound_train(net, false, ""));
   TrainCtx c(net, stream);
-  if (const int i = vy_hpool_tap(net, name); i >= 0) {  // a pooled plane: its gradient, or the pre-pool plane it was made of
-    const vy_net::HierPool& hp = net->hpools[i];
+  TapRef t;
+  VY_TRY(vy_resolve_tap(net, name, &t));
+  if (t.hpool >= 0) {  // a pooled plane: its gradient, or the pre-pool plane it was made of
+    const vy_net::HierPool& hp = net->hpools[t.hpool];
     if (which != VY_TAP_GRAD_PADDED && which != VY_TAP_INPUT_PADDED)
       return fail(VY_ERR_INVALID, "'%s' has the taps VY_TAP_GRAD_PADDED and VY_TAP_INPUT_PADDED only", name);
     const bool grad = which == VY_TAP_GRAD_PADDED;
@@ -1246,63 +1229,61 @@ int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* d
                                              hp.C, dst_dev, c.s));
     return 0;
   }
-  for (int ci = 0; ci < (int)net->convs.size(); ++ci) {
-    const ConvT& cv = net->convs[ci];
-    if (cv.name != name) continue;
-    const TrainCell& cell = c.cell(ci);
-    const bool bn = cv.p_gamma >= 0;
-    int32_t d[4] = {net->conv_batch(cv), cv.cout, 0, 0};
-    const float* src = nullptr;
-    int cs = 0, co = 0;
-    switch (which) {
-      case VY_TAP_Z:
-        if (!bn) return fail(VY_ERR_INVALID, "'%s' has no z plane", name);
-        src = c.zplane(ci);
-        d[2] = cell.Ho + 2;
-        d[3] = cell.Wo + 2;
-        cs = cell.z_cs;
-        break;
-      case VY_TAP_BN:
-        if (!bn) return fail(VY_ERR_INVALID, "'%s' has no BatchNorm", name);
-        d[0] = 4;
-        d[2] = d[3] = 1;
-        break;
-      case VY_TAP_GRAD_PADDED: {
-        const PlaneAt p = net->plane(cv.out_plane);
-        src = c.gplane(cv.out_plane);
-        d[2] = p.H + 2;
-        d[3] = p.W + 2;
-        cs = p.C;
-        co = cv.out_co;
-        break;
-      }
-      case VY_TAP_INPUT_PADDED: {
-        if (cv.is_stem) return fail(VY_ERR_INVALID, "the stem reads the image, not a plane");
-        const PlaneAt p = net->plane(cv.in_plane);
-        src = net->plane_ptr(cv.in_plane);
-        d[1] = cv.cin;
-        d[2] = p.H + 2;
-        d[3] = p.W + 2;
-        cs = p.C;
-        co = cv.in_co;
-        break;
-      }
-      default:
-        return fail(VY_ERR_INVALID, "unknown tap %d", which);
+  if (t.conv < 0) return fail(VY_ERR_INVALID, "no cell named '%s'", name);  // (a pooled route: vy_net_read_grad_activation reads it)
+  const int ci = t.conv;
+  const ConvT& cv = net->convs[ci];
+  const TrainCell& cell = c.cell(ci);
+  const bool bn = cv.p_gamma >= 0;
+  int32_t d[4] = {net->conv_batch(cv), cv.cout, 0, 0};
+  const float* src = nullptr;
+  int cs = 0, co = 0;
+  switch (which) {
+    case VY_TAP_Z:
+      if (!bn) return fail(VY_ERR_INVALID, "'%s' has no z plane", name);
+      src = c.zplane(ci);
+      d[2] = cell.Ho + 2;
+      d[3] = cell.Wo + 2;
+      cs = cell.z_cs;
+      break;
+    case VY_TAP_BN:
+      if (!bn) return fail(VY_ERR_INVALID, "'%s' has no BatchNorm", name);
+      d[0] = 4;
+      d[2] = d[3] = 1;
+      break;
+    case VY_TAP_GRAD_PADDED: {
+      const PlaneAt p = net->plane(cv.out_plane);
+      src = c.gplane(cv.out_plane);
+      d[2] = p.H + 2;
+      d[3] = p.W + 2;
+      cs = p.C;
+      co = cv.out_co;
+      break;
     }
-    if (dims) memcpy(dims, d, sizeof d);
-    if (!dst_dev) return 0;
-    if (which == VY_TAP_BN) {
-      const BnViews v = c.bn_views(ci);
-      const float* rows[4] = {v.save_mean, v.save_invstd, v.scale, v.shift};
-      for (int r = 0; r < 4; ++r)
-        HIP_TRY(hipMemcpyAsync(dst_dev + (size_t)r * cv.cout, rows[r], sizeof(float) * cv.cout, hipMemcpyDeviceToDevice, c.s));
-      return 0;
+    case VY_TAP_INPUT_PADDED: {
+      if (cv.is_stem) return fail(VY_ERR_INVALID, "the stem reads the image, not a plane");
+      const PlaneAt p = net->plane(cv.in_plane);
+      src = net->plane_ptr(cv.in_plane);
+      d[1] = cv.cin;
+      d[2] = p.H + 2;
+      d[3] = p.W + 2;
+      cs = p.C;
+      co = cv.in_co;
+      break;
     }
-    HIP_TRY(vy_launch_padded_plane_to_nchw(src, d[0], d[2], d[3], cs, co, d[1], dst_dev, c.s));
+    default:
+      return fail(VY_ERR_INVALID, "unknown tap %d", which);
+  }
+  if (dims) memcpy(dims, d, sizeof d);
+  if (!dst_dev) return 0;
+  if (which == VY_TAP_BN) {
+    const BnViews v = c.bn_views(ci);
+    const float* rows[4] = {v.save_mean, v.save_invstd, v.scale, v.shift};
+    for (int r = 0; r < 4; ++r)
+      HIP_TRY(hipMemcpyAsync(dst_dev + (size_t)r * cv.cout, rows[r], sizeof(float) * cv.cout, hipMemcpyDeviceToDevice, c.s));
     return 0;
   }
-  return fail(VY_ERR_INVALID, "no cell named '%s'", name);
+  HIP_TRY(vy_launch_padded_plane_to_nchw(src, d[0], d[2], d[3], cs, co, d[1], dst_dev, c.s));
+  return 0;
 }
 
 int vy_net_train_conv_plan(const vy_net* net, int32_t i, int32_t* wgrad_splits, int32_t* wgrad_k_per_split,

@@ -17,9 +17,11 @@
 // correctly rounded, so every value equals numpy's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
-#include "../../include/vyolo.h"
-#include "net_internal.h"
+#include <algorithm>
+
+#include "vy_support.h"
 
 namespace {
 

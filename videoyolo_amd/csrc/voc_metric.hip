@@ -20,7 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/vyolo.h"
-#include "net_internal.h"
+#include "vy_support.h"
 
 namespace {
 

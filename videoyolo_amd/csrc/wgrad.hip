@@ -16,31 +16,13 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "conv_device.h"  // f32x16, LDS_PTR, lds_dma16_s, wgrad_pixel_offsets
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-// LDS-DMA as inline asm (see conv_igemm.hip: keeps hipcc from serialising it against the ds_reads);
-// ordered by hand: s_waitcnt vmcnt(0) before the barrier that precedes the first read of the tile.
-__device__ __forceinline__ void lds_dma16(const float* gptr, unsigned lds_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gptr), "s"(lds_addr) : "memory", "m0");
-#endif
-}
-
-// the same through a wave-uniform base (SGPR pair) + a per-lane 32-bit byte offset (see conv_igemm.hip)
-__device__ __forceinline__ void lds_dma16_s(unsigned voff, const float* sbase, unsigned lds_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_addr)
-               : "memory", "m0");
-#endif
-}
-
 // Pixel table of one conv (built once per plan by wgrad_table_kernel): for output pixel p the byte offset of its dz
-// vector inside the dz plane and of its (stride-scaled) centre pixel inside the input plane, shifted by one row and
-// one column so that every tap offset is non-negative.  Entries M .. pad are "dead" pixels: a zero border pixel of
+// vector inside the dz plane and of its (stride-scaled) centre pixel inside the input plane (wgrad_pixel_offsets), shifted
+// by one row and one column so that every tap offset is non-negative.  Entries M .. pad are "dead" pixels: a zero border pixel of
 // the dz plane (contributes 0 to every sum) and a valid input pixel.  With it the k-loop needs no coordinates at all:
 // the fp32 MFMA shares the vector pipe (tools/probe/coissue_probe.hip), and the incremental per-lane coordinates of
 // round 1 cost 92 vector instructions per 64 MFMAs.
@@ -49,16 +31,6 @@ __device__ __forceinline__ void lds_dma16_s(unsigned voff, const float* sbase, u
 // 4 GiB): the planes themselves may be of any size.  The kernel adds the split's base — wgrad_split_base, the same
 // formulas — to its wave-uniform DMA base once per block.  Dead entries point at the bottom-left border pixel of the LAST
 // image (zero, and behind every valid pixel) and at the last valid input pixel.
-struct WgradPix {
-  unsigned long long zo, ao;
-};
-__device__ __forceinline__ WgradPix wgrad_pixel_offsets(int p, int Ho, int Wo, int z_cs, int a_Hp, int a_Wp, int a_cs, int stride) {
-  const int x = p % Wo, t = p / Wo, y = t % Ho, b = t / Ho;
-  WgradPix o;
-  o.zo = ((unsigned long long)(b * (Ho + 2) + y + 1) * (Wo + 2) + x + 1) * z_cs * 4ull;
-  o.ao = ((unsigned long long)(b * a_Hp + y * stride + 1) * a_Wp + x * stride + 1) * a_cs * 4ull;
-  return o;
-}
 
 __global__ __launch_bounds__(256) void wgrad_table_kernel(uint2* __restrict__ tab, int M, int n_entries, int Ho, int Wo,
                                                           int z_cs, int a_Hp, int a_Wp, int a_cs, int stride, int B,

@@ -19,39 +19,25 @@
 #include <cstdlib>
 
 #include "kernels.h"
-#include "conv_device.h"
+#include "split_device.h"  // cvt_pk_bf16
 
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef __bf16 ws_bf16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ unsigned ws_cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
+// split8 (split_device.h) with scalar differences: the instruction stream this kernel was measured with
 __device__ __forceinline__ void ws_split8(const f32x4 v0, const f32x4 v1, vy_u32x4& H, vy_u32x4& M, vy_u32x4& L) {
   const float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const float x0 = x[2 * j], x1 = x[2 * j + 1];
-    const unsigned h = ws_cvt_pk_bf16(x0, x1);
+    const unsigned h = cvt_pk_bf16(x0, x1);
     const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    const unsigned m = ws_cvt_pk_bf16(r0, r1);
+    const unsigned m = cvt_pk_bf16(r0, r1);
     const float l0 = r0 - __builtin_bit_cast(float, m << 16), l1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
     H[j] = h;
     M[j] = m;
-    L[j] = ws_cvt_pk_bf16(l0, l1);
+    L[j] = cvt_pk_bf16(l0, l1);
   }
-}
-struct WsPix {
-  unsigned long long zo, ao;
-};
-__device__ __forceinline__ WsPix ws_pixel_offsets(int p, int Ho, int Wo, int z_cs, int a_Hp, int a_Wp, int a_cs, int stride) {
-  const int x = p % Wo, t = p / Wo, y = t % Ho, b = t / Ho;
-  WsPix o;
-  o.zo = ((unsigned long long)(b * (Ho + 2) + y + 1) * (Wo + 2) + x + 1) * z_cs * 4ull;
-  o.ao = ((unsigned long long)(b * a_Hp + y * stride + 1) * a_Wp + x * stride + 1) * a_cs * 4ull;
-  return o;
 }
 #endif
 
@@ -91,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a, 
   const int cin = b_ok ? bn - tap * a.Cin : 0;
   const int pad = a.k >> 1;
   const int dy = a.k == 3 ? tap / 3 - pad : 0, dx = a.k == 3 ? tap % 3 - pad : 0;
-  const WsPix sb = ws_pixel_offsets(p_begin, a.Ho, a.Wo, a.z_cs, a.a_Hp, a.a_Wp, a.a_cs, a.stride);
+  const WgradPix sb = wgrad_pixel_offsets(p_begin, a.Ho, a.Wo, a.z_cs, a.a_Hp, a.a_Wp, a.a_cs, a.stride);
   const unsigned char* z_base = reinterpret_cast<const unsigned char*>(a.dz) + sb.zo + (long long)oc * 4;
   const unsigned char* a_base = reinterpret_cast<const unsigned char*>(a.a) + sb.ao +
                                 ((long long)a.a_co + (long long)(dy * a.a_Wp + dx) * a.a_cs + cin) * 4;

@@ -191,8 +191,10 @@ class YOLOV3(object):
         return x.shape[0], x.shape[2], x.shape[3]
 
     def _tap_batch(self, name):
-        """Leading dimension of the tap of cell `name` in the bound plan."""
-        return self._plan[0]
+        """Leading dimension of tap `name` in the bound plan: the library's frames per batch entry, whatever the net."""
+        fm = ctypes.c_int32(0)
+        _lib.check(self._lib.vy_net_tap_frames(self._h, name.encode(), ctypes.byref(fm)))
+        return self._plan[0] * fm.value
 
     @staticmethod
     def _key(name):
@@ -1009,10 +1011,10 @@ class YOLOV3(object):
 
     def profile(self, x):
         """One timed forward: list of (launch name, ms, flops, bytes) from HIP events around every
-        kernel launch on the current stream."""
+        kernel launch on the current stream (a hierarchical net: the pools are the launches ``hpool.<i>``)."""
         torch = _torch()
         x = self._as_input(x)
-        b, _, h, w = x.shape
+        b, h, w = self._bhw(x)
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w)
             outs = self._detect_outputs(b, self._out_rows(), keep=False)
@@ -1150,9 +1152,6 @@ class YOLOV3Window(YOLOV3):
     def _bhw(self, x):
         return x.shape[0], x.shape[3], x.shape[4]
 
-    def _tap_batch(self, name):
-        return self._plan[0] * (self._k if name.startswith("stages.") else 1)
-
     def set_parameters(self, arrays, allow_missing=False, ignore_extra=False):
         """As ``YOLOV3.set_parameters``; stage keys may also come in the single-frame form (``stages.N.<rest>``)."""
         super().set_parameters(OrderedDict((self._key(k), v) for k, v in arrays.items()), allow_missing=allow_missing,
@@ -1269,11 +1268,6 @@ class YOLOV3Hier(YOLOV3):
     def _bhw(self, x):
         return x.shape[0], x.shape[3], x.shape[4]
 
-    def _tap_batch(self, name):
-        fm = ctypes.c_int32(0)
-        _lib.check(self._lib.vy_net_tap_frames(self._h, name.encode(), ctypes.byref(fm)))
-        return self._plan[0] * fm.value
-
     def set_parameters(self, arrays, allow_missing=False, ignore_extra=False):
         """As ``YOLOV3.set_parameters``; backbone keys may also come as ``d_model.features.N.<rest>``."""
         super().set_parameters(OrderedDict((self._key(k), v) for k, v in arrays.items()), allow_missing=allow_missing,
@@ -1293,22 +1287,6 @@ class YOLOV3Hier(YOLOV3):
         if mode != "exact":
             raise NotImplementedError("conv mode %r: a hierarchical net runs the exact fp32 kernels only" % (mode,))
         super().set_conv_mode(mode)
-
-    def profile(self, x):
-        """As ``YOLOV3.profile``, for a ``(B, T, 3, H, W)`` batch of clips; the pools are the launches ``hpool.<i>``."""
-        torch = _torch()
-        x = self._as_input(x)
-        b, h, w = self._bhw(x)
-        with torch.cuda.device(self._device):
-            self._ensure_plan(b, h, w)
-            outs = self._detect_outputs(b, self._out_rows(), keep=False)
-            cap = 256
-            stats = (_lib.LaunchStat * cap)()
-            n = ctypes.c_int32(cap)
-            _lib.check(self._lib.vy_net_profile_infer(self._h, *_ptrs((x,) + outs[:3]), stats, ctypes.byref(n),
-                                                      self._stream()))
-        return [(stats[i].name.decode(), float(stats[i].ms), float(stats[i].flops), float(stats[i].bytes))
-                for i in range(n.value)]
 
     def _not_hierarchical(self, *args, **kwargs):
         raise NotImplementedError("not available on a hierarchical net (yolo3_darknet53 with hierarchical=...): use a "
