@@ -376,7 +376,10 @@ int vy_stream_destroy(void* stream);
 /* Frame pre-processing in front of the path: (batch,H,W,3) uint8 HWC device
  * frames -> (batch,3,H,W) fp32 NCHW, y = (x/255 - mean[c]) / std[c] — mx.nd.image.to_tensor +
  * mx.nd.image.normalize at models/definitions/yolo/transforms.py:331-334.  mean3/std3 are host
- * pointers to 3 floats.  Frames that are not at the network size yet: vy_preprocess_resize_frames below. */
+ * pointers to 3 floats.  Any height, width >= 1 and any byte address of frames_hwc are accepted: where
+ * height*width is a multiple of 4, frames_hwc is 4-byte and out_nchw 16-byte aligned, a thread converts 4
+ * pixels with 32-bit loads; otherwise a thread converts one pixel with byte loads, the same arithmetic per value.
+ * Frames that are not at the network size yet: vy_preprocess_resize_frames below. */
 int vy_preprocess_frames(const uint8_t* frames_hwc, float* out_nchw, int32_t batch, int32_t height,
                          int32_t width, const float* mean3, const float* std3, void* stream);
 
@@ -387,7 +390,9 @@ int vy_preprocess_frames(const uint8_t* frames_hwc, float* out_nchw, int32_t bat
  * [UPSTREAM-RECALLED: gluoncv, mxnet and OpenCV are not available here; oracle/resize_oracle.py states the
  * arithmetic and tests/test_resize_oracle.py cross-checks it against torch / exact area definitions]) -> the
  * uint8 value the reference's resized NDArray would hold -> to_tensor + normalize -> (batch,3,height,width)
- * fp32 NCHW.  The resized frame itself is never materialised.  Area shrink factors above 10 are rejected. */
+ * fp32 NCHW.  The resized frame itself is never materialised.  Fractional area shrink factors above 10 on
+ * either axis are rejected; integer factors on both axes are block means of any size.  Frames already at
+ * (height, width) are copied (cv::resize to the same size), at any size: vy_preprocess_frames. */
 int vy_preprocess_resize_frames(const uint8_t* frames_hwc, int32_t src_height, int32_t src_width, float* out_nchw,
                                 int32_t batch, int32_t height, int32_t width, const float* mean3, const float* std3,
                                 void* stream);

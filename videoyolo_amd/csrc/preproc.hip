@@ -3,7 +3,9 @@
 // models/definitions/yolo/transforms.py:331-334 (to_tensor: HWC uint8 -> CHW float32 / 255;
 // normalize: (x - mean[c]) / std[c], mean (0.485,0.456,0.406), std (0.229,0.224,0.225)).
 // HBM-bound byte work: each thread converts 4 consecutive pixels (12 input bytes, read as three
-// 32-bit words; three float4 stores, one per channel plane).
+// 32-bit words; three float4 stores, one per channel plane).  That needs H*W % 4 == 0 (a group stays in one
+// image and every plane offset is 16-byte aligned) and a 4-byte aligned source; any other size or pointer
+// takes the scalar kernel below it: one thread per pixel, byte loads, the same arithmetic per value.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -38,6 +40,18 @@ __global__ __launch_bounds__(256) void to_tensor_normalize_kernel(const uint8_t*
     for (int i = 0; i < 4; ++i) o[i] = ((float)px[i * 3 + c] / 255.0f - mean[c]) / stdv[c];
     *reinterpret_cast<f32x4*>(dst + (b * 3 + c) * hw + r) = o;
   }
+}
+
+__global__ __launch_bounds__(256) void to_tensor_normalize_scalar_kernel(const uint8_t* __restrict__ src,
+                                                                         float* __restrict__ dst, long long npix,
+                                                                         long long hw, float m0, float m1, float m2,
+                                                                         float s0, float s1, float s2) {
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;  // pixel, global over B*H*W
+  if (p >= npix) return;
+  const long long b = p / hw, r = p - b * hw;
+  const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * hw + r] = ((float)src[p * 3 + c] / 255.0f - mean[c]) / stdv[c];
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -264,11 +278,17 @@ extern "C" int vy_preprocess_frames(const uint8_t* frames_hwc, float* out_nchw, 
   if (!frames_hwc || !out_nchw || !mean3 || !std3 || batch < 1 || height < 1 || width < 1)
     return fail(VY_ERR_INVALID, "bad argument");
   const long long hw = (long long)height * width;
-  if (hw % 4) return fail(VY_ERR_INVALID, "height*width must be a multiple of 4");
-  const long long n4 = (long long)batch * hw / 4;
-  hipLaunchKernelGGL(to_tensor_normalize_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), frames_hwc, out_nchw, n4, hw, mean3[0], mean3[1], mean3[2],
-                     std3[0], std3[1], std3[2]);
+  if (hw % 4 == 0 && reinterpret_cast<uintptr_t>(frames_hwc) % 4 == 0 && reinterpret_cast<uintptr_t>(out_nchw) % 16 == 0) {
+    const long long n4 = (long long)batch * hw / 4;
+    hipLaunchKernelGGL(to_tensor_normalize_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), frames_hwc, out_nchw, n4, hw, mean3[0], mean3[1], mean3[2],
+                       std3[0], std3[1], std3[2]);
+  } else {  // a 4-pixel group would straddle two images, or its 32-bit loads / 16-byte stores would be misaligned
+    const long long n = (long long)batch * hw;
+    hipLaunchKernelGGL(to_tensor_normalize_scalar_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), frames_hwc, out_nchw, n, hw, mean3[0], mean3[1], mean3[2],
+                       std3[0], std3[1], std3[2]);
+  }
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -38,13 +38,15 @@ def _torch():
 class HostFedDetector(object):
     """net: a ``yolo3_darknet53`` object on its device.  ``global_batch`` frames of ``src_hw`` uint8 pixels arrive per
     step (the same clip batch on every rank — a shared decoder / file; a rank touches only its slice), are resized to
-    ``size`` and detected; ``gather`` brings every rank's rows to all ranks (rank 0 copies them to the host)."""
+    ``size`` (one int for a square input, or (height, width)) and detected; ``gather`` brings every rank's rows to all
+    ranks (rank 0 copies them to the host)."""
 
     def __init__(self, net, global_batch, src_hw, size, depth=2, gather=True, mean=MEAN, std=STD):
         torch = _torch()
         if net._device is None:
             raise RuntimeError("net.collect_params().reset_ctx(device) first")
-        self.net, self.size, self.depth = net, int(size), int(depth)
+        self.net, self.depth = net, int(depth)
+        self.size = (int(size), int(size)) if np.ndim(size) == 0 else (int(size[0]), int(size[1]))   # (height, width)
         if self.depth < 1:
             raise ValueError("depth must be at least 1 slot, got %r" % (depth,))
         depth = self.depth
@@ -65,7 +67,7 @@ class HostFedDetector(object):
             self.s_in, self.s_out = torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev)
             self.pin_in = [torch.empty((self.b, self.h, self.w, 3), dtype=torch.uint8).pin_memory() for _ in range(depth)]
             self.dev_in = [torch.empty((self.b, self.h, self.w, 3), dtype=torch.uint8, device=self.dev) for _ in range(depth)]
-            self.x = [torch.empty((self.b, 3, self.size, self.size), dtype=torch.float32, device=self.dev) for _ in range(depth)]
+            self.x = [torch.empty((self.b, 3) + self.size, dtype=torch.float32, device=self.dev) for _ in range(depth)]
             self.dev_out = [torch.empty((out_b, rows, 6), dtype=torch.float32, device=self.dev) for _ in range(depth)]
             self.pin_out = [torch.empty((out_b, rows, 6), dtype=torch.float32).pin_memory() for _ in range(depth)]
             ev = lambda: [torch.cuda.Event() for _ in range(depth)]  # noqa: E731
@@ -120,7 +122,7 @@ class HostFedDetector(object):
                 # previous batch's matrix-bound convs instead of in front of this batch's
                 _lib.check(self._lib.vy_preprocess_resize_frames(
                     ctypes.c_void_p(self.dev_in[k].data_ptr()), self.h, self.w, ctypes.c_void_p(self.x[k].data_ptr()), self.b,
-                    self.size, self.size, self._mean.ctypes.data_as(ctypes.c_void_p), self._std.ctypes.data_as(ctypes.c_void_p),
+                    self.size[0], self.size[1], self._mean.ctypes.data_as(ctypes.c_void_p), self._std.ctypes.data_as(ctypes.c_void_p),
                     ctypes.c_void_p(self.s_in.cuda_stream)))
                 self.e_pre[k].record(self.s_in)
             cur.wait_event(self.e_pre[k])
