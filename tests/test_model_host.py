@@ -224,7 +224,7 @@ def test_trainer_uses_the_scheduler(voc_classes):
 
 def test_fastdiv_formula_is_exact():
     """The conv kernel's row tables divide by the feature-map width / height with one multiply-high
-    (csrc/conv_igemm.hip make_fastdiv / fd_div): the same integer arithmetic, checked here against // for every
+    (csrc/kernels.h vy_fastdiv / conv_device.h fd_div): the same integer arithmetic, checked here against // for every
     divisor a plan can produce and n across the 32-bit range."""
     def make(d):
         l = 0

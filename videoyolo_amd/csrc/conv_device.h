@@ -2,6 +2,9 @@
 // conv_wino.hip) and the weight gradients (wgrad.hip, wgrad_split.hip).
 #pragma once
 #include "kernels.h"
+#include "../../include/vy_math.h"
+
+#include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -68,6 +71,254 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #endif
 }
+
+// ---- what the three conv kernels do around their k-loops: ONE definition each of the block order, the pixel of a GEMM
+// row, the row tables, the epilogue and the batch-statistics sums.  `Args` is ConvArgs in the address space the caller
+// reads it from (a kernel parameter, or the kernarg segment for the stream-K instances, which re-read it per work item):
+// always passed on by reference, never copied.  Everything derived from the thread index comes in as an argument, so a
+// caller that made it opaque per item keeps it un-hoisted.  The register allocation of the callers is held to
+// profiles/conv_shared_parts.txt (tools/asm_counts.py): it is sensitive to how this code is written, not only to what it
+// computes — see the notes at conv_epilogue and at MfmaCd32.
+
+// XCD-aware order: blocks L, L+8, ... share an XCD (L2); give each XCD a contiguous run of tiles (stream-K: of the
+// k-step sequence) with n fastest so neighbours in time re-use the same A rows and the whole W panel.
+__device__ __forceinline__ int vy_xcd_tile(const int L, const int nblk) {
+  const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// GEMM row m -> pixel (b, y, x) of the logical LH x LW grid
+// (two multiply-highs instead of two emulated 32-bit divisions per row: the prologue is on the critical path of
+// the short launches at small batches)
+struct ConvPixel {
+  int b, y, x;
+};
+template <typename Args>
+__device__ __forceinline__ ConvPixel conv_pixel(const int m, Args& a) {
+  const int t = (int)fd_div((unsigned)m, a.fd_lw);
+  const int x = m - t * a.LW;
+  const int b = (int)fd_div((unsigned)t, a.fd_lh);
+  const int y = t - b * a.LH;
+  return {b, y, x};
+}
+// ... its pixel index in the output plane (and in the addend plane, which has the output's pixel map) ...
+template <typename Args>
+__device__ __forceinline__ long long conv_out_pixel(const ConvPixel p, Args& a) {
+  return (long long)(p.b * a.o_Hp + p.y * a.o_s + a.o_oy) * a.o_Wp + p.x * a.o_s + a.o_ox;
+}
+// ... and the element offset of its centre pixel's first channel in the A operand plane
+template <typename Args>
+__device__ __forceinline__ long long conv_in_offset(const ConvPixel p, Args& a) {
+  return ((long long)(p.b * a.a_Hp + p.y * a.a_s + a.a_oy) * a.a_Wp + p.x * a.a_s + a.a_ox) * a.a_cs + a.a_co;
+}
+// x2-replicated store (nearest upsample fused, layers.py:11-20) cropped to the route's size (slice_like,
+// yolo3.py:1177): bit 0 / bit 1 drop the pixel's second column / second row
+template <typename Args>
+__device__ __forceinline__ unsigned conv_ups2_crop(const ConvPixel p, Args& a) {
+  return (2 * p.x + 1 >= a.o_Wp - 2 ? 1u : 0u) | (2 * p.y + 1 >= a.o_Hp - 2 ? 2u : 0u);
+}
+// output pixel of a tile's first row (m0 < M always): wave-uniform
+template <typename Args>
+__device__ __forceinline__ long long conv_tile_pix0(const int m0, Args& a) {
+  const long long p = conv_out_pixel(conv_pixel(m0, a), a);
+#if defined(__HIP_DEVICE_COMPILE__)
+  return ((long long)__builtin_amdgcn_readfirstlane((int)(p >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)p);
+#else
+  return p;
+#endif
+}
+
+// Row tables of a tile: in_off = element offset of the row's A pixel; o_off / r_off = byte offset of the row's output
+// pixel (and of its addend pixel) relative to the tile's first pixel; kInvalidRow for rows past M.  The epilogue
+// addresses memory through buffer descriptors based at the tile's first pixel: 32-bit offsets (one v_add per element
+// instead of 64-bit multiply-adds), and an offset with bit 31 set is out of range for the descriptor, so the
+// hardware drops the store / returns 0 for the load — no per-element branches.  With ups == 2 the two low bits of
+// the (4-byte aligned) output offset carry conv_ups2_crop.
+constexpr unsigned kInvalidRow = 0x80000000u;
+template <int BM, int NT, typename Args>
+__device__ __forceinline__ void conv_row_tables(Args& a, const int tid, const int m0, const long long pix0, long long* in_off,
+                                                unsigned* o_off, unsigned* r_off) {
+  for (int rr = tid; rr < BM; rr += NT) {
+    const int m = m0 + rr;
+    const ConvPixel p = conv_pixel(m < a.M ? m : a.M - 1, a);
+    in_off[rr] = conv_in_offset(p, a);
+    const unsigned rel = (unsigned)(conv_out_pixel(p, a) - pix0);
+    unsigned oo_row = (m < a.M) ? rel * (unsigned)a.o_cs * 4u : kInvalidRow;
+    if (a.ups == 2 && m < a.M) oo_row |= conv_ups2_crop(p, a);
+    o_off[rr] = oo_row;
+    r_off[rr] = (m < a.M) ? rel * (unsigned)a.r_cs * 4u : kInvalidRow;
+  }
+}
+
+// C/D register maps of the two MFMA shapes the kernels use.  A lane holds ONE column of a TS x TS tile, col(lane), and
+// NR of its rows: accumulator register r is row row(row0, group(lane), r) of the tile whose first row is row0.  The
+// kernels compute a lane's column and row group once, at their top, and hand both to the functions below (recomputed
+// from the lane inside the epilogue they cost the exact kernel a VGPR and the Winograd kernel 24 more LDS reads); row()
+// takes row0 so that the sum associates as (row0 + row in tile) + 4 grp, the form the LDS offsets fold best from.
+struct MfmaCd32 {  // v_mfma_f32_32x32x*: 16 registers
+  static constexpr int TS = 32, NR = 16;
+  static __device__ __forceinline__ int col(const int lane) { return lane & 31; }
+  static __device__ __forceinline__ int group(const int lane) { return lane >> 5; }
+  static __device__ __forceinline__ int row(const int row0, const int grp, const int r) {
+    return row0 + (r & 3) + 8 * (r >> 2) + 4 * grp;
+  }
+};
+struct MfmaCd16 {  // v_mfma_f32_16x16x*: 4 registers
+  static constexpr int TS = 16, NR = 4;
+  static __device__ __forceinline__ int col(const int lane) { return lane & 15; }
+  static __device__ __forceinline__ int group(const int lane) { return lane >> 4; }
+  static __device__ __forceinline__ int row(const int row0, const int grp, const int r) { return row0 + 4 * grp + r; }
+};
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// The epilogue's descriptors, based at the tile's first pixel and column (see the row tables above)
+constexpr int kRsrcFlags = 0x00020000;  // raw dword buffer, gfx9 data format 32
+template <typename Args>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t conv_out_rsrc(Args& a, const long long pix0, const int n0) {
+  return __builtin_amdgcn_make_buffer_rsrc(a.out + (pix0 * a.o_cs + a.o_co + n0), 0, 0x7fffffff, kRsrcFlags);
+}
+template <typename Args>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t conv_res_rsrc(Args& a, const long long pix0, const int n0) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res + (pix0 * a.r_cs + a.r_co + n0) : a.in), 0,
+                                           0x7fffffff, kRsrcFlags);
+}
+
+// The epilogue of a tile: affine (folded BN or bias) -> leaky -> + addend -> store (x1 or x2-replicated).  The wave
+// (wm, wn) holds TM x TN MFMA tiles of Map's shape; tile (i, j) covers rows (wm * TM + i) * TS ... and columns
+// (wn * TN + j) * TS ... of the block tile; lcol / lgrp: the lane's Map::col / Map::group.  The caller's own variables
+// are taken by reference, as a lambda in the caller would capture them: taken by value, conv_split_kernel<128, 128>
+// came out with a different instruction mix.
+template <typename Map, int TM, int TN, typename Args, typename Acc>
+__device__ __forceinline__ void conv_epilogue(Args& a, const Acc (&acc)[TM][TN], unsigned* const& o_off, unsigned* const& r_off,
+                                              const long long& pix0, const int& n0, const int& wm, const int& wn, const int& lcol,
+                                              const int& lgrp) {
+  constexpr int TS = Map::TS, NR = Map::NR;
+  const __amdgpu_buffer_rsrc_t out_rsrc = conv_out_rsrc(a, pix0, n0);
+  const __amdgpu_buffer_rsrc_t res_rsrc = conv_res_rsrc(a, pix0, n0);
+  const int ups_dx = a.o_cs * 4, ups_dy = a.o_Wp * a.o_cs * 4;
+  // The epilogue variant (which of scale / shift / leaky / addend / x2-replicate apply) is uniform for the
+  // launch; it is resolved ONCE, outside the element loops, into a straight-line instance per combination —
+  // with the tests inside the loops hipcc emitted a branch (and a serialising wait) per element.
+  auto epilogue = [&](auto has_scale_, auto has_shift_, auto leaky_, auto has_res_, auto ups2_) {
+    constexpr bool has_scale = decltype(has_scale_)::value, has_shift = decltype(has_shift_)::value;
+    constexpr bool leaky = decltype(leaky_)::value, has_res = decltype(has_res_)::value, ups2 = decltype(ups2_)::value;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int ncol = (wn * TN + j) * TS + lcol;
+      const int n = n0 + ncol;
+      const bool nvalid = n < a.N;
+      const int nc = nvalid ? n : a.N - 1;
+      // the lane's column offset with bit 31 set for a column past N; added to a row offset with a SATURATING add, so
+      // that "invalid row" + "invalid column" stays out of the descriptor's range (one instruction per address)
+      const unsigned colc = (unsigned)ncol * 4u | (nvalid ? 0u : kInvalidRow);
+      float sc = 1.0f, sh = 0.0f;
+      if (has_scale) sc = a.scale[nc];
+      if (has_scale || has_shift) sh = a.shift[nc];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        unsigned oo[NR];
+        float rv[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          const int row = Map::row((wm * TM + i) * TS, lgrp, r);
+          oo[r] = __builtin_elementwise_add_sat(o_off[row], colc);
+          if (has_res) rv[r] = buf_load_f32(res_rsrc, __builtin_elementwise_add_sat(r_off[row], colc));
+        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          float vv = acc[i][j][r];
+          if (has_scale)
+            vv = fmaf(vv, sc, sh);
+          else if (has_shift)
+            vv = vv + sh;
+          if (leaky) vv = vy_leaky(vv);
+          if (has_res) vv = vv + rv[r];
+          if (!ups2) {
+            buf_store_f32(vv, out_rsrc, oo[r], 0);
+          } else {  // an offset with bit 31 set is out of the descriptor's range: that store is dropped
+            const unsigned base = oo[r] & ~3u;
+            const unsigned no_dx = (oo[r] & 1u) << 31, no_dy = (oo[r] & 2u) << 30;
+            buf_store_f32(vv, out_rsrc, base, 0);
+            buf_store_f32(vv, out_rsrc, base | no_dx, ups_dx);
+            buf_store_f32(vv, out_rsrc, base | no_dy, ups_dy);
+            buf_store_f32(vv, out_rsrc, base | no_dx | no_dy, ups_dy + ups_dx);
+          }
+        }
+      }
+    }
+  };
+  using T = std::true_type;
+  using F = std::false_type;
+  const bool f_scale = a.scale != nullptr, f_shift = a.shift != nullptr, f_leaky = a.leaky != 0;
+  const bool f_res = a.res != nullptr, f_ups2 = a.ups == 2;
+  if (f_scale && f_shift && f_leaky && !f_ups2) {           // conv + BN + leaky (+ residual): inference cells
+    if (f_res) epilogue(T{}, T{}, T{}, T{}, F{});
+    else epilogue(T{}, T{}, T{}, F{}, F{});
+  } else if (f_scale && f_shift && f_leaky && !f_res) {     // transition cells: x2-replicated store
+    epilogue(T{}, T{}, T{}, F{}, T{});
+  } else if (!f_scale && !f_leaky && !f_ups2) {             // raw conv (training forward) / bias / gradients (+ accumulate)
+    if (f_shift) {
+      if (f_res) epilogue(F{}, T{}, F{}, T{}, F{});
+      else epilogue(F{}, T{}, F{}, F{}, F{});
+    } else {
+      if (f_res) epilogue(F{}, F{}, F{}, T{}, F{});
+      else epilogue(F{}, F{}, F{}, F{}, F{});
+    }
+  } else {
+    __builtin_trap();  // no launch site builds any other combination (vy_conv_epilogue_supported, kernels.h)
+  }
+}
+
+// train-mode BatchNorm: per-tile column sums of the raw accumulators of a 32x32-MFMA tile into a.stats
+// ([tile_m][2][N]; deterministic: fixed order inside the tile, tiles are combined in order by the finalize kernel).
+// `smem`: the block's LDS from its start — the operand stages, reused as [WM][2][BN] doubles.  (conv_igemm.hip keeps
+// these statements in line: see there.)
+template <int BN, int WM, int TM, int TN, typename Args, typename Acc>
+__device__ __forceinline__ void conv_bn_stats(Args& a, const Acc (&acc)[TM][TN], unsigned* const& o_off, unsigned char* const& smem,
+                                              const int& tile_m, const int& n0, const int& wm, const int& wn, const int& lcol,
+                                              const int& lgrp, const int& tid) {
+  // double accumulation: var = E[x^2] - mean^2 cancels badly in fp32 when |mean| >> std, and the
+  // batch statistics must round to the same fp32 mean / var as the CPU checker's
+  double s1[TN], s2[TN];
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    s1[j] = 0.0;
+    s2[j] = 0.0;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = MfmaCd32::row((wm * TM + i) * 32, lgrp, r);
+        const double vv = o_off[row] != kInvalidRow ? (double)acc[i][j][r] : 0.0;
+        s1[j] += vv;
+        s2[j] += vv * vv;
+      }
+    s1[j] += __shfl_xor(s1[j], 32);
+    s2[j] += __shfl_xor(s2[j], 32);
+  }
+  __syncthreads();  // every wave is past its last LDS tile read
+  double* red = reinterpret_cast<double*>(smem);  // [WM][2][BN]
+  if (lgrp == 0) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int col = (wn * TN + j) * 32 + lcol;
+      red[(wm * 2 + 0) * BN + col] = s1[j];
+      red[(wm * 2 + 1) * BN + col] = s2[j];
+    }
+  }
+  __syncthreads();
+  if (tid < BN && n0 + tid < a.N) {
+    double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+    for (int w = 0; w < WM; ++w) {
+      t1 += red[(w * 2 + 0) * BN + tid];
+      t2 += red[(w * 2 + 1) * BN + tid];
+    }
+    a.stats[((long long)tile_m * 2 + 0) * a.N + n0 + tid] = t1;
+    a.stats[((long long)tile_m * 2 + 1) * a.N + n0 + tid] = t2;
+  }
+}
+#endif  // __HIP_DEVICE_COMPILE__
 
 // The weight gradients' view of output pixel p of a conv (wgrad.hip, the pixel table): the byte offset of its dz vector
 // inside the dz plane and of its (stride-scaled) centre pixel inside the input plane, both zero-bordered

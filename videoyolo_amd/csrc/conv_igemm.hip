@@ -73,15 +73,9 @@ __device__ __forceinline__ void conv_tile(Args& a, const int tiles_n, const SkAr
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   static_assert(A_INSTR >= 1 && B_INSTR >= 1, "tile too small for the wave count");
   static_assert(TM >= 1 && TN >= 1, "tile");
-  long long* in_off = reinterpret_cast<long long*>(smem + NS * STAGE);
-  // epilogue row tables: byte offset of the row's output pixel (and of its addend pixel) relative to the
-  // tile's first pixel; kInvalidRow for rows past M.  The epilogue addresses memory through buffer
-  // descriptors based at the tile's first pixel: 32-bit offsets (one v_add per element instead of
-  // 64-bit multiply-adds), and an offset with bit 31 set is out of range for the descriptor, so the
-  // hardware drops the store / returns 0 for the load — no per-element branches.
+  long long* in_off = reinterpret_cast<long long*>(smem + NS * STAGE);  // the row tables (conv_device.h)
   unsigned* o_off = reinterpret_cast<unsigned*>(in_off + BM);
   unsigned* r_off = o_off + BM;
-  constexpr unsigned kInvalidRow = 0x80000000u;
 
   int tid_ = threadIdx.x;
   // SK: the tile body runs in a loop over work items.  Everything derived from the thread index is loop-invariant, and
@@ -99,42 +93,15 @@ __device__ __forceinline__ void conv_tile(Args& a, const int tiles_n, const SkAr
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  const int h = lane >> 5;
+  const int h = MfmaCd32::group(lane);  // the lane's half-wave: the k pair it feeds and its C/D row group
   const int cchunks = a.Kc >> 5;
 
   if (SK) __syncthreads();  // the previous item's epilogue is done with the row tables
   const int tile_m = v / tiles_n, tile_n = v - tile_m * tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
-  // output pixel of the tile's first row (m0 < M always): wave-uniform
-  long long pix0;
-  {
-    const int t = (int)fd_div((unsigned)m0, a.fd_lw);
-    const int x = m0 - t * a.LW;
-    const int b = (int)fd_div((unsigned)t, a.fd_lh);
-    const int y = t - b * a.LH;
-    const long long p = (long long)(b * a.o_Hp + y * a.o_s + a.o_oy) * a.o_Wp + x * a.o_s + a.o_ox;
-    pix0 = ((long long)__builtin_amdgcn_readfirstlane((int)(p >> 32)) << 32) |
-           (unsigned)__builtin_amdgcn_readfirstlane((int)p);
-  }
-  for (int rr = tid; rr < BM; rr += NT) {
-    const int m = m0 + rr;
-    const int mm = m < a.M ? m : a.M - 1;
-    // (two multiply-highs instead of two emulated 32-bit divisions per row: the prologue is on the critical path of
-    // the short launches at small batches)
-    const int t = (int)fd_div((unsigned)mm, a.fd_lw);
-    const int x = mm - t * a.LW;
-    const int b = (int)fd_div((unsigned)t, a.fd_lh);
-    const int y = t - b * a.LH;
-    in_off[rr] = ((long long)(b * a.a_Hp + y * a.a_s + a.a_oy) * a.a_Wp + x * a.a_s + a.a_ox) * a.a_cs + a.a_co;
-    const unsigned rel = (unsigned)(((long long)(b * a.o_Hp + y * a.o_s + a.o_oy) * a.o_Wp + x * a.o_s + a.o_ox) - pix0);
-    unsigned oo_row = (m < a.M) ? rel * (unsigned)a.o_cs * 4u : kInvalidRow;
-    // x2-replicated store (nearest upsample fused, layers.py:11-20) cropped to the route's size (slice_like,
-    // yolo3.py:1177): bit 0 / bit 1 of the (4-byte aligned) offset drop the row's second column / second row
-    if (a.ups == 2 && m < a.M) oo_row |= (2 * x + 1 >= a.o_Wp - 2 ? 1u : 0u) | (2 * y + 1 >= a.o_Hp - 2 ? 2u : 0u);
-    o_off[rr] = oo_row;
-    r_off[rr] = (m < a.M) ? rel * (unsigned)a.r_cs * 4u : kInvalidRow;
-  }
+  const long long pix0 = conv_tile_pix0(m0, a);
+  conv_row_tables<BM, NT>(a, tid, m0, pix0, in_off, o_off, r_off);
   __syncthreads();
 
   // LDS-DMA sources: wave-uniform base (advanced per k-step by the uniform tap / k offset) + per-lane 32-bit byte
@@ -224,7 +191,7 @@ __device__ __forceinline__ void conv_tile(Args& a, const int tiles_n, const SkAr
   const unsigned lds0 = (unsigned)(unsigned long long)LDS_PTR(smem);
   const int T = ke - kb;
 
-  const int lrow = lane & 31;
+  const int lrow = MfmaCd32::col(lane);
   // ---- k-loop.  Wave-uniform tile state (tap, channel chunk -> A / W offsets) is advanced once per tile
   // with scalar arithmetic; the last tile is peeled (no prefetch); fragments are double-buffered in
   // registers; sched_barriers pin the order  [MFMA steps 0,1] [a third of the next tile's DMA] [step 2]
@@ -593,87 +560,8 @@ __device__ __forceinline__ void conv_tile(Args& a, const int tiles_n, const SkAr
     return;
   }
 #endif
-  // epilogue: affine (folded BN or bias) -> leaky -> + addend -> store (x1 or x2-replicated), through
-  // buffer descriptors based at the tile's first pixel and column (see the row tables above)
-  constexpr int kRsrcFlags = 0x00020000;  // raw dword buffer, gfx9 data format 32
-  const __amdgpu_buffer_rsrc_t out_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(a.out + (pix0 * a.o_cs + a.o_co + n0), 0, 0x7fffffff, kRsrcFlags);
-  const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.res ? a.res + (pix0 * a.r_cs + a.r_co + n0) : a.in), 0, 0x7fffffff, kRsrcFlags);
-  const int ups_dx = a.o_cs * 4, ups_dy = a.o_Wp * a.o_cs * 4;
-  // The epilogue variant (which of scale / shift / leaky / addend / x2-replicate apply) is uniform for the
-  // launch; it is resolved ONCE, outside the element loops, into a straight-line instance per combination —
-  // with the tests inside the loops hipcc emitted a branch (and a serialising wait) per element.
-  auto epilogue = [&](auto has_scale_, auto has_shift_, auto leaky_, auto has_res_, auto ups2_) {
-    constexpr bool has_scale = decltype(has_scale_)::value, has_shift = decltype(has_shift_)::value;
-    constexpr bool leaky = decltype(leaky_)::value, has_res = decltype(has_res_)::value, ups2 = decltype(ups2_)::value;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int ncol = (wn * TN + j) * 32 + lrow;
-      const int n = n0 + ncol;
-      const bool nvalid = n < a.N;
-      const int nc = nvalid ? n : a.N - 1;
-      // the lane's column offset with bit 31 set for a column past N; added to a row offset with a SATURATING add, so
-      // that "invalid row" + "invalid column" stays out of the descriptor's range (one instruction per address)
-      const unsigned colc = (unsigned)ncol * 4u | (nvalid ? 0u : kInvalidRow);
-      float sc = 1.0f, sh = 0.0f;
-      if (has_scale) sc = a.scale[nc];
-      if (has_scale || has_shift) sh = a.shift[nc];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        unsigned oo[16];
-        float rv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          oo[r] = __builtin_elementwise_add_sat(o_off[row], colc);
-          if (has_res) rv[r] = buf_load_f32(res_rsrc, __builtin_elementwise_add_sat(r_off[row], colc));
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float vv = acc[i][j][r];
-          if (has_scale)
-            vv = fmaf(vv, sc, sh);
-          else if (has_shift)
-            vv = vv + sh;
-          if (leaky) vv = vy_leaky(vv);
-          if (has_res) vv = vv + rv[r];
-          if (!ups2) {
-            buf_store_f32(vv, out_rsrc, oo[r], 0);
-          } else {  // an offset with bit 31 set is out of the descriptor's range: that store is dropped
-            const unsigned base = oo[r] & ~3u;
-            const unsigned no_dx = (oo[r] & 1u) << 31, no_dy = (oo[r] & 2u) << 30;
-            buf_store_f32(vv, out_rsrc, base, 0);
-            buf_store_f32(vv, out_rsrc, base | no_dx, ups_dx);
-            buf_store_f32(vv, out_rsrc, base | no_dy, ups_dy);
-            buf_store_f32(vv, out_rsrc, base | no_dx | no_dy, ups_dy + ups_dx);
-          }
-        }
-      }
-    }
-  };
-  {
-    using T = std::true_type;
-    using F = std::false_type;
-    const bool f_scale = a.scale != nullptr, f_shift = a.shift != nullptr, f_leaky = a.leaky != 0;
-    const bool f_res = a.res != nullptr, f_ups2 = a.ups == 2;
-    if (f_scale && f_shift && f_leaky && !f_ups2) {           // conv + BN + leaky (+ residual): inference cells
-      if (f_res) epilogue(T{}, T{}, T{}, T{}, F{});
-      else epilogue(T{}, T{}, T{}, F{}, F{});
-    } else if (f_scale && f_shift && f_leaky && !f_res) {     // transition cells: x2-replicated store
-      epilogue(T{}, T{}, T{}, F{}, T{});
-    } else if (!f_scale && !f_leaky && !f_ups2) {             // raw conv / bias / gradients (+ accumulate)
-      if (f_shift) {
-        if (f_res) epilogue(F{}, T{}, F{}, T{}, F{});
-        else epilogue(F{}, T{}, F{}, F{}, F{});
-      } else {
-        if (f_res) epilogue(F{}, F{}, F{}, T{}, F{});
-        else epilogue(F{}, F{}, F{}, F{}, F{});
-      }
-    } else {
-      __builtin_trap();  // no launch site builds any other combination (vy_launch_conv_igemm rejects them)
-    }
-  }
+  // epilogue: affine (folded BN or bias) -> leaky -> + addend -> store (x1 or x2-replicated)
+  conv_epilogue<MfmaCd32>(a, acc, o_off, r_off, pix0, n0, wm, wn, lrow, h);
 
   VY_TRACE(3)
 #ifdef VY_CONV_TRACE
@@ -682,11 +570,10 @@ __device__ __forceinline__ void conv_tile(Args& a, const int tiles_n, const SkAr
     a.trace[(long long)blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg(20 | (31 << 11));  // XCC_ID
   }
 #endif
-  // train-mode BatchNorm: per-tile column sums of the raw accumulators (deterministic: fixed
-  // order inside the tile, tiles are combined in order by the finalize kernel)
+  // train-mode BatchNorm: the column sums of conv_bn_stats (conv_device.h), statement for statement.  This kernel keeps
+  // them in line: called as a function they cost the three plain 128x128 instances one or two SGPRs of difference in the
+  // register allocation (profiles/conv_shared_parts.txt), and the instances of this file are held to their counts
   if (a.stats) {
-    // double accumulation: var = E[x^2] - mean^2 cancels badly in fp32 when |mean| >> std, and the
-    // batch statistics must round to the same fp32 mean / var as the CPU checker's
     double s1[TN], s2[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -696,7 +583,7 @@ __device__ __forceinline__ void conv_tile(Args& a, const int tiles_n, const SkAr
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          const int row = MfmaCd32::row((wm * TM + i) * 32, h, r);
           const double vv = o_off[row] != kInvalidRow ? (double)acc[i][j][r] : 0.0;
           s1[j] += vv;
           s2[j] += vv * vv;
@@ -752,16 +639,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_igemm_kernel(const ConvA
 #define VY_CONV_PAD_LDS 0
 #endif
   __shared__ __attribute__((aligned(16))) unsigned char smem[NS * STAGE + 2 * BM * 8 + (NS == 2 ? VY_CONV_PAD_LDS : 0)];
-  // XCD-aware order: blocks L, L+8, ... share an XCD (L2); give each XCD a contiguous run of tiles (SK: of the
-  // k-step sequence) with n fastest so neighbours in time re-use the same A rows and the whole W panel.
-  int vblk;
-  {
-    const int nblk = gridDim.x, L = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
-    vblk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int vblk = vy_xcd_tile((int)blockIdx.x, (int)gridDim.x);
   const int T_all = a.ntaps * (a.Kc >> 5);  // k-steps of a whole tile
-
 
   if constexpr (!SK) {
     conv_tile<BM, BN, WM, WN, DGRAD, NS, SK, CK, const ConvArgs>(a, tiles_n, sk, smem, vblk, vblk, 0, T_all, false, false, 0,
@@ -1014,16 +893,6 @@ int vy_conv_tiles_m(const ConvArgs& a) {
   return (a.M + bm - 1) / bm;
 }
 
-static VyFastDiv make_fastdiv(unsigned d) {
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  VyFastDiv f;
-  f.m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
-  f.s1 = l < 1 ? l : 1;
-  f.s2 = l > 0 ? l - 1 : 0;
-  return f;
-}
-
 // tile choice -> template instance; `sk_query`: see launch_cfg
 static hipError_t run_cfg(const ConvArgs& a, hipStream_t s, bool* sk_query, int* ks_query = nullptr, VyConvForm* form = nullptr) {
   int bm, bn;
@@ -1081,21 +950,11 @@ size_t vy_conv_chunk_scratch_bytes(long long M, int N, int runs) {
 hipError_t vy_launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
   ConvArgs a = a_in;
   if (a.LW < 1 || a.LH < 1) return hipErrorInvalidValue;
-  a.fd_lw = make_fastdiv((unsigned)a.LW);
-  a.fd_lh = make_fastdiv((unsigned)a.LH);
-  a.pk_dy = a.pk_dx = 0;
-  a.pk_w = 0;
-  for (int t = 0; t < a.ntaps; ++t) {
-    if (a.tap_dy[t] < -1 || a.tap_dy[t] > 1 || a.tap_dx[t] < -1 || a.tap_dx[t] > 1 || a.tap_w[t] > 15) return hipErrorInvalidValue;
-    a.pk_dy |= (unsigned)(a.tap_dy[t] + 1) << (2 * t);
-    a.pk_dx |= (unsigned)(a.tap_dx[t] + 1) << (2 * t);
-    a.pk_w |= (unsigned long long)a.tap_w[t] << (4 * t);
-  }
+  a.fd_lw = vy_fastdiv((unsigned)a.LW);
+  a.fd_lh = vy_fastdiv((unsigned)a.LH);
+  if (!vy_conv_pack_taps(a)) return hipErrorInvalidValue;
   if (a.Kc % 32 != 0 || a.ntaps < 1 || a.ntaps > 9 || a.M <= 0 || a.N <= 0) return hipErrorInvalidValue;
   if (a.dgrad && (a.N % 4 != 0)) return hipErrorInvalidValue;
-  {  // epilogue combinations the kernel instantiates (see `epilogue` in conv_igemm_kernel)
-    const bool bn_cell = a.scale && a.shift && a.leaky, plain = !a.scale && !a.leaky;
-    if (!((bn_cell && (a.ups != 2 || !a.res)) || (plain && a.ups != 2))) return hipErrorInvalidValue;
-  }
+  if (!vy_conv_epilogue_supported(a)) return hipErrorInvalidValue;
   return run_cfg(a, s, nullptr);
 }

@@ -226,15 +226,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvArgs a, co
   long long* in_off = reinterpret_cast<long long*>(smem + NSA * A_ST + NSW * W_ST);
   unsigned* o_off = reinterpret_cast<unsigned*>(in_off + BM);
   unsigned* r_off = o_off + BM;
-  constexpr unsigned kInvalidRow = 0x80000000u;
 
-  // XCD-aware order (conv_igemm.hip): blocks L, L+8, ... share an L2; contiguous run of tiles per XCD, n fastest
-  int vblk;
-  {
-    const int nblk = gridDim.x, L = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
-    vblk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int vblk = vy_xcd_tile((int)blockIdx.x, (int)gridDim.x);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -246,30 +239,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvArgs a, co
   const int tile_m = vtile / tiles_n, tile_n = vtile - tile_m * tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
-  long long pix0;
-  {
-    const int t = (int)fd_div((unsigned)m0, a.fd_lw);
-    const int x = m0 - t * a.LW;
-    const int b = (int)fd_div((unsigned)t, a.fd_lh);
-    const int y = t - b * a.LH;
-    const long long p = (long long)(b * a.o_Hp + y * a.o_s + a.o_oy) * a.o_Wp + x * a.o_s + a.o_ox;
-    pix0 = ((long long)__builtin_amdgcn_readfirstlane((int)(p >> 32)) << 32) |
-           (unsigned)__builtin_amdgcn_readfirstlane((int)p);
-  }
-  for (int rr = tid; rr < BM; rr += NT) {
-    const int m = m0 + rr;
-    const int mm = m < a.M ? m : a.M - 1;
-    const int t = (int)fd_div((unsigned)mm, a.fd_lw);
-    const int x = mm - t * a.LW;
-    const int b = (int)fd_div((unsigned)t, a.fd_lh);
-    const int y = t - b * a.LH;
-    in_off[rr] = ((long long)(b * a.a_Hp + y * a.a_s + a.a_oy) * a.a_Wp + x * a.a_s + a.a_ox) * a.a_cs + a.a_co;
-    const unsigned rel = (unsigned)(((long long)(b * a.o_Hp + y * a.o_s + a.o_oy) * a.o_Wp + x * a.o_s + a.o_ox) - pix0);
-    unsigned oo_row = (m < a.M) ? rel * (unsigned)a.o_cs * 4u : kInvalidRow;
-    if (a.ups == 2 && m < a.M) oo_row |= (2 * x + 1 >= a.o_Wp - 2 ? 1u : 0u) | (2 * y + 1 >= a.o_Hp - 2 ? 2u : 0u);
-    o_off[rr] = oo_row;
-    r_off[rr] = (m < a.M) ? rel * (unsigned)a.r_cs * 4u : kInvalidRow;
-  }
+  const long long pix0 = conv_tile_pix0(m0, a);
+  conv_row_tables<BM, NT>(a, tid, m0, pix0, in_off, o_off, r_off);
   __syncthreads();
 
   // A side: thread -> (row, channel octet) of the tile; pointer to the row's centre pixel
@@ -293,8 +264,9 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvArgs a, co
   const unsigned char* w_tile = reinterpret_cast<const unsigned char*>(a.w_split) + (long long)(n0 >> 5) * KS * 3072;
 
   constexpr bool M16 = VY_SPLIT_M16 != 0;
-  constexpr int TS = M16 ? 16 : 32;                  // rows / columns of one MFMA tile
-  constexpr int TMs = BM / WM / TS, TNs = BN / WN / TS, NR = TS * TS / 64;  // tiles per wave, accumulator registers per tile
+  using Map = std::conditional_t<M16, MfmaCd16, MfmaCd32>;  // C/D map of the MFMA shape (conv_device.h)
+  constexpr int TS = Map::TS, NR = Map::NR;          // rows / columns of one MFMA tile, accumulator registers per tile
+  constexpr int TMs = BM / WM / TS, TNs = BN / WN / TS;  // tiles per wave
   typedef float accv __attribute__((ext_vector_type(NR)));
   accv acc[TMs][TNs];
 #pragma unroll
@@ -354,6 +326,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvArgs a, co
   // SECOND plane of the instruction's pair: A pairs (l|h) (m|m) (h|h), W pairs (h|l) (m|h) — so that
   //   A(l|h) W(h|l) = l h + h l,   A(m|m) W(m|h) = m m + m h,   A(h|h) W(m|h) = h m + h h     (plane 0 = h, 1 = m, 2 = l)
   const int q16 = lane >> 4, r16 = lane & 15, up = lane >> 5;
+  const int lcol = Map::col(lane), lgrp = Map::group(lane);  // the lane's column and row group in the C/D map
   const unsigned fa = M16 ? (unsigned)((wm * (BM / WM) + r16) * 32 + ((q16 & 1) << 4))
                           : (unsigned)((wm * (BM / WM) + lrow) * 32 + (VY_SPLIT_SLOT(lrow, h) << 4));
   const unsigned fw = M16 ? (unsigned)(W_BASE + (wn * (BN / WN) + r16) * 32 + ((q16 & 1) << 4))
@@ -480,136 +453,22 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvArgs a, co
     float* slab = a.splitk_slabs + (long long)ks_idx * a.M * a.N;
 #pragma unroll
     for (int j = 0; j < TNs; ++j) {
-      const int n = n0 + wn * (BN / WN) + j * TS + (M16 ? r16 : lrow);
+      const int n = n0 + wn * (BN / WN) + j * TS + lcol;
 #pragma unroll
       for (int i = 0; i < TMs; ++i)
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-          const int m = m0 + wm * (BM / WM) + i * TS + (M16 ? 4 * q16 + r : (r & 3) + 8 * (r >> 2) + 4 * h);
+          const int m = Map::row(m0 + wm * (BM / WM) + i * TS, lgrp, r);
           if (m < a.M && n < a.N) slab[(long long)m * a.N + n] = acc[i][j][r];
         }
     }
     return;
   }
-  // ---- epilogue (conv_igemm.hip): affine -> leaky -> + addend -> store (x1 or x2-replicated)
-  constexpr int kRsrcFlags = 0x00020000;
-  const __amdgpu_buffer_rsrc_t out_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(a.out + (pix0 * a.o_cs + a.o_co + n0), 0, 0x7fffffff, kRsrcFlags);
-  const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.res ? a.res + (pix0 * a.r_cs + a.r_co + n0) : a.in), 0, 0x7fffffff, kRsrcFlags);
-  const int ups_dx = a.o_cs * 4, ups_dy = a.o_Wp * a.o_cs * 4;
-  auto epilogue = [&](auto has_scale_, auto has_shift_, auto leaky_, auto has_res_, auto ups2_) {
-    constexpr bool has_scale = decltype(has_scale_)::value, has_shift = decltype(has_shift_)::value;
-    constexpr bool leaky = decltype(leaky_)::value, has_res = decltype(has_res_)::value, ups2 = decltype(ups2_)::value;
-#pragma unroll
-    for (int j = 0; j < TNs; ++j) {
-      // C/D maps: 32x32: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5); 16x16: column lane & 15, row 4 (lane >> 4) + r
-      const int ncol = wn * (BN / WN) + j * TS + (M16 ? r16 : lrow);
-      const int n = n0 + ncol;
-      const bool nvalid = n < a.N;
-      const int nc = nvalid ? n : a.N - 1;
-      const unsigned colc = (unsigned)ncol * 4u | (nvalid ? 0u : kInvalidRow);
-      float sc = 1.0f, sh = 0.0f;
-      if (has_scale) sc = a.scale[nc];
-      if (has_scale || has_shift) sh = a.shift[nc];
-#pragma unroll
-      for (int i = 0; i < TMs; ++i) {
-        unsigned oo[NR];
-        float rv[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          const int row = wm * (BM / WM) + i * TS + (M16 ? 4 * q16 + r : (r & 3) + 8 * (r >> 2) + 4 * h);
-          oo[r] = __builtin_elementwise_add_sat(o_off[row], colc);
-          if (has_res) rv[r] = buf_load_f32(res_rsrc, __builtin_elementwise_add_sat(r_off[row], colc));
-        }
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-          float vv = acc[i][j][r];
-          if (has_scale)
-            vv = fmaf(vv, sc, sh);
-          else if (has_shift)
-            vv = vv + sh;
-          if (leaky) vv = vy_leaky(vv);
-          if (has_res) vv = vv + rv[r];
-          if (!ups2) {
-            buf_store_f32(vv, out_rsrc, oo[r], 0);
-          } else {
-            const unsigned base = oo[r] & ~3u;
-            const unsigned no_dx = (oo[r] & 1u) << 31, no_dy = (oo[r] & 2u) << 30;
-            buf_store_f32(vv, out_rsrc, base, 0);
-            buf_store_f32(vv, out_rsrc, base | no_dx, ups_dx);
-            buf_store_f32(vv, out_rsrc, base | no_dy, ups_dy);
-            buf_store_f32(vv, out_rsrc, base | no_dx | no_dy, ups_dy + ups_dx);
-          }
-        }
-      }
-    }
-  };
-  {
-    using T_ = std::true_type;
-    using F_ = std::false_type;
-    const bool f_scale = a.scale != nullptr, f_shift = a.shift != nullptr, f_leaky = a.leaky != 0;
-    const bool f_res = a.res != nullptr, f_ups2 = a.ups == 2;
-    if (f_scale && f_shift && f_leaky && !f_ups2) {            // conv + BN + leaky (+ residual): inference cells
-      if (f_res) epilogue(T_{}, T_{}, T_{}, T_{}, F_{});
-      else epilogue(T_{}, T_{}, T_{}, F_{}, F_{});
-    } else if (f_scale && f_shift && f_leaky && !f_res) {      // transition cells: x2-replicated store
-      epilogue(T_{}, T_{}, T_{}, F_{}, T_{});
-    } else if (!f_scale && !f_leaky && !f_ups2) {              // raw conv (training forward) / bias / gradients (+ accumulate)
-      if (f_shift) {
-        if (f_res) epilogue(F_{}, T_{}, F_{}, T_{}, F_{});
-        else epilogue(F_{}, T_{}, F_{}, F_{}, F_{});
-      } else {
-        if (f_res) epilogue(F_{}, F_{}, F_{}, T_{}, F_{});
-        else epilogue(F_{}, F_{}, F_{}, F_{}, F_{});
-      }
-    } else {
-      __builtin_trap();
-    }
-  }
+  // epilogue: affine -> leaky -> + addend -> store (x1 or x2-replicated)
+  conv_epilogue<Map>(a, acc, o_off, r_off, pix0, n0, wm, wn, lcol, lgrp);
   // train-mode BatchNorm: per-tile column sums of the raw accumulators in double, as conv_igemm.hip writes them
-  // ([tile_m][2][N]; fixed order inside the tile, tiles combined in order by the finalize kernel)
   if constexpr (!M16) {
-    if (a.stats) {
-      double s1[TNs], s2[TNs];
-#pragma unroll
-      for (int j = 0; j < TNs; ++j) {
-        s1[j] = 0.0;
-        s2[j] = 0.0;
-#pragma unroll
-        for (int i = 0; i < TMs; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = wm * (BM / WM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const double vv = o_off[row] != kInvalidRow ? (double)acc[i][j][r] : 0.0;
-            s1[j] += vv;
-            s2[j] += vv * vv;
-          }
-        s1[j] += __shfl_xor(s1[j], 32);
-        s2[j] += __shfl_xor(s2[j], 32);
-      }
-      __syncthreads();  // every wave is past its last LDS tile read
-      double* red = reinterpret_cast<double*>(smem);  // [WM][2][BN]
-      if (h == 0) {
-#pragma unroll
-        for (int j = 0; j < TNs; ++j) {
-          const int col = wn * (BN / WN) + j * 32 + lrow;
-          red[(wm * 2 + 0) * BN + col] = s1[j];
-          red[(wm * 2 + 1) * BN + col] = s2[j];
-        }
-      }
-      __syncthreads();
-      if (tid < BN && n0 + tid < a.N) {
-        double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-        for (int w = 0; w < WM; ++w) {
-          t1 += red[(w * 2 + 0) * BN + tid];
-          t2 += red[(w * 2 + 1) * BN + tid];
-        }
-        a.stats[((long long)tile_m * 2 + 0) * a.N + n0 + tid] = t1;
-        a.stats[((long long)tile_m * 2 + 1) * a.N + n0 + tid] = t2;
-      }
-    }
+    if (a.stats) conv_bn_stats<BN, WM>(a, acc, o_off, smem, tile_m, n0, wm, wn, lcol, lgrp, tid);
   }
 #endif
 }
@@ -618,10 +477,7 @@ bool vy_conv_split_supported(const ConvArgs& a) {
   if (!a.w_split) return false;
   if (a.stats && VY_SPLIT_M16) return false;
   if (a.Kc % 32 != 0 || a.N % 64 != 0 || a.ntaps < 1 || a.ntaps > 9) return false;
-  // epilogues the kernel instantiates (the exact kernel's set): BN cell (+ residual | x2-replicated), or plain
-  // (raw / bias / gradient, + accumulate)
-  const bool bn_cell = a.scale && a.shift && a.leaky, plain = !a.scale && !a.leaky;
-  return (bn_cell && (a.ups != 2 || !a.res)) || (plain && a.ups != 2);
+  return vy_conv_epilogue_supported(a);
 }
 
 // block tile and k-split of a launch: the cost model's choice (conv_cost_model.h) among 128x128, 128x64 and, for the
@@ -659,16 +515,6 @@ bool vy_conv_split_pays(const ConvArgs& a) {
          0.97 * vy_conv_predict_us(a);
 }
 
-static VyFastDiv split_fastdiv(unsigned d) {
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  VyFastDiv f;
-  f.m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
-  f.s1 = l < 1 ? l : 1;
-  f.s2 = l > 0 ? l - 1 : 0;
-  return f;
-}
-
 // second launch of a split-K conv: out = epilogue(sum over s of slab s), slabs added in index order (deterministic).
 // One thread = 4 consecutive channels of one output pixel.
 __global__ __launch_bounds__(256) void splitk_finish_kernel(const ConvArgs a, const int ksplit) {
@@ -683,11 +529,8 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const ConvArgs a, co
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] += t[e];
   }
-  const int t = (int)fd_div((unsigned)m, a.fd_lw);
-  const int x = m - t * a.LW;
-  const int b = (int)fd_div((unsigned)t, a.fd_lh);
-  const int y = t - b * a.LH;
-  const long long pix = (long long)(b * a.o_Hp + y * a.o_s + a.o_oy) * a.o_Wp + x * a.o_s + a.o_ox;
+  const ConvPixel px = conv_pixel(m, a);
+  const long long pix = conv_out_pixel(px, a);
   f32x4 sh = {0.f, 0.f, 0.f, 0.f};
   if (a.shift) sh = *reinterpret_cast<const f32x4*>(a.shift + n);
   if (a.scale) {
@@ -709,8 +552,9 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const ConvArgs a, co
   }
   float* o = a.out + pix * a.o_cs + a.o_co + n;
   *reinterpret_cast<f32x4*>(o) = v;
-  if (a.ups == 2) {  // x2-replicated store cropped to the route's size (conv_igemm.hip, row tables)
-    const bool dx = 2 * x + 1 < a.o_Wp - 2, dy = 2 * y + 1 < a.o_Hp - 2;
+  if (a.ups == 2) {  // x2-replicated store cropped to the route's size
+    const unsigned crop = conv_ups2_crop(px, a);
+    const bool dx = !(crop & 1u), dy = !(crop & 2u);
     if (dx) *reinterpret_cast<f32x4*>(o + a.o_cs) = v;
     if (dy) *reinterpret_cast<f32x4*>(o + (long long)a.o_Wp * a.o_cs) = v;
     if (dx && dy) *reinterpret_cast<f32x4*>(o + (long long)(a.o_Wp + 1) * a.o_cs) = v;
@@ -731,16 +575,9 @@ static hipError_t launch_split(const ConvArgs& a, int ksplit, hipStream_t s) {
 hipError_t vy_launch_conv_split(const ConvArgs& a_in, hipStream_t s) {
   ConvArgs a = a_in;
   if (!vy_conv_split_supported(a) || a.LW < 1 || a.LH < 1 || a.M <= 0) return hipErrorInvalidValue;
-  a.fd_lw = split_fastdiv((unsigned)a.LW);
-  a.fd_lh = split_fastdiv((unsigned)a.LH);
-  a.pk_dy = a.pk_dx = 0;
-  a.pk_w = 0;
-  for (int t = 0; t < a.ntaps; ++t) {
-    if (a.tap_dy[t] < -1 || a.tap_dy[t] > 1 || a.tap_dx[t] < -1 || a.tap_dx[t] > 1 || a.tap_w[t] > 15) return hipErrorInvalidValue;
-    a.pk_dy |= (unsigned)(a.tap_dy[t] + 1) << (2 * t);
-    a.pk_dx |= (unsigned)(a.tap_dx[t] + 1) << (2 * t);
-    a.pk_w |= (unsigned long long)a.tap_w[t] << (4 * t);
-  }
+  a.fd_lw = vy_fastdiv((unsigned)a.LW);
+  a.fd_lh = vy_fastdiv((unsigned)a.LH);
+  if (!vy_conv_pack_taps(a)) return hipErrorInvalidValue;
   int bm, bn, ks;
   vy_conv_split_cfg(a, &bm, &bn, &ks);
   // (Two more instances were built, measured on the MI355X and removed — profiles/r04_negative_results.txt sections 3 and

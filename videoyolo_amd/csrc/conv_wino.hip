@@ -98,25 +98,19 @@ __global__ __launch_bounds__(BM * 4, BM == 64 ? 2 : 1) void conv_wino_kernel(con
   constexpr int TNs = 2;  // wave tile: 32 pairs x 64 channels
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * A_ST + 2 * W_ST + BM * 24];
   long long* in_off = reinterpret_cast<long long*>(smem + 2 * A_ST + 2 * W_ST);  // element offset of the centre pixel of x0
-  // byte offsets of the pair's two pixels in `out` and in `res`, relative to the tile's first pixel (conv_split.hip's row
-  // tables); kInvalidRow: no such pixel (rows past the last pair; x0 + 1 of an odd width) — the store / load is dropped
+  // byte offsets of the pair's two pixels in `out` and in `res`, relative to the tile's first pixel (the row tables of
+  // conv_device.h, one pair per row); kInvalidRow: no such pixel (rows past the last pair; x0 + 1 of an odd width) — the
+  // store / load is dropped
   unsigned* o_off0 = reinterpret_cast<unsigned*>(in_off + BM);
   unsigned* o_off1 = o_off0 + BM;
   unsigned* r_off0 = o_off1 + BM;
   unsigned* r_off1 = r_off0 + BM;
-  constexpr unsigned kInvalidRow = 0x80000000u;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  const int h = lane >> 5, lrow = lane & 31;
+  const int h = MfmaCd32::group(lane), lrow = MfmaCd32::col(lane);
   const int cch = a.Kc >> 4;
-  // XCD-aware order (conv_igemm.hip): blocks L, L+8, ... share an L2; contiguous run of tiles per XCD, n fastest
-  int vblk;
-  {
-    const int nblk = gridDim.x, L = blockIdx.x;
-    const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
-    vblk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int vblk = vy_xcd_tile((int)blockIdx.x, (int)gridDim.x);
   const int tile_m = vblk / tiles_n, tile_n = vblk - tile_m * tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   long long pix0;
@@ -314,14 +308,9 @@ __global__ __launch_bounds__(BM * 4, BM == 64 ? 2 : 1) void conv_wino_kernel(con
   phase(std::integral_constant<int, 0>{});
   phase(std::integral_constant<int, 1>{});
 
-  // output transform, then the cell's epilogue (conv_igemm.hip): affine -> leaky -> + addend -> store, for both pixels,
-  // through buffer descriptors based at the tile's first pixel (an offset with bit 31 set is out of range: dropped).
-  // C/D map of the 32x32 MFMA: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-  constexpr int kRsrcFlags = 0x00020000;
-  const __amdgpu_buffer_rsrc_t out_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(a.out + (pix0 * a.o_cs + a.o_co + n0), 0, 0x7fffffff, kRsrcFlags);
-  const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.res ? a.res + (pix0 * a.r_cs + a.r_co + n0) : a.in), 0, 0x7fffffff, kRsrcFlags);
+  // output transform, then the cell's epilogue: affine -> leaky -> + addend -> store, for both pixels, through the
+  // descriptors and the C/D map of conv_device.h.  Its own element loop: two pixels per accumulator set, one variant pair
+  const __amdgpu_buffer_rsrc_t out_rsrc = conv_out_rsrc(a, pix0, n0), res_rsrc = conv_res_rsrc(a, pix0, n0);
   auto epilogue = [&](auto has_res_) {
     constexpr bool has_res = decltype(has_res_)::value;
 #pragma unroll
@@ -333,7 +322,7 @@ __global__ __launch_bounds__(BM * 4, BM == 64 ? 2 : 1) void conv_wino_kernel(con
       float rv0[16], rv1[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int row = MfmaCd32::row(wm * 32, h, r);
         oo0[r] = __builtin_elementwise_add_sat(o_off0[row], colc);
         oo1[r] = __builtin_elementwise_add_sat(o_off1[row], colc);
         if (has_res) {

@@ -80,6 +80,35 @@ struct ConvArgs {
 #define VY_SK_PARTIAL_BYTES (32u << 20)  // 512 blocks x 128x128 fp32 (the largest instance: 2 blocks per CU x 256 CUs)
 #define VY_SK_FLAGS 2048
 
+// What every conv launcher does to its ConvArgs before the launch (conv_igemm.hip, conv_split.hip).
+static inline VyFastDiv vy_fastdiv(unsigned d) {
+  unsigned l = 0;
+  while ((1ull << l) < d) ++l;
+  VyFastDiv f;
+  f.m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
+  f.s1 = l < 1 ? l : 1;
+  f.s2 = l > 0 ? l - 1 : 0;
+  return f;
+}
+// fills pk_dy / pk_dx / pk_w from the tap tables; false: a tap offset outside -1 .. 1 or a weight tap index above 15
+static inline bool vy_conv_pack_taps(ConvArgs& a) {
+  a.pk_dy = a.pk_dx = 0;
+  a.pk_w = 0;
+  for (int t = 0; t < a.ntaps; ++t) {
+    if (a.tap_dy[t] < -1 || a.tap_dy[t] > 1 || a.tap_dx[t] < -1 || a.tap_dx[t] > 1 || a.tap_w[t] > 15) return false;
+    a.pk_dy |= (unsigned)(a.tap_dy[t] + 1) << (2 * t);
+    a.pk_dx |= (unsigned)(a.tap_dx[t] + 1) << (2 * t);
+    a.pk_w |= (unsigned long long)a.tap_w[t] << (4 * t);
+  }
+  return true;
+}
+// the epilogue combinations the kernels instantiate (conv_epilogue, conv_device.h): BN cell (+ residual | x2-replicated),
+// or plain (raw / bias / gradient, + accumulate)
+static inline bool vy_conv_epilogue_supported(const ConvArgs& a) {
+  const bool bn_cell = a.scale && a.shift && a.leaky, plain = !a.scale && !a.leaky;
+  return (bn_cell && (a.ups != 2 || !a.res)) || (plain && a.ups != 2);
+}
+
 // 3x3/1x1 implicit-GEMM convolution on v_mfma_f32_32x32x2_f32.
 hipError_t vy_launch_conv_igemm(const ConvArgs& a, hipStream_t s);
 int vy_conv_tiles_m(const ConvArgs& a);
