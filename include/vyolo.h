@@ -37,7 +37,8 @@ enum vy_status {
   VY_ERR_INVALID = -1,      /* bad argument / unsupported configuration */
   VY_ERR_STATE = -2,        /* call order: buffers not bound, not planned, ... */
   VY_ERR_HIP = -3,          /* a HIP runtime call or kernel launch failed */
-  VY_ERR_UNSUPPORTED = -4   /* reference feature outside the hot path (temporal variants ...) */
+  VY_ERR_UNSUPPORTED = -4,  /* reference feature outside the hot path (temporal variants ...) */
+  VY_ERR_RANGE = -5         /* an index past the end of a list (vy_net_plan_region); leaves no error text */
 };
 
 enum vy_param_kind {
@@ -603,6 +604,26 @@ size_t vy_net_train_workspace_bytes(const vy_net* net, int32_t batch, int32_t he
  * ("training workspace not bound") until vy_net_bind_train is called again. */
 int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, int32_t height,
                       int32_t width, void* dev_grads, void* dev_momentum, void* stream);
+
+/* The regions a plan carves out of the workspace, one per call, in offset order: region `index` of the clip plan
+ * (VY_PLAN_CLIP: what vy_net_workspace_bytes sizes; frames, ring ignored), the training plan (VY_PLAN_TRAIN: the clip plan
+ * with every plane kept, then the training regions) or the video plan (VY_PLAN_VIDEO: batch counts clips) of the shape.
+ * name: the carve — "fold", "det.state" .. "det.score", "sk.flags", "sk.slabs", "ck", "wsplit:<cell>", "wino:<cell>",
+ * "plane:<the first cell that writes the slot>", "ring"; "dgrad_image:<cell>", "grad:<plane>", "z:<cell>", "train.save" ..
+ * "train.chunk", "wgrad_table:<cell>".  bytes: what the plan means the kernels to use, from offset on; span: the bytes up
+ * to the next region's offset (to the plan's total for the last one): bytes, the rounding to 256 and the guard gap.
+ * With VY_PLAN_GUARD=<n> in the environment when the net is created (0, the default, or a multiple of 256 up to 1 MiB;
+ * anything else counts as 0) every region is followed by n bytes that no launch may touch; the sizing queries and the
+ * binds count them in.  A host-side query like the sizing queries: it needs no device and no bound workspace, plans anew
+ * and changes nothing on the handle.  VY_ERR_RANGE for an index past the last region, VY_ERR_INVALID for a shape the
+ * matching sizing query refuses.  Tests only. */
+enum vy_plan_kind { VY_PLAN_CLIP = 0, VY_PLAN_TRAIN = 1, VY_PLAN_VIDEO = 2 };
+typedef struct vy_plan_region {
+  char name[96];
+  size_t offset, bytes, span;
+} vy_plan_region;
+int vy_net_plan_region(const vy_net* net, int32_t plan, int32_t batch, int32_t height, int32_t width, int32_t frames,
+                       int32_t ring, int32_t index, vy_plan_region* out);
 
 /* YOLOV3T(ignore_iou_thresh=0.7) (yolo3.py:962) and net._target_generator._label_smooth
  * (train_yolov3.py:499-500, yolo_target.py:272-278). */

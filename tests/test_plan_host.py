@@ -3,7 +3,9 @@
 tests/golden/net_plan_totals.json holds vy_net_workspace_bytes, vy_net_train_workspace_bytes and
 vy_net_video_workspace_bytes over a table that reaches every branch of the planner, recorded from the library as it was
 before the inference plan became a value (NetPlan): the totals must stay byte for byte.  A total pins the last offset of
-a plan; the offsets before it are held by the bit-exact GPU comparisons (tests/test_gpu_plan.py and the suites it names).
+a plan; the offsets before it are held region by region: tests/test_ws_guard_host.py pins the region table of every plan
+(ascending, disjoint, ending at the total), and tests/test_gpu_ws_guard.py shows on the device that no launch leaves the
+region it was given (the bit-exact comparisons of tests/test_gpu_plan.py see a stray write only where it lands on live bytes).
 Nothing here launches a kernel: the library plans without a device (vy_cu_count then answers 256, the MI355X's count).
 """
 import ctypes
@@ -72,6 +74,13 @@ def table(lib, setenv):
     return rows
 
 
+def _queries(lib, h, kind, b, hh, ww):
+    """_sizes, and as a fourth query the region tables of the same plans (vy_net_plan_region; tests/ws_guard.py)"""
+    import ws_guard
+    plans = [("clip", (b, hh, ww)), ("train", (b, hh, ww))] + [("video", (f, c, r, hh, ww)) for f, c, r in VIDEO if kind.startswith("window")]
+    return _sizes(lib, h, kind, b, hh, ww) + [ws_guard.regions(lib, h, plan, shape) for plan, shape in plans]
+
+
 def _cus_are_256():
     """The training totals depend on the CU count (the weight-gradient split-K): 256 without a device, and on an MI355X."""
     import torch
@@ -105,22 +114,22 @@ def test_totals_are_the_recorded_ones(monkeypatch):
 @pytest.mark.parametrize("kind", ["full", "heads", "window2"])
 def test_a_query_leaves_no_trace(kind):
     """A sizing query at another shape — and a conv-mode switch and back — between two identical queries: the second
-    answers what the first did, for all three queries."""
+    answers what the first did, for all three queries and for the region tables of their plans."""
     lib = _lib.load()
     h = _create(lib, kind, 20)
     try:
         for keep in (0, 1):
             _lib.check(lib.vy_net_set_keep_activations(h, keep))
             for a, b in ((SHAPES[1], SHAPES[3]), (SHAPES[3], SHAPES[0])):
-                first = _sizes(lib, h, kind, *a)
-                assert all(v > 0 for v in first), (kind, a, first)
-                other = _sizes(lib, h, kind, *b)
+                first = _queries(lib, h, kind, *a)
+                assert all(first), (kind, a, first)
+                other = _queries(lib, h, kind, *b)
                 assert other != first
                 if not kind.startswith("window"):
                     for mode in (_lib.VY_CONV_SPLIT_BF16X3, _lib.VY_CONV_SPLIT_BF16X3_TRAIN):
                         _lib.check(lib.vy_net_set_conv_mode(h, mode))
                         assert _sizes(lib, h, kind, *b)[0] > other[0]  # the weight images are in the plan
                     _lib.check(lib.vy_net_set_conv_mode(h, _lib.VY_CONV_EXACT_FP32))
-                assert _sizes(lib, h, kind, *a) == first, (kind, keep, a, b)
+                assert _queries(lib, h, kind, *a) == first, (kind, keep, a, b)
     finally:
         lib.vy_net_destroy(h)

@@ -46,6 +46,14 @@ class Semantics(ctypes.Structure):
                 ("bn_running_var_unbiased", ctypes.c_int32), ("reserved", ctypes.c_int32 * 10)]
 
 
+class PlanRegion(ctypes.Structure):
+    """vy_plan_region (include/vyolo.h): one carve of a workspace plan.  Tests only."""
+    _fields_ = [("name", ctypes.c_char * 96), ("offset", ctypes.c_size_t), ("bytes", ctypes.c_size_t), ("span", ctypes.c_size_t)]
+
+
+VY_PLAN_CLIP, VY_PLAN_TRAIN, VY_PLAN_VIDEO = 0, 1, 2
+VY_ERR_RANGE = -5
+
 _vp, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_size_t
 
 # name -> (restype, argtypes); the single source of truth for the exported-symbols test
@@ -93,6 +101,7 @@ SIGNATURES.update({
     "vy_preprocess_resize_frames": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vy_net_train_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "vy_net_bind_train": (ctypes.c_int, [_vp, _vp, _sz, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "vy_net_plan_region": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(PlanRegion)]),
     "vy_net_set_train_options": (ctypes.c_int, [_vp, _f32, _i32]),
     "vy_net_train_forward": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vy_net_train_mode_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -74,17 +74,29 @@ struct Scratch {
 
 __host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-__host__ __device__ inline Scratch carve(void* base, int B) {
+// bytes of the five sub-regions, in carve order (the score cache: C * n_items floats per image; carve does not need it)
+__host__ __device__ inline void scratch_sizes(int B, size_t score_floats, size_t* sz) {
+  sz[0] = sizeof(SelState) * (size_t)B;
+  sz[1] = sizeof(uint32_t) * (size_t)B * kBins;
+  sz[2] = sizeof(Entry) * (size_t)B * VY_NMS_MAX_TOPK;
+  sz[3] = sizeof(unsigned long long) * (size_t)B * kListCap;
+  sz[4] = sizeof(float) * (size_t)B * score_floats;
+}
+
+// guard: unused bytes the plan leaves behind each sub-region (DetArgs::guard; 0 outside the tests)
+__host__ __device__ inline Scratch carve(void* base, int B, int guard) {
   unsigned char* p = (unsigned char*)base;
+  size_t sz[5];
+  scratch_sizes(B, 0, sz);
   Scratch s;
   s.st = (SelState*)p;
-  p += align256(sizeof(SelState) * (size_t)B);
+  p += align256(sz[0]) + guard;
   s.hist = (uint32_t*)p;
-  p += align256(sizeof(uint32_t) * (size_t)B * kBins);
+  p += align256(sz[1]) + guard;
   s.ent = (Entry*)p;
-  p += align256(sizeof(Entry) * (size_t)B * VY_NMS_MAX_TOPK);
+  p += align256(sz[2]) + guard;
   s.list = (unsigned long long*)p;
-  p += align256(sizeof(unsigned long long) * (size_t)B * kListCap);
+  p += align256(sz[3]) + guard;
   s.score = (float*)p;
   return s;
 }
@@ -208,7 +220,7 @@ __host__ __device__ inline int hist_blocks_of(int hw, int cs) { return (hw + his
 
 __global__ __launch_bounds__(kHistThreads) void hist_kernel(const DetArgs d, void* scratch, int pass, int n_items) {
   const int b = blockIdx.y;
-  Scratch sc = carve(scratch, d.B);
+  Scratch sc = carve(scratch, d.B, d.guard);
   __shared__ __attribute__((aligned(16))) float tile[kTileFloats];
   __shared__ float conf[kPxMax * 3];
   __shared__ uint32_t lh[kBins];
@@ -260,7 +272,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const DetArgs d, voi
 // fix that digit, zero the histogram for the next pass.
 __global__ __launch_bounds__(kBins) void select_kernel(const DetArgs d, void* scratch, int pass) {
   const int b = blockIdx.x;
-  Scratch sc = carve(scratch, d.B);
+  Scratch sc = carve(scratch, d.B, d.guard);
   SelState* st = sc.st + b;
   if (st->done) return;
   uint32_t* gh = sc.hist + (size_t)b * kBins;
@@ -367,7 +379,7 @@ __device__ __forceinline__ void put_entry(const DetArgs& d, Entry* ent, SelState
 template <int IPT>
 __global__ __launch_bounds__(kHistThreads) void compact_kernel(const DetArgs d, void* scratch, int n_items, int cg_per_z) {
   const int b = blockIdx.y;
-  Scratch sc = carve(scratch, d.B);
+  Scratch sc = carve(scratch, d.B, d.guard);
   SelState* stp = sc.st + b;
   const uint32_t Tb = stp->Tb;
   if (stp->k_eff <= 0) return;
@@ -413,7 +425,7 @@ __global__ __launch_bounds__(kHistThreads) void compact_kernel(const DetArgs d, 
 // score cache), then the list members at or above the exact threshold become entries
 __global__ __launch_bounds__(kBins) void refine_kernel(const DetArgs d, void* scratch, int n_items) {
   const int b = blockIdx.x, t = threadIdx.x;
-  Scratch sc = carve(scratch, d.B);
+  Scratch sc = carve(scratch, d.B, d.guard);
   SelState* stp = sc.st + b;
   __shared__ SelState st;
   __shared__ uint32_t hist[kBins];
@@ -521,7 +533,7 @@ __global__ __launch_bounds__(kNmsThreads) void sort_nms_kernel(const DetArgs d, 
                                                                float* scores, float* bboxes, int32_t* keep_idx) {
   static_assert(kNmsThreads == VY_NMS_MAX_TOPK, "one candidate per thread");
   const int b = blockIdx.x;
-  Scratch sc = carve(scratch, d.B);
+  Scratch sc = carve(scratch, d.B, d.guard);
   const SelState st = sc.st[b];
   const Entry* ent = sc.ent + (size_t)b * VY_NMS_MAX_TOPK;
   __shared__ __attribute__((aligned(16))) unsigned long long key[VY_NMS_MAX_TOPK];
@@ -720,7 +732,7 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
                                                               int topk_cap, float* ids, float* scores, float* bboxes,
                                                               int32_t* keep_idx) {
   const int b = blockIdx.x, t = threadIdx.x;
-  Scratch sc = carve(scratch, d.B);
+  Scratch sc = carve(scratch, d.B, d.guard);
   const float* cache = sc.score + (size_t)b * d.C * n_items;
   __shared__ uint32_t hist[kBins];
   __shared__ unsigned long long key[VY_NMS_MAX_TOPK];
@@ -993,10 +1005,15 @@ hipError_t vy_launch_raw_detections(const DetArgs& a, float* ids, float* scores,
   return hipGetLastError();
 }
 
-size_t vy_det_scratch_bytes(int B, int n_items, int C) {
-  return align256(sizeof(SelState) * (size_t)B) + align256(sizeof(uint32_t) * (size_t)B * kBins) +
-         align256(sizeof(Entry) * (size_t)B * VY_NMS_MAX_TOPK) +
-         align256(sizeof(unsigned long long) * (size_t)B * kListCap) + align256(sizeof(float) * (size_t)B * C * n_items);
+size_t vy_det_scratch_layout(int B, int n_items, int C, int guard, size_t* off, size_t* used) {
+  size_t sz[5], at = 0;
+  scratch_sizes(B, (size_t)C * n_items, sz);
+  for (int i = 0; i < 5; ++i) {
+    if (off) off[i] = at;
+    if (used) used[i] = sz[i];
+    at += align256(sz[i]) + guard;
+  }
+  return at;
 }
 
 hipError_t vy_launch_detect(const DetArgs& a, void* scratch, float* ids, float* scores, float* bboxes,
@@ -1009,11 +1026,14 @@ hipError_t vy_launch_detect(const DetArgs& a, void* scratch, float* ids, float* 
   // rows of the output: post_nms, else nms_topk (no slice, yolo3.py:1201-1202), else — both "disabled" — all N*C rows
   const int rows = a.post_nms > 0 ? a.post_nms : (a.topk > 0 ? a.topk : a.n_cand);
   // state + histogram region back to zero (entries need no clearing)
-  hipError_t e = hipMemsetAsync(scratch, 0,
-                                align256(sizeof(SelState) * (size_t)a.B) +
-                                    align256(sizeof(uint32_t) * (size_t)a.B * kBins),
-                                s);
+  size_t sz[5];
+  scratch_sizes(a.B, 0, sz);
+  hipError_t e = hipMemsetAsync(scratch, 0, a.guard ? sz[0] : align256(sz[0]) + align256(sz[1]), s);
   if (e != hipSuccess) return e;
+  if (a.guard) {  // (two regions with a gap between them: neither the gap nor the slack is touched)
+    e = hipMemsetAsync(carve(scratch, a.B, a.guard).hist, 0, sz[1], s);
+    if (e != hipSuccess) return e;
+  }
   int n_items = 0;
   for (int i = 0; i < 3; ++i) n_items += a.head[i].H * a.head[i].W * 3;
   const int per_block = kHistThreads * kItemsPerThread;

@@ -341,8 +341,12 @@ struct DetArgs {
   int tie_desc;         // equal scores in descending candidate row (default: ascending)
   int topk_after;       // the top-k cut follows suppression (default: precedes it)
   int iou_plus1;        // IoU with +1 on widths and heights (default: without)
+  int guard;            // bytes the plan leaves unused behind each sub-region of the scratch (VY_PLAN_GUARD; 0 otherwise)
 };
-size_t vy_det_scratch_bytes(int B, int n_items, int C);  // n_items = anchors per image (N), C = classes
+// The scratch of the tail: five sub-regions laid end to end — state, histogram, entries, bucket list, score cache — each
+// rounded to 256 bytes and followed by `guard` bytes.  n_items = anchors per image (N), C = classes.  Returns the total;
+// off / used (5 each, may be null): where each sub-region starts and the bytes the kernels use of it
+size_t vy_det_scratch_layout(int B, int n_items, int C, int guard, size_t* off, size_t* used);
 // full tail: decode -> radix select of the top-k valid scores -> sort -> per-class NMS -> outputs
 // nms off: the full (B, N*C, .) detection tensor in the reference's row order
 hipError_t vy_launch_raw_detections(const DetArgs& a, float* ids, float* scores, float* bboxes, int32_t* keep_idx,

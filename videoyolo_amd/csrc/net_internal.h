@@ -93,7 +93,9 @@ struct NetPlan {
   // pooled routes on hold B clips, and behind the planes lies a ring of video_R slots of per-frame routes (video.hip).
   // 0: the clip plan — binding either way switches the net over
   int video_F = 0, video_R = 0;
-  size_t fold_desc_off = 0, det_scratch_off = 0, sk_off = 0;  // byte offsets in the workspace
+  size_t fold_desc_off = 0, det_scratch_off = 0;  // byte offsets in the workspace
+  size_t sk_off = 0, sk_slabs_off = 0;  // stream-K scratch of the conv launches (conv_igemm.hip): the flags, the slabs
+  int guard = 0;  // unused bytes behind every carve (VY_PLAN_GUARD; 0 outside the tests)
   size_t ck_off = 0, ck_bytes = 0;  // running-sum scratch of the convs whose K is summed in runs (conv_igemm.hip)
   size_t wsplit_off = 0, planes_off = 0;
   size_t ring_off = 0;             // the ring of a video plan
@@ -111,6 +113,13 @@ struct NetPlan {
   };
   std::vector<Plane> planes;  // per plane of the graph
   std::vector<Conv> convs;    // per conv
+};
+
+// One carve of a plan, for the tests' region table (vy_net_plan_region): its name, its byte offset in the workspace and the
+// bytes the kernels are meant to use of it — the rounding to 256 and the guard gap follow
+struct PlanRegion {
+  std::string name;
+  size_t off, used;
 };
 
 // a plane of the graph where the committed plan put it (vy_net::plane)
@@ -579,17 +588,38 @@ struct vy_net {
     return slot;
   }
 
+  // what a plane is called in the region table: the first cell that writes it, else the pool of a hierarchical net that
+  // does, else the route that is imported / pooled into it
+  std::string plane_name(int p) const {
+    for (const ConvT& c : convs)
+      if (c.out_plane == p) return c.name;
+    for (size_t i = 0; i < hpools.size(); ++i)
+      if (hpools[i].dst == p) return "hpool." + std::to_string(i);
+    for (int i = 0; i < 3; ++i)
+      if (routes[i].plane == p) return "route." + std::to_string(i);
+    return "plane." + std::to_string(p);
+  }
+
   // frames / ring: a video plan (vy_net_bind_video) — `frames` single frames in the stem and stage planes instead of b*k,
-  // b clips from the pooled routes on, and `ring` route slots behind the planes; 0, 0: the clip plan
-  NetPlan plan(int b, int h, int w, bool keep_all, int frames = 0, int ring = 0) const {
+  // b clips from the pooled routes on, and `ring` route slots behind the planes; 0, 0: the clip plan.
+  // regions (tests: vy_net_plan_region): every carve is appended to it, in offset order
+  NetPlan plan(int b, int h, int w, bool keep_all, int frames = 0, int ring = 0, std::vector<PlanRegion>* regions = nullptr) const {
     NetPlan p;
     p.B = b;
     p.H = h;
     p.W = w;
     p.planes_shared = !keep_all;
+    p.guard = knobs.plan_guard;
     size_t off = 0;
-    p.fold_desc_off = off;
-    off += al(sizeof(FoldDesc) * folds.size());
+    // one carve: `bytes` at the running offset, rounded up to 256, then the guard gap; no bytes, no carve
+    auto take = [&](size_t bytes, const char* kind, const std::string& what = std::string()) {
+      const size_t at = off;
+      if (!bytes) return at;
+      if (regions) regions->push_back({what.empty() ? std::string(kind) : kind + (":" + what), at, bytes});
+      off += al(bytes) + (size_t)p.guard;
+      return at;
+    };
+    p.fold_desc_off = take(sizeof(FoldDesc) * folds.size(), "fold");
     p.det_scratch_off = off;
     int n_items = 0;
     // a plane's spatial size = ceil(input / div): every stride-2 3x3 pad-1 conv maps n rows to ceil(n / 2), and the
@@ -597,12 +627,17 @@ struct vy_net {
     // multiples of 32
     auto cdiv = [](int a, int d) { return (a + d - 1) / d; };
     for (int i = 0; i < 3; ++i) n_items += 3 * cdiv(h, planes[head_plane[i]].div) * cdiv(w, planes[head_plane[i]].div);
-    off += al(vy_det_scratch_bytes(b, n_items, num_class));
-    p.sk_off = off;  // stream-K scratch of the conv launches (conv_igemm.hip): flags first, then the slabs
-    off += al((size_t)VY_SK_FLAGS * sizeof(unsigned)) + al(VY_SK_PARTIAL_BYTES);
+    {  // the detection scratch carves its five sub-regions itself (detect.hip)
+      static const char* const kDet[5] = {"det.state", "det.hist", "det.entries", "det.list", "det.score"};
+      size_t d_off[5], d_used[5];
+      const size_t det_bytes = vy_det_scratch_layout(b, n_items, num_class, p.guard, d_off, d_used);
+      for (int i = 0; i < 5 && regions; ++i) regions->push_back({kDet[i], off + d_off[i], d_used[i]});
+      off += det_bytes;
+    }
+    p.sk_off = take((size_t)VY_SK_FLAGS * sizeof(unsigned), "sk.flags");
+    p.sk_slabs_off = take(VY_SK_PARTIAL_BYTES, "sk.slabs");
     // parked chains of the convs whose K is summed in runs (vy_conv_k_chunks; conv_igemm.hip `boundary`): runs - 1 tile-shaped
     // slabs per output tile of the conv that needs most
-    p.ck_off = off;
     for (const ConvT& c : convs) {
       const int runs = c.is_stem ? 1 : vy_conv_runs(c.k * c.k, (c.cin + 31) >> 5);
       if (runs < 2) continue;
@@ -610,21 +645,17 @@ struct vy_net {
       const long long Mo = (long long)backbone_frames(op, b, frames) * cdiv(h, op.div) * cdiv(w, op.div);
       p.ck_bytes = std::max(p.ck_bytes, vy_conv_chunk_scratch_bytes(Mo, c.cout, runs));
     }
-    off += al(p.ck_bytes);
+    p.ck_off = take(p.ck_bytes, "ck");
     p.wsplit_off = off;  // split-fp32 weight images (conv mode VY_CONV_SPLIT_BF16X3 only)
     p.convs.resize(convs.size());
     for (size_t i = 0; i < convs.size(); ++i) {
       const ConvT& c = convs[i];
       if (!split_eligible(c)) continue;
-      p.convs[i].split_off = (int64_t)(off - p.wsplit_off);
-      off += al(vy_split_weight_bytes(c.cout, c.k * c.k, c.cin));
-      if (c.k == 3 && c.stride == 1 && c.ups == 1 && c.cout % 128 == 0) {
-        p.convs[i].wino_off = (int64_t)(off - p.wsplit_off);
-        off += al(vy_wino_weight_bytes(c.cout, c.cin));
-      }
+      p.convs[i].split_off = (int64_t)(take(vy_split_weight_bytes(c.cout, c.k * c.k, c.cin), "wsplit", c.name) - p.wsplit_off);
+      if (c.k == 3 && c.stride == 1 && c.ups == 1 && c.cout % 128 == 0)
+        p.convs[i].wino_off = (int64_t)(take(vy_wino_weight_bytes(c.cout, c.cin), "wino", c.name) - p.wsplit_off);
     }
     p.planes_off = off;
-    size_t fl = 0;
     const std::vector<int> slot = plane_slots(keep_all);
     p.planes.resize(planes.size());
     for (size_t i = 0; i < planes.size(); ++i) {
@@ -632,19 +663,17 @@ struct vy_net {
       NetPlan::Plane& q = p.planes[i];
       q.H = cdiv(h, g.div);
       q.W = cdiv(w, g.div);
-      if ((size_t)slot[i] == i) {  // owns its storage
-        q.off = fl;
-        fl += ((size_t)backbone_frames(g, b, frames) * (q.H + 2) * (q.W + 2) * g.C + 63) & ~(size_t)63;
-      }
+      if ((size_t)slot[i] == i)  // owns its storage
+        q.off = (take((size_t)backbone_frames(g, b, frames) * (q.H + 2) * (q.W + 2) * g.C * sizeof(float), "plane",
+                      regions ? plane_name((int)i) : std::string()) - p.planes_off) / sizeof(float);
     }
     for (size_t i = 0; i < planes.size(); ++i) p.planes[i].off = p.planes[slot[i]].off;  // (an owner may come later)
-    off += fl * sizeof(float);
-    p.ring_off = al(off);
+    p.ring_off = off;
     if (ring > 0) {
       p.video_F = frames;
       p.video_R = ring;
       p.ring_slot_floats = slot_floats(h, w);
-      off = p.ring_off + (size_t)ring * p.ring_slot_floats * sizeof(float);
+      take((size_t)ring * p.ring_slot_floats * sizeof(float), "ring");
     }
     p.total = off;
     return p;
@@ -767,7 +796,7 @@ struct vy_net {
 
   int sk_begin(hipStream_t s) {
     if (sk_dirty && dev_ws) {
-      HIP_TRY(hipMemsetAsync(dev_ws + cur.sk_off, 0, al((size_t)VY_SK_FLAGS * sizeof(unsigned)), s));
+      HIP_TRY(hipMemsetAsync(dev_ws + cur.sk_off, 0, (size_t)VY_SK_FLAGS * sizeof(unsigned), s));
       sk_dirty = false;
     }
     return 0;
@@ -784,7 +813,7 @@ struct vy_net {
   void launch_env(ConvArgs& a, bool k_runs, bool splitk) const {
     a.knobs = &knobs;
     a.cus = cus;
-    float* const sk_slabs = reinterpret_cast<float*>(dev_ws + cur.sk_off + al((size_t)VY_SK_FLAGS * sizeof(unsigned)));
+    float* const sk_slabs = reinterpret_cast<float*>(dev_ws + cur.sk_slabs_off);
     if (k_runs) {
       a.ck_scratch = cur.ck_bytes ? reinterpret_cast<float*>(dev_ws + cur.ck_off) : nullptr;
       a.ck_bytes = cur.ck_bytes;
@@ -852,6 +881,7 @@ struct vy_net {
     d.tie_desc = sem.nms_tie_descending;
     d.topk_after = sem.nms_topk_after;
     d.iou_plus1 = sem.nms_iou_plus_one;
+    d.guard = cur.guard;
     return d;
   }
 

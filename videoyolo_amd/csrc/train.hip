@@ -206,15 +206,25 @@ void wgrad_split_k(long long M, long long tiles, long long held, int* splits, in
 
 // The training regions behind the inference plan `fwd` (of the same shape, every plane kept: backward reads them all), and
 // everything the step derives from the shape.  Reads the per-parameter options of `opt`; writes nothing.
-TrainPlan plan_train(const vy_net& net, const VyTrain& opt, const NetPlan& fwd, int b, int h, int w) {
+// regions (tests: vy_net_plan_region): every carve is appended to it, in offset order
+TrainPlan plan_train(const vy_net& net, const VyTrain& opt, const NetPlan& fwd, int b, int h, int w,
+                     std::vector<PlanRegion>* regions = nullptr) {
   TrainPlan p;
   p.B = b;
   p.H = h;
   p.W = w;
-  struct {  // carves 256-byte aligned regions off the workspace, in call order
-    size_t off;
-    size_t take(size_t bytes) { return std::exchange(off, off + vy_net::al(bytes)); }
-  } ws{vy_net::al(fwd.total)};
+  // carves 256-byte aligned regions off the workspace, in call order, each followed by the guard gap of the inference plan
+  // (VY_PLAN_GUARD; 0 outside the tests); no bytes, no carve
+  struct {
+    size_t off, guard;
+    std::vector<PlanRegion>* regions;
+    size_t take(size_t bytes, const char* kind, const std::string& what = std::string()) {
+      if (!bytes) return off;
+      if (regions) regions->push_back({what.empty() ? std::string(kind) : kind + (":" + what), off, bytes});
+      return std::exchange(off, off + vy_net::al(bytes) + guard);
+    }
+  } ws{vy_net::al(fwd.total), (size_t)fwd.guard, regions};
+  const size_t gap_fl = ws.guard / sizeof(float);  // the gap behind a gradient or z plane, in floats
   const size_t n = net.convs.size();
   p.cells.resize(n);
   // split-fp32 training mode: the data gradients whose N (= cin) the split kernel has a tile for get their own weight
@@ -233,16 +243,19 @@ TrainPlan plan_train(const vy_net& net, const VyTrain& opt, const NetPlan& fwd, 
     cell.bucket = c.name.rfind("stages.2", 0) == 0 ? 1 : c.name.rfind("stages.1", 0) == 0 ? 2 : c.name.rfind("stages.0", 0) == 0 ? 3 : 0;
     cell.fwd_split = images && st != 3 && net.split_eligible(c);
     if (images && !c.is_stem && c.cin % 64 == 0) {
-      cell.dsplit = (long long)(ws.take(vy_split_weight_dgrad_bytes(c.cout, c.k * c.k, c.cin)) - p.dsplit_off);
+      cell.dsplit = (long long)(ws.take(vy_split_weight_dgrad_bytes(c.cout, c.k * c.k, c.cin), "dgrad_image", c.name) - p.dsplit_off);
       cell.dgrad_split = st != 2;
     }
   }
-  // gradient planes mirror the activation planes
-  size_t gfl = 0;
-  for (auto& pl : net.planes) gfl += ((size_t)b * pl.fm * (h / pl.div + 2) * (w / pl.div + 2) * pl.C + 63) & ~(size_t)63;
-  p.g_off = ws.take(gfl * sizeof(float));
+  // gradient planes mirror the activation planes (of a plan that keeps them all: fwd.planes[i].off, gaps included)
+  p.g_off = ws.off;
+  for (size_t i = 0; i < net.planes.size(); ++i) {
+    const PlaneT& pl = net.planes[i];
+    ws.take((size_t)b * pl.fm * (h / pl.div + 2) * (w / pl.div + 2) * pl.C * sizeof(float), "grad", regions ? net.plane_name((int)i) : std::string());
+  }
   // z planes and saved statistics: one per BN conv; the partial-sum and slab scratch: the largest any conv needs
   size_t zfl = 0, sfl = 0, part = 0, slab = 0;
+  std::vector<size_t> z_used(n, 0);  // bytes of each z plane
   for (size_t i = 0; i < n; ++i) {
     const ConvT& c = net.convs[i];
     TrainCell& cell = p.cells[i];
@@ -251,7 +264,8 @@ TrainPlan plan_train(const vy_net& net, const VyTrain& opt, const NetPlan& fwd, 
     if (c.p_gamma >= 0) {
       cell.z_cs = c.cout;
       cell.z_off = zfl;
-      zfl += ((size_t)cell.B * (cell.Ho + 2) * (cell.Wo + 2) * c.cout + 63) & ~(size_t)63;
+      z_used[i] = (size_t)cell.B * (cell.Ho + 2) * (cell.Wo + 2) * c.cout * sizeof(float);
+      zfl += vy_net::al(z_used[i]) / sizeof(float) + gap_fl;
       cell.save_off = sfl;
       sfl += 2 * (size_t)((c.cout + 63) & ~63);
       // partials: forward stats, backward sums
@@ -275,21 +289,22 @@ TrainPlan plan_train(const vy_net& net, const VyTrain& opt, const NetPlan& fwd, 
       slab = std::max(slab, (size_t)cell.splits * c.cout * Ntot);
     }
   }
-  p.z_off = ws.take(zfl * sizeof(float));
-  p.save_off = ws.take(sfl * sizeof(float));
-  p.coef_off = ws.take(3 * 1024 * sizeof(float));
-  p.sums_off = ws.take(2 * 2 * 1024 * sizeof(double));  // [global | local] x [2][C]
-  p.slice_off = ws.take((size_t)VY_REDUCE_SLICES * 2 * 1024 * sizeof(double));  // slice sums of long per-tile statistics lists
-  p.part_off = ws.take(part * sizeof(float));
-  p.slab_off = ws.take(slab * sizeof(float));
+  p.z_off = ws.off;
+  for (size_t i = 0; i < n; ++i) ws.take(z_used[i], "z", net.convs[i].name);  // (cell.z_off: the same walk, above)
+  p.save_off = ws.take(sfl * sizeof(float), "train.save");
+  p.coef_off = ws.take(3 * 1024 * sizeof(float), "train.coef");
+  p.sums_off = ws.take(2 * 2 * 1024 * sizeof(double), "train.sums");  // [global | local] x [2][C]
+  p.slice_off = ws.take((size_t)VY_REDUCE_SLICES * 2 * 1024 * sizeof(double), "train.slices");  // slice sums of long per-tile statistics lists
+  p.part_off = ws.take(part * sizeof(float), "train.part");
+  p.slab_off = ws.take(slab * sizeof(float), "train.slab");
   int N = 0;
   for (int i = 0; i < 3; ++i) {
     const int dv = net.planes[net.head_plane[i]].div;
     N += 3 * (h / dv) * (w / dv);
   }
-  p.loss_part_off = ws.take((size_t)vy_loss_blocks_per_image(N) * b * 4 * sizeof(float));
-  p.loss_off = ws.take((size_t)4 * b * sizeof(float));
-  p.zero_off = ws.take(1024);
+  p.loss_part_off = ws.take((size_t)vy_loss_blocks_per_image(N) * b * 4 * sizeof(float), "train.loss_part");
+  p.loss_off = ws.take((size_t)4 * b * sizeof(float), "train.loss");
+  p.zero_off = ws.take(1024, "train.zero");
   // SGD segment tables
   for (size_t i = 0; i < net.params.size(); ++i) {
     const vy_param_info& pi = net.params[i].info;
@@ -304,10 +319,10 @@ TrainPlan plan_train(const vy_net& net, const VyTrain& opt, const NetPlan& fwd, 
   }
   // weight-gradient pixel tables (wgrad.hip): 8 bytes per output pixel of every conv but the stem
   for (size_t i = 0; i < n; ++i)
-    if (!net.convs[i].is_stem) p.cells[i].tab_off = ws.take(vy_wgrad_table_entries(p.cells[i].M) * 8);
-  p.sdesc_off = ws.take(sizeof(SplitDesc) * 2 * n);
-  p.seg_off = ws.take(p.segs.size() * sizeof(SgdSeg));
-  p.chunk_off = ws.take(p.chunk_seg.size() * sizeof(int32_t));
+    if (!net.convs[i].is_stem) p.cells[i].tab_off = ws.take(vy_wgrad_table_entries(p.cells[i].M) * 8, "wgrad_table", net.convs[i].name);
+  p.sdesc_off = ws.take(sizeof(SplitDesc) * 2 * n, "train.sdesc");
+  p.seg_off = ws.take(p.segs.size() * sizeof(SgdSeg), "train.seg");
+  p.chunk_off = ws.take(p.chunk_seg.size() * sizeof(int32_t), "train.chunk");
   p.total = ws.off;
   // the image sets and the gradient buckets' parameter ranges
   int64_t lo[4] = {INT64_MAX, INT64_MAX, INT64_MAX, INT64_MAX}, hi[4] = {0, 0, 0, 0};
@@ -1026,6 +1041,37 @@ size_t vy_net_train_workspace_bytes(const vy_net* net, int32_t batch, int32_t he
   VyTrain fresh;  // (a query allocates nothing on the net)
   default_options(*net, &fresh);
   return plan_train(*net, fresh, fwd, batch, height, width).total;
+}
+
+// Plans anew at every call, as the sizing queries do, and keeps nothing
+int vy_net_plan_region(const vy_net* net, int32_t plan, int32_t batch, int32_t height, int32_t width, int32_t frames,
+                       int32_t ring, int32_t index, vy_plan_region* out) {
+  if (!net || !out || index < 0) return fail(VY_ERR_INVALID, "vy_net_plan_region: bad argument");
+  std::vector<PlanRegion> regions;
+  size_t total = 0;
+  if (plan == VY_PLAN_CLIP) {
+    if (!vy_net_workspace_bytes(net, batch, height, width)) return VY_ERR_INVALID;
+    total = net->plan(batch, height, width, net->keep_activations, 0, 0, &regions).total;
+  } else if (plan == VY_PLAN_VIDEO) {
+    if (!vy_net_video_workspace_bytes(net, frames, batch, ring, height, width)) return VY_ERR_INVALID;
+    total = net->plan(batch, height, width, net->keep_activations, frames, ring, &regions).total;
+  } else if (plan == VY_PLAN_TRAIN) {
+    if (!vy_net_train_workspace_bytes(net, batch, height, width)) return VY_ERR_INVALID;
+    const NetPlan fwd = net->plan(batch, height, width, /*keep_all=*/true, 0, 0, &regions);
+    VyTrain fresh;
+    if (!net->train) default_options(*net, &fresh);
+    total = plan_train(*net, net->train ? *net->train : fresh, fwd, batch, height, width, &regions).total;
+  } else {
+    return fail(VY_ERR_INVALID, "vy_net_plan_region: plan %d", plan);
+  }
+  if ((size_t)index >= regions.size()) return VY_ERR_RANGE;  // (the end of the list: not worth an error text)
+  const PlanRegion& r = regions[index];
+  memset(out, 0, sizeof *out);
+  snprintf(out->name, sizeof out->name, "%s", r.name.c_str());
+  out->offset = r.off;
+  out->bytes = r.used;
+  out->span = ((size_t)index + 1 < regions.size() ? regions[index + 1].off : total) - r.off;
+  return 0;
 }
 
 int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, int32_t height, int32_t width,
