@@ -112,6 +112,37 @@ def _ptrs(tensors):
     return [None if t is None else ctypes.c_void_p(t.data_ptr()) for t in tensors]
 
 
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else tuple(np.shape(a))
+
+
+_ROUTES = ((256, 8), (512, 16), (1024, 32))  # (channels, stride) of the three Darknet-53 routes: features[:15], [15:24], [24:]
+
+
+def _route_shapes(n, h, w, unit=1):
+    """Shapes of the three routes of n frames of h x w (sizes rounded up); h, w in units of `unit` pixels — 8: the first
+    route's own size."""
+    return [(n, c, -(-h // (s // unit)), -(-w // (s // unit))) for c, s in _ROUTES]
+
+
+def _route_geometry(fs):
+    """(n, h, w) of the first of the shapes `fs` if they are the three routes of the same n >= 1 frames with h, w in [4, 512],
+    else None: the caller words the error."""
+    if any(len(s) != 4 for s in fs):
+        return None
+    n, _, h8, w8 = fs[0]
+    if fs != _route_shapes(n, h8, w8, 8) or n < 1 or min(h8, w8) < 4 or max(h8, w8) > 512:
+        return None
+    return n, h8, w8
+
+
+def _refusal(message):
+    """An entry point that a kind of net does not have: the method that raises NotImplementedError(message)."""
+    def refuse(self, *args, **kwargs):
+        raise NotImplementedError(message)
+    return refuse
+
+
 def _read_param_file(filename):
     """{name: array} of a parameter file in either container (sniffed from the first bytes: zip = .npz, else mxnet's
     NDArray-dict layout, 0x112)."""
@@ -128,7 +159,13 @@ class YOLOV3(object):
     """yolo3_darknet53 detector bound to one device / stream."""
 
     _CREATE = "vy_net_create"  # the library constructor of this graph
-    _TRAIN_ENTRY = ""          # suffix of the library's training entries ("_routes": they take the three route tensors)
+    _ENTRY = ""                # suffix of the library's forward entries ("_routes": they take the three route tensors)
+    _BACKWARD = "vy_net_train_backward"
+    # the library's backward reads the inputs of the recorded forward, so they are held until then (False: it ignores them
+    # for this kind — nothing is back-propagated into banks, include/vyolo.h vy_net_train_backward_routes — takes None in
+    # their place, and nothing needs to be held)
+    _BACKWARD_READS_INPUTS = True
+    _USAGE = "training call: net(x, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)"
     _ONE_RANK = None           # a kind of net that trains on one rank only names itself here (_single_rank)
     _EXCHANGES = True          # train-mode forwards keep the replicas and the SyncBatchNorm statistics of the ranks in step
 
@@ -154,8 +191,9 @@ class YOLOV3(object):
             info = _lib.ParamInfo()
             _lib.check(self._lib.vy_net_param_info(self._h, i, ctypes.byref(info)))
             p = Parameter(self, i, info)
+            p.name = self._key(p.name)
             self._params[p.name] = p
-        self._host = {}          # name -> numpy (reference layout) while not on a device
+        self._host = {}          # name -> numpy (reference layout) until reset_ctx moves them to a device
         self._dev_params = None  # torch uint8 tensor holding the device parameter buffer
         self._ws = None          # torch uint8 workspace
         self._plan = None        # (B, H, W, train?) the workspace is planned for
@@ -186,9 +224,16 @@ class YOLOV3(object):
         """Constructor arguments beyond the common ones that a copy of this net needs (reset_class, deepcopy)."""
         return {}
 
-    def _bhw(self, x):
-        """(batch, height, width) of an input checked by ``_as_input``."""
-        return x.shape[0], x.shape[2], x.shape[3]
+    def _need_device(self):
+        """The one device check.  ``_dev_params`` and ``_device`` are set together (reset_ctx) and cleared together
+        (reset_class), so either says it; the buffer is the one that is still None after a reset_ctx that failed half way."""
+        if self._dev_params is None:
+            raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
+
+    def _drop_plan(self):
+        """The plan changed or the binding went: size and bind the workspace again at the next call."""
+        self._plan = None
+        self._graphs = {}
 
     def _tap_batch(self, name):
         """Leading dimension of tap `name` in the bound plan: the library's frames per batch entry, whatever the net."""
@@ -198,7 +243,8 @@ class YOLOV3(object):
 
     @staticmethod
     def _key(name):
-        """Structural library name -> this model's parameter key (the same, for every net but the window net)."""
+        """Structural library name, or a file's spelling of it -> this model's parameter key (the same, for the
+        single-frame nets)."""
         return name
 
     def __del__(self):
@@ -396,6 +442,7 @@ class YOLOV3(object):
         """Load a {structural name: array} dict (reference layouts).  The anchors / offsets Constants of a
         reference checkpoint are checked against the built-in ones (a file made with other anchors cannot be
         run by this fixed-anchor path) and otherwise consumed silently; they may also be absent."""
+        arrays = OrderedDict((self._key(k), v) for k, v in arrays.items())
         consts = None
         for k, v in arrays.items():
             m = self._CONST_RE.match(k)
@@ -460,8 +507,7 @@ class YOLOV3(object):
         batch 64), like the intermediates of the reference's hybridized graph; training plans always keep them."""
         _lib.check(self._lib.vy_net_set_keep_activations(self._h, int(bool(keep))))
         self._keep_activations = bool(keep)
-        self._plan = None      # the plan changed: size and bind the workspace again at the next call
-        self._graphs = {}
+        self._drop_plan()
 
     def set_conv_mode(self, mode="exact"):
         """Arithmetic of the inference convolutions (no counterpart in the reference: mxnet picks its conv
@@ -476,8 +522,7 @@ class YOLOV3(object):
             raise ValueError("conv mode %r: expected one of %s" % (mode, sorted(modes)))
         _lib.check(self._lib.vy_net_set_conv_mode(self._h, modes[mode]))
         self._conv_mode = mode
-        self._plan = None      # the plan changed: size and bind the workspace again at the next call
-        self._graphs = {}
+        self._drop_plan()
         tw = getattr(self, "_twin", None)
         if tw is not None:
             # the twin never trains: any split mode is the inference one there, as at its creation (detect_two_streams) —
@@ -624,30 +669,37 @@ class YOLOV3(object):
         return twin
 
     # ------------------------------------------------------------------ execution
-    def _ensure_plan(self, b, h, w, train=False):
-        torch = _torch()
-        if self._dev_params is None:
-            raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
-        if self._plan is not None and self._plan[:3] == (b, h, w) and (self._plan[3] or not train):
-            return
-        fn = self._lib.vy_net_train_workspace_bytes if train else self._lib.vy_net_workspace_bytes
-        need = fn(self._h, b, h, w)
+    def _size_and_bind(self, ws, need, bind):
+        """The workspace of a plan that the library sized at `need` bytes — 0: it refused the plan, and its message is
+        raised: `ws` if that uint8 device tensor is large enough, else a fresh one, handed to ``bind(pointer, bytes)``.  A
+        caller that wants one that is too small released before its successor is allocated drops its reference first."""
         if need == 0:
             raise _lib.VyError(-1, self._lib.vy_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self._device)
-        if train:
+        if ws is None or ws.numel() < need:
+            ws = _torch().empty(need, dtype=_torch().uint8, device=self._device)
+        _lib.check(bind(ctypes.c_void_p(ws.data_ptr()), ws.numel()))
+        return ws
+
+    def _ensure_plan(self, b, h, w, train=False):
+        if self._plan is not None and self._plan[:3] == (b, h, w) and (self._plan[3] or not train):
+            return  # (a net that has a plan has its parameters on the device)
+        self._need_device()
+
+        def bind(ws, nbytes):
+            if not train:
+                return self._lib.vy_net_bind_workspace(self._h, ws, nbytes, b, h, w, self._stream())
             if self._grads is None:
+                torch = _torch()
                 n = self._lib.vy_net_param_bytes(self._h) // 4
                 self._grads = torch.zeros(n, dtype=torch.float32, device=self._device)
                 self._mom = torch.zeros(n, dtype=torch.float32, device=self._device)
-            _lib.check(self._lib.vy_net_bind_train(
-                self._h, ctypes.c_void_p(self._ws.data_ptr()), self._ws.numel(), b, h, w,
-                ctypes.c_void_p(self._grads.data_ptr()), ctypes.c_void_p(self._mom.data_ptr()), self._stream()))
-        else:
-            _lib.check(self._lib.vy_net_bind_workspace(self._h, ctypes.c_void_p(self._ws.data_ptr()),
-                                                       self._ws.numel(), b, h, w, self._stream()))
+            return self._lib.vy_net_bind_train(self._h, ws, nbytes, b, h, w, ctypes.c_void_p(self._grads.data_ptr()),
+                                               ctypes.c_void_p(self._mom.data_ptr()), self._stream())
+        fn = self._lib.vy_net_train_workspace_bytes if train else self._lib.vy_net_workspace_bytes
+        need = fn(self._h, b, h, w)
+        if self._ws is not None and self._ws.numel() < need:
+            self._ws = None  # released before its successor is allocated
+        self._ws = self._size_and_bind(self._ws, need, bind)
         self._plan = (b, h, w, bool(train))
         self._graphs = {}
 
@@ -668,25 +720,33 @@ class YOLOV3(object):
         return (torch.empty((b, rows, 1), **f32), torch.empty((b, rows, 1), **f32), torch.empty((b, rows, 4), **f32),
                 torch.empty((b, rows), dtype=torch.int32, device=self._device) if keep else None)
 
-    def _as_input(self, x):
+    def _inputs(self, x):
+        """The input adapter of this kind of net: the leading arguments of a call, checked before anything launches ->
+        (device tensors, (B, H, W) of the plan, extra), `extra` the library arguments that sit between the inputs and the
+        rest of an entry's (none, but for banks).  Here: one (B, 3, H, W) batch of images."""
         torch = _torch()
         if not isinstance(x, torch.Tensor):
             x = torch.as_tensor(np.asarray(x, np.float32))
-        if self._device is None:
-            raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
+        self._need_device()
         x = x.to(device=self._device, dtype=torch.float32).contiguous()
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError("expected (B,3,H,W) input, got %s" % (tuple(x.shape),))
-        return x
+        return [x], (x.shape[0], x.shape[2], x.shape[3]), ()
+
+    def _train_call(self, usage, lead, args):
+        """A call in training mode (``autograd.is_training()``; outside it a call is its net's ``detect``), the mode by
+        the autograd state like YOLOV3T.hybrid_forward (yolo3.py:1179-1192): `lead` are the inputs, `args` what followed
+        them — the six targets when recording."""
+        if autograd.is_recording():
+            if len(args) != 6:
+                raise ValueError(usage)
+            return self.forward_train(*lead, *args)
+        return self.forward_train_mode(*lead)
 
     def __call__(self, x, *args, return_index=False):
         """Mode is selected by the autograd state, like YOLOV3T.hybrid_forward (yolo3.py:1179-1206)."""
         if autograd.is_training():
-            if autograd.is_recording():
-                if len(args) != 6:
-                    raise ValueError("training call: net(x, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)")
-                return self.forward_train(x, *args)
-            return self.forward_train_mode(x)
+            return self._train_call(self._USAGE, (x,), args)
         if self.two_stream_batch and len(x) >= self.two_stream_batch and not getattr(self, "_hybrid", False):
             return self.detect_two_streams(x, return_index=return_index)
         return self.detect(x, return_index=return_index)
@@ -697,19 +757,14 @@ class YOLOV3(object):
             a = torch.as_tensor(np.asarray(a, np.float32))
         return a.to(device=self._device, dtype=torch.float32).contiguous()
 
-    def _train_inputs(self, x):
-        """The network inputs of a train-mode call, checked -> (device tensors, (B, H, W) of the plan)."""
-        x = self._as_input(x)
-        return [x], self._bhw(x)
-
     def _single_rank(self):
         if self._ONE_RANK:
             from . import parallel
             if parallel.world_size() > 1:
                 raise NotImplementedError("multi-rank training of %s is not supported: train it on one rank" % self._ONE_RANK)
 
-    def _train_entry(self, name):
-        return getattr(self._lib, name + self._TRAIN_ENTRY)
+    def _entry(self, name):
+        return getattr(self._lib, name + self._ENTRY)
 
     def forward_train(self, *args):
         """Recording branch (yolo3.py:1181-1187), ``net.forward_train(x, gt_boxes, obj_t, centers_t, scales_t, weights_t,
@@ -717,7 +772,7 @@ class YOLOV3(object):
         produced by ``autograd.backward(...)`` / ``net.backward()`` afterwards."""
         torch = _torch()
         self._single_rank()
-        xs, (b, h, w) = self._train_inputs(*args[:-6])
+        xs, (b, h, w), extra = self._inputs(*args[:-6])
         tg = [self._dev(t) for t in args[-6:]]
         m = int(tg[0].shape[1])
         if self._EXCHANGES:
@@ -741,10 +796,10 @@ class YOLOV3(object):
                 self._h, self._ignore_iou_thresh, int(bool(self._target_generator._label_smooth))))
             losses = torch.empty((4, b), dtype=torch.float32, device=self._device)
             p = _ptrs(tg)
-            _lib.check(self._train_entry("vy_net_train_forward")(
-                self._h, *_ptrs(xs), p[0], m, p[1], p[2], p[3], p[4], p[5], ctypes.c_void_p(losses.data_ptr()),
+            _lib.check(self._entry("vy_net_train_forward")(
+                self._h, *_ptrs(xs), *extra, p[0], m, p[1], p[2], p[3], p[4], p[5], ctypes.c_void_p(losses.data_ptr()),
                 self._stream()))
-        self._train_x = xs
+        self._train_x = xs if self._BACKWARD_READS_INPUTS else [None] * len(xs)
         autograd._register(self)
         return tuple(autograd.loss_vector(losses[i], self, i) for i in range(4))
 
@@ -779,7 +834,7 @@ class YOLOV3(object):
         if self._train_x is None:
             raise RuntimeError("backward() without a recorded forward")
         with torch.cuda.device(self._device):
-            _lib.check(self._train_entry("vy_net_train_backward")(self._h, *_ptrs(self._train_x), self._stream()))
+            _lib.check(getattr(self._lib, self._BACKWARD)(self._h, *_ptrs(self._train_x), self._stream()))
         self._train_x = None
 
     def forward_train_mode(self, *inputs):
@@ -791,7 +846,7 @@ class YOLOV3(object):
         shape (numpy), which is all the reference's consumer reads."""
         torch = _torch()
         self._single_rank()
-        xs, (b, h, w) = self._train_inputs(*inputs)
+        xs, (b, h, w), extra = self._inputs(*inputs)
         anchors, offsets, fms = self._train_mode_constants(h, w)
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w, train=True)
@@ -800,7 +855,7 @@ class YOLOV3(object):
             n = self._lib.vy_net_num_anchors(self._h)
             c = len(self._classes)
             outs = [torch.empty((b, n, k), dtype=torch.float32, device=self._device) for k in (4, 2, 2, 1, c)]
-            _lib.check(self._train_entry("vy_net_train_mode_forward")(self._h, *_ptrs(xs + outs), self._stream()))
+            _lib.check(self._entry("vy_net_train_mode_forward")(self._h, *_ptrs(xs), *extra, *_ptrs(outs), self._stream()))
         return (outs[0], anchors, offsets, fms, outs[1], outs[2], outs[3], outs[4])
 
     def extract_features(self, x):
@@ -809,13 +864,11 @@ class YOLOV3(object):
         (B, 1024, H/32, W/32) (sizes rounded up).  One launch sequence of the stem and the stages and one transpose out; no
         head runs.  What ``yolo3_no_backbone(...)(f1, f2, f3)`` takes."""
         torch = _torch()
-        x = self._as_input(x)
-        b, _, h, w = x.shape
+        xs, (b, h, w), _ = self._inputs(x)
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w)
-            outs = [torch.empty((b, c, -(-h // s), -(-w // s)), dtype=torch.float32, device=self._device)
-                    for c, s in ((256, 8), (512, 16), (1024, 32))]
-            _lib.check(self._lib.vy_net_forward_features(self._h, *_ptrs([x] + outs), self._stream()))
+            outs = [torch.empty(shape, dtype=torch.float32, device=self._device) for shape in _route_shapes(b, h, w)]
+            _lib.check(self._lib.vy_net_forward_features(self._h, *_ptrs(xs + outs), self._stream()))
         return tuple(outs)
 
     def grad(self, name):
@@ -878,20 +931,25 @@ class YOLOV3(object):
     def detect(self, x, return_index=False):
         """Inference branch of YOLOV3T.hybrid_forward (yolo3.py:1194-1206): returns
         (ids (B,R,1), scores (B,R,1), bboxes (B,R,4)) fp32 device tensors, R = post_nms."""
-        torch = _torch()
-        x = self._as_input(x)
-        b, h, w = self._bhw(x)
-        with torch.cuda.device(self._device):
-            replanned = self._plan is None or self._plan[:3] != (b, h, w)
-            self._ensure_plan(b, h, w)
-            rows = self._out_rows()
-            if getattr(self, "_hybrid", False) and self._use_graphs:
-                if replanned:
-                    self._graphs = {}
-                outs = self._graph_forward(x, rows)
-            else:
-                outs = self._detect_outputs(b, rows, return_index)
-                _lib.check(self._lib.vy_net_forward_infer(self._h, *_ptrs((x,) + outs), self._stream()))
+        xs, bhw, extra = self._inputs(x)
+        if not (getattr(self, "_hybrid", False) and self._use_graphs):
+            return self._detect("vy_net_forward_infer", xs, bhw, extra, return_index)
+        with _torch().cuda.device(self._device):
+            self._ensure_plan(*bhw)  # a re-plan drops the graphs
+            outs = self._graph_forward(xs[0], self._out_rows())
+        return outs if return_index else outs[:3]
+
+    def _detect(self, entry, xs, bhw, extra, return_index):
+        """The detect body of every kind of net: plan for `bhw`, then ``_detect_call`` on the checked inputs `xs`."""
+        with _torch().cuda.device(self._device):
+            self._ensure_plan(*bhw)
+            return self._detect_call(entry, bhw[0], (*_ptrs(xs), *extra), return_index)
+
+    def _detect_call(self, entry, b, args, return_index):
+        """One call of the library's detect entry `entry` on the bound plan: ``entry(net, *args, ids, scores, bboxes, keep,
+        stream)`` with fresh outputs at batch b -> ``(ids, scores, bboxes[, keep])``."""
+        outs = self._detect_outputs(b, self._out_rows(), return_index)
+        _lib.check(getattr(self._lib, entry)(self._h, *args, *_ptrs(outs), self._stream()))
         return outs if return_index else outs[:3]
 
     def detect_heads(self, heads, size, return_index=False):
@@ -899,9 +957,7 @@ class YOLOV3(object):
         (B, 3*(5+C), H_i, W_i) for strides 32, 16, 8 of a ``size`` = (height, width) input — what
         ``net.yolo_outputs[i](pred)`` (yolo3.py:132-199), the concat (:1195), ``box_nms`` and the slice (:1197-1206)
         make of them.  Honours ``set_nms`` like a forward."""
-        torch = _torch()
-        if self._device is None:
-            raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
+        self._need_device()
         h, w = (size, size) if isinstance(size, int) else size
         hs = [self._dev(t) for t in heads]
         if len(hs) != 3:
@@ -912,11 +968,7 @@ class YOLOV3(object):
             want = (b, c, -(-h // div), -(-w // div))
             if tuple(t.shape) != want:
                 raise ValueError("head of stride %d: shape %s, expected %s" % (div, tuple(t.shape), want))
-        with torch.cuda.device(self._device):
-            self._ensure_plan(b, h, w)
-            outs = self._detect_outputs(b, self._out_rows(), return_index)
-            _lib.check(self._lib.vy_net_detect_heads(self._h, *_ptrs(tuple(hs) + outs), self._stream()))
-        return outs if return_index else outs[:3]
+        return self._detect("vy_net_detect_heads", hs, (b, h, w), (), return_index)
 
     def detect_two_streams(self, x, return_index=False):
         """Frames are independent, so a large batch is run as two half-batches on two HIP streams (a twin
@@ -925,8 +977,7 @@ class YOLOV3(object):
         flight the last, partly filled round of one kernel overlaps with the other stream's kernels, and
         block prologues/epilogues overlap too.  Results are identical to detect()."""
         torch = _torch()
-        x = self._as_input(x)
-        b, _, h, w = x.shape
+        (x,), (b, h, w), _ = self._inputs(x)
         if b < 2 or b % 2:
             return self.detect(x, return_index=return_index)
         hb = b // 2
@@ -950,11 +1001,10 @@ class YOLOV3(object):
             _lib.check(self._lib.vy_net_set_semantics(tw["h"], ctypes.byref(sem)))
             cur = torch.cuda.current_stream(self._device)
             if tw["plan"] != (hb, h, w):
-                need = self._lib.vy_net_workspace_bytes(tw["h"], hb, h, w)
-                if tw["ws"] is None or tw["ws"].numel() < need:
-                    tw["ws"] = torch.empty(need, dtype=torch.uint8, device=self._device)
-                _lib.check(self._lib.vy_net_bind_workspace(tw["h"], ctypes.c_void_p(tw["ws"].data_ptr()),
-                                                           tw["ws"].numel(), hb, h, w, ctypes.c_void_p(cur.cuda_stream)))
+                tw["ws"] = self._size_and_bind(
+                    tw["ws"], self._lib.vy_net_workspace_bytes(tw["h"], hb, h, w),
+                    lambda ws, nbytes: self._lib.vy_net_bind_workspace(tw["h"], ws, nbytes, hb, h, w,
+                                                                       ctypes.c_void_p(cur.cuda_stream)))
                 tw["plan"] = (hb, h, w)
             outs = self._detect_outputs(b, self._out_rows(), return_index)
             side = tw["stream"]
@@ -1013,8 +1063,7 @@ class YOLOV3(object):
         """One timed forward: list of (launch name, ms, flops, bytes) from HIP events around every
         kernel launch on the current stream (a hierarchical net: the pools are the launches ``hpool.<i>``)."""
         torch = _torch()
-        x = self._as_input(x)
-        b, h, w = self._bhw(x)
+        (x,), (b, h, w), _ = self._inputs(x)
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w)
             outs = self._detect_outputs(b, self._out_rows(), keep=False)
@@ -1051,60 +1100,85 @@ class YOLOV3NoBackbone(YOLOV3):
     back-propagated into the routes."""
 
     _CREATE = "vy_net_create_heads"
-    _TRAIN_ENTRY = "_routes"
+    _ENTRY = "_routes"
+    _BACKWARD = "vy_net_train_backward_routes"
+    _USAGE = "training call: net(f1, f2, f3, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)"
     _ONE_RANK = "a heads-only net (yolo3_no_backbone)"
     _EXCHANGES = False  # no SyncBatchNorm cell among the heads (a SyncBatchNorm norm_layer is accepted: DESIGN §10)
 
-    def _as_routes(self, f1, f2, f3):
-        """Check the three routes against each other (before anything launches) -> (device tensors, (B, H, W)) with H, W
-        the smallest image size they can come from (the plan only depends on the route sizes)."""
-        fs = []
-        for f in (f1, f2, f3):
-            shape = tuple(f.shape) if hasattr(f, "shape") else tuple(np.shape(f))
-            fs.append(shape)
-        b = fs[0][0] if fs[0] else None
-        h8, w8 = (fs[0][2], fs[0][3]) if len(fs[0]) == 4 else (0, 0)
-        want = [(b, 256, h8, w8), (b, 512, -(-h8 // 2), -(-w8 // 2)), (b, 1024, -(-h8 // 4), -(-w8 // 4))]
-        if any(len(s) != 4 for s in fs) or fs != want or b < 1 or min(h8, w8) < 4 or max(h8, w8) > 512:
+    def _inputs(self, f1, f2, f3):
+        """The three routes, checked against each other; H, W of the plan are the smallest image size they can come from
+        (the plan only depends on the route sizes)."""
+        fs = [_shape(f) for f in (f1, f2, f3)]
+        geometry = _route_geometry(fs)
+        if geometry is None:
             raise ValueError("route shapes %s are not the three Darknet-53 routes of one (B, 3, H, W) batch: expected "
                              "(B, 256, h, w), (B, 512, ceil(h/2), ceil(w/2)), (B, 1024, ceil(h/4), ceil(w/4)) with h, w in "
                              "[4, 512]" % (fs,))
-        if self._device is None:
-            raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
-        return [self._dev(f) for f in (f1, f2, f3)], (b, 8 * h8, 8 * w8)
-
-    _train_inputs = _as_routes
+        self._need_device()
+        b, h8, w8 = geometry
+        return [self._dev(f) for f in (f1, f2, f3)], (b, 8 * h8, 8 * w8), ()
 
     def __call__(self, f1, f2, f3, *args, return_index=False):
         """YOLOV3_noback.hybrid_forward(F, x1, x2, x3, *args): mode by the autograd state."""
         if autograd.is_training():
-            if autograd.is_recording():
-                if len(args) != 6:
-                    raise ValueError("training call: net(f1, f2, f3, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)")
-                return self.forward_train(f1, f2, f3, *args)
-            return self.forward_train_mode(f1, f2, f3)
+            return self._train_call(self._USAGE, (f1, f2, f3), args)
         return self.detect(f1, f2, f3, return_index=return_index)
 
     def detect(self, f1, f2, f3, return_index=False):
         """Inference branch: (ids, scores, bboxes[, keep_idx]) exactly as ``YOLOV3.detect`` returns them."""
-        torch = _torch()
-        fs, (b, h, w) = self._as_routes(f1, f2, f3)
-        with torch.cuda.device(self._device):
-            self._ensure_plan(b, h, w)
-            outs = self._detect_outputs(b, self._out_rows(), return_index)
-            _lib.check(self._lib.vy_net_forward_infer_routes(self._h, *_ptrs(tuple(fs) + outs), self._stream()))
-        return outs if return_index else outs[:3]
+        return self._detect("vy_net_forward_infer_routes", *self._inputs(f1, f2, f3), return_index)
 
-    def _no_image(self, *args, **kwargs):
-        raise NotImplementedError("a heads-only net (yolo3_no_backbone) takes route tensors, not images")
-
-    extract_features = detect_two_streams = profile = load_darknet53_backbone = _no_image
+    extract_features = detect_two_streams = profile = load_darknet53_backbone = _refusal(
+        "a heads-only net (yolo3_no_backbone) takes route tensors, not images")
 
 
 YOLOV3_noback = YOLOV3NoBackbone
 
 
-class YOLOV3Window(YOLOV3):
+class _ClipNet(YOLOV3):
+    """The input adapter of the nets over ``(B, T, 3, H, W)`` clips; a subclass says how many frames a clip has
+    (``_clip_frames``) and what its error says such a net takes (``_clip_takes``).  The frames go through the single-frame adapter as one ``B * T`` batch."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.two_stream_batch = 0
+
+    def _inputs(self, x):
+        shape = _shape(x)
+        if len(shape) != 5 or shape[1] != self._clip_frames or shape[2] != 3:
+            raise ValueError("%s, got %s" % (self._clip_takes(), shape))
+        torch = _torch()
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x, np.float32))
+        (x,), _, extra = super()._inputs(x.reshape((-1,) + shape[2:]))
+        return [x.view(shape)], (shape[0], shape[3], shape[4]), extra
+
+
+class _Windowed:
+    """``k`` / ``k_join_type`` of the two window classes, in front of the net they extend: the constructor's check, the
+    fields, the library constructor's arguments and the arguments of a copy.  ``_WINDOWED`` names the class in the error."""
+
+    _JOINS = {"max": _lib.VY_JOIN_MAX, "mean": _lib.VY_JOIN_MEAN}
+
+    def __init__(self, classes, *args, k=2, k_join_type="max", **kwargs):
+        if int(k) < 2 or k_join_type not in self._JOINS:
+            raise ValueError("%s: k >= 2 and k_join_type in %s (got k=%r, %r)"
+                             % (self._WINDOWED, sorted(self._JOINS), k, k_join_type))
+        self._k, self._join_type = int(k), k_join_type
+        super().__init__(classes, *args, **kwargs)
+
+    k = property(lambda self: self._k)
+    k_join_type = property(lambda self: self._join_type)
+
+    def _create_handle(self, num_class, out):
+        return getattr(self._lib, self._CREATE)(num_class, self._k, self._JOINS[self._join_type], out)
+
+    def _ctor_kwargs(self):
+        return dict(k=self._k, k_join_type=self._join_type)
+
+
+class YOLOV3Window(_Windowed, _ClipNet):
     """``YOLOV3T`` with ``k > 1`` and ``k_join_pos='early'`` (yolo3.py:1016-1121): a detector over k-frame clips.  Input
     is ``(B, k, 3, H, W)``; the Darknet-53 stages run on the ``B * k`` frames (``TimeDistributed``, frame t of clip b is
     frame ``b * k + t``), each route is pooled over the clip's k frames (``TemporalPooling`` 'direct': max or mean) and
@@ -1116,55 +1190,17 @@ class YOLOV3Window(YOLOV3):
 
     _CREATE = "vy_net_create_window"
     _ONE_RANK = "a window net (yolo3_darknet53 with k > 1)"
-    _JOINS = {"max": _lib.VY_JOIN_MAX, "mean": _lib.VY_JOIN_MEAN}
+    _WINDOWED = "window net"
     _STAGE_RE = re.compile(r"^(stages\.\d+)\.(?!model\.)")
-
-    def __init__(self, classes, *args, k=2, k_join_type="max", **kwargs):
-        if int(k) < 2 or k_join_type not in self._JOINS:
-            raise ValueError("window net: k >= 2 and k_join_type in %s (got k=%r, %r)" % (sorted(self._JOINS), k, k_join_type))
-        self._k, self._join_type = int(k), k_join_type
-        super().__init__(classes, *args, **kwargs)
-        renamed = ParameterDict(self)
-        for p in self._params.values():
-            p.name = self._key(p.name)
-            renamed[p.name] = p
-        self._params = renamed
-        self.two_stream_batch = 0
-
-    @property
-    def k(self):
-        return self._k
-
-    @property
-    def k_join_type(self):
-        return self._join_type
-
-    def _create_handle(self, num_class, out):
-        return self._lib.vy_net_create_window(num_class, self._k, self._JOINS[self._join_type], out)
-
-    def _ctor_kwargs(self):
-        return dict(k=self._k, k_join_type=self._join_type)
 
     @classmethod
     def _key(cls, name):
         return cls._STAGE_RE.sub(r"\1.model.", name)
 
-    def _bhw(self, x):
-        return x.shape[0], x.shape[3], x.shape[4]
+    _clip_frames = _Windowed.k
 
-    def set_parameters(self, arrays, allow_missing=False, ignore_extra=False):
-        """As ``YOLOV3.set_parameters``; stage keys may also come in the single-frame form (``stages.N.<rest>``)."""
-        super().set_parameters(OrderedDict((self._key(k), v) for k, v in arrays.items()), allow_missing=allow_missing,
-                               ignore_extra=ignore_extra)
-
-    def _as_input(self, x):
-        shape = tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
-        if len(shape) != 5 or shape[1] != self._k or shape[2] != 3:
-            raise ValueError("a window net takes (B, k, 3, H, W) clips with k = %d, got %s" % (self._k, shape))
-        torch = _torch()
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x, np.float32))
-        return super()._as_input(x.reshape((-1,) + shape[2:])).view(shape)
+    def _clip_takes(self):
+        return "a window net takes (B, k, 3, H, W) clips with k = %d" % self._k
 
     # ---- over a whole video: the backbone once per frame (videoyolo_amd/video.py)
     _video = None  # the VideoSession that holds the workspace binding, if one does
@@ -1196,10 +1232,8 @@ class YOLOV3Window(YOLOV3):
         tail = session.flush(return_index=return_index)
         return tuple(torch.cat([a, b], 0) for a, b in zip(head, tail))
 
-    def _not_windowed(self, *args, **kwargs):
-        raise NotImplementedError("not available on a window net (yolo3_darknet53 with k > 1): use a single-frame net")
-
-    extract_features = detect_two_streams = profile = _not_windowed
+    extract_features = detect_two_streams = profile = _refusal(
+        "not available on a window net (yolo3_darknet53 with k > 1): use a single-frame net")
 
 
 def hier_pools(hierarchical):
@@ -1215,7 +1249,7 @@ def hier_pools(hierarchical):
     return n
 
 
-class YOLOV3Hier(YOLOV3):
+class YOLOV3Hier(_ClipNet):
     """``yolo3_darknet53(classes, new_model=True, hierarchical=[3,3,1,1,1], h_join_type='max')``: ``YOLOV3TB`` over
     ``HDarknet`` (h_darknet.py:103-188), a detector over clips of ``T = 3 ** n`` frames, n the number of leading 3s.  Input
     is ``(B, T, 3, H, W)``, frame t of clip b is frame ``b * T + t``.  The stem runs per frame; in front of each of the first
@@ -1236,7 +1270,6 @@ class YOLOV3Hier(YOLOV3):
                              "one 1 (got %r)" % (hierarchical,))
         self._hier, self._pools = tuple(int(v) for v in hierarchical), n
         super().__init__(classes, *args, **kwargs)
-        self.two_stream_batch = 0
 
     @property
     def hierarchical(self):
@@ -1265,37 +1298,21 @@ class YOLOV3Hier(YOLOV3):
         si = 0 if f < 15 else (1 if f < 24 else 2)
         return "stages.%d.%d.%s" % (si, f - (0, 15, 24)[si], name[m.end():])
 
-    def _bhw(self, x):
-        return x.shape[0], x.shape[3], x.shape[4]
+    _clip_frames = frames
 
-    def set_parameters(self, arrays, allow_missing=False, ignore_extra=False):
-        """As ``YOLOV3.set_parameters``; backbone keys may also come as ``d_model.features.N.<rest>``."""
-        super().set_parameters(OrderedDict((self._key(k), v) for k, v in arrays.items()), allow_missing=allow_missing,
-                               ignore_extra=ignore_extra)
-
-    def _as_input(self, x):
-        shape = tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
-        if len(shape) != 5 or shape[1] != self.frames or shape[2] != 3:
-            raise ValueError("a hierarchical net %r takes (B, T, 3, H, W) clips with T = %d, got %s"
-                             % (self.hierarchical, self.frames, shape))
-        torch = _torch()
-        if not isinstance(x, torch.Tensor):
-            x = torch.as_tensor(np.asarray(x, np.float32))
-        return super()._as_input(x.reshape((-1,) + shape[2:])).view(shape)
+    def _clip_takes(self):
+        return "a hierarchical net %r takes (B, T, 3, H, W) clips with T = %d" % (self.hierarchical, self.frames)
 
     def set_conv_mode(self, mode="exact"):
         if mode != "exact":
             raise NotImplementedError("conv mode %r: a hierarchical net runs the exact fp32 kernels only" % (mode,))
         super().set_conv_mode(mode)
 
-    def _not_hierarchical(self, *args, **kwargs):
-        raise NotImplementedError("not available on a hierarchical net (yolo3_darknet53 with hierarchical=...): use a "
-                                  "single-frame net")
-
-    extract_features = detect_two_streams = _not_hierarchical
+    extract_features = detect_two_streams = _refusal(
+        "not available on a hierarchical net (yolo3_darknet53 with hierarchical=...): use a single-frame net")
 
 
-class YOLOV3NoBackboneWindow(YOLOV3NoBackbone):
+class YOLOV3NoBackboneWindow(_Windowed, YOLOV3NoBackbone):
     """``yolo3_no_backbone(classes, k=k, k_join_type=..., k_join_pos='early')``: the head half of ``YOLOV3Window``, for the
     reference's ``--features_dir --window k`` workflow (datasets/imgnetvid.py:146-174 stacks the k frames' saved routes
     into ``(k, C, h, w)``).  With the early join and max / mean pooling the heads of a window net see nothing but the pooled
@@ -1307,32 +1324,17 @@ class YOLOV3NoBackboneWindow(YOLOV3NoBackbone):
     (rows may repeat a frame).  The mode follows ``autograd``.  ``B * k`` is at most ``_lib.VY_VIDEO_TABLE_MAX``."""
 
     _CREATE = "vy_net_create_heads_window"
-    _TRAIN_ENTRY = "_bank"
+    _ENTRY = "_bank"
+    _BACKWARD_READS_INPUTS = False
+    _BANK_USAGE = "training call: net.from_bank(f1, f2, f3, table, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)"
     _ONE_RANK = "a windowed heads-only net (yolo3_no_backbone with k > 1)"
-    _JOINS = YOLOV3Window._JOINS
+    _WINDOWED = "windowed heads net"
 
-    def __init__(self, classes, *args, k=2, k_join_type="max", **kwargs):
-        if int(k) < 2 or k_join_type not in self._JOINS:
-            raise ValueError("windowed heads net: k >= 2 and k_join_type in %s (got k=%r, %r)"
-                             % (sorted(self._JOINS), k, k_join_type))
-        self._k, self._join_type = int(k), k_join_type
-        self._bank_args = None  # (frames of the bank, ctypes table) of the call in progress
-        super().__init__(classes, *args, **kwargs)
-
-    k = property(lambda self: self._k)
-    k_join_type = property(lambda self: self._join_type)
-
-    def _create_handle(self, num_class, out):
-        return self._lib.vy_net_create_heads_window(num_class, self._k, self._JOINS[self._join_type], out)
-
-    def _ctor_kwargs(self):
-        return dict(k=self._k, k_join_type=self._join_type)
-
-    def _as_bank(self, f1, f2, f3, table=None):
-        """Check a call's routes and table (before anything launches; the table is a host array: nothing here touches the
-        device) -> (the three banks as (T, C, h, w) device tensors, (B, H, W) of the plan).  ``table=None``: the routes
-        are (B, k, C, h, w), a bank of B * k frames with the identity table."""
-        fs = [tuple(f.shape) if hasattr(f, "shape") else tuple(np.shape(f)) for f in (f1, f2, f3)]
+    def _inputs(self, f1, f2, f3, table=None):
+        """A call's routes and table (a host array: nothing here touches the device) -> the three banks as (T, C, h, w)
+        device tensors, the plan of the B clips and ``extra`` = (T, the table as the library takes it).  ``table=None``: the
+        routes are (B, k, C, h, w), a bank of B * k frames with the identity table."""
+        fs = [_shape(f) for f in (f1, f2, f3)]
         rank = 5 if table is None else 4
         if any(len(s) != rank for s in fs):
             raise ValueError("route shapes %s: expected %s" % (fs, "three (B, k, C, h, w) tensors" if table is None else
@@ -1349,38 +1351,21 @@ class YOLOV3NoBackboneWindow(YOLOV3NoBackbone):
                 raise ValueError("table of shape %s, dtype %s: expected a (B, k) integer array with k = %d"
                                  % (tab.shape, tab.dtype, self._k))
             b = tab.shape[0]
-        t, h8, w8 = fs[0][0], fs[0][2], fs[0][3]
-        want = [(t, 256, h8, w8), (t, 512, -(-h8 // 2), -(-w8 // 2)), (t, 1024, -(-h8 // 4), -(-w8 // 4))]
-        if fs != want or t < 1 or min(h8, w8) < 4 or max(h8, w8) > 512:
+        geometry = _route_geometry(fs)
+        if geometry is None:
             raise ValueError("route shapes %s are not the three Darknet-53 routes of the same frames: expected (.., 256, h, w), "
                              "(.., 512, ceil(h/2), ceil(w/2)), (.., 1024, ceil(h/4), ceil(w/4)) with h, w in [4, 512]" % (fs,))
+        t, h8, w8 = geometry
         if b < 1 or b * self._k > _lib.VY_VIDEO_TABLE_MAX:
             raise ValueError("B * k = %d x %d: between 1 and %d table entries (they travel in the kernel arguments)"
                              % (b, self._k, _lib.VY_VIDEO_TABLE_MAX))
         if tab.size and (int(tab.min()) < 0 or int(tab.max()) >= t):
             raise ValueError("table entries must lie in [0, %d), the frames of the bank (got %d ... %d)"
                              % (t, int(tab.min()), int(tab.max())))
-        if self._device is None:
-            raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
+        self._need_device()
         flat = np.ascontiguousarray(tab, dtype=np.int32).reshape(-1)
-        self._bank_args = (t, (ctypes.c_int32 * flat.size).from_buffer_copy(flat.tobytes()))
-        return [self._dev(f).reshape(s) for f, s in zip((f1, f2, f3), fs)], (b, 8 * h8, 8 * w8)
-
-    _train_inputs = _as_bank
-
-    def _train_entry(self, name):
-        fn = getattr(self._lib, name + self._TRAIN_ENTRY)
-        n_frames, table = self._bank_args
-        return lambda h, f0, f1, f2, *rest: fn(h, f0, f1, f2, n_frames, table, *rest)
-
-    def backward(self):
-        """As ``YOLOV3.backward``: nothing is back-propagated into the routes, so the library takes none here."""
-        torch = _torch()
-        if self._train_x is None:
-            raise RuntimeError("backward() without a recorded forward")
-        with torch.cuda.device(self._device):
-            _lib.check(self._lib.vy_net_train_backward_routes(self._h, None, None, None, self._stream()))
-        self._train_x = None
+        extra = (t, (ctypes.c_int32 * flat.size).from_buffer_copy(flat.tobytes()))
+        return [self._dev(f).reshape(s) for f, s in zip((f1, f2, f3), fs)], (b, 8 * h8, 8 * w8), extra
 
     def from_bank(self, f1, f2, f3, table, *args, return_index=False):
         """``net(...)`` on windows gathered out of banks: ``f1, f2, f3`` are ``(T, 256 | 512 | 1024, h, w)`` per-frame routes
@@ -1389,25 +1374,12 @@ class YOLOV3NoBackboneWindow(YOLOV3NoBackbone):
         if table is None:
             raise ValueError("from_bank needs a (B, k) table")
         if autograd.is_training():
-            if autograd.is_recording():
-                if len(args) != 6:
-                    raise ValueError("training call: net.from_bank(f1, f2, f3, table, gt_boxes, obj_t, centers_t, scales_t, "
-                                     "weights_t, clas_t)")
-                return self.forward_train(f1, f2, f3, table, *args)
-            return self.forward_train_mode(f1, f2, f3, table)
+            return self._train_call(self._BANK_USAGE, (f1, f2, f3, table), args)
         return self.detect(f1, f2, f3, return_index=return_index, table=table)
 
     def detect(self, f1, f2, f3, return_index=False, table=None):
         """Inference branch: (ids, scores, bboxes[, keep_idx]) per clip, exactly as ``YOLOV3Window.detect`` returns them."""
-        torch = _torch()
-        fs, (b, h, w) = self._as_bank(f1, f2, f3, table)
-        n_frames, tab = self._bank_args
-        with torch.cuda.device(self._device):
-            self._ensure_plan(b, h, w)
-            outs = self._detect_outputs(b, self._out_rows(), return_index)
-            p = _ptrs(tuple(fs) + outs)
-            _lib.check(self._lib.vy_net_forward_infer_bank(self._h, p[0], p[1], p[2], n_frames, tab, *p[3:], self._stream()))
-        return outs if return_index else outs[:3]
+        return self._detect("vy_net_forward_infer_bank", *self._inputs(f1, f2, f3, table), return_index)
 
     def detect_video_features(self, f1, f2, f3, step=1, clips_per_step=16, return_index=False):
         """``(ids, scores, bboxes)`` for every frame of a stored video, ``f1, f2, f3`` its ``(T, C, h, w)`` routes: the clips

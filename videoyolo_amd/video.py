@@ -15,7 +15,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .model import _ptrs
+from .model import _ptrs, _route_shapes
 
 
 def window_indices(n_frames, k, step=1):
@@ -113,8 +113,7 @@ class VideoSession:
         from . import parallel
         if parallel.world_size() > 1:
             raise NotImplementedError("video detection of a window net is not supported on more than one rank")
-        if net._device is None:
-            raise RuntimeError("parameters are not on a device: call net.collect_params().reset_ctx(ctx)")
+        net._need_device()
         self._net = net
         self._sched = RingSchedule(net.k, step, frames_per_step, clips_per_step, ring)
         self._hw = None    # frame size of the bound plan
@@ -130,14 +129,11 @@ class VideoSession:
     # ------------------------------------------------------------------ binding
     def _take_binding(self):
         """The net's next clip / training call must bind its own plan again, and this session its own."""
-        net = self._net
-        net._plan = None
-        net._graphs = {}
-        net._video = self
+        self._net._drop_plan()
+        self._net._video = self
         self._bound = False
 
     def _ensure_bound(self, h, w):
-        import torch
         net, s = self._net, self._sched
         if net._video is not self:
             if s.pushed:
@@ -150,13 +146,10 @@ class VideoSession:
         if s.pushed:
             raise ValueError("frame size changed from %s to %s inside a video: flush() first" % (self._hw, (h, w)))
         need = net._lib.vy_net_video_workspace_bytes(net._h, s.F, s.B, s.R, h, w)
-        if need == 0:
-            raise _lib.VyError(-1, net._lib.vy_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=net._device)
-        _lib.check(net._lib.vy_net_bind_video(net._h, ctypes.c_void_p(self._ws.data_ptr()), self._ws.numel(), s.F, s.B, s.R,
-                                              h, w, net._stream()))
+        if self._ws is not None and self._ws.numel() < need:
+            self._ws = None  # released before its successor is allocated
+        self._ws = net._size_and_bind(self._ws, need, lambda ws, nbytes: net._lib.vy_net_bind_video(
+            net._h, ws, nbytes, s.F, s.B, s.R, h, w, net._stream()))
         self._xbuf = None
         self._hw, self._bound = (h, w), True
 
@@ -173,9 +166,7 @@ class VideoSession:
         flat = [int(v) for row in table for v in row]
         if len(flat) != b * net.k:
             raise ValueError("slot table of %d entries, expected %d x %d" % (len(flat), b, net.k))
-        outs = net._detect_outputs(b, net._out_rows(), return_index)
-        _lib.check(net._lib.vy_net_video_detect(net._h, (ctypes.c_int32 * len(flat))(*flat), *_ptrs(outs), net._stream()))
-        return outs if return_index else outs[:3]
+        return net._detect_call("vy_net_video_detect", b, [(ctypes.c_int32 * len(flat))(*flat)], return_index)
 
     def slot_of(self, frame):
         """Ring slot that holds (or held) frame `frame` of the current video."""
@@ -187,8 +178,7 @@ class VideoSession:
         import torch
         net = self._net
         h, w = self._hw
-        outs = [torch.empty((1, c, -(-h // s), -(-w // s)), dtype=torch.float32, device=net._device)
-                for c, s in ((256, 8), (512, 16), (1024, 32))]
+        outs = [torch.empty(shape, dtype=torch.float32, device=net._device) for shape in _route_shapes(1, h, w)]
         with torch.cuda.device(net._device):
             _lib.check(net._lib.vy_net_video_read_slot(net._h, int(slot), *_ptrs(outs), net._stream()))
         return tuple(outs)
