@@ -11,9 +11,10 @@ A form is (pass, tile + schedule):
             turn with parked chains, "ck<S>sk" stream-K pieces of those
 
 The training step writes the form of every launch itself (VY_TRAIN_LABELS, the '# via exact <tile><schedule>' lines:
-train.hip's LabelLog, from the launcher's own vy_conv_form).  The inference profile's label has the tile and sk / ks<S>
-only; infer_form() adds the stages and the parked chains by RESTATING two rules of the launcher (run_cfg's four-stage
-condition in conv_igemm.hip and vy_conv_runs of include/vy_math.h) — a restatement, to be kept in step by hand.
+train.hip's LabelLog, from the plan the launch executed: vy_conv_plan_label of conv_launch.h).  The inference profile's
+label is the same plan in its shorter style, the tile and sk / ks<S> only; infer_form() adds the stages and the parked
+chains by RESTATING two rules of the plan (the four-stage condition of vy_conv_plan_exact in conv_launch.h and
+vy_conv_runs of include/vy_math.h) — a restatement, to be kept in step by hand.
 
 FORCED lists the switch settings under which the per-cell tests run; names are the test ids."""
 import re

@@ -93,9 +93,9 @@ int main(int argc, char** argv) {
     a.sk_bytes = VY_SK_PARTIAL_BYTES;
     a.sk_nflags = VY_SK_FLAGS;
   }
-  int bm, bn;
-  vy_conv_cfg(a, &bm, &bn);
-  const bool streamk = vy_conv_streamk(a);
+  const VyConvPlan plan = vy_conv_plan(a);  // (no weight images: the exact kernel)
+  const int bm = plan.bm, bn = plan.bn;
+  const bool streamk = plan.sk;
   const long long tiles = (long long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
   unsigned long long* trace;
   CK(hipMalloc(&trace, (size_t)tiles * 8 * 8));

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libvyolo.so")
 SOURCES = ["net.hip", "train.hip", "conv_igemm.hip", "conv_split.hip", "conv_wino.hip", "wgrad.hip", "wgrad_split.hip", "misc_kernels.hip", "train_kernels.hip", "detect.hip", "preproc.hip", "targets.hip", "routes.hip", "temporal.hip", "hier.hip", "video.hip", "augment.hip", "vid_metric.hip", "voc_metric.hip", "coco_metric.hip"]
-HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "knobs.h"), os.path.join(CSRC, "net_internal.h"), os.path.join(CSRC, "vy_support.h"), os.path.join(CSRC, "conv_device.h"), os.path.join(CSRC, "sk_schedule.h"), os.path.join(CSRC, "conv_cost_model.h"), os.path.join(CSRC, "split_device.h"),
+HEADERS = [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "knobs.h"), os.path.join(CSRC, "net_internal.h"), os.path.join(CSRC, "vy_support.h"), os.path.join(CSRC, "conv_device.h"), os.path.join(CSRC, "sk_schedule.h"), os.path.join(CSRC, "conv_cost_model.h"), os.path.join(CSRC, "conv_launch.h"), os.path.join(CSRC, "split_device.h"),
            os.path.join(HERE, "..", "include", "vyolo.h"),
            os.path.join(HERE, "..", "include", "vy_math.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,6 +1,7 @@
 // conv_cost_model.h — the launch cost model of the implicit-GEMM conv: which block tile a launch uses and whether it runs
-// as a chain-preserving stream-K launch.  Host-only, plain C++ (no HIP types): conv_igemm.hip includes it, and so does
-// tests/conv_cost_model_check.cpp, which the CPU test suite compiles with g++ to pin the decisions for BASELINE's shapes.
+// as a chain-preserving stream-K launch.  Host-only, plain C++ (no HIP types): conv_launch.h — the one place that decides a launch — evaluates
+// it, for the library and for tests/conv_cost_model_check.cpp, which the CPU test suite compiles with g++ to pin the decisions
+// for BASELINE's shapes.
 //
 // Measured on the MI355X (tools/train_layers.sh with VY_CONV_FORCE, 416x416 batch 16 and 608x608 batch 64): a launch of T
 // tiles takes ceil(T / 256) x (alpha(tile) x K + O(tile)) — every CU works through its share of the tiles at a rate that
@@ -17,8 +18,8 @@
 // device the launch goes to (`cus`: vy_cu_count(), hipDeviceAttributeMultiprocessorCount) and count their rounds in it —
 // a round is what ONE CU does with its share, which does not depend on how many CUs there are.  What does depend on the
 // chip is every comparison BETWEEN kernels (the split and Winograd instances were fitted against the exact kernel under
-// this part's power cap and L2 / LDS-DMA rates): vy_model_fitted(cus) is false for any other count, and the callers then
-// stay on the exact kernel's own tile model (vy_conv_split_pays / vy_conv_wino_pays refuse, as stream-K does through
+// this part's power cap and L2 / LDS-DMA rates): vy_model_fitted(cus) is false for any other count, and the caller then
+// stays on the exact kernel's own tile model (vy_conv_plan, conv_launch.h, refuses both, as stream-K does through
 // vy_sk_verify_topology) — a partition mode (DPX 128, QPX 64, CPX 32 CUs) or a CU-masked queue gets correct, unsurprising
 // launches instead of choices that silently refer to a different chip.
 #pragma once

@@ -43,7 +43,7 @@
 
 #include "conv_device.h"
 #include "sk_schedule.h"
-#include "conv_cost_model.h"
+#include "conv_launch.h"
 
 // Stream-K hand-off between the block that starts a tile and the block that finishes it (SK instances only).
 // `tiles` tiles in the launch (the grid is smaller); partials: [grid][BM * BN] floats; flags: [grid] words, zero between
@@ -747,214 +747,78 @@ int vy_sk_verify_topology(unsigned* scratch_dev, hipStream_t s) {
   return ok;
 }
 
-// ---- the launch cost model (conv_cost_model.h), shared by the tile choice (select_cfg) and the stream-K decision ----
-// Data gradients are never stream-K by the model (in the training step the weight-gradient stream runs beside them and
-// its blocks already fill the CUs a partly filled round leaves idle; measured, stream-K there only moves the idle time);
-// VY_CONV_SK_SLOTS (tests) forces it on them too
-static bool sk_allowed(const ConvArgs& a) {
-  const VyKnobs& k = vy_args_knobs(a);
-  return k.conv_sk && a.sk_partials && a.sk_flags && (!a.dgrad || k.conv_sk_slots > 0);
-}
-static VySkPolicy sk_policy(const ConvArgs& a) {
-  const VyKnobs& k = vy_args_knobs(a);
-  return VySkPolicy{sk_allowed(a), k.conv_sk_gain, k.conv_sk_cost};
-}
-
-// `sk_query` != nullptr: nothing is launched, *sk_query tells whether the launch would be a stream-K one (the profile's label)
-// `form` (with sk_query): the LDS stages and the runs of K of this instance as well
+// ---- executing a plan (conv_launch.h: the tile, the stages and the schedule were decided there) ------------------------
 template <int BM, int BN, int WM, int WN, int NS = 2>
-static hipError_t launch_cfg(const ConvArgs& a_in, hipStream_t s, bool* sk_query = nullptr, int* ks_query = nullptr,
-                             VyConvForm* form = nullptr) {
-  ConvArgs a = a_in;
+static hipError_t launch_cfg(const ConvArgs& a, const VyConvPlan& p, hipStream_t s) {
   const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
-  const long long tiles = (long long)tiles_m * tiles_n;
+  const dim3 grid((unsigned)p.grid), block(WM * WN * 64);
   SkArgs sk = {nullptr, nullptr, 0, 0};
-  // the runs of the pinned summation order (forward launches only; gradients are not held to the oracle's bits)
-  const int T_runs = a.ntaps * (a.Kc >> 5);
-  const int ksplit_S = a.dgrad ? 1 : vy_conv_runs(a.ntaps, a.Kc >> 5);
-  a.k_chunk = 0;
-  if (ks_query) *ks_query = 0;
-  if (form) {
-    form->ns = NS;
-    form->ck = ksplit_S > 1 ? ksplit_S : 0;
+  if (p.sk || p.ks) {
+    sk.partials = a.sk_partials;
+    sk.flags = a.sk_flags;
+    sk.tiles = tiles_m * tiles_n;
+    sk.ksplit = p.ks;
   }
-  if (ksplit_S > 1) {
-    a.k_chunk = T_runs / ksplit_S;
-    // a workgroup that runs more than one run of a tile parks the finished runs' sum in the tile's scratch
-    if (!sk_query && (!a.ck_scratch || (ksplit_S - 1) * tiles * BM * BN * 4ll > (long long)a.ck_bytes)) return hipErrorInvalidValue;
-  }
-  // Stream-K when the cost model says it pays (predict_launch): the launches whose last round of the CUs is poorly
-  // filled.  ON by default for forward launches since the hand-off is write-through and the schedule keeps a plain
-  // launch's locality (profiles/r03_negative_results.txt section 2 has the two builds that lost and why): 608x608
-  // batch 64 +0.7 %, 416x416 +0.6 %, the training forward -0.3 ms; VY_CONV_SK=0 restores plain launches.
-  if (sk_allowed(a)) {
-    static const int res_f = resident_blocks(conv_igemm_kernel<BM, BN, WM, WN, false, NS, true>, WM * WN * 64);
-    static const int res_d = resident_blocks(conv_igemm_kernel<BM, BN, WM, WN, true, NS, true>, WM * WN * 64);
-    const int sk_slots = vy_args_knobs(a).conv_sk_slots;
-    const int cus = vy_args_cus(a);
-    // blocks per CU: as many as fit, but never so many that a share is shorter than one tile (a share is at most
-    // [head][whole tiles][tail]).  344 tiles (the 13x13 maps at batch 16): ONE block per CU with 1.34 tiles each, where
-    // the plain launch leaves 88 CUs with two tiles and 168 with one
-    const long long per_cu = std::min<long long>(a.dgrad ? res_d : res_f, tiles / cus);
-    const long long G = sk_slots > 0 ? sk_slots : (long long)cus * per_cu;
-    // Split-K: a launch whose K is summed in S > 1 runs (the pinned order, vy_math.h) and whose tiles leave at least half
-    // of the CUs empty goes out as tiles x S workgroups, one run each; the last run's workgroup adds the others' sums in
-    // run order (conv_tile, ks_reduce) — the same arithmetic as one workgroup running the runs one after the other.
-    // Measured (profiles/r06_ksplit_probe.txt, one frame): 13x13 / 19x19 3x3 cells on 512 channels 75 -> 33 / 47 us; a
-    // launch of 184 tiles cut in two lost 4 %: hence tiles <= CUs / 2.  VY_CONV_KSPLIT=0: never.
-    if (ksplit_S > 1) {
-      const long long cap = (long long)cus * res_f;
-      if (vy_args_knobs(a).conv_ksplit && sk_slots == 0 && 2 * tiles <= cus && tiles * ksplit_S <= cap && tiles * ksplit_S * BM * BN * 4ll <= (long long)a.sk_bytes &&
-          tiles * ksplit_S <= a.sk_nflags) {
-        if (sk_query) {
-          *sk_query = false;
-          if (ks_query) *ks_query = ksplit_S;
-          return hipSuccess;
-        }
-        sk.partials = a.sk_partials;
-        sk.flags = a.sk_flags;
-        sk.tiles = (int)tiles;
-        sk.ksplit = ksplit_S;
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS, true>), dim3((unsigned)(tiles * ksplit_S)),
-                           dim3(WM * WN * 64), 0, s, a, tiles_n, sk);
-        return hipGetLastError();
-      }
-    }
-    bool pays = false;
-    if (const VyTileModel* tm = vy_tile_model(BM, BN))
-      vy_predict_launch(a.M, a.N, (double)a.ntaps * a.Kc, *tm, sk_policy(a), &pays, cus);
-    if (G > 0 && tiles > G && tiles * (G + 8) < (1ll << 31) && 2 * (G / 8 + 1) * (long long)(a.ntaps * (a.Kc >> 5)) < (1ll << 31) &&
-        (sk_slots > 0 || pays) && G * BM * BN * 4ll <= (long long)a.sk_bytes && G <= a.sk_nflags) {
-      if (sk_query) {
-        *sk_query = true;
-        return hipSuccess;
-      }
-      sk.partials = a.sk_partials;
-      sk.flags = a.sk_flags;
-      sk.tiles = (int)tiles;
-      if (a.dgrad)
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, true, NS, true>), dim3((unsigned)G), dim3(WM * WN * 64), 0, s,
-                           a, tiles_n, sk);
-      else if (a.k_chunk > 0)
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS, true, true>), dim3((unsigned)G), dim3(WM * WN * 64), 0, s,
-                           a, tiles_n, sk);
-      else
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS, true>), dim3((unsigned)G), dim3(WM * WN * 64), 0, s,
-                           a, tiles_n, sk);
-      return hipGetLastError();
-    }
-  }
-  if (sk_query) {
-    *sk_query = false;
-    return hipSuccess;
-  }
-  if (a.dgrad)
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, true, NS>), dim3(tiles_m * tiles_n), dim3(WM * WN * 64), 0, s,
-                       a, tiles_n, sk);
+  if (p.ks)  // split-K: tiles x S workgroups, one run each
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS, true>), grid, block, 0, s, a, tiles_n, sk);
+  else if (p.sk && a.dgrad)
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, true, NS, true>), grid, block, 0, s, a, tiles_n, sk);
+  else if (p.sk && a.k_chunk > 0)
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS, true, true>), grid, block, 0, s, a, tiles_n, sk);
+  else if (p.sk)
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS, true>), grid, block, 0, s, a, tiles_n, sk);
+  else if (a.dgrad)
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, true, NS>), grid, block, 0, s, a, tiles_n, sk);
   else if (a.k_chunk > 0)
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS, false, true>), dim3(tiles_m * tiles_n), dim3(WM * WN * 64), 0,
-                       s, a, tiles_n, sk);
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS, false, true>), grid, block, 0, s, a, tiles_n, sk);
   else
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS>), dim3(tiles_m * tiles_n), dim3(WM * WN * 64), 0, s,
-                       a, tiles_n, sk);
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, false, NS>), grid, block, 0, s, a, tiles_n, sk);
   return hipGetLastError();
 }
 
-// Tile choice: conv_cost_model.h, or the tile VY_CONV_FORCE names (tools/train_layers.sh, tools/probe/run_model_sweep.sh)
-static void select_cfg(const ConvArgs& a, int* bm, int* bn) {
-  const VyKnobs& k = vy_args_knobs(a);
-  if (k.conv_force_bm) {
-    *bm = k.conv_force_bm;
-    *bn = k.conv_force_bn;
-    return;
-  }
-  if (a.N <= 32) {
-    *bm = 128;
-    *bn = 32;
-    return;
-  }
-  bool sk_unused;
-  vy_select_tile(a.M, a.N, (double)a.ntaps * a.Kc, sk_policy(a), bm, bn, &sk_unused, vy_args_cus(a));
-}
-
-void vy_conv_cfg(const ConvArgs& a, int* bm, int* bn) { select_cfg(a, bm, bn); }
-
-// predicted time (microseconds) of the launch on this (exact fp32) kernel: what the split-fp32 instance has to beat
-double vy_conv_predict_us(const ConvArgs& a) {
-  if (a.N <= 32) return 0.0;  // own tile, no model: never handed to the split kernel (cout % 64 != 0 anyway)
-  int bm, bn;
-  bool sk;
-  return vy_select_tile(a.M, a.N, (double)a.ntaps * a.Kc, sk_policy(a), &bm, &bn, &sk, vy_args_cus(a));
-}
-
-int vy_conv_tiles_m(const ConvArgs& a) {
-  int bm, bn;
-  select_cfg(a, &bm, &bn);
-  return (a.M + bm - 1) / bm;
-}
-
-// tile choice -> template instance; `sk_query`: see launch_cfg
-static hipError_t run_cfg(const ConvArgs& a, hipStream_t s, bool* sk_query, int* ks_query = nullptr, VyConvForm* form = nullptr) {
-  int bm, bn;
-  select_cfg(a, &bm, &bn);
-  if (sk_query) *sk_query = false;
-  if (ks_query) *ks_query = 0;
-  if (bn == 32) return launch_cfg<128, 32, 4, 1>(a, s, sk_query, ks_query, form);
-  if (bm == 128 && bn == 64) return launch_cfg<128, 64, 2, 2>(a, s, sk_query, ks_query, form);
-  if (bm == 64) {
-    // few blocks (at most two per CU) and a k-loop long enough to fill it: the four-stage pipeline
-    const long long nb = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-    if (nb <= 512 && a.ntaps * (a.Kc >> 5) >= 8) return launch_cfg<64, 64, 2, 2, 4>(a, s, sk_query, ks_query, form);
-    return launch_cfg<64, 64, 2, 2>(a, s, sk_query, ks_query, form);
-  }
-  return launch_cfg<128, 128, 2, 2>(a, s, sk_query, ks_query, form);
-}
-
-bool vy_conv_streamk(const ConvArgs& a) {
-  bool sk = false;
-  return run_cfg(a, nullptr, &sk) == hipSuccess && sk;
-}
-
-int vy_conv_ksplit(const ConvArgs& a) {
-  bool sk = false;
-  int ks = 0;
-  return run_cfg(a, nullptr, &sk, &ks) == hipSuccess ? ks : 0;
-}
-
-void vy_conv_form(const ConvArgs& a, VyConvForm* f) {
-  bool sk = false;
-  int ks = 0;
-  memset(f, 0, sizeof *f);
-  select_cfg(a, &f->bm, &f->bn);
-  if (run_cfg(a, nullptr, &sk, &ks, f) != hipSuccess) return;
-  f->sk = sk;
-  f->ks = ks;
-  if (ks) f->ck = 0;  // one workgroup per run: nothing is parked
-}
-
-void vy_conv_form_label(const ConvArgs& a, char* buf, size_t n) {
-  VyConvForm f;
-  vy_conv_form(a, &f);
-  char sched[24] = "";
-  if (f.ks) snprintf(sched, sizeof sched, "ks%d", f.ks);
-  else if (f.ck) snprintf(sched, sizeof sched, "ck%d%s", f.ck, f.sk ? "sk" : "");
-  else if (f.sk) snprintf(sched, sizeof sched, "sk");
-  snprintf(buf, n, "%dx%d%s%s", f.bm, f.bn, f.ns == 4 ? "s4" : "", sched);
-}
-
-size_t vy_conv_chunk_scratch_bytes(long long M, int N, int runs) {
-  const long long m = (M + 127) / 128 * 128, n = ((long long)N + 127) / 128 * 128;
-  return runs > 1 ? (size_t)((runs - 1) * m * n * 4) : 0;
-}
-
-hipError_t vy_launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
+hipError_t vy_launch_conv_igemm(const ConvArgs& a_in, const VyConvPlan& p, hipStream_t s) {
   ConvArgs a = a_in;
-  if (a.LW < 1 || a.LH < 1) return hipErrorInvalidValue;
+  if (p.kernel != VY_KERNEL_EXACT || a.LW < 1 || a.LH < 1) return hipErrorInvalidValue;
   a.fd_lw = vy_fastdiv((unsigned)a.LW);
   a.fd_lh = vy_fastdiv((unsigned)a.LH);
   if (!vy_conv_pack_taps(a)) return hipErrorInvalidValue;
   if (a.Kc % 32 != 0 || a.ntaps < 1 || a.ntaps > 9 || a.M <= 0 || a.N <= 0) return hipErrorInvalidValue;
   if (a.dgrad && (a.N % 4 != 0)) return hipErrorInvalidValue;
-  if (!vy_conv_epilogue_supported(a)) return hipErrorInvalidValue;
-  return run_cfg(a, s, nullptr);
+  a.k_chunk = p.k_chunk;
+  // (hipcc emits the kernels in the order this function and launch_cfg first name them, and their register allocation
+  // follows that order: tools/asm_counts.py shows a reordering as changed instruction text)
+  if (p.bm == 128 && p.bn == 32) return launch_cfg<128, 32, 4, 1>(a, p, s);
+  if (p.bm == 128 && p.bn == 64) return launch_cfg<128, 64, 2, 2>(a, p, s);
+  if (p.bm == 64 && p.bn == 64 && p.ns == 4) return launch_cfg<64, 64, 2, 2, 4>(a, p, s);
+  if (p.bm == 64 && p.bn == 64) return launch_cfg<64, 64, 2, 2>(a, p, s);
+  if (p.bm == 128 && p.bn == 128) return launch_cfg<128, 128, 2, 2>(a, p, s);
+  return hipErrorInvalidValue;
 }
+
+// the exact kernel whatever weight images the arguments carry (tools/probe: hand-made ConvArgs)
+hipError_t vy_launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
+  ConvArgs a = a_in;
+  a.w_split = a.w_wino = nullptr;
+  return vy_launch_conv_igemm(a, vy_conv_plan(a), s);
+}
+
+// blocks of the five instances one CU holds (their stream-K build: the schedule's shares are counted in it)
+template <int BM, int BN, int WM, int WN, int NS>
+static void resident_of(VyConvResidency* r, int inst) {
+  r->fwd[inst] = resident_blocks(conv_igemm_kernel<BM, BN, WM, WN, false, NS, true>, WM * WN * 64);
+  r->dgrad[inst] = resident_blocks(conv_igemm_kernel<BM, BN, WM, WN, true, NS, true>, WM * WN * 64);
+}
+static VyConvResidency query_residency() {
+  VyConvResidency r;
+  resident_of<128, 128, 2, 2, 2>(&r, VY_EXACT_128x128);
+  resident_of<128, 64, 2, 2, 2>(&r, VY_EXACT_128x64);
+  resident_of<128, 32, 4, 1, 2>(&r, VY_EXACT_128x32);
+  resident_of<64, 64, 2, 2, 2>(&r, VY_EXACT_64x64);
+  resident_of<64, 64, 2, 2, 4>(&r, VY_EXACT_64x64_S4);
+  return r;
+}
+const VyConvResidency& vy_conv_residency() {
+  static const VyConvResidency r = query_residency();
+  return r;
+}
+VyConvPlan vy_conv_plan(const ConvArgs& a) { return vy_conv_plan(a, vy_conv_residency()); }

@@ -34,7 +34,7 @@
 #include "kernels.h"
 #include "../../include/vy_math.h"
 #include "conv_device.h"
-#include "conv_cost_model.h"
+#include "conv_launch.h"
 
 #include "split_device.h"
 
@@ -473,48 +473,6 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const ConvArgs a, co
 #endif
 }
 
-bool vy_conv_split_supported(const ConvArgs& a) {
-  if (!a.w_split) return false;
-  if (a.stats && VY_SPLIT_M16) return false;
-  if (a.Kc % 32 != 0 || a.N % 64 != 0 || a.ntaps < 1 || a.ntaps > 9) return false;
-  return vy_conv_epilogue_supported(a);
-}
-
-// block tile and k-split of a launch: the cost model's choice (conv_cost_model.h) among 128x128, 128x64 and, for the
-// 64-channel layers, 256x64; k-split > 1 only where the slabs fit the scratch the net provides
-static long long split_max_ksplit(const ConvArgs& a) {
-  if (!a.splitk_slabs || a.stats) return 1;  // (the per-tile statistics need whole sums)
-  return std::max<long long>(1, (long long)(a.splitk_bytes / ((unsigned long long)a.M * a.N * 4ull)));
-}
-
-void vy_conv_split_cfg(const ConvArgs& a, int* bm, int* bn, int* ksplit) {
-  const long long max_ks = std::min<long long>(split_max_ksplit(a), 64);
-  vy_predict_split(a.M, a.N, (double)a.ntaps * a.Kc, (int)max_ks, bm, bn, ksplit, vy_args_cus(a));
-  // VY_SPLIT_FORCE (tests: the forms no small shape reaches): the named tile where the launch's channels divide by it;
-  // the named k-split as far as the slabs' scratch, the per-tile statistics (whole sums) and the k-steps allow
-  // NOTE: this reaches forms the cost model never picks — 256x64 on layers of 128 channels and more (the model keeps the
-  // 256-row tile for the 64-channel layers) and k-slices down to ONE k-step (the model wants steps / S >= 6; T = 1 is
-  // served by the k-loop's tail, and the clamp below keeps T >= 1).  The kernel is correct on them, and the per-cell tests
-  // that run under this knob certify them too; the census ties plans to walked forms only as (tile, k1 | k>1).
-  const VyKnobs& k = vy_args_knobs(a);
-  if (k.split_force_bm && a.N % k.split_force_bn == 0) {
-    *bm = k.split_force_bm;
-    *bn = k.split_force_bn;
-  }
-  if (k.split_force_ks)
-    *ksplit = (int)std::max<long long>(1, std::min<long long>({(long long)k.split_force_ks, max_ks, (long long)a.ntaps * (a.Kc >> 4)}));
-}
-
-bool vy_conv_split_pays(const ConvArgs& a) {
-  if (!vy_conv_split_supported(a)) return false;
-  if (vy_args_knobs(a).split_always) return true;  // tests: every supported launch, however small
-  const int cus = vy_args_cus(a);
-  if (!vy_model_fitted(cus)) return false;  // the comparison between the two kernels was fitted on 256 CUs (conv_cost_model.h)
-  int bm, bn, ks;
-  return vy_predict_split(a.M, a.N, (double)a.ntaps * a.Kc, (int)std::min<long long>(split_max_ksplit(a), 64), &bm, &bn, &ks, cus) <
-         0.97 * vy_conv_predict_us(a);
-}
-
 // second launch of a split-K conv: out = epilogue(sum over s of slab s), slabs added in index order (deterministic).
 // One thread = 4 consecutive channels of one output pixel.
 __global__ __launch_bounds__(256) void splitk_finish_kernel(const ConvArgs a, const int ksplit) {
@@ -572,19 +530,18 @@ static hipError_t launch_split(const ConvArgs& a, int ksplit, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t vy_launch_conv_split(const ConvArgs& a_in, hipStream_t s) {
+// the plan's tile and k-slices (conv_launch.h) -> template instance
+hipError_t vy_launch_conv_split(const ConvArgs& a_in, const VyConvPlan& p, hipStream_t s) {
   ConvArgs a = a_in;
-  if (!vy_conv_split_supported(a) || a.LW < 1 || a.LH < 1 || a.M <= 0) return hipErrorInvalidValue;
+  if (p.kernel != VY_KERNEL_SPLIT || !vy_conv_split_supported(a) || a.LW < 1 || a.LH < 1 || a.M <= 0) return hipErrorInvalidValue;
   a.fd_lw = vy_fastdiv((unsigned)a.LW);
   a.fd_lh = vy_fastdiv((unsigned)a.LH);
   if (!vy_conv_pack_taps(a)) return hipErrorInvalidValue;
-  int bm, bn, ks;
-  vy_conv_split_cfg(a, &bm, &bn, &ks);
   // (Two more instances were built, measured on the MI355X and removed — profiles/r04_negative_results.txt sections 3 and
   // 7: a deep pipeline for launches that leave a CU with one block, loads three k-steps ahead: no gain; the A operand
   // pre-split into bf16 planes and DMA'd like the weights: 3.5-14 % slower.)
-  if (bm == 128 && bn == 128) return launch_split<128, 128, 3>(a, ks, s);
-  if (bm == 256 && bn == 64) return launch_split<256, 64, 2>(a, ks, s);
-  if (bm == 128 && bn == 64) return launch_split<128, 64, 3>(a, ks, s);
+  if (p.bm == 128 && p.bn == 128) return launch_split<128, 128, 3>(a, p.split_ks, s);
+  if (p.bm == 256 && p.bn == 64) return launch_split<256, 64, 2>(a, p.split_ks, s);
+  if (p.bm == 128 && p.bn == 64) return launch_split<128, 64, 3>(a, p.split_ks, s);
   return hipErrorInvalidValue;
 }

@@ -22,7 +22,7 @@
 // loads and W DMA run one k-step ahead; the wait before a barrier is counted (the four A loads are younger than the DMA).
 // Measured beside the 128 x 128 direct tile at 608x608 batch 64 (profiles/r04_wino_probe.txt): 76x76 128->256 +9 %,
 // 38x38 256->512 +16 %, 19x19 512->1024 +15 %; in the net (tools/layer_profile.py, VY_SPLIT_WINO=2 / 0) every supported cell
-// wins from batch 8 on, none of a single frame's (those stay on conv_split.hip's k-split): vy_conv_wino_pays.
+// wins from batch 8 on, none of a single frame's (those stay on conv_split.hip's k-split): vy_conv_plan (conv_launch.h).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -31,7 +31,7 @@
 #include "kernels.h"
 #include "../../include/vy_math.h"
 #include "split_device.h"
-#include "conv_cost_model.h"
+#include "conv_launch.h"
 
 // weights [cout][3][3][cin] fp32 -> four images (xi) of [cout / 32][3 cin / 16][plane][32 rows][2 slots][8 channels]
 __global__ void wino_weights_kernel(const float* __restrict__ w, unsigned short* __restrict__ img, const int cout, const int cin,
@@ -348,62 +348,18 @@ __global__ __launch_bounds__(BM * 4, BM == 64 ? 2 : 1) void conv_wino_kernel(con
 #endif
 }
 
-bool vy_conv_wino_supported(const ConvArgs& a) {
-  if (!a.w_wino || a.ntaps != 9 || a.a_s != 1 || a.ups != 1 || a.o_s != 1 || a.dgrad || a.stats) return false;
-  if (!a.scale || !a.shift || !a.leaky) return false;  // the conv + BN + leaky cell (+ residual)
-  if (a.Kc % 32 != 0 || a.N % 128 != 0 || a.LW < 2) return false;
-  for (int t = 0; t < 9; ++t)
-    if (a.tap_dy[t] != t / 3 - 1 || a.tap_dx[t] != t % 3 - 1 || a.tap_w[t] != t) return false;
-  return true;
-}
-
-static long long wino_tiles(const ConvArgs& a, int bm) {
-  const long long pairs = (long long)a.B * a.LH * ((a.LW + 1) / 2);
-  return ((pairs + bm - 1) / bm) * (a.N / 128);
-}
-
-// pairs per block of the launch (probe builds: VY_WINO_BM=128)
-static int wino_bm(const ConvArgs& a) {
-#ifdef VY_WINO_BM128
-  if (vy_args_knobs(a).wino_bm == 128) return 128;
-#endif
-  return 64;
-}
-
-// Per launch, where the cost models say it wins (conv_cost_model.h: vy_predict_wino against the split kernel's and the
-// exact kernel's predictions): at 608x608 every supported cell from batch 8 on, the 152x152 / 76x76 ones from batch 2, none of
-// a single frame's (the split kernel's k-split covers those).  VY_SPLIT_WINO=0: never, =2: wherever supported (tests)
-bool vy_conv_wino_pays(const ConvArgs& a) {
-  if (!vy_conv_wino_supported(a)) return false;
-  const int mode = vy_args_knobs(a).split_wino;
-  if (mode == 0) return false;
-  if (mode == 2) return true;
-  const int cus = vy_args_cus(a);
-  if (!vy_model_fitted(cus)) return false;  // fitted on 256 CUs (conv_cost_model.h)
-  const long long pairs = (long long)a.B * a.LH * ((a.LW + 1) / 2);
-  const double t_wino = vy_predict_wino(pairs, a.N, a.Kc, cus);
-  double t_other = vy_conv_predict_us(a);
-  if (vy_conv_split_supported(a)) {
-    const long long max_ks = a.splitk_slabs ? std::max<long long>(1, (long long)(a.splitk_bytes / ((unsigned long long)a.M * a.N * 4ull))) : 1;
-    int bm, bn, ks;
-    t_other = std::min(t_other, vy_predict_split(a.M, a.N, 9.0 * a.Kc, (int)std::min<long long>(max_ks, 64), &bm, &bn, &ks, cus));
-  }
-  return t_wino < 0.97 * t_other;
-}
-
-hipError_t vy_launch_conv_wino(const ConvArgs& a, hipStream_t s) {
-  if (!vy_conv_wino_supported(a) || a.LH < 1 || a.M <= 0) return hipErrorInvalidValue;
+hipError_t vy_launch_conv_wino(const ConvArgs& a, const VyConvPlan& p, hipStream_t s) {
+  if (p.kernel != VY_KERNEL_WINO || !vy_conv_wino_supported(a) || a.LH < 1 || a.M <= 0) return hipErrorInvalidValue;
   const int Wp2 = (a.LW + 1) / 2, Mp = a.B * a.LH * Wp2, tiles_n = a.N / 128;
   ConvArgs k = a;
   k.w_split = a.w_wino;  // (the kernel reads its images through the same field)
-  const int bm = wino_bm(a);
   const long long wb = (long long)vy_split_weight_bytes(a.w_cout, 3, a.Kc);
 #ifdef VY_WINO_BM128
-  if (bm == 128) {
-    hipLaunchKernelGGL(conv_wino_kernel<128>, dim3((unsigned)wino_tiles(a, 128)), dim3(512), 0, s, k, tiles_n, Wp2, Mp, wb);
+  if (p.bm == 128) {
+    hipLaunchKernelGGL(conv_wino_kernel<128>, dim3((unsigned)p.grid), dim3(512), 0, s, k, tiles_n, Wp2, Mp, wb);
     return hipGetLastError();
   }
 #endif
-  hipLaunchKernelGGL(conv_wino_kernel<64>, dim3((unsigned)wino_tiles(a, bm)), dim3(256), 0, s, k, tiles_n, Wp2, Mp, wb);
+  hipLaunchKernelGGL(conv_wino_kernel<64>, dim3((unsigned)p.grid), dim3(256), 0, s, k, tiles_n, Wp2, Mp, wb);
   return hipGetLastError();
 }

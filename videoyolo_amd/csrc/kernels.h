@@ -109,27 +109,14 @@ static inline bool vy_conv_epilogue_supported(const ConvArgs& a) {
   return (bn_cell && (a.ups != 2 || !a.res)) || (plain && a.ups != 2);
 }
 
-// 3x3/1x1 implicit-GEMM convolution on v_mfma_f32_32x32x2_f32.
+// 3x3/1x1 implicit-GEMM convolution on v_mfma_f32_32x32x2_f32.  Which kernel, tile and schedule a launch gets, and the
+// launchers that take that plan: conv_launch.h.  This one plans and launches on the exact kernel only (tools/probe)
 hipError_t vy_launch_conv_igemm(const ConvArgs& a, hipStream_t s);
-int vy_conv_tiles_m(const ConvArgs& a);
-void vy_conv_cfg(const ConvArgs& a, int* bm, int* bn);  // block tile the launch will use
-double vy_conv_predict_us(const ConvArgs& a);             // the cost model's time for the launch (conv_cost_model.h)
 int vy_cu_count();                                        // CUs of the CURRENT device (nets resolve theirs once: vy_net::cus)
 int vy_cu_count_of(int device);                           // ... of a given device ordinal
 int vy_cu_count_of_ptr(const void* dev_ptr);              // ... of the device that owns an allocation (0: not a device pointer)
 static inline int vy_args_cus(const ConvArgs& a) { return a.cus > 0 ? a.cus : vy_cu_count(); }
 static inline const VyKnobs& vy_args_knobs(const ConvArgs& a) { return a.knobs ? *a.knobs : vy_knobs_default(); }
-bool vy_conv_streamk(const ConvArgs& a);                  // ... and whether it will be a stream-K launch (label "<BM>x<BN>sk")
-int vy_conv_ksplit(const ConvArgs& a);                    // ... or a split-K one: the S workgroups per tile (label "<BM>x<BN>ks<S>"), else 0
-// ... the whole form in one query (the training step's launch labels): block tile, LDS stages (2 / 4), and the schedule —
-// sk: stream-K; ks: split-K workgroups per tile; ck: the runs of K one workgroup takes in turn with parked chains (0: K
-// is one run, or the launch is split-K).  Label "<BM>x<BN>[s4][sk | ks<S> | ck<S> | ck<S>sk]"
-struct VyConvForm {
-  int bm, bn, ns, sk, ks, ck;
-};
-void vy_conv_form(const ConvArgs& a, VyConvForm* f);
-void vy_conv_form_label(const ConvArgs& a, char* buf, size_t n);
-size_t vy_conv_chunk_scratch_bytes(long long M, int N, int runs);   // ck_scratch bytes a conv of M x N outputs summed in `runs` runs may need (any tile)
 
 // stream-K is enabled per net only after this has seen the MI355X's SPX placement (8 XCDs, blocks L and L + 8 on one
 // XCD, 256 CUs) on the current device; `scratch_dev`: >= 512 words the probe may use and leaves zeroed.  Synchronises `s`
@@ -137,7 +124,7 @@ size_t vy_conv_chunk_scratch_bytes(long long M, int N, int runs);   // ck_scratc
 int vy_sk_verify_topology(unsigned* scratch_dev, hipStream_t s);
 
 // Opt-in split-fp32 forward conv on the bf16 matrix core (conv_split.hip: bf16 x 3, six products, fp32 accumulate).
-// Same ConvArgs / planes as vy_launch_conv_igemm, plus a.w_split = the conv's weights as bf16 tile images.
+// Same ConvArgs / planes as the exact kernel, plus a.w_split = the conv's weights as bf16 tile images.
 size_t vy_split_weight_bytes(int cout, int taps, int cin);
 hipError_t vy_launch_split_weights(const float* w, void* img, int cout, int taps, int cin, hipStream_t s);
 // ... and as the [k = cout][n = cin] operand of the data gradient (cin % 32 == 0; cout zero-padded to 32)
@@ -158,15 +145,6 @@ hipError_t vy_launch_split_weights_batch(const float* params, void* ws, const Sp
 // a.w_wino = the transformed image sets)
 size_t vy_wino_weight_bytes(int cout, int cin);
 hipError_t vy_launch_wino_weights(const float* w, void* img, int cout, int cin, hipStream_t s);
-bool vy_conv_wino_supported(const ConvArgs& a);
-bool vy_conv_wino_pays(const ConvArgs& a);          // the cost models' verdict (conv_cost_model.h: vy_predict_wino); VY_SPLIT_WINO=0 / 2
-hipError_t vy_launch_conv_wino(const ConvArgs& a, hipStream_t s);
-bool vy_conv_split_supported(const ConvArgs& a);   // forward, N % 64 == 0, Kc % 32 == 0, an epilogue the kernel has
-void vy_conv_split_cfg(const ConvArgs& a, int* bm, int* bn, int* ksplit);  // block tile and k-split the launch will use
-// conv mode VY_CONV_SPLIT_BF16X3, per launch: supported AND predicted faster than the exact kernel (small launches —
-// a single frame's deep layers — stay on the exact kernel, which has the small tiles and stream-K)
-bool vy_conv_split_pays(const ConvArgs& a);
-hipError_t vy_launch_conv_split(const ConvArgs& a, hipStream_t s);
 
 // stem: 3x3 stride-1 conv from the caller's NCHW image (Cin = 3) into a plane, fused affine+leaky.
 // BN fold: scale = gamma / sqrt(var + eps), shift = beta - mean*scale for n_layers BN layers.

@@ -14,6 +14,7 @@
 
 #include "vy_support.h"
 #include "kernels.h"
+#include "conv_launch.h"
 #include "../../include/vy_math.h"
 
 // VY_ERR_INVALID unless (batch, h, w) is a shape the planner takes (defined in net.hip)
@@ -922,11 +923,6 @@ struct vy_net {
     return 0;
   }
 
-  enum ConvKernel { kExact, kSplit, kWino };
-  static hipError_t launch_conv(ConvKernel kernel, const ConvArgs& a, hipStream_t s) {
-    return kernel == kWino ? vy_launch_conv_wino(a, s) : kernel == kSplit ? vy_launch_conv_split(a, s) : vy_launch_conv_igemm(a, s);
-  }
-
   // the cells [first, last) of the conv list; x: the image batch the stem reads (unused unless the span holds it)
   template <typename Hook>
   int run_cells(int first, int last, const float* x, hipStream_t s, Hook& hook) {
@@ -948,30 +944,18 @@ struct vy_net {
         continue;
       }
       const ConvArgs a = conv_args(ci);
-      const ConvKernel kernel = a.w_wino && vy_conv_wino_pays(a) ? kWino : a.w_split && vy_conv_split_pays(a) ? kSplit : kExact;
-      if (!kLabels<Hook>) {  // plain forward: no label, no second tile / stream-K query per launch (batch-1 latency path)
-        HIP_TRY(launch_conv(kernel, a, s));
+      const VyConvPlan plan = vy_conv_plan(a);
+      if (!kLabels<Hook>) {  // plain forward: no label (batch-1 latency path)
+        HIP_TRY(vy_launch_conv(a, plan, s));
         continue;
       }
       const double fl = 2.0 * a.M * (double)a.N * a.ntaps * a.Kc;
       const double by = 4.0 * ((double)a.B * (a.a_Hp - 2) * (a.a_Wp - 2) * a.Kc + (double)a.M * a.N * a.ups * a.ups +
                                (double)a.N * a.ntaps * a.Kc + (a.res ? (double)a.M * a.N : 0.0));
-      char nm[96];
-      int bm, bn, ks;
-      if (kernel == kWino) {
-        snprintf(nm, sizeof nm, "%s|wino64x128", c.name.c_str());
-      } else if (kernel == kSplit) {
-        vy_conv_split_cfg(a, &bm, &bn, &ks);
-        if (ks > 1) snprintf(nm, sizeof nm, "%s|split%dx%dk%d", c.name.c_str(), bm, bn, ks);
-        else snprintf(nm, sizeof nm, "%s|split%dx%d", c.name.c_str(), bm, bn);
-      } else {
-        vy_conv_cfg(a, &bm, &bn);
-        if ((ks = vy_conv_ksplit(a)))
-          snprintf(nm, sizeof nm, "%s|%dx%dks%d", c.name.c_str(), bm, bn, ks);
-        else
-          snprintf(nm, sizeof nm, "%s|%dx%d%s", c.name.c_str(), bm, bn, vy_conv_streamk(a) ? "sk" : "");
-      }
-      HOOKED(hook, nm, fl, by, launch_conv(kernel, a, s));
+      char form[32], nm[96];
+      vy_conv_plan_label(plan, VY_LABEL_PROFILE, form, sizeof form);
+      snprintf(nm, sizeof nm, "%s|%s", c.name.c_str(), form);
+      HOOKED(hook, nm, fl, by, vy_launch_conv(a, plan, s));
     }
     return 0;
   }

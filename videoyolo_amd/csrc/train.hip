@@ -115,18 +115,11 @@ struct LabelLog {
   // which kernel the preceding line went to, and in which form (tests assert that the launches they mean to cover really
   // ran; tools/train_layers.py skips '#' lines):
   //   "# via split 128x128 k2"          fwd / dgrad on the split-fp32 kernel
-  //   "# via exact 128x64sk"            fwd / dgrad on the exact kernel: vy_conv_form_label's tile, stages and schedule
+  //   "# via exact 128x64sk"            fwd / dgrad on the exact kernel: tile, stages and schedule (vy_conv_plan_label)
   //   "# via wgrad_kernel<32,64> splits 14 reduce wide<8> stream side"   wgrad: the kernel instance, its slabs, their
   //                                     reduce (plain / wide<8> / wide<32>) and the stream both went to (side / main)
   void via(const char* text) {
     if (f) fprintf(f, "# via %s\n", text);
-  }
-  void via_exact(const ConvArgs& a) {
-    if (!f) return;
-    char form[48], t[64];
-    vy_conv_form_label(a, form, sizeof form);
-    snprintf(t, sizeof t, "exact %s", form);
-    via(t);
   }
   void via_wgrad(const char* kernel, int splits, bool side) {
     if (!f) return;
@@ -428,22 +421,17 @@ int refresh_split_images(const TrainCtx& c) {
   return 0;
 }
 
-// the conv launch of the training passes: the split-fp32 kernel where the launch has its weight images (a.w_split: see
-// TrainCell::fwd_split / dgrad_split) and the cost model predicts a gain; the exact kernel otherwise
-static int launch_conv(const ConvArgs& a, hipStream_t s) {
-  if (a.w_split && vy_conv_split_pays(a)) {
-    if (g_labels.f) {
-      int bm, bn, ks;
-      char t[64];
-      vy_conv_split_cfg(a, &bm, &bn, &ks);
-      snprintf(t, sizeof t, "split %dx%d k%d", bm, bn, ks);
-      g_labels.via(t);
-    }
-    HIP_TRY(vy_launch_conv_split(a, s));
-  } else {
-    g_labels.via_exact(a);
-    HIP_TRY(vy_launch_conv_igemm(a, s));
+// the conv launch of the training passes, by its plan (conv_launch.h): the split-fp32 kernel where the launch has its weight
+// images (a.w_split: see TrainCell::fwd_split / dgrad_split) and the cost model predicts a gain; the exact kernel otherwise.
+// Never the Winograd kernel: it serves the conv + BN + leaky cell only, and no training launch is one — the recorded forward
+// carries a.stats, a data gradient a.dgrad, a prediction conv no scale (vy_conv_wino_supported refuses each)
+static int launch_conv(const ConvArgs& a, const VyConvPlan& plan, hipStream_t s) {
+  if (g_labels.f) {
+    char t[64];
+    vy_conv_plan_label(plan, VY_LABEL_TRAIN, t, sizeof t);
+    g_labels.via(t);
   }
+  HIP_TRY(vy_launch_conv(a, plan, s));
   return 0;
 }
 
@@ -453,9 +441,7 @@ int pred_conv(const TrainCtx& c, int ci) {
   const ConvT& cv = c.net->convs[ci];
   const ConvArgs a = c.net->conv_args(ci);
   g_labels.note(c.net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
-  g_labels.via_exact(a);
-  HIP_TRY(vy_launch_conv_igemm(a, c.s));
-  return 0;
+  return launch_conv(a, vy_conv_plan(a), c.s);  // (no weight images for a conv without BatchNorm: the exact kernel)
 }
 
 // the raw conv of a BatchNorm cell (the stem: from the image batch x) into its z plane, with the per-tile channel sums
@@ -487,14 +473,9 @@ int raw_conv(const TrainCtx& c, int ci, const float* x, int* n_part) {
   a.stats = reinterpret_cast<double*>(c.partials());
   if (!cell.fwd_split) a.w_split = nullptr;
   g_labels.note(net, "fwd", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
-  VY_TRY(launch_conv(a, c.s));
-  if (a.w_split && vy_conv_split_pays(a)) {  // the per-tile statistics rows follow the tile that ran
-    int sbm, sbn, sks;
-    vy_conv_split_cfg(a, &sbm, &sbn, &sks);
-    *n_part = (a.M + sbm - 1) / sbm;
-  } else {
-    *n_part = vy_conv_tiles_m(a);
-  }
+  const VyConvPlan plan = vy_conv_plan(a);
+  VY_TRY(launch_conv(a, plan, c.s));
+  *n_part = plan.stat_rows;  // the per-tile statistics rows follow the tile that ran
   return 0;
 }
 
@@ -842,7 +823,7 @@ int data_grad(const TrainCtx& c, int ci, DzView dz, BwdState& st) {
     }
     g_labels.note(net, "dgrad", cv.name, a.M, a.N, (double)a.ntaps * a.Kc);
     if (train_abl(net) & 16) continue;  // (bound measurement: no data-gradient kernel)
-    VY_TRY(launch_conv(a, c.s));
+    VY_TRY(launch_conv(a, vy_conv_plan(a), c.s));
   }
   if (cov == 0) st.touched[cv.in_plane].push_back({lo, hi});
   return 0;
