@@ -537,6 +537,32 @@ int vy_voc_match(int32_t batch, int32_t rows, int32_t n_gt, const float* det_box
                  const float* det_score, const float* gt_box, const int32_t* gt_label, const uint8_t* gt_difficult,
                  float iou_thresh, int32_t* best, int8_t* flags, void* stream);
 
+/* The per-frame mean AP (detect_yolo3.py:451-534, add_metrics_to_predictions: metric.reset(); metric.update(one frame);
+ * metric.get() per frame, the eighth column of its prediction files and what summary.txt ranks clips by) for a batch of
+ * images on the device, one launch, from the flags of the match above.  videoyolo_amd/metrics.py states the rule
+ * (frame_map_host); the kernel (csrc/voc_metric.hip) runs one 256-thread workgroup per image.  Needs no vy_net.
+ *
+ * det_label, det_score (batch, rows) fp32 and flags (batch, rows) int8 as given to and written by the match (1 TP, 0 FP,
+ * -1 matched a difficult ground truth: neither, -2 padding); gt_label (batch, n_gt) int32 class-mapped, < 0 = skip;
+ * gt_difficult (batch, n_gt) bytes or NULL — the same arrays.
+ * Per image: class c has npos = its ground truths that are not difficult; only classes with npos > 0 are averaged (one
+ * without a detection with AP 0; one with detections and npos = 0 not at all).  A class's rows rank by score descending, at
+ * equal scores the lower row first; tp / fp at a row count the flag-1 / flag-0 rows at or ahead of it, prec = tp / (tp + fp)
+ * (0 / 0 -> 0), rec = tp / npos.  use_07 == 0, area AP: the sum over the class's TP rows of (tp / npos - (tp - 1) / npos) x
+ * the largest prec at or behind the row.  use_07 != 0, 11-point AP: for k = 0..10, t = 0.0 + k * 0.1, ap += (the largest
+ * prec over rows with rec >= t, else 0) / 11.  All float64, the divides correctly rounded.
+ * frame_ap (batch) float64: the sum of the classes' AP / their number, NaN when there is none.  frame_classes (batch)
+ * int32: that number.  The sum is formed in a fixed order without floating-point atomics: an image's value is the same
+ * bits on every run and in any batch.
+ * rows <= VY_VOC_ROWS_MAX per image: 25 bytes of LDS per row, 25 KiB at the limit.  n_gt is not limited; counting the
+ * scored classes costs up to n_gt^2 / 256 label reads per lane and image.
+ * Checked before anything is launched, else VY_ERR_INVALID: null pointers (gt_difficult excepted), negative counts, rows
+ * above the limit.  batch == 0: VY_OK without a launch; rows == 0 is launched (0.0 with ground truth, NaN without).
+ * Asynchronous on `stream`; no device memory of the library's, no copy, no synchronisation. */
+int vy_voc_frame_ap(int32_t batch, int32_t rows, int32_t n_gt, const float* det_label, const float* det_score,
+                    const int8_t* flags, const int32_t* gt_label, const uint8_t* gt_difficult, int32_t use_07,
+                    double* frame_ap, int32_t* frame_classes, void* stream);
+
 /* The matching step of the COCO detection metric (metrics/mscoco.py, COCODetectionMetric: the second metric the detect
  * driver builds by default, detect_yolo3.py:185; the reference hands the evaluation to pycocotools' COCOeval, iouType
  * 'bbox', whose per-image rule is restated in videoyolo_amd/metrics.py, coco_match_host, [UPSTREAM-RECALLED]) for a batch

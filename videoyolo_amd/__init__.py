@@ -21,8 +21,9 @@ from .lr_scheduler import LRScheduler, LRSequential  # noqa: F401,E402
 from . import metrics  # noqa: F401,E402
 from .metrics import VIDDetectionMetric  # noqa: F401,E402
 from .metrics import COCODetectionMetric  # noqa: F401,E402
+from .metrics import FrameMApMetric  # noqa: F401,E402
 from .transforms import MixupDetection, MixedClip  # noqa: F401,E402
 
 __all__ = ["yolo3_darknet53", "yolo3_no_backbone", "YOLOV3", "YOLOV3T", "YOLOV3NoBackbone", "YOLOV3_noback", "YOLOV3Window", "YOLOV3Hier", "YOLOV3NoBackboneWindow",
            "BatchNorm", "SyncBatchNorm", "autograd", "Trainer", "parallel", "lr_scheduler", "video", "VideoSession", "window_indices",
-           "LRScheduler", "LRSequential", "metrics", "VIDDetectionMetric", "COCODetectionMetric", "MixupDetection", "MixedClip"]
+           "LRScheduler", "LRSequential", "metrics", "VIDDetectionMetric", "COCODetectionMetric", "FrameMApMetric", "MixupDetection", "MixedClip"]

@@ -189,6 +189,8 @@ VY_VOC_ROWS_MAX = 1024
 SIGNATURES.update({
     # the PASCAL-VOC metric's matching step (videoyolo_amd/metrics.py, csrc/voc_metric.hip)
     "vy_voc_match": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+    # the per-frame mean AP from the match's flags (metrics.FrameMApMetric, csrc/voc_metric.hip)
+    "vy_voc_frame_ap": (ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
 })
 
 VY_COCO_ROWS_MAX = 1024

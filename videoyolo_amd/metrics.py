@@ -14,6 +14,9 @@ Accepts numpy arrays, torch tensors (any device) or lists of them (one per devic
 along the batch axis like utils/general.py:6-17 ``as_numpy``).  float32 tensors on a GPU are matched there
 (``voc_match_host`` states the rule, csrc/voc_metric.hip applies it) and copied once, by ``get()``.
 
+After them: the per-frame mean AP and the worst-clip ranking (``frame_map_host``, ``FrameMApMetric``), scored on the
+device from the same match.
+
 Further down: the ImageNet-VID motion / area mAP (``VIDDetectionMetric``) and the COCO detection metric
 (``COCODetectionMetric``), each with its matching rule stated on the host and applied on the device the same way.
 """
@@ -148,6 +151,82 @@ def _chunks_to_host(chunks):
     return [tuple(h) for h in host]
 
 
+class _VocDeviceBatch(object):
+    """A batch the VOC matching accepts on the device, as vy_voc_match takes it: contiguous tensors of one GPU."""
+    __slots__ = ("dev", "batch", "rows", "n_gt", "boxes", "labels", "scores", "gt_boxes", "mapped", "diff")
+
+
+def _voc_device_batch(class_map, luts, pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults):
+    """The acceptance test of the VOC metrics' device path (VOCMApMetric, FrameMApMetric): float32 tensors of one GPU
+    (predictions and ground-truth boxes; labels and difficults of any numeric dtype there), at most VY_VOC_ROWS_MAX rows
+    per image, ``class_map`` None or a sequence.  Returns the batch ready for the kernels — ground-truth labels through
+    the class map (``luts``: its upload per device), difficults as bytes — or None: the call is the host path's."""
+    cm = class_map
+    if not (cm is None or isinstance(cm, (list, tuple, np.ndarray))):
+        return None
+    args = [_gather(x) for x in (pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults)]
+    if not all(hasattr(x, "is_cuda") for x in args[:5]):
+        return None
+    import torch
+    pb, pl, ps, gb, gl, gd = args
+    if not all(_is_gpu_f32(x) for x in (pb, pl, ps, gb)):
+        return None
+    others = [gl] if gd is None else [gl, gd]
+    if not all(isinstance(x, torch.Tensor) and not x.is_complex() for x in others):
+        return None
+    dev = pb.device
+    if any(x.device != dev for x in (pl, ps, gb) + tuple(others)):
+        return None
+    from . import _lib
+    batch = int(pb.shape[0])
+    rows = int(np.prod(pl.shape[1:])) if batch else 0
+    n_gt = int(np.prod(gl.shape[1:])) if batch else 0
+    if rows > _lib.VY_VOC_ROWS_MAX or pb.numel() != batch * rows * 4 or ps.numel() != batch * rows or \
+            gb.numel() != batch * n_gt * 4 or gl.shape[0] != batch or (gd is not None and gd.numel() != batch * n_gt):
+        return None
+    d = _VocDeviceBatch()
+    d.dev, d.batch, d.rows, d.n_gt = dev, batch, rows, n_gt
+    d.boxes = d.labels = d.scores = d.gt_boxes = d.mapped = d.diff = None
+    if batch == 0:
+        return d
+    gl = gl.reshape(batch, n_gt)
+    if cm is None:
+        mapped = torch.where(gl >= 0, gl.to(torch.int32), -1)
+    else:
+        lut = luts.get(dev)
+        if lut is None:
+            lut = luts[dev] = torch.tensor([int(v) for v in cm], dtype=torch.int32).to(dev)
+        n = len(lut)
+        idx = gl.to(torch.int64)                                  # a negative label counts from the end, as on the host
+        inside = (idx >= -n) & (idx < n)
+        if n:
+            mapped = torch.where(inside, lut[torch.where(inside, idx, 0)], -1)
+        else:
+            mapped = torch.full_like(idx, -1, dtype=torch.int32)
+    d.mapped = mapped.contiguous()
+    d.diff = None if gd is None else (gd.reshape(batch, n_gt) != 0).to(torch.uint8).contiguous()
+    d.labels, d.scores = pl.reshape(batch, rows).contiguous(), ps.reshape(batch, rows).contiguous()
+    d.boxes, d.gt_boxes = pb.reshape(batch, rows, 4).contiguous(), gb.reshape(batch, n_gt, 4).contiguous()
+    return d
+
+
+def _voc_match_device(d, iou_thresh):
+    """vy_voc_match on an accepted batch, on the current stream: the (batch, rows) int8 flags, a device tensor.  No rows:
+    no launch."""
+    import torch
+    flags = torch.empty((d.batch, d.rows), dtype=torch.int8, device=d.dev)
+    if d.rows:
+        from . import _lib
+        lib = _lib.load()
+        best = torch.empty((d.batch, d.rows), dtype=torch.int32, device=d.dev)
+        devp = lambda t: _devp(t if t.numel() else best)          # noqa: E731  a valid address for arrays without elements
+        with torch.cuda.device(d.dev):
+            _lib.check(lib.vy_voc_match(d.batch, d.rows, d.n_gt, devp(d.boxes), devp(d.labels), devp(d.scores),
+                                        devp(d.gt_boxes), devp(d.mapped), None if d.diff is None else devp(d.diff),
+                                        float(iou_thresh), devp(best), devp(flags), _streamp(d.dev)))
+    return flags
+
+
 class VOCMApMetric(object):
     """Mean average precision, area under the monotone precision envelope (VOC 2010+ style).
 
@@ -230,64 +309,16 @@ class VOCMApMetric(object):
     # ------------------------------------------------------------------ accumulation on the device
     def _update_device(self, pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults):
         """Matches the batch on the device and returns True, or returns False: the call is the host path's."""
-        cm = self.class_map
-        if not (cm is None or isinstance(cm, (list, tuple, np.ndarray))):
+        d = _voc_device_batch(self.class_map, self._class_luts, pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels,
+                              gt_difficults)
+        if d is None:
             return False
-        args = [_gather(x) for x in (pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults)]
-        if not all(hasattr(x, "is_cuda") for x in args[:5]):
-            return False
-        import torch
-        pb, pl, ps, gb, gl, gd = args
-        if not all(_is_gpu_f32(x) for x in (pb, pl, ps, gb)):
-            return False
-        others = [gl] if gd is None else [gl, gd]
-        if not all(isinstance(x, torch.Tensor) and not x.is_complex() for x in others):
-            return False
-        dev = pb.device
-        if any(x.device != dev for x in (pl, ps, gb) + tuple(others)):
-            return False
-        from . import _lib
-        batch = int(pb.shape[0])
-        rows = int(np.prod(pl.shape[1:])) if batch else 0
-        n_gt = int(np.prod(gl.shape[1:])) if batch else 0
-        if rows > _lib.VY_VOC_ROWS_MAX or pb.numel() != batch * rows * 4 or ps.numel() != batch * rows or \
-                gb.numel() != batch * n_gt * 4 or gl.shape[0] != batch or (gd is not None and gd.numel() != batch * n_gt):
-            return False
-        if batch == 0:
+        if d.batch == 0:
             return True
-        gl = gl.reshape(batch, n_gt)
-        if cm is None:
-            mapped = torch.where(gl >= 0, gl.to(torch.int32), -1)
-        else:
-            lut = self._class_luts.get(dev)
-            if lut is None:
-                lut = self._class_luts[dev] = torch.tensor([int(v) for v in cm], dtype=torch.int32).to(dev)
-            n = len(lut)
-            idx = gl.to(torch.int64)                                  # a negative label counts from the end, as on the host
-            inside = (idx >= -n) & (idx < n)
-            if n:
-                mapped = torch.where(inside, lut[torch.where(inside, idx, 0)], -1)
-            else:
-                mapped = torch.full_like(idx, -1, dtype=torch.int32)
-        mapped = mapped.contiguous()
-        diff = None if gd is None else (gd.reshape(batch, n_gt) != 0).to(torch.uint8).contiguous()
-        pl, ps = pl.reshape(batch, rows).contiguous(), ps.reshape(batch, rows).contiguous()
-        if rows:
-            lib = _lib.load()
-            pb, gb = pb.reshape(batch, rows, 4).contiguous(), gb.reshape(batch, n_gt, 4).contiguous()
-            best = torch.empty((batch, rows), dtype=torch.int32, device=dev)
-            flags = torch.empty((batch, rows), dtype=torch.int8, device=dev)
-            spare = best                                              # a valid address for arrays without elements
-            devp = lambda t: _devp(t if t.numel() else spare)         # noqa: E731
-            with torch.cuda.device(dev):
-                _lib.check(lib.vy_voc_match(batch, rows, n_gt, devp(pb), devp(pl), devp(ps), devp(gb), devp(mapped),
-                                            None if diff is None else devp(diff), float(self.iou_thresh), devp(best),
-                                            devp(flags), _streamp(dev)))
-            self.device_updates += 1
-        else:
-            flags = torch.empty((batch, 0), dtype=torch.int8, device=dev)
-        self._chunks.append((pl.reshape(-1), ps.reshape(-1), mapped.reshape(-1), flags.reshape(-1),
-                             None if diff is None else diff.reshape(-1), rows))
+        flags = _voc_match_device(d, self.iou_thresh)
+        self.device_updates += 1 if d.rows else 0
+        self._chunks.append((d.labels.reshape(-1), d.scores.reshape(-1), d.mapped.reshape(-1), flags.reshape(-1),
+                             None if d.diff is None else d.diff.reshape(-1), d.rows))
         return True
 
     def _fold(self):
@@ -365,6 +396,151 @@ class VOC07MApMetric(VOCMApMetric):
             hit = rec >= t
             ap += (np.max(p[hit]) if hit.any() else 0.0) / 11.0
         return float(ap)
+
+
+# ====================================================================================================================
+# The per-frame mAP and the worst-clip ranking: detect_yolo3.py --per_frame_metric (add_metrics_to_predictions, :451-534,
+# built at :855-862), which runs metric.reset(); metric.update(<one frame>); metric.get() on a VOCMApMetric for every
+# frame, writes the mean AP as an eighth column beside the frame's predictions and ranks frames, or videos by their mean,
+# worst first (summary.txt, what --worst_video_path renders from).
+# ====================================================================================================================
+def frame_map_host(pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults=None, iou_thresh=0.5,
+                   class_map=None, use_07_metric=False):
+    """The per-frame mean AP, (B,) float64: for image b exactly what a fresh ``VOCMApMetric`` (``VOC07MApMetric`` with
+    ``use_07_metric``) gives for ``update(<image b alone>); get()``, NaN for a frame with nothing to score.  This is the
+    definition the device kernel (csrc/voc_metric.hip, vy_voc_frame_ap) is held to.  Spelled out per frame:
+
+      detections: the rows with label >= 0; voc_match_host's flags say what each is (1 TP, 0 FP, -1 neither)
+      class c: npos = its mapped ground truths that are not difficult.  Only classes with npos > 0 enter the mean: one
+        with detections and no such ground truth is NaN and drops out of the nanmean, one with ground truth and no
+        detection enters with AP 0
+      rank: a class's rows by score descending (among equal scores the device takes the lower row first, the host what its
+        unstable argsort gives); at a row tp / fp count the flag-1 / flag-0 rows at or ahead of it;
+        prec = tp / (tp + fp) (0 / 0 -> 0), rec = tp / npos, float64
+      area AP: the sum over the class's TP rows of (tp / npos - (tp - 1) / npos) * the largest prec at or behind the row
+      11-point AP: for k = 0..10, t = 0.0 + k * 0.1: ap += (the largest prec over rows with rec >= t, else 0) / 11.0
+      frame score: the sum of the classes' APs / the number of classes with npos > 0; NaN when there is none
+    """
+    import warnings
+    arrays = [_to_numpy(x) for x in (pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels)]
+    gd = _to_numpy(gt_difficults) if gt_difficults is not None else None
+    cls = VOC07MApMetric if use_07_metric else VOCMApMetric
+    out = np.full(len(arrays[0]), np.nan, np.float64)
+    for b in range(len(out)):
+        m = cls(iou_thresh=iou_thresh, class_map=class_map)
+        m._update_host(*[a[b:b + 1] for a in arrays], gt_difficults=None if gd is None else gd[b:b + 1])
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)           # nanmean of nothing but NaN: the frame is NaN
+            out[b] = m.get()[1]
+    return out
+
+
+def frame_metric_lines(img_path, rows, score):
+    """The reference's per-frame metric file format (detect_yolo3.py:517): ``path,class,score,x1,y1,x2,y2,frame_score``
+    per detection, ``rows`` as transforms.prediction_lines takes them, ``score`` the frame's mean AP."""
+    return ["{},{},{},{},{},{},{},{}\n".format(img_path, int(r[0]), r[1], r[2], r[3], r[4], r[5], score) for r in rows]
+
+
+class FrameMApMetric(object):
+    """The mean AP of every frame on its own, and the ranking of the worst frames and videos by it.
+
+    ``update`` takes what ``VOCMApMetric.update`` takes, and ``keys``: one hashable per image (a sample id, a path, a
+    ``(video, frame)`` pair); default the running index since ``reset``.  On the input ``VOCMApMetric`` matches on the
+    device — float32 tensors of one GPU, at most 1024 rows per image, ``class_map`` None or a sequence — it launches
+    vy_voc_match and vy_voc_frame_ap on the current stream and keeps the (B,) scores as a device tensor: nothing is
+    copied and nothing synchronises until ``get()`` copies all of them at once.  Everything else takes
+    ``frame_map_host``; both may feed one metric, in arrival order.  ``device_updates`` counts the launched updates.
+
+    Where this differs from the reference, on purpose: there a frame with nothing to score is NaN, poisons its video's
+    mean and leaves the sort undefined.  Here NaN frames are left out of ``worst`` and of the videos' means and frame
+    counts and are reported in ``unscored``; a video without a scored frame comes last, its mean NaN.  Among equal scores
+    the device ranks the lower row first (``VOCMApMetric``'s stated rule)."""
+
+    def __init__(self, iou_thresh=0.5, class_names=None, class_map=None, use_07_metric=False):
+        self.iou_thresh = iou_thresh
+        self.class_names = list(class_names) if class_names is not None else None
+        self.class_map = class_map
+        self.use_07_metric = bool(use_07_metric)
+        self.name = 'FrameMeanAP'
+        self.device_updates = 0
+        self._class_luts = {}
+        self.reset()
+
+    def reset(self):
+        self._keys = []
+        self._chunks = []    # per update, in arrival order: the (B,) scores, a float64 numpy array or a device tensor
+
+    def update(self, pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults=None, keys=None):
+        d = _voc_device_batch(self.class_map, self._class_luts, pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels,
+                              gt_difficults)
+        if d is None:
+            scores = frame_map_host(pred_bboxes, pred_labels, pred_scores, gt_bboxes, gt_labels, gt_difficults,
+                                    self.iou_thresh, self.class_map, self.use_07_metric)
+            batch = len(scores)
+        else:
+            batch = d.batch
+        if keys is None:
+            keys = range(len(self._keys), len(self._keys) + batch)
+        keys = list(keys)
+        if len(keys) != batch:
+            raise ValueError("%d keys for a batch of %d frames" % (len(keys), batch))
+        if d is not None and batch:
+            scores = self._frame_ap_device(d)[0]
+            self.device_updates += 1
+        if batch:
+            self._keys.extend(keys)
+            self._chunks.append(scores)
+
+    def _frame_ap_device(self, d):
+        """vy_voc_match, then vy_voc_frame_ap on its flags, on the current stream: (scores (B,) float64, classes (B,)
+        int32), device tensors."""
+        import torch
+        from . import _lib
+        lib = _lib.load()
+        flags = _voc_match_device(d, self.iou_thresh)
+        ap = torch.empty(d.batch, dtype=torch.float64, device=d.dev)
+        n_cls = torch.empty(d.batch, dtype=torch.int32, device=d.dev)
+        devp = lambda t: _devp(t if t.numel() else ap)            # noqa: E731  a valid address for arrays without elements
+        with torch.cuda.device(d.dev):
+            _lib.check(lib.vy_voc_frame_ap(d.batch, d.rows, d.n_gt, devp(d.labels), devp(d.scores), devp(flags),
+                                           devp(d.mapped), None if d.diff is None else devp(d.diff),
+                                           int(self.use_07_metric), devp(ap), devp(n_cls), _streamp(d.dev)))
+        return ap, n_cls
+
+    def get(self):
+        """``(keys, scores)``: the keys in arrival order and their frames' mean AP, a float64 numpy array (NaN: nothing to
+        score).  The device results are copied here, all at once."""
+        on_dev = [i for i, c in enumerate(self._chunks) if not isinstance(c, np.ndarray)]
+        if on_dev:
+            for i, (h,) in zip(on_dev, _chunks_to_host([(self._chunks[i],) for i in on_dev])):
+                self._chunks[i] = h.copy()
+        scores = np.concatenate(self._chunks) if self._chunks else np.zeros(0, np.float64)
+        return list(self._keys), scores
+
+    @property
+    def unscored(self):
+        """The keys of the frames with nothing to score (NaN), in arrival order."""
+        keys, scores = self.get()
+        return [k for k, s in zip(keys, scores) if s != s]
+
+    def worst(self, n=None):
+        """``[(key, score)]`` of the scored frames, the lowest score first (equal scores in arrival order), the first
+        ``n`` of them."""
+        keys, scores = self.get()
+        scored = [(k, float(s)) for k, s in zip(keys, scores) if s == s]
+        scored.sort(key=lambda ks: ks[1])
+        return scored if n is None else scored[:n]
+
+    def by_video(self, video_of=lambda key: key[0]):
+        """``[(video, mean, frames)]`` sorted by ``(mean, -frames)`` — the order of the reference's summary.txt
+        (detect_yolo3.py:521-527): the lowest mean first, among equal means the video with more frames.  ``mean`` and
+        ``frames`` are over the video's scored frames; a video without one comes last with NaN and 0."""
+        keys, scores = self.get()
+        per_video = {}
+        for k, s in zip(keys, scores):
+            per_video.setdefault(video_of(k), []).extend([float(s)] if s == s else [])
+        ranked = sorted(((v, sum(s) / len(s), len(s)) for v, s in per_video.items() if s), key=lambda r: (r[1], -r[2]))
+        return ranked + [(v, float('nan'), 0) for v, s in per_video.items() if not s]
 
 
 # ====================================================================================================================
