@@ -235,6 +235,9 @@ def all_cases():
     out.append(_case("cap1025", cap, {"tie_ascending", "topk_first"}, classes=80, nms_topk=1025, path="cap"))
     # (its first 100 survivors all come from the upper level: only the tie order shows in them)
     out.append(_case("cap1025/post100", cap, {"tie_ascending"}, classes=80, nms_topk=1025, post_nms=100, path="cap"))
+    # a second chunk of 276 candidates — the lower-level ties left of the cut —: a chunk of more than 32 and fewer than 1024
+    # keys, which the kernel's rank sort splits over several thread groups; 774 rows kept, from both score levels
+    out.append(_case("cap1300", cap, {"tie_ascending", "topk_first"}, classes=80, nms_topk=1300, path="cap"))
     third = float(F32(240.0) / F32(720.0))
     pair = cap_pair_heads()
     flips = {"strict_valid", "strict_iou", "tie_ascending", "plus_one"}

@@ -74,30 +74,33 @@ struct Scratch {
 
 __host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// bytes of the five sub-regions, in carve order (the score cache: C * n_items floats per image; carve does not need it)
-__host__ __device__ inline void scratch_sizes(int B, size_t score_floats, size_t* sz) {
-  sz[0] = sizeof(SelState) * (size_t)B;
-  sz[1] = sizeof(uint32_t) * (size_t)B * kBins;
-  sz[2] = sizeof(Entry) * (size_t)B * VY_NMS_MAX_TOPK;
-  sz[3] = sizeof(unsigned long long) * (size_t)B * kListCap;
-  sz[4] = sizeof(float) * (size_t)B * score_floats;
+// The layout, in one place: where each of the five sub-regions starts and the bytes the kernels use of it, in the order of
+// Scratch.  Each is rounded to 256 bytes and followed by `guard` unused bytes (DetArgs::guard; 0 outside the tests).  The
+// score cache is the last one: C * n_items floats per image, which no offset depends on.  Returns the total.
+__host__ __device__ inline size_t scratch_layout(int B, size_t score_floats, int guard, size_t* off, size_t* used) {
+  used[0] = sizeof(SelState) * (size_t)B;
+  used[1] = sizeof(uint32_t) * (size_t)B * kBins;
+  used[2] = sizeof(Entry) * (size_t)B * VY_NMS_MAX_TOPK;
+  used[3] = sizeof(unsigned long long) * (size_t)B * kListCap;
+  used[4] = sizeof(float) * (size_t)B * score_floats;
+  size_t at = 0;
+  for (int i = 0; i < 5; ++i) {
+    off[i] = at;
+    at += align256(used[i]) + guard;
+  }
+  return at;
 }
 
-// guard: unused bytes the plan leaves behind each sub-region (DetArgs::guard; 0 outside the tests)
 __host__ __device__ inline Scratch carve(void* base, int B, int guard) {
   unsigned char* p = (unsigned char*)base;
-  size_t sz[5];
-  scratch_sizes(B, 0, sz);
+  size_t off[5], used[5];
+  scratch_layout(B, 0, guard, off, used);
   Scratch s;
-  s.st = (SelState*)p;
-  p += align256(sz[0]) + guard;
-  s.hist = (uint32_t*)p;
-  p += align256(sz[1]) + guard;
-  s.ent = (Entry*)p;
-  p += align256(sz[2]) + guard;
-  s.list = (unsigned long long*)p;
-  p += align256(sz[3]) + guard;
-  s.score = (float*)p;
+  s.st = (SelState*)(p + off[0]);
+  s.hist = (uint32_t*)(p + off[1]);
+  s.ent = (Entry*)(p + off[2]);
+  s.list = (unsigned long long*)(p + off[3]);
+  s.score = (float*)(p + off[4]);
   return s;
 }
 
@@ -161,6 +164,11 @@ struct Item {
   int cstride;      // candidate index stride between classes = H*W*A
 };
 
+// element e of the prediction vector of pixel (y, x) of image b: the head planes carry a one-pixel border
+__device__ __forceinline__ const float* pred_at(const HeadView& hv, int b, int y, int x, int e) {
+  return hv.pred + ((long long)(b * (hv.H + 2) + y + 1) * (hv.W + 2) + x + 1) * hv.cs + hv.co + e;
+}
+
 __device__ __forceinline__ bool locate(const DetArgs& d, int b, int it, Item& o) {
   int s = 0;
 #pragma unroll
@@ -180,7 +188,7 @@ __device__ __forceinline__ bool locate(const DetArgs& d, int b, int it, Item& o)
   o.a = a;
   o.cstride = hv.H * hv.W * 3;
   o.cand0 = hv.cand_base + it;
-  o.p = hv.pred + ((long long)(b * (hv.H + 2) + y + 1) * (hv.W + 2) + x + 1) * hv.cs + hv.co + a * (5 + d.C);
+  o.p = pred_at(hv, b, y, x, a * (5 + d.C));
   return true;
 }
 
@@ -202,6 +210,54 @@ __device__ __forceinline__ uint32_t pass_digit(int pass, uint32_t bucket, uint32
   }
 }
 
+// One step of the radix select, by a workgroup of kBins threads: thread t brings the count of bin t (`mine`).  Suffix sums
+// in suf[] (suf[i] = sum_{j >= i} count[j]), then the bin holding rank k_rem, counted from the top, fixes its digit in the
+// state.  Pass 0 opens the select: its rank is k_eff = min(#valid, k_limit).  `st` lives in LDS or in global memory, and
+// every thread reads it: a barrier stands between each read of it here and the write that follows, and one ends the step,
+// so the caller may read st right after it.
+__device__ __forceinline__ void sel_step(SelState& st, int pass, uint32_t* suf, uint32_t mine, int k_limit) {
+  const int t = threadIdx.x;
+  suf[t] = mine;
+  __syncthreads();
+  for (int off = 1; off < kBins; off <<= 1) {
+    const uint32_t add = (t + off < kBins) ? suf[t + off] : 0u;
+    __syncthreads();
+    suf[t] += add;
+    __syncthreads();
+  }
+  if (pass == 0) {  // uniform
+    if (t == 0) {
+      const int nvalid = (int)suf[0];
+      const int k_eff = nvalid < k_limit ? nvalid : k_limit;
+      st.k_eff = k_eff;
+      st.k_rem = k_eff;
+      if (k_eff == 0) st.done = 1;
+    }
+    __syncthreads();
+  }
+  const int k_rem = st.k_rem;
+  const uint32_t above = (t + 1 < kBins) ? suf[t + 1] : 0u;  // candidates in strictly higher bins
+  __syncthreads();  // every thread holds k_rem before the bin's thread replaces it
+  if (k_rem > 0 && above < (uint32_t)k_rem && (uint32_t)k_rem <= above + mine) {
+    // this is the bin
+    const int rem = k_rem - (int)above;
+    st.k_rem = rem;
+    const uint32_t dgt = (uint32_t)t;
+    switch (pass) {
+      case 0: st.Tb = dgt; st.bucket_n = (int32_t)mine; break;
+      case 1: st.Ts |= dgt << 20; st.smask |= 1023u << 20; break;
+      case 2: st.Ts |= dgt << 10; st.smask |= 1023u << 10; break;
+      case 3: st.Ts |= dgt; st.smask |= 1023u; break;
+      case 4: st.Ti |= dgt << 20; st.imask |= 1023u << 20; break;
+      case 5: st.Ti |= dgt << 10; st.imask |= 1023u << 10; break;
+      default: st.Ti |= dgt; st.imask |= 1023u; break;
+    }
+    // every candidate of this bin is wanted: the threshold "prefix, rest zero" is already exact
+    if ((uint32_t)rem == mine || pass == 6) st.done = 1;
+  }
+  __syncthreads();
+}
+
 // Pass 0: decode every class score, keep it, histogram it into the 1024 linear buckets.
 // A block owns kPx consecutive pixels of ONE head of one image: their prediction vectors (kPx x cs floats,
 // contiguous inside an image row of the padded plane) are copied to LDS with 16-B loads — every 128-B line of the
@@ -218,7 +274,7 @@ __host__ __device__ inline int hist_px(int cs) {
 }
 __host__ __device__ inline int hist_blocks_of(int hw, int cs) { return (hw + hist_px(cs) - 1) / hist_px(cs); }
 
-__global__ __launch_bounds__(kHistThreads) void hist_kernel(const DetArgs d, void* scratch, int pass, int n_items) {
+__global__ __launch_bounds__(kHistThreads) void hist_kernel(const DetArgs d, void* scratch, int n_items) {
   const int b = blockIdx.y;
   Scratch sc = carve(scratch, d.B, d.guard);
   __shared__ __attribute__((aligned(16))) float tile[kTileFloats];
@@ -243,8 +299,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const DetArgs d, voi
   for (int e = threadIdx.x; e < npx * cs4; e += kHistThreads) {
     const int px = e / cs4, q = e - px * cs4;
     const int p = p0 + px, x = p % hv.W, y = p / hv.W;
-    const float4 v = *reinterpret_cast<const float4*>(
-        hv.pred + ((long long)(b * (hv.H + 2) + y + 1) * (hv.W + 2) + x + 1) * hv.cs + hv.co + q * 4);
+    const float4 v = *reinterpret_cast<const float4*>(pred_at(hv, b, y, x, q * 4));
     *reinterpret_cast<float4*>(tile + px * hv.cs + q * 4) = v;
   }
   __syncthreads();
@@ -252,14 +307,12 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const DetArgs d, voi
   for (int i = threadIdx.x; i < nit; i += kHistThreads) conf[i] = vy_sigmoidf(tile[(i / 3) * hv.cs + (i % 3) * P + 4]);
   __syncthreads();
   float* cache = sc.score + (size_t)b * d.C * n_items + item0 + p0 * 3;
-  const int cstride = hw * 3;
   for (int idx = threadIdx.x; idx < nit * d.C; idx += kHistThreads) {
     const int c = idx / nit, i = idx - c * nit;  // i = pixel * 3 + anchor inside the block: the candidate order
     const float sv = vy_sigmoidf(tile[(i / 3) * hv.cs + (i % 3) * P + 5 + c]) * conf[i];
     cache[(size_t)c * n_items + i] = sv;
     if (det_valid(d, sv)) atomicAdd(&lh[score_bucket(sv)], 1u);
   }
-  (void)cstride;
   __syncthreads();
   uint32_t* gh = sc.hist + (size_t)b * kBins;
   for (int i = threadIdx.x; i < kBins; i += kHistThreads) {
@@ -268,58 +321,16 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(const DetArgs d, voi
   }
 }
 
-// one block (kBins threads) per image: find the bin holding rank k_rem (counted from the top),
-// fix that digit, zero the histogram for the next pass.
-__global__ __launch_bounds__(kBins) void select_kernel(const DetArgs d, void* scratch, int pass) {
-  const int b = blockIdx.x;
+// one block (kBins threads) per image: pass 0 of the select on the histogram of hist_kernel, on the image's state in global
+// memory (zeroed by the launcher); the histogram is left zeroed.
+__global__ __launch_bounds__(kBins) void select_kernel(const DetArgs d, void* scratch) {
+  const int b = blockIdx.x, t = threadIdx.x;
   Scratch sc = carve(scratch, d.B, d.guard);
-  SelState* st = sc.st + b;
-  if (st->done) return;
   uint32_t* gh = sc.hist + (size_t)b * kBins;
-  __shared__ uint32_t suf[kBins];  // suffix sums: suf[i] = sum_{j >= i} hist[j]
-  const int t = threadIdx.x;
+  __shared__ uint32_t suf[kBins];
   const uint32_t mine = gh[t];
   gh[t] = 0;
-  suf[t] = mine;
-  __syncthreads();
-  for (int off = 1; off < kBins; off <<= 1) {
-    const uint32_t add = (t + off < kBins) ? suf[t + off] : 0u;
-    __syncthreads();
-    suf[t] += add;
-    __syncthreads();
-  }
-  __shared__ int32_t k_rem_s;
-  if (t == 0) {
-    if (pass == 0) {
-      const int nvalid = (int)suf[0];
-      const int k_eff = nvalid < d.topk ? nvalid : d.topk;
-      st->k_eff = k_eff;
-      st->k_rem = k_eff;
-      if (k_eff == 0) st->done = 1;
-    }
-    k_rem_s = st->k_rem;
-  }
-  __syncthreads();
-  const int k_rem = k_rem_s;
-  if (k_rem <= 0) return;
-  const uint32_t above = (t + 1 < kBins) ? suf[t + 1] : 0u;  // candidates in strictly higher bins
-  if (above < (uint32_t)k_rem && (uint32_t)k_rem <= above + mine) {
-    // this is the bin
-    const int rem = k_rem - (int)above;
-    st->k_rem = rem;
-    const uint32_t dgt = (uint32_t)t;
-    switch (pass) {
-      case 0: st->Tb = dgt; st->bucket_n = (int32_t)mine; break;
-      case 1: st->Ts |= dgt << 20; st->smask |= 1023u << 20; break;
-      case 2: st->Ts |= dgt << 10; st->smask |= 1023u << 10; break;
-      case 3: st->Ts |= dgt; st->smask |= 1023u; break;
-      case 4: st->Ti |= dgt << 20; st->imask |= 1023u << 20; break;
-      case 5: st->Ti |= dgt << 10; st->imask |= 1023u << 10; break;
-      default: st->Ti |= dgt; st->imask |= 1023u; break;
-    }
-    // every candidate of this bin is wanted: the threshold "prefix, rest zero" is already exact
-    if ((uint32_t)rem == mine || pass == 6) st->done = 1;
-  }
+  sel_step(sc.st[b], 0, suf, mine, d.topk);
 }
 
 __device__ __forceinline__ void decode_box(const DetArgs& d, const Item& im, float& x1, float& y1, float& x2,
@@ -356,7 +367,17 @@ __device__ __forceinline__ void locate_cand(const DetArgs& d, int b, uint32_t r,
   im.a = a;
   im.cstride = n_s;
   im.cand0 = hv.cand_base + it;
-  im.p = hv.pred + ((long long)(b * (hv.H + 2) + im.y + 1) * (hv.W + 2) + im.x + 1) * hv.cs + hv.co + a * (5 + d.C);
+  im.p = pred_at(hv, b, im.y, im.x, a * (5 + d.C));
+}
+
+// cached score idx = c * n_items + it (class c, anchor item it of the image) -> its candidate row
+__device__ __forceinline__ uint32_t cache_row(const DetArgs& d, int n_items, int idx, int& c, int& it) {
+  const int n0 = d.head[0].H * d.head[0].W * 3, n1 = d.head[1].H * d.head[1].W * 3;
+  c = idx / n_items;
+  it = idx - c * n_items;
+  if (it < n0) return (uint32_t)(d.head[0].cand_base + c * n0 + it);
+  if (it < n0 + n1) return (uint32_t)(d.head[1].cand_base + c * n1 + (it - n0));
+  return (uint32_t)(d.head[2].cand_base + c * (n_items - n0 - n1) + (it - n0 - n1));
 }
 
 __device__ __forceinline__ void put_entry(const DetArgs& d, Entry* ent, SelState* stp, const Item& im, int c,
@@ -437,7 +458,6 @@ __global__ __launch_bounds__(kBins) void refine_kernel(const DetArgs d, void* sc
   const unsigned long long* list = sc.list + (size_t)b * kListCap;
   const float* cache = sc.score + (size_t)b * d.C * n_items;
   const int n = from_list ? st.bucket_n : d.C * n_items;
-  const int n0 = d.head[0].H * d.head[0].W * 3, n1 = d.head[1].H * d.head[1].W * 3;
   // element idx of the source -> (in the bucket?, sbits, inv)
   auto fetch = [&](int idx, uint32_t& sbits, uint32_t& inv) -> bool {
     if (from_list) {
@@ -448,16 +468,9 @@ __global__ __launch_bounds__(kBins) void refine_kernel(const DetArgs d, void* sc
     }
     const float s = cache[idx];
     if (!det_valid(d, s) || score_bucket(s) != st.Tb) return false;
-    const int c = idx / n_items, it = idx - c * n_items;
-    uint32_t r;
-    if (it < n0)
-      r = (uint32_t)(d.head[0].cand_base + c * n0 + it);
-    else if (it < n0 + n1)
-      r = (uint32_t)(d.head[1].cand_base + c * n1 + (it - n0));
-    else
-      r = (uint32_t)(d.head[2].cand_base + c * (n_items - n0 - n1) + (it - n0 - n1));
+    int c, it;
     sbits = vy_f32_to_bits(s);
-    inv = det_key_word(d, r);
+    inv = det_key_word(d, cache_row(d, n_items, idx, c, it));
     return true;
   };
   for (int pass = 1; pass < 7; ++pass) {
@@ -471,32 +484,7 @@ __global__ __launch_bounds__(kBins) void refine_kernel(const DetArgs d, void* sc
       atomicAdd(&hist[pass_digit(pass, st.Tb, sbits, inv)], 1u);
     }
     __syncthreads();
-    const uint32_t mine = hist[t];
-    suf[t] = mine;
-    __syncthreads();
-    for (int off = 1; off < kBins; off <<= 1) {
-      const uint32_t add = (t + off < kBins) ? suf[t + off] : 0u;
-      __syncthreads();
-      suf[t] += add;
-      __syncthreads();
-    }
-    const int k_rem = st.k_rem;
-    const uint32_t above = (t + 1 < kBins) ? suf[t + 1] : 0u;
-    __syncthreads();
-    if (k_rem > 0 && above < (uint32_t)k_rem && (uint32_t)k_rem <= above + mine) {
-      st.k_rem = k_rem - (int)above;
-      const uint32_t dgt = (uint32_t)t;
-      switch (pass) {
-        case 1: st.Ts |= dgt << 20; st.smask |= 1023u << 20; break;
-        case 2: st.Ts |= dgt << 10; st.smask |= 1023u << 10; break;
-        case 3: st.Ts |= dgt; st.smask |= 1023u; break;
-        case 4: st.Ti |= dgt << 20; st.imask |= 1023u << 20; break;
-        case 5: st.Ti |= dgt << 10; st.imask |= 1023u << 10; break;
-        default: st.Ti |= dgt; st.imask |= 1023u; break;
-      }
-      if ((uint32_t)(k_rem - (int)above) == mine || pass == 6) st.done = 1;
-    }
-    __syncthreads();
+    sel_step(st, pass, suf, hist[t], 0);  // (pass 0, which alone has a k_limit, was select_kernel's)
   }
   // the bucket's members at or above the threshold
   Entry* ent = sc.ent + (size_t)b * VY_NMS_MAX_TOPK;
@@ -522,6 +510,83 @@ extern "C" int vy_debug_nms_trace(unsigned long long* out) {
 #else
 #define NMS_STAMP(n) do { } while (0)
 #endif
+
+// ---- the steps the two suppressing kernels share.  Both run kNmsThreads threads per image over LDS arrays of
+// VY_NMS_MAX_TOPK candidates: key[], the box corners, the class, alive[], and the counters pos[].
+
+// Rank sort, descending: the keys are distinct (their low half is the candidate index), so a candidate's place is the
+// number of larger keys; it is added up in pos[i].  All 1024 threads count: candidate t & (kp - 1), a 1 / G slice of the
+// keys each, four keys per step (two 16-byte LDS reads of addresses the whole wave shares: broadcasts); no barrier inside.
+// On entry: key[k .. k4) hold 0 (below every valid key: valid keys have sbits > 0), pos[] holds 0, both fenced by a barrier.
+// The caller puts one barrier before it reads the ranks.  (The bitonic network this replaces: 45 barrier-separated passes
+// for 400 candidates, 12 us.)
+__device__ __forceinline__ void rank_of(const unsigned long long* key, int* pos, int k, int t) {
+  int kp = 1;
+  while (kp < k) kp <<= 1;
+  const int G = kNmsThreads / kp, i = t & (kp - 1), part = t / kp;
+  const int len = (((k + G - 1) / G) + 3) & ~3;
+  if (i < k) {
+    typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+    const unsigned long long my = key[i];
+    const int k4 = (k + 3) & ~3;  // <= 1024
+    int j = part * len, cnt = 0;
+    const int j_end = j + len < k4 ? j + len : k4;
+    for (; j < j_end; j += 4) {
+      const u64x2 a = *reinterpret_cast<const u64x2*>(&key[j]), c = *reinterpret_cast<const u64x2*>(&key[j + 2]);
+      cnt += (a[0] > my ? 1 : 0) + (a[1] > my ? 1 : 0) + (c[0] > my ? 1 : 0) + (c[1] > my ? 1 : 0);
+    }
+    if (cnt) atomicAdd(&pos[i], cnt);
+  }
+}
+
+// Greedy suppression of the k sorted candidates, one survivor at a time: candidate i, if still alive, takes out the later
+// ones of its class that it overlaps.  Any k; a barrier per candidate.
+template <bool kPlus1>
+__device__ __forceinline__ void greedy_serial(const DetArgs& d, int k, int t, uint8_t* alive, const float* bcls,
+                                              const float* bx1, const float* by1, const float* bx2, const float* by2) {
+  for (int i = 0; i < k; ++i) {
+    if (!alive[i]) continue;  // uniform: alive[] is only written before the barrier below
+    const float ax1 = bx1[i], ay1 = by1[i], ax2 = bx2[i], ay2 = by2[i], ac = bcls[i];
+    for (int j = i + 1 + t; j < k; j += kNmsThreads) {
+      if (alive[j] && bcls[j] == ac) {
+        if (det_suppresses<kPlus1>(d, ax1, ay1, ax2, ay2, bx1[j], by1[j], bx2[j], by2[j])) alive[j] = 0;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// inclusive scan of alive[0 .. k) into pos[] (k <= 1024, one element per thread): survivor i is number pos[i] - 1 among
+// the survivors.  Returns how many there are.  The caller has fenced the last use of pos[] and alive[] with a barrier.
+__device__ __forceinline__ int alive_scan(int* pos, const uint8_t* alive, int k, int t) {
+  pos[t] = (t < k && alive[t]) ? 1 : 0;
+  __syncthreads();
+  for (int off = 1; off < VY_NMS_MAX_TOPK; off <<= 1) {
+    const int v = t >= off ? pos[t - off] : 0;
+    __syncthreads();
+    pos[t] += v;
+    __syncthreads();
+  }
+  return pos[VY_NMS_MAX_TOPK - 1];
+}
+
+// row o of the outputs (o counts over the whole batch); `row` is the candidate row, for keep_idx where the caller asked
+__device__ __forceinline__ void write_row(float* ids, float* scores, float* bboxes, int32_t* keep_idx, size_t o, float id,
+                                          float score, float x1, float y1, float x2, float y2, int32_t row) {
+  ids[o] = id;
+  scores[o] = score;
+  bboxes[o * 4 + 0] = x1;
+  bboxes[o * 4 + 1] = y1;
+  bboxes[o * 4 + 2] = x2;
+  bboxes[o * 4 + 3] = y2;
+  if (keep_idx) keep_idx[o] = row;
+}
+// rows from .. rows - 1 of image b: the -1 filler
+__device__ __forceinline__ void fill_rows(float* ids, float* scores, float* bboxes, int32_t* keep_idx, int b, int rows,
+                                          int from, int t) {
+  for (int r = from + t; r < rows; r += kNmsThreads)
+    write_row(ids, scores, bboxes, keep_idx, (size_t)b * rows + r, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1.0f, -1);
+}
 
 // one workgroup per image: sort the <= topk collected entries by key (descending), greedy
 // per-class suppression in that order, compact, write the first `rows` rows.
@@ -557,28 +622,7 @@ __global__ __launch_bounds__(kNmsThreads) void sort_nms_kernel(const DetArgs d, 
   pos[t] = 0;
   __syncthreads();
   NMS_STAMP(1);
-  // Rank sort, descending: the keys are distinct (their low half is the candidate index), so a candidate's place is the
-  // number of larger keys.  All 1024 threads count: candidate t & (kp - 1), a 1 / G slice of the keys each, four keys
-  // per step (two 16-byte LDS reads of addresses the whole wave shares: broadcasts); no barrier until the ranks are
-  // complete.  (The bitonic network this replaces: 45 barrier-separated passes for 400 candidates, 12 us.)
-  {
-    int kp = 1;
-    while (kp < k) kp <<= 1;
-    const int G = kNmsThreads / kp, i = t & (kp - 1), part = t / kp;
-    const int len = (((k + G - 1) / G) + 3) & ~3;
-    if (i < k) {
-      typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-      const unsigned long long my = key[i];
-      const int k4 = (k + 3) & ~3;  // <= 1024: slots k .. k4 hold 0
-      int j = part * len, cnt = 0;
-      const int j_end = j + len < k4 ? j + len : k4;
-      for (; j < j_end; j += 4) {
-        const u64x2 a = *reinterpret_cast<const u64x2*>(&key[j]), c = *reinterpret_cast<const u64x2*>(&key[j + 2]);
-        cnt += (a[0] > my ? 1 : 0) + (a[1] > my ? 1 : 0) + (c[0] > my ? 1 : 0) + (c[1] > my ? 1 : 0);
-      }
-      if (cnt) atomicAdd(&pos[i], cnt);
-    }
-  }
+  rank_of(key, pos, k, t);
   __syncthreads();
   NMS_STAMP(2);
   if (t < k) {
@@ -593,7 +637,7 @@ __global__ __launch_bounds__(kNmsThreads) void sort_nms_kernel(const DetArgs d, 
   }
   __syncthreads();
   NMS_STAMP(3);
-  if (d.do_nms) det_with_iou(d, [&](auto plus1) {
+  det_with_iou(d, [&](auto plus1) {
     constexpr bool kPlus1 = decltype(plus1)::value;
     if (k <= kMaskRows) {
       // the usual case (topk 400): all pairwise "i would suppress j" bits in parallel, then the greedy pass, whose only
@@ -662,54 +706,22 @@ __global__ __launch_bounds__(kNmsThreads) void sort_nms_kernel(const DetArgs d, 
       }
       __syncthreads();
     } else {
-      for (int i = 0; i < k; ++i) {
-        if (!alive[i]) continue;  // uniform: alive[] is only written before the barrier below
-        const float ax1 = bx1[i], ay1 = by1[i], ax2 = bx2[i], ay2 = by2[i], ac = bcls[i];
-        for (int j = i + 1 + t; j < k; j += kNmsThreads) {
-          if (alive[j] && bcls[j] == ac) {
-            if (det_suppresses<kPlus1>(d, ax1, ay1, ax2, ay2, bx1[j], by1[j], bx2[j], by2[j])) alive[j] = 0;
-          }
-        }
-        __syncthreads();
-      }
+      greedy_serial<kPlus1>(d, k, t, alive, bcls, bx1, by1, bx2, by2);
     }
   });
-  // compaction: inclusive scan of alive[] (k <= 1024, one element per thread)
+  // compaction
   NMS_STAMP(5);
   __syncthreads();  // (the rank counters in pos[] were last read before the barriers above)
-  pos[t] = (t < k && alive[t]) ? 1 : 0;
-  __syncthreads();
-  for (int off = 1; off < VY_NMS_MAX_TOPK; off <<= 1) {
-    const int v = t >= off ? pos[t - off] : 0;
-    __syncthreads();
-    pos[t] += v;
-    __syncthreads();
-  }
-  const int n_keep = pos[VY_NMS_MAX_TOPK - 1];
+  const int n_keep = alive_scan(pos, alive, k, t);
   NMS_STAMP(6);
   for (int i = t; i < k; i += kNmsThreads) {
     if (!alive[i]) continue;
     const int r = pos[i] - 1;
     if (r >= rows) continue;
-    const size_t o = (size_t)b * rows + r;
-    ids[o] = bcls[i];
-    scores[o] = vy_bits_to_f32((uint32_t)(key[i] >> 32));
-    bboxes[o * 4 + 0] = bx1[i];
-    bboxes[o * 4 + 1] = by1[i];
-    bboxes[o * 4 + 2] = bx2[i];
-    bboxes[o * 4 + 3] = by2[i];
-    if (keep_idx) keep_idx[o] = (int32_t)det_key_row(d, (uint32_t)(key[i] & 0xffffffffull));
+    write_row(ids, scores, bboxes, keep_idx, (size_t)b * rows + r, bcls[i], vy_bits_to_f32((uint32_t)(key[i] >> 32)), bx1[i],
+              by1[i], bx2[i], by2[i], (int32_t)det_key_row(d, (uint32_t)(key[i] & 0xffffffffull)));
   }
-  for (int r = n_keep + t; r < rows; r += kNmsThreads) {
-    const size_t o = (size_t)b * rows + r;
-    ids[o] = -1.0f;
-    scores[o] = -1.0f;
-    bboxes[o * 4 + 0] = -1.0f;
-    bboxes[o * 4 + 1] = -1.0f;
-    bboxes[o * 4 + 2] = -1.0f;
-    bboxes[o * 4 + 3] = -1.0f;
-    if (keep_idx) keep_idx[o] = -1;
-  }
+  fill_rows(ids, scores, bboxes, keep_idx, b, rows, n_keep, t);
   NMS_STAMP(7);
 }
 
@@ -719,47 +731,36 @@ __global__ __launch_bounds__(kNmsThreads) void sort_nms_kernel(const DetArgs d, 
 // sorts EVERY valid candidate (up to N*C per image) and suppresses greedily; the caller keeps the first
 // post_nms survivors.  A survivor only depends on the survivors before it, so the sorted list can be consumed
 // in chunks: one workgroup per image repeatedly (1) radix-selects the next <= 1024 largest keys below the
-// previous chunk's threshold from the cached class scores, (2) decodes and bitonic-sorts them, (3) suppresses
-// them against the rows kept so far and among themselves, (4) appends the survivors to the output — until
-// post_nms rows are kept or the valid candidates are exhausted.  Typical inputs finish in one or two chunks; the
-// worst case (everything suppressed) walks all N*C candidates, like the reference's unbounded O(n^2) loop.
-constexpr int kAllThreads = 1024;
-
+// previous chunk's threshold from the cached class scores (sel_step), (2) decodes and rank-sorts them (rank_of), (3)
+// suppresses them against the rows kept so far and among themselves (greedy_serial), (4) appends the survivors to the
+// output — until post_nms rows are kept or the valid candidates are exhausted.  Typical inputs finish in one or two chunks;
+// the worst case (everything suppressed) walks all N*C candidates, like the reference's unbounded O(n^2) loop.
+//
 // The same loop serves nms_topk > VY_NMS_MAX_TOPK (`topk_cap` > 0): box_nms keeps the topk best valid candidates and
 // suppresses among those, so the chunks stop once topk_cap candidates have been consumed (the last chunk is
 // shortened to what is left of the cap).
-__global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, void* scratch, int n_items, int rows,
+__global__ __launch_bounds__(kNmsThreads) void nms_all_kernel(const DetArgs d, void* scratch, int n_items, int rows,
                                                               int topk_cap, float* ids, float* scores, float* bboxes,
                                                               int32_t* keep_idx) {
+  static_assert(kNmsThreads == kBins, "the select step's bins and the sort's candidates: one per thread");
   const int b = blockIdx.x, t = threadIdx.x;
   Scratch sc = carve(scratch, d.B, d.guard);
   const float* cache = sc.score + (size_t)b * d.C * n_items;
   __shared__ uint32_t hist[kBins];
-  __shared__ unsigned long long key[VY_NMS_MAX_TOPK];
-  __shared__ uint16_t perm[VY_NMS_MAX_TOPK];
+  __shared__ __attribute__((aligned(16))) unsigned long long key[VY_NMS_MAX_TOPK];
   __shared__ float bx1[VY_NMS_MAX_TOPK], by1[VY_NMS_MAX_TOPK], bx2[VY_NMS_MAX_TOPK], by2[VY_NMS_MAX_TOPK];
   __shared__ float bcls[VY_NMS_MAX_TOPK];
   __shared__ uint8_t alive[VY_NMS_MAX_TOPK];
-  __shared__ int pos[VY_NMS_MAX_TOPK];
+  __shared__ int pos[VY_NMS_MAX_TOPK];  // in turn: the select's suffix sums, the sort's rank counters, the scan of alive[]
   __shared__ float kx1[VY_NMS_MAX_TOPK], ky1[VY_NMS_MAX_TOPK], kx2[VY_NMS_MAX_TOPK], ky2[VY_NMS_MAX_TOPK];
   __shared__ float kcls[VY_NMS_MAX_TOPK];
   __shared__ SelState st;
   __shared__ int n_kept, n_taken;
-  const int n0 = d.head[0].H * d.head[0].W * 3, n1 = d.head[1].H * d.head[1].W * 3;
   const int total = d.C * n_items;
   const bool kept_in_lds = rows <= VY_NMS_MAX_TOPK;
   // rows that suppression may keep: all `rows` of the output, or — the top-k cut applied AFTER suppression (topk_after: the
   // host passes no candidate cut then) — the first nms_topk survivors; rows past that are filler
   const int keep_cap = (d.topk_after && d.topk > 0 && d.topk < rows) ? d.topk : rows;
-  // candidate row of cached score idx = c*n_items + item
-  auto cand_of = [&](int idx, int& c, int& it) -> uint32_t {
-    c = idx / n_items;
-    it = idx - c * n_items;
-    if (it < n0) return (uint32_t)(d.head[0].cand_base + c * n0 + it);
-    if (it < n0 + n1) return (uint32_t)(d.head[1].cand_base + c * n1 + (it - n0));
-    const int n2 = n_items - n0 - n1;
-    return (uint32_t)(d.head[2].cand_base + c * n2 + (it - n0 - n1));
-  };
   if (t == 0) n_kept = 0;
   // exclusive upper bound on the key of the candidates still to be consumed (none yet)
   uint32_t bound_s = 0xffffffffu, bound_i = 0xffffffffu;
@@ -779,63 +780,29 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
       if (st.done) break;  // uniform: st is only written between barriers
       hist[t] = 0;
       __syncthreads();
-      for (int idx = t; idx < total; idx += kAllThreads) {
+      for (int idx = t; idx < total; idx += kNmsThreads) {
         const float s = cache[idx];
         if (!det_valid(d, s)) continue;
         int c, it;
         const uint32_t sbits = vy_f32_to_bits(s);
-        const uint32_t inv = det_key_word(d, cand_of(idx, c, it));
+        const uint32_t inv = det_key_word(d, cache_row(d, n_items, idx, c, it));
         if (!first && !(sbits < bound_s || (sbits == bound_s && inv < bound_i))) continue;
         const uint32_t bucket = score_bucket(s);
         if (!prefix_match(st, pass, bucket, sbits, inv)) continue;
         atomicAdd(&hist[pass_digit(pass, bucket, sbits, inv)], 1u);
       }
       __syncthreads();
-      const uint32_t mine = hist[t];
-      pos[t] = (int)mine;  // suffix sums in pos[]
-      __syncthreads();
-      for (int off = 1; off < kBins; off <<= 1) {
-        const int add = (t + off < kBins) ? pos[t + off] : 0;
-        __syncthreads();
-        pos[t] += add;
-        __syncthreads();
-      }
-      if (t == 0 && pass == 0) {
-        const int nvalid = pos[0];
-        st.k_eff = nvalid < k_limit ? nvalid : k_limit;
-        st.k_rem = st.k_eff;
-        if (st.k_eff == 0) st.done = 1;
-      }
-      __syncthreads();
-      const int k_rem = st.k_rem;
-      const uint32_t above = (t + 1 < kBins) ? (uint32_t)pos[t + 1] : 0u;
-      __syncthreads();
-      if (k_rem > 0 && above < (uint32_t)k_rem && (uint32_t)k_rem <= above + mine) {
-        const int rem = k_rem - (int)above;
-        st.k_rem = rem;
-        const uint32_t dgt = (uint32_t)t;
-        switch (pass) {
-          case 0: st.Tb = dgt; break;
-          case 1: st.Ts |= dgt << 20; st.smask |= 1023u << 20; break;
-          case 2: st.Ts |= dgt << 10; st.smask |= 1023u << 10; break;
-          case 3: st.Ts |= dgt; st.smask |= 1023u; break;
-          case 4: st.Ti |= dgt << 20; st.imask |= 1023u << 20; break;
-          case 5: st.Ti |= dgt << 10; st.imask |= 1023u << 10; break;
-          default: st.Ti |= dgt; st.imask |= 1023u; break;
-        }
-        if ((uint32_t)rem == mine || pass == 6) st.done = 1;
-      }
-      __syncthreads();
+      sel_step(st, pass, reinterpret_cast<uint32_t*>(pos), hist[t], k_limit);
     }
     const int k = st.k_eff;
     if (k == 0) break;  // no valid candidate left
     // ---- collect + decode the chunk
-    for (int idx = t; idx < total; idx += kAllThreads) {
+    for (int idx = t; idx < total; idx += kNmsThreads) {
       const float s = cache[idx];
       if (!det_valid(d, s)) continue;
       int c, it;
       const uint32_t sbits = vy_f32_to_bits(s);
-      const uint32_t inv = det_key_word(d, cand_of(idx, c, it));
+      const uint32_t inv = det_key_word(d, cache_row(d, n_items, idx, c, it));
       if (!first && !(sbits < bound_s || (sbits == bound_s && inv < bound_i))) continue;
       const uint32_t bucket = score_bucket(s);
       const bool take = bucket > st.Tb || (bucket == st.Tb && (sbits > st.Ts || (sbits == st.Ts && inv >= st.Ti)));
@@ -847,34 +814,35 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
       decode_box(d, im, bx1[slot], by1[slot], bx2[slot], by2[slot]);
       bcls[slot] = (float)c;
       key[slot] = ((unsigned long long)sbits << 32) | inv;
-      perm[slot] = (uint16_t)slot;
+    }
+    // ---- sort: slot t's candidate into registers, its rank counted, then written at its rank.  rank_of wants zero keys
+    // past the k collected ones and zero counters: pos[] held the select's suffix sums, last read before sel_step's
+    // closing barriers
+    if (t >= k) key[t] = 0ull;
+    pos[t] = 0;
+    __syncthreads();
+    rank_of(key, pos, k, t);
+    unsigned long long my_key = 0ull;
+    float x1 = 0.0f, y1 = 0.0f, x2 = 0.0f, y2 = 0.0f, cls = 0.0f;
+    if (t < k) {
+      my_key = key[t];
+      x1 = bx1[t];
+      y1 = by1[t];
+      x2 = bx2[t];
+      y2 = by2[t];
+      cls = bcls[t];
     }
     __syncthreads();
-    int kp = 1;
-    while (kp < k) kp <<= 1;
-    for (int i = k + t; i < kp; i += kAllThreads) {
-      key[i] = 0ull;
-      perm[i] = 0;
+    if (t < k) {
+      const int r = pos[t];
+      key[r] = my_key;  // every slot was read before the barrier above
+      bx1[r] = x1;
+      by1[r] = y1;
+      bx2[r] = x2;
+      by2[r] = y2;
+      bcls[r] = cls;
     }
     __syncthreads();
-    for (int size = 2; size <= kp; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int i = t; i < (kp >> 1); i += kAllThreads) {
-          const int lo = ((i / stride) * (stride << 1)) + (i % stride);
-          const int hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const unsigned long long a = key[lo], c = key[hi];
-          if ((a < c) == desc) {
-            key[lo] = c;
-            key[hi] = a;
-            const uint16_t pa = perm[lo];
-            perm[lo] = perm[hi];
-            perm[hi] = pa;
-          }
-        }
-        __syncthreads();
-      }
-    }
     // ---- suppression: first by the rows kept in earlier chunks, then greedily inside the chunk.  The kept rows live
     // in LDS while the output has at most VY_NMS_MAX_TOPK rows; a longer output (nms_topk > 1024 or <= 0 together with
     // post_nms <= 0 or > 1024) IS the list of kept rows, so they are read back from it (written by this workgroup,
@@ -883,64 +851,38 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
     det_with_iou(d, [&](auto plus1) {
       constexpr bool kPlus1 = decltype(plus1)::value;
       if (t < k) {
-        const int e = perm[t];
         bool ok = true;
         if (kept_in_lds) {
           for (int j = 0; j < nk && ok; ++j)
-            if (kcls[j] == bcls[e] && det_suppresses<kPlus1>(d, kx1[j], ky1[j], kx2[j], ky2[j], bx1[e], by1[e], bx2[e], by2[e]))
+            if (kcls[j] == bcls[t] && det_suppresses<kPlus1>(d, kx1[j], ky1[j], kx2[j], ky2[j], bx1[t], by1[t], bx2[t], by2[t]))
               ok = false;
         } else {
           const float* kb = bboxes + (size_t)b * rows * 4;
           const float* kc = ids + (size_t)b * rows;
           for (int j = 0; j < nk && ok; ++j)
-            if (kc[j] == bcls[e] &&
-                det_suppresses<kPlus1>(d, kb[j * 4 + 0], kb[j * 4 + 1], kb[j * 4 + 2], kb[j * 4 + 3], bx1[e], by1[e], bx2[e], by2[e]))
+            if (kc[j] == bcls[t] &&
+                det_suppresses<kPlus1>(d, kb[j * 4 + 0], kb[j * 4 + 1], kb[j * 4 + 2], kb[j * 4 + 3], bx1[t], by1[t], bx2[t], by2[t]))
               ok = false;
         }
         alive[t] = ok ? 1 : 0;
       }
       __syncthreads();
-      for (int i = 0; i < k; ++i) {
-        if (!alive[i]) continue;  // uniform
-        const int ei = perm[i];
-        const float ax1 = bx1[ei], ay1 = by1[ei], ax2 = bx2[ei], ay2 = by2[ei], ac = bcls[ei];
-        for (int j = i + 1 + t; j < k; j += kAllThreads) {
-          const int ej = perm[j];
-          if (alive[j] && bcls[ej] == ac && det_suppresses<kPlus1>(d, ax1, ay1, ax2, ay2, bx1[ej], by1[ej], bx2[ej], by2[ej]))
-            alive[j] = 0;
-        }
-        __syncthreads();
-      }
+      greedy_serial<kPlus1>(d, k, t, alive, bcls, bx1, by1, bx2, by2);
     });
-    // ---- append the survivors in order
-    pos[t] = (t < k && alive[t]) ? 1 : 0;
-    __syncthreads();
-    for (int off = 1; off < VY_NMS_MAX_TOPK; off <<= 1) {
-      const int v = t >= off ? pos[t - off] : 0;
-      __syncthreads();
-      pos[t] += v;
-      __syncthreads();
-    }
-    const int add = pos[VY_NMS_MAX_TOPK - 1];
+    // ---- append the survivors in order (the rank counters in pos[] were last read before the barriers above)
+    const int add = alive_scan(pos, alive, k, t);
     if (t < k && alive[t]) {
       const int r = nk + pos[t] - 1;
       if (r < keep_cap) {
-        const int e = perm[t];
         if (kept_in_lds) {
-          kx1[r] = bx1[e];
-          ky1[r] = by1[e];
-          kx2[r] = bx2[e];
-          ky2[r] = by2[e];
-          kcls[r] = bcls[e];
+          kx1[r] = bx1[t];
+          ky1[r] = by1[t];
+          kx2[r] = bx2[t];
+          ky2[r] = by2[t];
+          kcls[r] = bcls[t];
         }
-        const size_t o = (size_t)b * rows + r;
-        ids[o] = bcls[e];
-        scores[o] = vy_bits_to_f32((uint32_t)(key[t] >> 32));
-        bboxes[o * 4 + 0] = bx1[e];
-        bboxes[o * 4 + 1] = by1[e];
-        bboxes[o * 4 + 2] = bx2[e];
-        bboxes[o * 4 + 3] = by2[e];
-        if (keep_idx) keep_idx[o] = (int32_t)det_key_row(d, (uint32_t)(key[t] & 0xffffffffull));
+        write_row(ids, scores, bboxes, keep_idx, (size_t)b * rows + r, bcls[t], vy_bits_to_f32((uint32_t)(key[t] >> 32)),
+                  bx1[t], by1[t], bx2[t], by2[t], (int32_t)det_key_row(d, (uint32_t)(key[t] & 0xffffffffull)));
       }
     }
     // next chunk: everything strictly below this chunk's smallest key
@@ -957,16 +899,7 @@ __global__ __launch_bounds__(kAllThreads) void nms_all_kernel(const DetArgs d, v
     first = false;
   }
   __syncthreads();
-  for (int r = n_kept + t; r < rows; r += kAllThreads) {
-    const size_t o = (size_t)b * rows + r;
-    ids[o] = -1.0f;
-    scores[o] = -1.0f;
-    bboxes[o * 4 + 0] = -1.0f;
-    bboxes[o * 4 + 1] = -1.0f;
-    bboxes[o * 4 + 2] = -1.0f;
-    bboxes[o * 4 + 3] = -1.0f;
-    if (keep_idx) keep_idx[o] = -1;
-  }
+  fill_rows(ids, scores, bboxes, keep_idx, b, rows, n_kept, t);
 }
 
 // nms_thresh outside (0,1): the reference returns the un-suppressed detection tensor itself (yolo3.py:1195-1206
@@ -982,6 +915,8 @@ __global__ __launch_bounds__(kHistThreads) void raw_detections_kernel(const DetA
   const float conf = vy_sigmoidf(im.p[4]);
   float x1, y1, x2, y2;
   decode_box(d, im, x1, y1, x2, y2);
+  // (the row is written here, not by write_row: through the helper this loop compiled to other code — 32 VGPRs for 39 — and
+  // a 64-frame batch took 349 us for 333: profiles/detect_tail_ab.txt)
   for (int c = 0; c < d.C; ++c) {
     const size_t o = (size_t)b * d.n_cand + (size_t)(im.cand0 + c * im.cstride);
     ids[o] = (float)c;
@@ -994,26 +929,31 @@ __global__ __launch_bounds__(kHistThreads) void raw_detections_kernel(const DetA
   }
 }
 
+// anchors per image: the work items of the anchor-level kernels, the row length of the score cache
+int n_items_of(const DetArgs& a) {
+  int n = 0;
+  for (int i = 0; i < 3; ++i) n += a.head[i].H * a.head[i].W * 3;
+  return n;
+}
+
 }  // namespace
 
 hipError_t vy_launch_raw_detections(const DetArgs& a, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
                                     hipStream_t s) {
-  int n_items = 0;
-  for (int i = 0; i < 3; ++i) n_items += a.head[i].H * a.head[i].W * 3;
+  const int n_items = n_items_of(a);
   dim3 grid((n_items + kHistThreads - 1) / kHistThreads, a.B);
   hipLaunchKernelGGL(raw_detections_kernel, grid, dim3(kHistThreads), 0, s, a, n_items, ids, scores, bboxes, keep_idx);
   return hipGetLastError();
 }
 
 size_t vy_det_scratch_layout(int B, int n_items, int C, int guard, size_t* off, size_t* used) {
-  size_t sz[5], at = 0;
-  scratch_sizes(B, (size_t)C * n_items, sz);
+  size_t o[5], u[5];
+  const size_t total = scratch_layout(B, (size_t)C * n_items, guard, o, u);
   for (int i = 0; i < 5; ++i) {
-    if (off) off[i] = at;
-    if (used) used[i] = sz[i];
-    at += align256(sz[i]) + guard;
+    if (off) off[i] = o[i];
+    if (used) used[i] = u[i];
   }
-  return at;
+  return total;
 }
 
 hipError_t vy_launch_detect(const DetArgs& a, void* scratch, float* ids, float* scores, float* bboxes,
@@ -1025,17 +965,18 @@ hipError_t vy_launch_detect(const DetArgs& a, void* scratch, float* ids, float* 
   const bool chunked = a.topk <= 0 || a.topk > VY_NMS_MAX_TOPK || a.topk_after;
   // rows of the output: post_nms, else nms_topk (no slice, yolo3.py:1201-1202), else — both "disabled" — all N*C rows
   const int rows = a.post_nms > 0 ? a.post_nms : (a.topk > 0 ? a.topk : a.n_cand);
-  // state + histogram region back to zero (entries need no clearing)
-  size_t sz[5];
-  scratch_sizes(a.B, 0, sz);
-  hipError_t e = hipMemsetAsync(scratch, 0, a.guard ? sz[0] : align256(sz[0]) + align256(sz[1]), s);
+  // state and histogram back to zero (entries need no clearing): in one memset from the start of the first to the end of
+  // the second, unless guard bytes lie between them — those are not touched, so then one memset each
+  size_t off[5], used[5];
+  scratch_layout(a.B, 0, a.guard, off, used);
+  unsigned char* base = (unsigned char*)scratch;
+  hipError_t e = hipMemsetAsync(base + off[0], 0, a.guard ? used[0] : off[1] + used[1] - off[0], s);
   if (e != hipSuccess) return e;
-  if (a.guard) {  // (two regions with a gap between them: neither the gap nor the slack is touched)
-    e = hipMemsetAsync(carve(scratch, a.B, a.guard).hist, 0, sz[1], s);
+  if (a.guard) {
+    e = hipMemsetAsync(base + off[1], 0, used[1], s);
     if (e != hipSuccess) return e;
   }
-  int n_items = 0;
-  for (int i = 0; i < 3; ++i) n_items += a.head[i].H * a.head[i].W * 3;
+  const int n_items = n_items_of(a);
   const int per_block = kHistThreads * kItemsPerThread;
   dim3 grid((n_items + per_block - 1) / per_block, a.B);
   int hblocks = 0;
@@ -1045,13 +986,13 @@ hipError_t vy_launch_detect(const DetArgs& a, void* scratch, float* ids, float* 
   }
   const dim3 hgrid(hblocks, a.B);
   if (chunked) {  // every valid candidate (or the topk > 1024 best) goes through NMS: pass 0 only fills the score cache
-    hipLaunchKernelGGL(hist_kernel, hgrid, dim3(kHistThreads), 0, s, a, scratch, 0, n_items);
-    hipLaunchKernelGGL(nms_all_kernel, dim3(a.B), dim3(kAllThreads), 0, s, a, scratch, n_items, rows,
+    hipLaunchKernelGGL(hist_kernel, hgrid, dim3(kHistThreads), 0, s, a, scratch, n_items);
+    hipLaunchKernelGGL(nms_all_kernel, dim3(a.B), dim3(kNmsThreads), 0, s, a, scratch, n_items, rows,
                        (a.topk > 0 && !a.topk_after) ? a.topk : 0, ids, scores, bboxes, keep_idx);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(hist_kernel, hgrid, dim3(kHistThreads), 0, s, a, scratch, 0, n_items);
-  hipLaunchKernelGGL(select_kernel, dim3(a.B), dim3(kBins), 0, s, a, scratch, 0);
+  hipLaunchKernelGGL(hist_kernel, hgrid, dim3(kHistThreads), 0, s, a, scratch, n_items);
+  hipLaunchKernelGGL(select_kernel, dim3(a.B), dim3(kBins), 0, s, a, scratch);
   const int c_groups = (a.C + 7) / 8;
   if ((long long)grid.x * a.B < 256) {
     hipLaunchKernelGGL(compact_kernel<1>, dim3((n_items + kHistThreads - 1) / kHistThreads, a.B, c_groups), dim3(kHistThreads), 0, s,

@@ -311,7 +311,6 @@ struct DetArgs {
   int n_cand;           // N*C candidates per image
   float valid_thresh, nms_thresh;
   int topk, post_nms;
-  int do_nms;           // 0: nms disabled (nms_thresh outside (0,1)): return first post_nms rows
   // the recalled box_nms choices (vy_semantics, include/vyolo.h), each 0 (default) or 1; uniform per launch.  detect.hip
   // reads them through its det_* helpers only
   int valid_ge;         // score >= valid_thresh is valid (default: >)

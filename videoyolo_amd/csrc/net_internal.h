@@ -876,7 +876,6 @@ struct vy_net {
     d.nms_thresh = nms_thresh;
     d.topk = nms_topk;
     d.post_nms = post_nms;
-    d.do_nms = 1;
     d.valid_ge = sem.nms_valid_ge;
     d.overlap_ge = sem.nms_overlap_ge;
     d.tie_desc = sem.nms_tie_descending;
