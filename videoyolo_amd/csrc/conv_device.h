@@ -1,5 +1,6 @@
 // conv_device.h — device-side helpers shared by the implicit-GEMM conv kernels (conv_igemm.hip, conv_split.hip,
-// conv_wino.hip) and the weight gradients (wgrad.hip, wgrad_split.hip).
+// conv_wino.hip) and the weight gradients (wgrad.hip, wgrad_split.hip), and the ordered column sum of the training
+// step's reductions (train_kernels.hip).
 #pragma once
 #include "kernels.h"
 #include "../../include/vy_math.h"
@@ -117,15 +118,20 @@ template <typename Args>
 __device__ __forceinline__ unsigned conv_ups2_crop(const ConvPixel p, Args& a) {
   return (2 * p.x + 1 >= a.o_Wp - 2 ? 1u : 0u) | (2 * p.y + 1 >= a.o_Hp - 2 ? 2u : 0u);
 }
+// A 64-bit value that every lane of the wave computed alike, as a wave-uniform one (an SGPR pair): two readfirstlanes.
+// The compiler cannot see the uniformity itself once a division was expanded into vector code on the way to the value
+template <typename T>  // long long or unsigned long long
+__device__ __forceinline__ T vy_uniform64(const T v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return ((T)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
+#else
+  return v;
+#endif
+}
 // output pixel of a tile's first row (m0 < M always): wave-uniform
 template <typename Args>
 __device__ __forceinline__ long long conv_tile_pix0(const int m0, Args& a) {
-  const long long p = conv_out_pixel(conv_pixel(m0, a), a);
-#if defined(__HIP_DEVICE_COMPILE__)
-  return ((long long)__builtin_amdgcn_readfirstlane((int)(p >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)p);
-#else
-  return p;
-#endif
+  return vy_uniform64(conv_out_pixel(conv_pixel(m0, a), a));
 }
 
 // Row tables of a tile: in_off = element offset of the row's A pixel; o_off / r_off = byte offset of the row's output
@@ -333,3 +339,117 @@ __device__ __forceinline__ WgradPix wgrad_pixel_offsets(int p, int Ho, int Wo, i
   return o;
 }
 
+// ---- what the two weight-gradient kernels (wgrad.hip, wgrad_split.hip) do around their k-loops, ONE definition each.
+// The k-loops themselves share nothing: one stages by LDS-DMA from the pixel table, the other splits in registers.
+
+// Block -> (split, tile) and the split's pixel range.  All tiles of a split read the same pixel range: every n-tile its dz
+// rows, every o-tile the input taps.  Blocks are dealt round-robin over the 8 XCDs (each with its own L2), so in launch
+// order every XCD saw every split and each re-read went out to the fabric (round 2: 22.6 GB per step against 5.2 GB
+// algorithmic).  So the linear block index goes through vy_xcd_tile: an XCD works through a CONTIGUOUS run of (split,
+// tile) pairs, tile fastest — whole splits per XCD, their re-reads served by that XCD's L2.
+// Grid: x over the tiles_m * tiles_n tiles of BM x BN, y over the splits; KP = pixels per k-step.
+struct WgradTile {
+  int split, o0, n0;  // the block's split, first output channel (slab row) and first GEMM column n = tap * Cin + cin
+  int Ntot;           // k * k * Cin: the slab's row length
+  int p_begin, T;     // first pixel of the split, and its k-steps of KP pixels
+};
+template <int BM, int BN, int KP>
+__device__ __forceinline__ WgradTile wgrad_tile(const WgradArgs& a, const int tiles_n) {
+  const int gx = gridDim.x;
+  const int v = vy_xcd_tile(blockIdx.y * gx + blockIdx.x, gx * gridDim.y);
+  WgradTile t;
+  t.split = v / gx;
+  const int tile_id = v - t.split * gx;
+  const int tile_m = tile_id / tiles_n, tile_n = tile_id - tile_m * tiles_n;
+  t.o0 = tile_m * BM;
+  t.n0 = tile_n * BN;
+  t.Ntot = a.k * a.k * a.Cin;
+  t.p_begin = t.split * a.k_per_split;
+  int p_end = t.p_begin + a.k_per_split;
+  if (p_end > a.M) p_end = a.M;
+  t.T = (p_end - t.p_begin + KP - 1) / KP;
+  return t;
+}
+// the split's slab [Cout][Ntot]
+__device__ __forceinline__ float* wgrad_slab(const WgradArgs& a, const WgradTile& t) {
+  return a.slabs + (long long)t.split * a.Cout * t.Ntot;
+}
+
+// byte offsets of the split's first pixel: the pixel table's entries are relative to it
+__device__ __forceinline__ WgradPix wgrad_split_base(const WgradArgs& a, const WgradTile& t) {
+  return wgrad_pixel_offsets(t.p_begin, a.Ho, a.Wo, a.z_cs, a.a_Hp, a.a_Wp, a.a_cs, a.stride);
+}
+
+// GEMM column bn of a staging lane (the first of its chunk; a chunk lies inside one tap, Cin being a multiple of 32) ->
+// tap offset (dy, dx) and input channel.  Columns past k*k*Cin: tap 0 / channel 0 (the column is never stored)
+struct WgradCol {
+  bool ok;
+  int tap, cin, dy, dx;
+};
+__device__ __forceinline__ WgradCol wgrad_column(const WgradArgs& a, const int bn, const int Ntot) {
+  WgradCol c;
+  c.ok = bn < Ntot;
+  c.tap = c.ok ? bn / a.Cin : 0;
+  c.cin = c.ok ? bn - c.tap * a.Cin : 0;
+  const int pad = a.k >> 1;
+  c.dy = a.k == 3 ? c.tap / 3 - pad : 0;
+  c.dx = a.k == 3 ? c.tap % 3 - pad : 0;
+  return c;
+}
+
+// Slab row (output channel) of accumulator register r of a 32x32 MFMA tile (MfmaCd32: grp = the lane's row group).
+// IL = 1: the tile covers rows row0 .. row0 + 31.  IL = 2: tile i of a pair whose operand rows were read interleaved
+// (wgrad_kernel's ds_read_b64: MFMA tile i holds the rows {2 l + i} of the pair's 64)
+template <int IL = 1>
+__device__ __forceinline__ int wgrad_slab_row(const int row0, const int grp, const int r, const int i = 0) {
+  return row0 + IL * MfmaCd32::row(0, grp, r) + i;
+}
+
+// ---- the ordered column sum: the second stage of the training step's reductions (train_kernels.hip: BatchNorm
+// statistics, BN-backward sums, bias and stem gradients).  A first stage leaves partial rows
+// [n_part][n_cols] in a fixed layout; a block of COLS columns x G row groups then adds them in ONE fixed tree: row group g
+// adds rows t0+g, t0+g+G, t0+g+2G, ... in that order (colsum_rows), then group 0 adds the G group sums in group order
+// (colsum_finish).  No atomics, nothing that depends on which block finishes first: a training step is bit-reproducible
+// run to run, and every caller gives the same bits as the others would for the same rows.  The float64 cell tests
+// (tests/test_gpu_train_cells.py and its siblings) pass a reordered tree within their tolerances, so they do not hold
+// the order; tools/train_bits.py does, and the SyncBatchNorm statistics exchange relies on every rank summing alike.
+// Geometry (COLS x G), the accumulator type Acc and the loads in flight U are compile-time arguments of the call.
+// (wgrad.hip's slab_reduce_wide_kernel adds the split-K slabs by a variant of this tree and keeps its own loop: see there.)
+
+// The rows of NC columns at once (their loads interleaved): p[k] points at column k's element of row 0, rs = row stride
+// in elements, t = the thread's first row (t0 + g), t1 = end of the row range.  U changes how many loads are in flight
+// (the loop is latency-bound), never the order of the additions.
+template <int G, int U, int NC, typename Acc, typename T>
+__device__ __forceinline__ void colsum_rows(const T* const (&p)[NC], const long long rs, int t, const int t1, Acc (&acc)[NC]) {
+  for (; t + (U - 1) * G < t1; t += U * G) {
+    T v[NC][U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int k = 0; k < NC; ++k) v[k][u] = p[k][(long long)(t + u * G) * rs];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int k = 0; k < NC; ++k) acc[k] += (Acc)v[k][u];
+  }
+  if (U > 1)
+    for (; t < t1; t += G)
+#pragma unroll
+      for (int k = 0; k < NC; ++k) acc[k] += (Acc)p[k][(long long)t * rs];
+}
+// The finish: every thread of the block (column cx, row group g) hands in its group sums; after it group 0 holds the
+// columns' totals in acc.  Contains the block's barrier: call it outside any column bound.
+template <int G, int COLS, int NC, typename Acc>
+__device__ __forceinline__ void colsum_finish(Acc (&acc)[NC], const int cx, const int g) {
+  __shared__ Acc red[NC][G][COLS + 1];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) red[k][g][cx] = acc[k];
+  __syncthreads();
+  if (g != 0) return;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) acc[k] = 0;
+#pragma unroll 8
+  for (int r = 0; r < G; ++r)
+#pragma unroll
+    for (int k = 0; k < NC; ++k) acc[k] += red[k][r][cx];
+}

@@ -164,11 +164,6 @@ struct Item {
   int cstride;      // candidate index stride between classes = H*W*A
 };
 
-// element e of the prediction vector of pixel (y, x) of image b: the head planes carry a one-pixel border
-__device__ __forceinline__ const float* pred_at(const HeadView& hv, int b, int y, int x, int e) {
-  return hv.pred + ((long long)(b * (hv.H + 2) + y + 1) * (hv.W + 2) + x + 1) * hv.cs + hv.co + e;
-}
-
 __device__ __forceinline__ bool locate(const DetArgs& d, int b, int it, Item& o) {
   int s = 0;
 #pragma unroll

@@ -305,6 +305,32 @@ struct HeadView {
   float aw[3], ah[3];   // anchors (pixels)
   int cand_base;        // first candidate index of this scale in the reference's concat order
 };
+// element e of the prediction vector of pixel (y, x) of image b: the head planes carry a one-pixel border
+__device__ __forceinline__ const float* pred_at(const HeadView& hv, int b, int y, int x, int e) {
+  return hv.pred + ((long long)(b * (hv.H + 2) + y + 1) * (hv.W + 2) + x + 1) * hv.cs + hv.co + e;
+}
+// Anchor n of image b in the order the reference concatenates the heads (scale -> cell -> anchor; n below the three
+// heads' total): its head s, cell (x, y), anchor an, and p = its 5 + C raw predictions [x, y, w, h, obj, cls...]
+struct HeadAnchor {
+  int s, x, y, an;
+  const float* p;
+};
+__device__ __forceinline__ HeadAnchor head_anchor(const HeadView (&head)[3], int b, int n, int C) {
+  HeadAnchor o;
+  int it = n;
+  for (o.s = 0; o.s < 3; ++o.s) {
+    const int cnt = head[o.s].H * head[o.s].W * 3;
+    if (it < cnt) break;
+    it -= cnt;
+  }
+  const HeadView& hv = head[o.s];
+  const int cell = it / 3;
+  o.an = it % 3;
+  o.x = cell % hv.W;
+  o.y = cell / hv.W;
+  o.p = pred_at(hv, b, o.y, o.x, o.an * (5 + C));
+  return o;
+}
 struct DetArgs {
   HeadView head[3];
   int B, C;             // batch, classes

@@ -9,32 +9,32 @@
 //   SGD                       gluon.Trainer('sgd', wd, momentum).step(batch_size), train_yolov3.py:527-530,634
 // All reductions are two-stage (per-block partials written in a fixed layout, then summed in index
 // order in double) so a training step is bit-reproducible run to run; no float atomics.
+//
+// Shared parts and where they live: the second stage of the reductions is the ordered column sum of conv_device.h
+// (colsum_rows, colsum_finish: reduce_partials_kernel, reduce2_finalize, reduce_slices_kernel); the accumulator row map of
+// the stem's weight gradient is wgrad_slab_row there; the anchor walk of the loss and raw-prediction kernels is
+// head_anchor, next to HeadView and pred_at in kernels.h; bn_z_offset and bn_bwd_terms, below, serve the BatchNorm kernels.
 #include <cstdlib>
 #include "kernels.h"
+#include "conv_device.h"  // f32x4, MfmaCd32, the ordered column sum (colsum_rows, colsum_finish)
 #include "../../include/vy_math.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ------------------------------------------------------------------------------------------------
+// The second stages below are instances of the ordered column sum of conv_device.h, which says why its order is fixed
+// and what depends on it.  This one: 32 columns x 32 row groups, in double.
+constexpr int kPartialsLoads = 8;  // in flight per thread
 template <typename T>
 __global__ __launch_bounds__(1024) void reduce_partials_kernel(const T* __restrict__ partials, int n_part,
                                                                int n_cols, double* __restrict__ out) {
-  // block = 32 columns x 32 row-groups; row-group r sums partials r, r+32, ... in order, then the 32
-  // group sums are added in order: a fixed summation tree (deterministic)
-  __shared__ double red[32][33];
   const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
   const int c = blockIdx.x * 32 + cx;
-  double acc = 0.0;
-  if (c < n_cols)
-    for (int t = ry; t < n_part; t += 32) acc += (double)partials[(long long)t * n_cols + c];
-  red[ry][cx] = acc;
-  __syncthreads();
-  if (ry == 0 && c < n_cols) {
-    double s = 0.0;
-#pragma unroll
-    for (int r = 0; r < 32; ++r) s += red[r][cx];
-    out[c] = s;
+  double acc[1] = {0.0};
+  if (c < n_cols) {
+    const T* const p[1] = {partials + c};
+    colsum_rows<32, kPartialsLoads>(p, n_cols, ry, n_part, acc);
   }
+  colsum_finish<32, 32>(acc, cx, ry);
+  if (ry == 0 && c < n_cols) out[c] = acc[0];
 }
 
 hipError_t vy_launch_reduce_partials(const float* partials, int n_part, int n_cols, double* out, hipStream_t s) {
@@ -92,53 +92,21 @@ __global__ void bn_finalize_kernel(const BnFinalizeArgs a) {
 }
 
 // Per-device BatchNorm (no statistics exchange between the reduce and the finalize): both in one launch.
-// Block = kRfCols channels x kRfGroups row groups; row group r sums partial rows r, r + kRfGroups, ... in that
-// order (eight loads in flight at a time: the loop is latency-bound, not bandwidth-bound), then the group sums
-// are added in group order: a fixed summation tree, for the channel's two columns (sum, sum of squares) at once.
-constexpr int kRfCols = 16, kRfGroups = 64;
+// Block = kRfCols channels x kRfGroups row groups of the ordered column sum, in double, eight loads in flight at a
+// time (the loop is latency-bound, not bandwidth-bound), for the channel's two columns (sum, sum of squares) at once.
+constexpr int kRfCols = 16, kRfGroups = 64, kRfLoads = 8;
 
 template <typename T, typename Args, typename Fin>
 __device__ __forceinline__ void reduce2_finalize(const T* __restrict__ partials, int n_part, const Args& a, Fin fin) {
-  __shared__ double red[2][kRfGroups][kRfCols + 1];
   const int cx = threadIdx.x % kRfCols, ry = threadIdx.x / kRfCols;
   const int c = blockIdx.x * kRfCols + cx;
-  double acc1 = 0.0, acc2 = 0.0;
+  double acc[2] = {0.0, 0.0};
   if (c < a.C) {
-    const T* p1 = partials + c;
-    const T* p2 = partials + a.C + c;
-    const long long rs = 2LL * a.C;
-    int t = ry;
-    constexpr int U = 8;
-    for (; t + (U - 1) * kRfGroups < n_part; t += U * kRfGroups) {
-      T v1[U], v2[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        v1[u] = p1[(long long)(t + u * kRfGroups) * rs];
-        v2[u] = p2[(long long)(t + u * kRfGroups) * rs];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        acc1 += (double)v1[u];
-        acc2 += (double)v2[u];
-      }
-    }
-    for (; t < n_part; t += kRfGroups) {
-      acc1 += (double)p1[(long long)t * rs];
-      acc2 += (double)p2[(long long)t * rs];
-    }
+    const T* const p[2] = {partials + c, partials + a.C + c};
+    colsum_rows<kRfGroups, kRfLoads>(p, 2LL * a.C, ry, n_part, acc);
   }
-  red[0][ry][cx] = acc1;
-  red[1][ry][cx] = acc2;
-  __syncthreads();
-  if (ry == 0 && c < a.C) {
-    double s1 = 0.0, s2 = 0.0;
-#pragma unroll 8
-    for (int r = 0; r < kRfGroups; ++r) {
-      s1 += red[0][r][cx];
-      s2 += red[1][r][cx];
-    }
-    fin(a, c, s1, s2);
-  }
+  colsum_finish<kRfGroups, kRfCols>(acc, cx, ry);
+  if (ry == 0 && c < a.C) fin(a, c, acc[0], acc[1]);
 }
 
 // The BatchNorm passes of the backward pass run on the main stream BESIDE the weight-gradient kernels of the side stream
@@ -160,36 +128,21 @@ __global__ __launch_bounds__(1024) void bn_reduce_finalize_kernel(const double* 
 
 // first stage for long partial lists (the 208x208 / 104x104 layers produce thousands of per-tile rows): S row
 // slices are summed by S x (n_cols / kRfCols) blocks into out[S][n_cols] (double), which the launch above then
-// finishes — two short launches instead of one launch whose C / 16 blocks walk every row.  Order: rows of a
-// slice by row group as above, groups in order: fixed.
+// finishes — two short launches instead of one launch whose C / 16 blocks walk every row.  The same ordered column
+// sum over the rows of a slice.
 __global__ __launch_bounds__(1024) void reduce_slices_kernel(const double* __restrict__ partials, int n_part, int n_cols,
                                                              int rows_per_slice, double* __restrict__ out) {
-  __shared__ double red[kRfGroups][kRfCols + 1];
   const int cx = threadIdx.x % kRfCols, ry = threadIdx.x / kRfCols;
   const int c = blockIdx.x * kRfCols + cx;
   const int t0 = blockIdx.y * rows_per_slice;
   const int t1 = t0 + rows_per_slice < n_part ? t0 + rows_per_slice : n_part;
-  double acc = 0.0;
+  double acc[1] = {0.0};
   if (c < n_cols) {
-    int t = t0 + ry;
-    constexpr int U = 8;
-    for (; t + (U - 1) * kRfGroups < t1; t += U * kRfGroups) {
-      double v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) v[u] = partials[(long long)(t + u * kRfGroups) * n_cols + c];
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc += v[u];
-    }
-    for (; t < t1; t += kRfGroups) acc += partials[(long long)t * n_cols + c];
+    const double* const p[1] = {partials + c};
+    colsum_rows<kRfGroups, kRfLoads>(p, n_cols, t0 + ry, t1, acc);
   }
-  red[ry][cx] = acc;
-  __syncthreads();
-  if (ry == 0 && c < n_cols) {
-    double s = 0.0;
-#pragma unroll 8
-    for (int r = 0; r < kRfGroups; ++r) s += red[r][cx];
-    out[(long long)blockIdx.y * n_cols + c] = s;
-  }
+  colsum_finish<kRfGroups, kRfCols>(acc, cx, ry);
+  if (ry == 0 && c < n_cols) out[(long long)blockIdx.y * n_cols + c] = acc[0];
 }
 
 hipError_t vy_launch_bn_reduce_finalize(const double* partials, int n_part, const BnFinalizeArgs& a, double* scratch,
@@ -216,6 +169,13 @@ hipError_t vy_launch_bn_finalize(const BnFinalizeArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// element offset of channel c of pixel (b, y, x) in the plane of the raw conv output z: (B, H + 2, W + 2, C), one-pixel
+// border (Args: BnApplyArgs or BnBwdArgs)
+template <typename Args>
+__device__ __forceinline__ long long bn_z_offset(const Args& a, int b, int y, int x, int c) {
+  return ((long long)(b * (a.H + 2) + y + 1) * (a.W + 2) + x + 1) * a.C + c;
+}
+
 // grid: x over ceil(W*C/4 / 256), y over B*H rows.  One thread = 4 channels of one pixel.
 __global__ __launch_bounds__(256) void bn_apply_kernel(const BnApplyArgs a) {
   bn_raise_prio();
@@ -224,8 +184,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnApplyArgs a) {
   if (q >= a.W * cq) return;
   const int x = q / cq, c = (q - x * cq) << 2;
   const int y = blockIdx.y % a.H, b = blockIdx.y / a.H;
-  const long long zp = ((long long)(b * (a.H + 2) + y + 1) * (a.W + 2) + x + 1) * a.C + c;
-  const f32x4 z = *reinterpret_cast<const f32x4*>(a.z + zp);
+  const f32x4 z = *reinterpret_cast<const f32x4*>(a.z + bn_z_offset(a, b, y, x, c));
   const f32x4 sc = *reinterpret_cast<const f32x4*>(a.scale + c);
   const f32x4 sh = *reinterpret_cast<const f32x4*>(a.shift + c);
   const long long op = (long long)(b * a.o_Hp + y * a.ups + 1) * a.o_Wp + x * a.ups + 1;
@@ -269,6 +228,16 @@ __device__ __forceinline__ f32x4 load_da(const BnBwdArgs& a, int b, int y, int x
 #pragma unroll
   for (int i = 0; i < 4; ++i) r[i] = (g00[i] + g01[i]) + (g10[i] + g11[i]);
   return r;
+}
+
+// The two per-element terms of the backward pass, from the raw conv output z and the gradient da of the cell's output:
+// dy = da through the leaky slope of y = z * scale + shift, and xhat = (z - mean) * invstd
+struct BnBwdTerms {
+  float dy, xh;
+};
+__device__ __forceinline__ BnBwdTerms bn_bwd_terms(float z, float da, float sc, float sh, float mu, float is) {
+  const float yv = fmaf(z, sc, sh);
+  return {yv > 0.0f ? da : 0.1f * da, (z - mu) * is};
 }
 
 // Sums of dy and dy*xhat over the pixels, per channel: the two planes (z, and the gradient of the cell's output)
@@ -326,16 +295,12 @@ __global__ __launch_bounds__(kBwdThreads) void bn_bwd_reduce_kernel(const BnBwdA
     auto accumulate = [&](const f32x4& z, const f32x4& da, f32x4& s1, f32x4& s2) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float yv = fmaf(z[i], sc[i], sh[i]);
-        const float dy = yv > 0.0f ? da[i] : 0.1f * da[i];
-        const float xh = (z[i] - mu[i]) * is[i];
-        s1[i] += dy;
-        s2[i] = fmaf(dy, xh, s2[i]);
+        const BnBwdTerms t = bn_bwd_terms(z[i], da[i], sc[i], sh[i], mu[i], is[i]);
+        s1[i] += t.dy;
+        s2[i] = fmaf(t.dy, t.xh, s2[i]);
       }
     };
-    auto zptr = [&]() {
-      return a.z + ((long long)(b * (a.H + 2) + y + 1) * (a.W + 2) + x + 1) * a.C + c;
-    };
+    auto zptr = [&]() { return a.z + bn_z_offset(a, b, y, x, c); };
     while (row < r1) {
       const f32x4 z0 = *reinterpret_cast<const f32x4*>(zptr());
       const f32x4 d0 = load_da(a, b, y, x, c);
@@ -441,7 +406,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a) {
   if (q >= a.W * cq) return;
   const int x = q / cq, c = (q - x * cq) << 2;
   const int y = blockIdx.y % a.H, b = blockIdx.y / a.H;
-  float* zp = a.z + ((long long)(b * (a.H + 2) + y + 1) * (a.W + 2) + x + 1) * a.C + c;
+  float* zp = a.z + bn_z_offset(a, b, y, x, c);
   const f32x4 z = *reinterpret_cast<const f32x4*>(zp);
   const f32x4 da = load_da(a, b, y, x, c);
   const f32x4 sc = *reinterpret_cast<const f32x4*>(a.scale + c);
@@ -454,10 +419,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdArgs a) {
   f32x4 dz;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const float yv = fmaf(z[i], sc[i], sh[i]);
-    const float dy = yv > 0.0f ? da[i] : 0.1f * da[i];
-    const float xh = (z[i] - mu[i]) * is[i];
-    dz[i] = c1[i] * ((dy - c2[i]) - xh * c3[i]);
+    const BnBwdTerms t = bn_bwd_terms(z[i], da[i], sc[i], sh[i], mu[i], is[i]);
+    dz[i] = c1[i] * ((t.dy - c2[i]) - t.xh * c3[i]);
   }
   *reinterpret_cast<f32x4*>(zp) = dz;
 }
@@ -525,8 +488,6 @@ int vy_stem_wgrad_blocks(int B, int H, int W) {
   return (int)(((long long)B * H * W + 4 * kStemWgradPix - 1) / (4 * kStemWgradPix));
 }
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   __shared__ float red[4][32][33];
@@ -543,7 +504,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) 
   int x = (int)(p % a.W);
   long long t = p / a.W;
   int y = (int)(t % a.H), b = (int)(t / a.H);
-  f32x16_t acc;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
   constexpr int U = 8;
@@ -569,9 +530,9 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradArgs a) 
 #pragma unroll
     for (int u = 0; u < U; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
   }
-  // acc[r] = D[o = (r&3) + 8*(r>>2) + 4*h][k = lrow]
+  // acc[r] = D[o = MfmaCd32::row(0, h, r)][k = lrow]
 #pragma unroll
-  for (int r = 0; r < 16; ++r) red[wave][(r & 3) + 8 * (r >> 2) + 4 * h][lrow] = acc[r];
+  for (int r = 0; r < 16; ++r) red[wave][wgrad_slab_row(0, h, r)][lrow] = acc[r];
   __syncthreads();
   for (int e = threadIdx.x; e < 32 * 27; e += 256) {
     const int o = e / 27, k = e - o * 27;
@@ -607,19 +568,11 @@ __global__ __launch_bounds__(kLossThreads) void loss_kernel(const LossArgs a) {
   const int n = blockIdx.x * kLossThreads + threadIdx.x;
   float l_obj = 0.0f, l_ctr = 0.0f, l_scl = 0.0f, l_cls = 0.0f;
   if (n < a.N) {
-    int it = n, s = 0;
-    for (; s < 3; ++s) {
-      const int cnt = a.head[s].H * a.head[s].W * 3;
-      if (it < cnt) break;
-      it -= cnt;
-    }
-    const HeadView& hv = a.head[s];
-    const int an = it % 3, cell = it / 3;
-    const int x = cell % hv.W, y = cell / hv.W;
-    const int P = 5 + a.C;
-    const long long po = ((long long)(b * (hv.H + 2) + y + 1) * (hv.W + 2) + x + 1) * hv.cs + hv.co + an * P;
-    const float* p = hv.pred + po;
-    float* dp = a.dpred[s] + po;
+    const HeadAnchor at = head_anchor(a.head, b, n, a.C);
+    const HeadView& hv = a.head[at.s];
+    const int an = at.an, x = at.x, y = at.y;
+    const float* p = at.p;
+    float* dp = a.dpred[at.s] + (p - hv.pred);  // the gradient planes have the prediction planes' layout
     const float rx = p[0], ry = p[1], rw = p[2], rh = p[3], ro = p[4];
     const float sx = vy_sigmoidf(rx), sy = vy_sigmoidf(ry);
     const long long tn = (long long)b * a.N + n;
@@ -709,17 +662,10 @@ __global__ __launch_bounds__(256) void raw_preds_kernel(const RawPredArgs a) {
   const int b = blockIdx.y;
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= a.N) return;
-  int it = n, s = 0;
-  for (; s < 3; ++s) {
-    const int cnt = a.head[s].H * a.head[s].W * 3;
-    if (it < cnt) break;
-    it -= cnt;
-  }
-  const HeadView& hv = a.head[s];
-  const int an = it % 3, cell = it / 3;
-  const int x = cell % hv.W, y = cell / hv.W;
-  const int P = 5 + a.C;
-  const float* p = hv.pred + ((long long)(b * (hv.H + 2) + y + 1) * (hv.W + 2) + x + 1) * hv.cs + hv.co + an * P;
+  const HeadAnchor at = head_anchor(a.head, b, n, a.C);
+  const HeadView& hv = a.head[at.s];
+  const int an = at.an, x = at.x, y = at.y;
+  const float* p = at.p;
   const float rx = p[0], ry = p[1], rw = p[2], rh = p[3];
   const float cx = (vy_sigmoidf(rx) + (float)x) * hv.stride, cy = (vy_sigmoidf(ry) + (float)y) * hv.stride;
   const float hw = vy_expf(rw) * hv.aw[an] / 2.0f, hh = vy_expf(rh) * hv.ah[an] / 2.0f;

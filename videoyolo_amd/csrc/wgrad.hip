@@ -12,11 +12,16 @@
 // the MFMA fragments A[i=o][k=p], B[k=p][j=n] are ds_read_b32 of 32 consecutive floats per
 // half-wave (conflict-free, no swizzle).  Block tile 128(o) x 128(n) x 32(p), 4 waves 2x2,
 // 64 accumulator VGPRs per lane, 64 KiB LDS double buffer -> 2 blocks / CU.
+//
+// Shared with wgrad_split.hip, in conv_device.h: the block's tile and pixel range (wgrad_tile, through vy_xcd_tile), the
+// split's base (wgrad_split_base), a staging lane's GEMM column (wgrad_column), the slab and the slab row of an
+// accumulator register (wgrad_slab, wgrad_slab_row), vy_uniform64.  The k-loop below is this kernel's own.
+// slab_reduce_wide_kernel is a variant of the ordered column sum (conv_device.h) that keeps its own loop: see there.
 #include <cstdlib>
 #include <type_traits>
 
 #include "kernels.h"
-#include "conv_device.h"  // f32x16, LDS_PTR, lds_dma16_s, wgrad_pixel_offsets
+#include "conv_device.h"  // f32x16, LDS_PTR, lds_dma16_s, the weight gradients' shared parts
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -78,34 +83,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a, const 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = BM == 128 ? wave >> 1 : 0, wn = BM == 128 ? wave & 1 : wave;
   const int h = lane >> 5, lrow = lane & 31;
-  // Block -> (split, tile).  All tiles of a split read the same pixel range: every n-tile its dz rows, every o-tile the
-  // input taps.  Blocks are dealt round-robin over the 8 XCDs (each with its own L2), so in launch order every XCD saw
-  // every split and each re-read went out to the fabric (round 2: 22.6 GB per step against 5.2 GB algorithmic).  So the
-  // linear block index is mapped so that an XCD works through a CONTIGUOUS run of (split, tile) pairs, tile fastest —
-  // whole splits per XCD, their re-reads served by that XCD's L2.
-  const int gx = gridDim.x, nblk = gx * gridDim.y, L = blockIdx.y * gx + blockIdx.x;
-  const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
-  const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  const int split = v / gx;
-  const int tile_id = v - split * gx;
-  const int tile_m = tile_id / tiles_n, tile_n = tile_id - tile_m * tiles_n;
-  const int o0 = tile_m * BM, n0 = tile_n * BN;
-  const int Ntot = a.k * a.k * a.Cin;
-  const int p_begin = split * a.k_per_split;
-  int p_end = p_begin + a.k_per_split;
-  if (p_end > a.M) p_end = a.M;
-  const int T = (p_end - p_begin + KP - 1) / KP;
+  const WgradTile tl = wgrad_tile<BM, BN, KP>(a, tiles_n);  // block -> (split, tile), XCD-aware (conv_device.h)
+  const int o0 = tl.o0, n0 = tl.n0, Ntot = tl.Ntot, p_begin = tl.p_begin, T = tl.T;
 
   // this lane's fixed column chunk in both tiles
   const int a_chunk = lane % A_CPR, a_sub = lane / A_CPR;  // dz: chunk inside the row, pixel row inside the instruction
   const int ao = o0 + a_chunk * 4;        // dz channel of this chunk
   const int chunk = lane & 31;            // activation tile: 16-B chunk inside a 512-B row
-  const int bn = n0 + chunk * 4;          // n column of this chunk
-  const bool b_ok = bn < Ntot;            // columns past k*k*Cin: tap 0 / channel 0 (the column is never stored)
-  const int tap = b_ok ? bn / a.Cin : 0;
-  const int cin = b_ok ? bn - tap * a.Cin : 0;
-  const int pad = a.k >> 1;
-  const int dy = a.k == 3 ? tap / 3 - pad : 0, dx = a.k == 3 ? tap % 3 - pad : 0;
+  const WgradCol col = wgrad_column(a, n0 + chunk * 4, Ntot);  // n column of this chunk -> tap, input channel
 
   f32x16 acc[2][TJ];
 #pragma unroll
@@ -125,15 +110,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a, const 
   const uint2* tab = a.tab + p_begin;                                      // wave-uniform
   // the split's first pixel: the table's offsets are relative to it (wave-uniform; 32-bit divisions + readfirstlane,
   // sk-kernel lesson: a 64-bit division is expanded into vector code whose results stop counting as uniform)
-  const WgradPix sb = wgrad_pixel_offsets(p_begin, a.Ho, a.Wo, a.z_cs, a.a_Hp, a.a_Wp, a.a_cs, a.stride);
-  auto uni64 = [](unsigned long long v) {
-    return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-           (unsigned)__builtin_amdgcn_readfirstlane((int)v);
-  };
-  const float* z_base = a.dz + (uni64(sb.zo) >> 2);
-  const float* a_base = a.a + (uni64(sb.ao) >> 2) + a.a_co - (long long)(a.a_Wp + 1) * a.a_cs;  // tap offsets become >= 0
+  const WgradPix sb = wgrad_split_base(a, tl);
+  const float* z_base = a.dz + (vy_uniform64(sb.zo) >> 2);
+  const float* a_base = a.a + (vy_uniform64(sb.ao) >> 2) + a.a_co - (long long)(a.a_Wp + 1) * a.a_cs;  // tap offsets become >= 0
   const unsigned zc = (unsigned)ao * 4u;
-  const unsigned ac = (unsigned)((((dy + 1) * a.a_Wp + (dx + 1)) * a.a_cs + cin) * 4);
+  const unsigned ac = (unsigned)((((col.dy + 1) * a.a_Wp + (col.dx + 1)) * a.a_cs + col.cin) * 4);
   const int zrow0 = A_RPI * wave + a_sub, arow0 = 2 * wave + h;  // + 4 * A_RPI * j / + 8 * j
   unsigned tz[NJA], ta[NJ];
   auto load_offsets = [&](int t) {
@@ -223,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a, const 
     if (t < T) kstep(P0{}, t);
   }
 
-  float* slab = a.slabs + (long long)split * a.Cout * Ntot;
+  float* slab = wgrad_slab(a, tl);
   if (BM == 128) {
     // acc[i][j][r] = D[o = o0 + wm*64 + 2*row(r,h) + i][n = n0 + wn*64 + 2*lrow + j]: the two column tiles of
     // a lane are adjacent in memory -> 8-B stores, 256 B contiguous per half-wave
@@ -233,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a, const 
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int o = o0 + wm * 64 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * h) + i;
+          const int o = wgrad_slab_row<2>(o0 + wm * 64, h, r, i);
           if (o < a.Cout) {
             f32x2 v = {acc[i][0][r], acc[i][TJ - 1][r]};
             *reinterpret_cast<f32x2*>(slab + (long long)o * Ntot + n) = v;
@@ -248,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a, const 
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int o = o0 + 2 * ((r & 3) + 8 * (r >> 2) + 4 * h) + i;
+          const int o = wgrad_slab_row<2>(o0, h, r, i);
           if (o < a.Cout) slab[(long long)o * Ntot + n] = acc[i][0][r];
         }
     }
@@ -290,6 +271,12 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
 // Many slabs over a small weight tensor (the early layers: up to ~500 slabs of a few thousand floats):
 // a thread per element would walk the slabs serially, so G thread groups each add every G-th slab of 32
 // columns and the G partial sums are combined in group order (still a fixed order: deterministic).
+// This is the ordered column sum of conv_device.h in fp32 with a group's slabs taken as two interleaved ranges (stride
+// 2 G from g and from g + G, the two sums then added) — and stays its own loop: written as two colsum_rows calls and a
+// colsum_finish it gave the same bits, and its one kernel trace read 12 % slower (16.5 -> 18.5 us at G = 32, 21.6 ->
+// 24.3 us at G = 8; the two ranges' loads no longer sit in one loop).  Beside the main stream's kernels this launch's
+// mean moves by as much between two traces of the SAME code, so the figure does not settle it either way
+// (profiles/train_shared_parts.txt); not shown to be as fast, it was left.
 template <int G>
 __global__ __launch_bounds__(32 * G) void slab_reduce_wide_kernel(const float* __restrict__ slabs, int splits, long long n,
                                                                   float* __restrict__ dst) {

@@ -15,31 +15,14 @@
 // fragment.  LDS image
 // per operand and stage: [plane][16 pixels][128 channels + 32 pad] bf16 — the 320-B row pitch puts the four pixel rows
 // of a transposed read on disjoint banks.  Two stages (60 KiB): two blocks per CU.
+//
+// Everything around the k-loop is wgrad.hip's, written once in conv_device.h (wgrad_tile, wgrad_split_base, wgrad_column,
+// wgrad_slab, wgrad_slab_row); the bf16 x 3 cut is split_device.h's split8, as in conv_split.hip.
 #include <cstdio>
 #include <cstdlib>
 
 #include "kernels.h"
-#include "split_device.h"  // cvt_pk_bf16
-
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __bf16 ws_bf16x8 __attribute__((ext_vector_type(8)));
-
-// split8 (split_device.h) with scalar differences: the instruction stream this kernel was measured with
-__device__ __forceinline__ void ws_split8(const f32x4 v0, const f32x4 v1, vy_u32x4& H, vy_u32x4& M, vy_u32x4& L) {
-  const float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float x0 = x[2 * j], x1 = x[2 * j + 1];
-    const unsigned h = cvt_pk_bf16(x0, x1);
-    const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    const unsigned m = cvt_pk_bf16(r0, r1);
-    const float l0 = r0 - __builtin_bit_cast(float, m << 16), l1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-    H[j] = h;
-    M[j] = m;
-    L[j] = cvt_pk_bf16(l0, l1);
-  }
-}
-#endif
+#include "split_device.h"  // split8, bf16x8; conv_device.h: the weight gradients' shared parts
 
 __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a, const int tiles_n) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -54,33 +37,17 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int h = lane >> 5, lrow = lane & 31;
-  // an XCD works through a contiguous run of (split, tile) pairs (wgrad.hip)
-  const int gx = gridDim.x, nblk = gx * gridDim.y, L = blockIdx.y * gx + blockIdx.x;
-  const int q = nblk >> 3, r = nblk & 7, xcd = L & 7, idx = L >> 3;
-  const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  const int split = v / gx;
-  const int tile_id = v - split * gx;
-  const int tile_m = tile_id / tiles_n, tile_n = tile_id - tile_m * tiles_n;
-  const int o0 = tile_m * BM, n0 = tile_n * BN;
-  const int Ntot = a.k * a.k * a.Cin;
-  const int p_begin = split * a.k_per_split;
-  int p_end = p_begin + a.k_per_split;
-  if (p_end > a.M) p_end = a.M;
-  const int T = (p_end - p_begin + KP - 1) / KP;
+  const WgradTile tl = wgrad_tile<BM, BN, KP>(a, tiles_n);  // block -> (split, tile), XCD-aware (conv_device.h)
+  const int o0 = tl.o0, n0 = tl.n0, Ntot = tl.Ntot, p_begin = tl.p_begin, T = tl.T;
 
   // staging role of this thread: pixel row `pix` of the k-step, 8-channel chunk `chunk` of both tiles
   const int pix = tid >> 4, chunk = tid & 15;
   const int oc = o0 + chunk * 8;                       // dz channels oc .. oc+7 (Cout % 128 == 0: always valid)
-  const int bn = n0 + chunk * 8;                       // n columns bn .. bn+7: one tap (Cin % 8 == 0)
-  const bool b_ok = bn < Ntot;                         // columns past taps*Cin: tap 0 / channel 0, never stored
-  const int tap = b_ok ? bn / a.Cin : 0;
-  const int cin = b_ok ? bn - tap * a.Cin : 0;
-  const int pad = a.k >> 1;
-  const int dy = a.k == 3 ? tap / 3 - pad : 0, dx = a.k == 3 ? tap % 3 - pad : 0;
-  const WgradPix sb = wgrad_pixel_offsets(p_begin, a.Ho, a.Wo, a.z_cs, a.a_Hp, a.a_Wp, a.a_cs, a.stride);
+  const WgradCol col = wgrad_column(a, n0 + chunk * 8, Ntot);  // n columns bn .. bn+7: one tap (Cin % 8 == 0)
+  const WgradPix sb = wgrad_split_base(a, tl);
   const unsigned char* z_base = reinterpret_cast<const unsigned char*>(a.dz) + sb.zo + (long long)oc * 4;
   const unsigned char* a_base = reinterpret_cast<const unsigned char*>(a.a) + sb.ao +
-                                ((long long)a.a_co + (long long)(dy * a.a_Wp + dx) * a.a_cs + cin) * 4;
+                                ((long long)a.a_co + (long long)(col.dy * a.a_Wp + col.dx) * a.a_cs + col.cin) * 4;
   const uint2* tab = a.tab + p_begin + pix;
   const unsigned st_off = (unsigned)(pix * PITCH + chunk * 16);  // this thread's 16 B inside a plane
 
@@ -104,11 +71,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a, 
   auto store = [&](int stage) {
     vy_u32x4 H, M, L;
     unsigned char* d = smem + stage * STAGE + st_off;
-    ws_split8(za[0], za[1], H, M, L);
+    split8(za[0], za[1], H, M, L);
     *reinterpret_cast<vy_u32x4*>(d) = H;
     *reinterpret_cast<vy_u32x4*>(d + PLANE) = M;
     *reinterpret_cast<vy_u32x4*>(d + 2 * PLANE) = L;
-    ws_split8(aa[0], aa[1], H, M, L);
+    split8(aa[0], aa[1], H, M, L);
     *reinterpret_cast<vy_u32x4*>(d + IMG) = H;
     *reinterpret_cast<vy_u32x4*>(d + IMG + PLANE) = M;
     *reinterpret_cast<vy_u32x4*>(d + IMG + 2 * PLANE) = L;
@@ -123,14 +90,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a, 
   const unsigned fb0 = lds0 + IMG + tr_off + (unsigned)(wn * 64 * 2);   // B tile: columns wn*64 ..
   typedef short ws_s16x4 __attribute__((ext_vector_type(4)));
   typedef short ws_s16x8 __attribute__((ext_vector_type(8)));
-  auto tr8 = [&](unsigned addr) -> ws_bf16x8 {
+  auto tr8 = [&](unsigned addr) -> bf16x8 {
     const ws_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ws_s16x4*)(unsigned long long)addr);
     const ws_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ws_s16x4*)(unsigned long long)(addr + 1280));
     const ws_s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(ws_bf16x8, v);
+    return __builtin_bit_cast(bf16x8, v);
   };
   auto compute = [&](int stage) {
-    ws_bf16x8 af[3][2], bf[3][2];
+    bf16x8 af[3][2], bf[3][2];
     constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};  // (l,h) (h,l) (m,m) (m,h) (h,m) (h,h)
     auto prod = [&](int t) {
 #pragma unroll
@@ -170,8 +137,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a, 
     }
   }
 
-  // D[o][n]: C/D map of the 32x32 MFMA: column = lane & 31 (n), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (o)
-  float* slab = a.slabs + (long long)split * a.Cout * Ntot;
+  // D[o][n]: C/D map of the 32x32 MFMA (MfmaCd32): column = lane & 31 (n), row group = lane >> 5 (o)
+  float* slab = wgrad_slab(a, tl);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int n = n0 + wn * 64 + j * 32 + lrow;
@@ -180,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(const WgradArgs a, 
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int o = o0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int o = wgrad_slab_row(o0 + wm * 64 + i * 32, h, r);
         if (o < a.Cout) slab[(long long)o * Ntot + n] = acc[i][j][r];
       }
   }
