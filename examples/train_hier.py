@@ -5,7 +5,12 @@ there on the net is the single-frame one on the clips.  The max has no parameter
 start.  A few augmented training steps (YOLO3VideoTrainTransform with k = T: one draw per clip, one launch per batch) from
 such a file, then a validation pass with detect_yolo3.py's surface.
 
-    python examples/train_hier.py [--size 416] [--clips 4] [--hier 3,3,1,1,1] [--steps 5] [--src 240x320]
+--join conv trains the reference's learned join instead (--h_join_type conv: a per-channel 3-tap filter over each triple,
+BatchNorm, LeakyReLU; videoyolo_amd.YOLOV3HierConv).  The joins have parameters of their own, which the single-frame file
+does not hold: it loads with allow_missing=True and the joins keep their start — here a mean, every weight 1/3, because the
+reference's own start, all zeros, makes every joined plane a constant until the first updates have moved the weights.
+
+    python examples/train_hier.py [--join max|conv] [--size 416] [--clips 4] [--hier 3,3,1,1,1] [--steps 5] [--src 240x320]
 """
 import argparse
 import os
@@ -24,6 +29,7 @@ def main():
     ap.add_argument("--hier", default="3,3,1,1,1")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--src", default="240x320", help="height x width of the synthetic source frames")
+    ap.add_argument("--join", choices=("max", "conv"), default="max", help="how a triple of frames is joined (h_join_type)")
     args = ap.parse_args()
 
     import random
@@ -42,10 +48,17 @@ def main():
     single.initialize(init="synthetic", seed=233)
     path = os.path.join(tempfile.mkdtemp(prefix="hier_"), "single.params")
     single.save_parameters(path)
-    net = vy.yolo3_darknet53(classes, pretrained_base=False, new_model=True, hierarchical=hier, h_join_type="max")
-    net.load_parameters(path, ctx=dev)
+    if args.join == "conv":
+        net = vy.YOLOV3HierConv(classes, hierarchical=hier)
+        net.initialize()                                                                 # the joins: zeros, as the reference
+        for name, p in net.collect_params(r"hjoin\.\d\.0\.weight").items():             # ... moved to a mean start
+            p.set_data(np.full(p.shape, 1.0 / 3.0, np.float32))
+        net.load_parameters(path, ctx=dev, allow_missing=True)
+    else:
+        net = vy.yolo3_darknet53(classes, pretrained_base=False, new_model=True, hierarchical=hier, h_join_type="max")
+        net.load_parameters(path, ctx=dev)
     t = net.frames
-    print("hierarchical %s: clips of %d frames" % (net.hierarchical, t))
+    print("hierarchical %s%s: clips of %d frames" % (net.hierarchical, " (conv join)" if args.join == "conv" else "", t))
 
     n = 2 * args.clips
     rng = np.random.default_rng(1)

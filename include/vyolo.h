@@ -116,9 +116,25 @@ int vy_net_window(const vy_net* net, int32_t* k, int32_t* join);
  * VY_TAP_INPUT_PADDED: the pre-pool plane) take "hpool.0" .. "hpool.<n_pools - 1>"; every tap has batch *
  * vy_net_tap_frames frames. */
 int vy_net_create_hier(int32_t num_class, int32_t n_pools, vy_net** out);
+/* The hierarchical net with the join named: VY_HJOIN_MAX is vy_net_create_hier, table for table; VY_HJOIN_CONV is
+ * h_join_type='conv' (`_conv1d`, layers.py:50-60; h_darknet.py:97-101, 116-119): in place of the max, per channel
+ *   z[n, c, y, x] = fmaf(w[c][2], x[3n + 2], fmaf(w[c][1], x[3n + 1], w[c][0] * x[3n]))     (first product rounded alone)
+ * then BatchNorm(eps 1e-5, momentum 0.9; train mode: statistics over the batch * frames * h * w pooled positions, never a
+ * synchronised one) and LeakyReLU(0.1).  Any other join, n_pools outside 1 .. 4: VY_ERR_INVALID.  Join i (C = 32, 64, 128,
+ * 256) has five parameters, appended BEHIND vy_net_create's table, which is a prefix of this one name for name and offset
+ * for offset: "hjoin.<i>.0.weight" of shape (C, 3) (the reference's (C, 1, 3, 1, 1)) and "hjoin.<i>.1.gamma" / ".beta" /
+ * ".running_mean" / ".running_var" (C,), all with backbone = 1 and the trainable flags of a cell's five.  The conv list is
+ * vy_net_create's: a join is not a conv.  Entries, refusals and conv modes are vy_net_create_hier's; the launches of
+ * vy_net_profile_infer and the taps are "hjoin.<i>" instead of "hpool.<i>" (each name is VY_ERR_INVALID on the other
+ * net): vy_net_read_activation the pooled plane, vy_net_read_grad_activation its gradient, vy_net_read_train_tap all four
+ * taps with a cell's meaning (VY_TAP_Z: the join's z, dz after the backward; VY_TAP_INPUT_PADDED: the pre-pool plane).
+ * Training: one rank, exact conv mode; the join's gradients travel with the gradient bucket of stages.0. */
+#define VY_HJOIN_MAX 0
+#define VY_HJOIN_CONV 1
+int vy_net_create_hier_join(int32_t num_class, int32_t n_pools, int32_t join, vy_net** out);
 /* pools and frames per clip (3^n_pools) of a hierarchical net; 0 and 1 for any other net. */
 int vy_net_hier(const vy_net* net, int32_t* n_pools, int32_t* frames);
-/* frames per batch entry of the tap `name` (a cell, "pool.<i>" or "hpool.<i>") of any net: its leading dimension in a plan
+/* frames per batch entry of the tap `name` (a cell, "pool.<i>", "hpool.<i>" or "hjoin.<i>") of any net: its leading dimension in a plan
  * bound for `batch` is batch * frames (a video plan aside).  VY_ERR_INVALID: no such tap. */
 int vy_net_tap_frames(const vy_net* net, const char* name, int32_t* frames);
 void vy_net_destroy(vy_net* net);

@@ -12,7 +12,17 @@ With --stats the child for T = 9 runs once more under `rocprofv3 --kernel-trace 
 hier_pool_kernel and hier_pool_bwd_kernel over all pool launches of the run, beside an elementwise copy kernel launched once
 for every pool launch with that launch's bytes.  The table goes to --out.
 
-    python tools/hier_step.py [--stats] [--size 416] [--clips 16] [--frames 3,9,27] [--steps 5] [--warmup 2] [--out PATH]
+With --join conv the hierarchical net is YOLOV3HierConv, the learned join (hier.hip's hier_join_* kernels), and every T is
+measured next to the max net at the same T in the same process; the forward launches are hjoin.i (the same bytes as a pool:
+three frames read, one written), and --stats times the two training kernels: hier_join_raw_kernel (three frames read, z
+written: 16 bytes per pooled element, plus its statistics rows) and hier_join_bwd_kernel (dz and three frames read, three
+gradients written: 28 bytes per pooled element, plus its weight-gradient rows).  The BatchNorm passes around them (finalize,
+apply, backward reduce / apply: z read twice more and written once, the gradient read twice) are the kernels every cell
+uses and are not listed.  There is no pass / fail bar: the rates are reported against the 0.7-of-copy target.  The table
+goes to profiles/hier_conv_step.txt unless --out says otherwise; the default, --join max, is unchanged.
+
+    python tools/hier_step.py [--join max|conv] [--stats] [--size 416] [--clips 16] [--frames 3,9,27] [--steps 5] [--warmup 2]
+                              [--out PATH]
 """
 import argparse
 import json
@@ -76,20 +86,35 @@ def measure(args):
         net.collect_params().reset_ctx(dev)
         return net
 
+    def make_conv(hierarchical):  # the joins at the synthetic start (weights 1/3), the cells as every other net here
+        net = vy.YOLOV3HierConv(classes, hierarchical=hierarchical)
+        net.initialize(init="synthetic", seed=233)
+        net.set_parameters(params, allow_missing=True)
+        net.collect_params().reset_ctx(dev)
+        return net
+
+    conv = args.join == "conv"
+    launch = "hjoin." if conv else "hpool."
+
     gen = torch.Generator().manual_seed(0)
     out = {"device": torch.cuda.get_device_name(0), "size": s, "clips": b, "steps": args.steps, "warmup": args.warmup,
-           "rounds": args.rounds, "hier": {}}
+           "rounds": args.rounds, "join": args.join, "hier": {}}
     for t in args.frames:
         n = {3: 1, 9: 2, 27: 3, 81: 4}[t]
         row = out["hier"][str(t)] = {"hierarchical": [3] * n + [1] * (5 - n)}
         try:
-            net = make(new_model=True, hierarchical=row["hierarchical"], h_join_type="max")
             x = torch.randn((b, t, 3, s, s), generator=gen).to(dev)
+            net = make(new_model=True, hierarchical=row["hierarchical"], h_join_type="max")
+            if conv:  # the max net first, then the conv-join net on the same clips
+                row["max_step_ms"], row["max_infer_ms"] = step_and_infer(net, x, b)
+                del net
+                torch.cuda.empty_cache()
+                net = make_conv(row["hierarchical"])
             row["step_ms"], row["infer_ms"] = step_and_infer(net, x, b)
             row["step_ms_per_frame"] = round(row["step_ms"] / (b * t), 4)
             row["infer_ms_per_frame"] = round(row["infer_ms"] / (b * t), 4)
             # the forward pool launches and copies of their bytes, alternating round by round
-            pools = {"hpool.%d" % i: 16 * pool_floats(s, b, t, i) for i in range(n)}
+            pools = {"%s%d" % (launch, i): 16 * pool_floats(s, b, t, i) for i in range(n)}
             big = max(pools.values()) // 2
             src = torch.empty(big // 4, dtype=torch.float32, device=dev).normal_()
             dst = torch.empty_like(src)
@@ -97,7 +122,7 @@ def measure(args):
             copy_ms = {k: [] for k in pools}
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             for r in range(args.rounds + 1):
-                prof = {name: v for name, v, _, _ in net.profile(x) if name.startswith("hpool.")}
+                prof = {name: v for name, v, _, _ in net.profile(x) if name.startswith(launch)}
                 for k, by in pools.items():
                     e0.record()
                     dst[:by // 8].copy_(src[:by // 8])  # by / 2 bytes read, by / 2 written
@@ -133,7 +158,11 @@ def stats_child(args):
     dev = torch.device("cuda", 0)
     classes = ["c%d" % i for i in range(20)]
     b, s, t = args.clips, args.size, 9
-    net = vy.yolo3_darknet53(classes, pretrained_base=False, new_model=True, hierarchical=[3, 3, 1, 1, 1], h_join_type="max")
+    conv = args.join == "conv"
+    if conv:
+        net = vy.YOLOV3HierConv(classes, hierarchical=[3, 3, 1, 1, 1])
+    else:
+        net = vy.yolo3_darknet53(classes, pretrained_base=False, new_model=True, hierarchical=[3, 3, 1, 1, 1], h_join_type="max")
     net.initialize(init="synthetic", seed=233)
     net.collect_params().reset_ctx(dev)
     x = torch.randn((b, t, 3, s, s), generator=torch.Generator().manual_seed(0)).to(dev)
@@ -148,27 +177,33 @@ def stats_child(args):
             l = net(x, gt, *fixed)
             autograd.backward([l[0] + l[1] + l[2] + l[3]])
         for f in fl:
-            for units in (4, 8):  # forward: 3 read + 1 written; backward: 5 read + 3 written
+            # forward: 3 read + 1 written; backward: 5 read + 3 written (max), dz + 3 read + 3 written (conv)
+            for units in (4, 7 if conv else 8):
                 torch.neg(src[:units * f // 2], out=dst[:units * f // 2])
     torch.cuda.synchronize()
     return {"frames": t, "steps": 2, "pool_floats": fl}
 
 
 def kernel_stats(args):
-    rows = _measure.kernel_rows(__file__, ["--stats-child", "--size", str(args.size), "--clips", str(args.clips)], CHILD_TIMEOUT_S,
-                                "hier_step_")
+    rows = _measure.kernel_rows(__file__, ["--stats-child", "--size", str(args.size), "--clips", str(args.clips), "--join", args.join],
+                                CHILD_TIMEOUT_S, "hier_step_")
     if isinstance(rows, dict):
         return rows
     fl = [pool_floats(args.size, args.clips, 9, i) for i in range(2)]
     found = {}
+    conv = args.join == "conv"
     for r in rows:
-        if "hier_pool_bwd_kernel" in r["name"]:
+        if "hier_join_bwd_kernel" in r["name"]:
+            found["hier_join_bwd"] = dict(_measure.stats_of(r), bytes_per_step=28 * sum(fl))
+        elif "hier_join_raw_kernel" in r["name"]:
+            found["hier_join_raw"] = dict(_measure.stats_of(r), bytes_per_step=16 * sum(fl))
+        elif "hier_pool_bwd_kernel" in r["name"]:
             found["hier_pool_bwd"] = dict(_measure.stats_of(r), bytes_per_step=32 * sum(fl))
         elif "hier_pool_kernel" in r["name"]:
             found["hier_pool"] = dict(_measure.stats_of(r), bytes_per_step=16 * sum(fl))
         elif "elementwise" in r["name"] and "neg" in r["name"].lower():  # torch.neg(src, out=dst): 8 launches in the run
             # (torch splits a launch whose byte offsets pass 2^31 in two: more than 8 calls, the same bytes)
-            found["copy"] = dict(_measure.stats_of(r), bytes_per_step=48 * sum(fl), kernel=r["name"][:80])
+            found["copy"] = dict(_measure.stats_of(r), bytes_per_step=(44 if conv else 48) * sum(fl), kernel=r["name"][:80])
     if "copy" not in found:
         found["elementwise_rows"] = [(r["name"][:80], r["calls"]) for r in rows if "elementwise" in r["name"]]
         return found
@@ -178,7 +213,9 @@ def kernel_stats(args):
 
 
 def table(res, stats):
-    lines = ["Hierarchical net next to the window net and the single-frame net: %s, %d clips of %d x %d" % (
+    conv = res.get("join") == "conv"
+    lines = ["Hierarchical net%s next to the window net and the single-frame net: %s, %d clips of %d x %d" % (
+        " with the learned 'conv' join (YOLOV3HierConv), and the max net at the same T," if conv else "",
         res["device"], res["clips"], res["size"], res["size"]),
         "(device events, %d steps after %d warm-up steps, one process; tools/hier_step.py)" % (res["steps"], res["warmup"]), "",
         "%-34s %8s %12s %14s %12s %14s" % ("net", "frames", "step ms", "step ms/frame", "infer ms", "infer ms/frame")]
@@ -188,14 +225,20 @@ def table(res, stats):
         if "error" in r:
             lines.append("%-34s %8d   did not run: %s" % (name, b * int(t), r["error"]))
             continue
+        if conv:
+            name = "hier conv %s" % r["hierarchical"]
+            lines.append("%-34s %8d %12.3f %14.4f %12.3f %14.4f" % ("hier max %s" % r["hierarchical"], b * int(t), r["max_step_ms"],
+                                                                     r["max_step_ms"] / (b * int(t)), r["max_infer_ms"],
+                                                                     r["max_infer_ms"] / (b * int(t))))
         lines.append("%-34s %8d %12.3f %14.4f %12.3f %14.4f" % (name, b * int(t), r["step_ms"], r["step_ms_per_frame"],
                                                                  r["infer_ms"], r["infer_ms_per_frame"]))
     for name, key, frames in (("window k=3 (max, early)", "window_k3", 3 * b), ("single frame", "single_frame", b)):
         r = res[key]
         lines.append("%-34s %8d %12.3f %14.4f %12.3f %14.4f" % (name, frames, r["step_ms"], r["step_ms"] / frames, r["infer_ms"],
                                                                  r["infer_ms"] / frames))
-    lines += ["", "Forward pool launches (events around the launch; a copy of the same bytes alternating in the same rounds; "
-              "medians of %d rounds; DESIGN's target for a streaming kernel: 0.7 of the copy rate)" % res["rounds"],
+    lines += ["", "Forward %s launches (events around the launch; a copy of the same bytes alternating in the same rounds; "
+              "medians of %d rounds; DESIGN's target for a streaming kernel: 0.7 of the copy rate)" % (
+                  "join" if conv else "pool", res["rounds"]),
               "%-10s %-8s %12s %10s %8s %10s %8s %10s" % ("T", "launch", "MB", "ms", "TB/s", "copy ms", "TB/s", "of copy")]
     for t, r in res["hier"].items():
         for k, p in r.get("pools", {}).items():
@@ -205,6 +248,10 @@ def table(res, stats):
     if stats is not None:
         lines += ["", "rocprofv3 --kernel-trace --stats, T = 9, two training steps; the copy is one elementwise kernel per pool "
                   "launch with that launch's bytes: %s" % json.dumps(stats)]
+        if conv:
+            lines += ["(bytes_per_step: hier_join_raw 16 per pooled element — three frames read, z written; hier_join_bwd 28 — dz and "
+                      "three frames read, three gradients written; their per-block partial rows and the BatchNorm passes around "
+                      "them are not counted.  No bar: the target is 0.7 of the copy's TB_per_s.)"]
     return "\n".join(lines) + "\n"
 
 
@@ -217,11 +264,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--stats", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hier_step.txt"))
+    ap.add_argument("--join", choices=("max", "conv"), default="max")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--stats-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     args.frames = [int(v) for v in str(args.frames).split(",")]
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "hier_conv_step.txt" if args.join == "conv" else "hier_step.txt")
     if any(t not in (3, 9, 27, 81) for t in args.frames):
         sys.exit("--frames: 3, 9, 27 or 81 frames per clip")
     if args.child:
@@ -231,7 +281,7 @@ def main():
         print(json.dumps(stats_child(args)))
         return
     argv = ["--size", str(args.size), "--clips", str(args.clips), "--frames", ",".join(str(t) for t in args.frames), "--steps",
-            str(args.steps), "--warmup", str(args.warmup), "--rounds", str(args.rounds)]
+            str(args.steps), "--warmup", str(args.warmup), "--rounds", str(args.rounds), "--join", args.join]
     res = _measure.run_child(__file__, ["--child"] + argv, CHILD_TIMEOUT_S)
     text = table(res, kernel_stats(args) if args.stats else None)
     with open(args.out, "w") as f:

@@ -10,7 +10,7 @@ import os as _os
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 from . import autograd  # noqa: F401,E402
-from .model import (YOLOV3, YOLOV3T, YOLOV3NoBackbone, YOLOV3_noback, YOLOV3Window, YOLOV3Hier, YOLOV3NoBackboneWindow, BatchNorm, SyncBatchNorm, yolo3_darknet53,  # noqa: F401,E402
+from .model import (YOLOV3, YOLOV3T, YOLOV3NoBackbone, YOLOV3_noback, YOLOV3Window, YOLOV3Hier, YOLOV3HierConv, YOLOV3NoBackboneWindow, BatchNorm, SyncBatchNorm, yolo3_darknet53,  # noqa: F401,E402
                     yolo3_no_backbone)
 from .trainer import Trainer  # noqa: F401,E402
 from . import parallel  # noqa: F401,E402
@@ -24,6 +24,6 @@ from .metrics import COCODetectionMetric  # noqa: F401,E402
 from .metrics import FrameMApMetric  # noqa: F401,E402
 from .transforms import MixupDetection, MixedClip  # noqa: F401,E402
 
-__all__ = ["yolo3_darknet53", "yolo3_no_backbone", "YOLOV3", "YOLOV3T", "YOLOV3NoBackbone", "YOLOV3_noback", "YOLOV3Window", "YOLOV3Hier", "YOLOV3NoBackboneWindow",
+__all__ = ["yolo3_darknet53", "yolo3_no_backbone", "YOLOV3", "YOLOV3T", "YOLOV3NoBackbone", "YOLOV3_noback", "YOLOV3Window", "YOLOV3Hier", "YOLOV3HierConv", "YOLOV3NoBackboneWindow",
            "BatchNorm", "SyncBatchNorm", "autograd", "Trainer", "parallel", "lr_scheduler", "video", "VideoSession", "window_indices",
            "LRScheduler", "LRSequential", "metrics", "VIDDetectionMetric", "COCODetectionMetric", "FrameMApMetric", "MixupDetection", "MixedClip"]

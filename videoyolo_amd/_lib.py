@@ -10,6 +10,7 @@ VY_MAX_TOPK = 1024
 VY_CONV_EXACT_FP32, VY_CONV_SPLIT_BF16X3, VY_CONV_SPLIT_BF16X3_TRAIN = 0, 1, 2
 VY_TAP_Z, VY_TAP_BN, VY_TAP_GRAD_PADDED, VY_TAP_INPUT_PADDED = 0, 1, 2, 3
 VY_JOIN_MAX, VY_JOIN_MEAN = 0, 1
+VY_HJOIN_MAX, VY_HJOIN_CONV = 0, 1
 VY_VIDEO_TABLE_MAX = 512
 
 
@@ -126,6 +127,7 @@ SIGNATURES.update({
     "vy_net_window": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     # hierarchical nets: frames max-pooled by threes inside the backbone (yolo3_darknet53 with new_model / hierarchical)
     "vy_net_create_hier": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(_vp)]),
+    "vy_net_create_hier_join": (ctypes.c_int, [_i32, _i32, _i32, ctypes.POINTER(_vp)]),  # ... or joined by a learned conv
     "vy_net_hier": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "vy_net_tap_frames": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.POINTER(_i32)]),
     # windowed heads-only nets: a bank of stored per-frame routes and a (B, k) table (yolo3_no_backbone with k > 1)

@@ -262,6 +262,31 @@ hipError_t vy_launch_hier_pool(const HierPoolArgs& a, hipStream_t s);
 // backward: gsrc frame 3n + t = gdst frame n where src == dst, +0 elsewhere
 hipError_t vy_launch_hier_pool_bwd(const HierPoolArgs& a, hipStream_t s);
 
+// ---- the learned join of a hierarchical net (hier.hip; `_conv1d`, layers.py:50-60): in place of the max, a depthwise
+// conv over the three frames of a triple — z[n, c] = fmaf(w[c][2], x[3n + 2, c], fmaf(w[c][1], x[3n + 1, c], w[c][0] *
+// x[3n, c])), the first product rounded on its own — then BatchNorm and LeakyReLU(0.1).  Same planes, grid and lane map as
+// the max (g: its geometry; g.dst / g.d_cs / g.d_co are the pooled plane the inference kernel writes).  C <= 1024.
+struct HierJoinArgs {
+  HierPoolArgs g;
+  const float* w;        // (C, 3): channel c, frame t at w[3 * c + t]
+  const float* scale;    // inference: the folded BatchNorm affine, per channel
+  const float* shift;
+  float* z;              // training: the join's z plane (g.frames, H + 2, W + 2, C) — raw: written; backward: dz, read
+  double* partials;      // training: one row per block, in block order (x fastest, then y, then z) — raw: [2][C] sums
+                         // of z and z^2; backward: [C][3] sums of x_t * dz
+};
+// blocks (= partial rows) of a training launch
+inline long long vy_hier_join_blocks(int frames, int H, int W, int C) {
+  return (((long long)W * (C / 4) + 255) / 256) * H * frames;
+}
+// inference: dst = leaky(fmaf(z, scale, shift)), interiors and channels [d_co, d_co + C) only
+hipError_t vy_launch_hier_join(const HierJoinArgs& a, hipStream_t s);
+// training forward: z into its plane (interior only) and the per-block statistics rows vy_launch_bn_reduce_finalize reads
+hipError_t vy_launch_hier_join_raw(const HierJoinArgs& a, hipStream_t s);
+// backward: gsrc frame 3n + t = w[c][t] * dz (written, never accumulated, interior only) and the per-block rows of
+// dw[c][t] = sum x_t * dz in double, for vy_launch_reduce_partials_f64
+hipError_t vy_launch_hier_join_bwd(const HierJoinArgs& a, hipStream_t s);
+
 // ---- per-frame route ring of a video plan (video.hip): the three routes of single frames, kept in R slots and pooled by
 // window.  A slot is the three routes back to back, tight NHWC without borders (only ring_pool and the test tap read it):
 // route i of slot s starts at ring + s * slot_stride (+ the sizes of the routes before it).  Frame -> slot and clip -> slots

@@ -39,9 +39,11 @@ static int check_create(int32_t num_class, vy_net** out) {
   if (num_class < 1 || num_class > 1000) return fail(VY_ERR_INVALID, "num_class %d out of range", num_class);
   return 0;
 }
-static vy_net* create(int32_t num_class, bool heads_only, int32_t k, int32_t join, int32_t hier_n = 0) {
+static vy_net* create(int32_t num_class, bool heads_only, int32_t k, int32_t join, int32_t hier_n = 0,
+                      int32_t hier_join = VY_HJOIN_MAX) {
   vy_net* n = new vy_net();
   n->hier_n = hier_n;
+  n->hier_join = hier_join;
   n->num_class = num_class;
   n->knobs = vy_knobs_read();
   n->heads_only = heads_only;
@@ -110,12 +112,18 @@ int vy_net_window(const vy_net* net, int32_t* k, int32_t* join) {
   return 0;
 }
 
-int vy_net_create_hier(int32_t num_class, int32_t n_pools, vy_net** out) {
+int vy_net_create_hier_join(int32_t num_class, int32_t n_pools, int32_t join, vy_net** out) {
   VY_TRY(check_create(num_class, out));
   if (n_pools < 1 || n_pools > 4)
     return fail(VY_ERR_INVALID, "n_pools = %d: a hierarchical net pools 1 ... 4 times (0: vy_net_create)", n_pools);
-  *out = create(num_class, false, 0, 0, n_pools);
+  if (join != VY_HJOIN_MAX && join != VY_HJOIN_CONV)
+    return fail(VY_ERR_INVALID, "join %d: VY_HJOIN_MAX (%d) or VY_HJOIN_CONV (%d)", join, VY_HJOIN_MAX, VY_HJOIN_CONV);
+  *out = create(num_class, false, 0, 0, n_pools, join);
   return 0;
+}
+
+int vy_net_create_hier(int32_t num_class, int32_t n_pools, vy_net** out) {
+  return vy_net_create_hier_join(num_class, n_pools, VY_HJOIN_MAX, out);
 }
 
 int vy_net_hier(const vy_net* net, int32_t* n_pools, int32_t* frames) {

@@ -226,9 +226,18 @@ struct vy_net {
   // plane of a third of the frames, which that conv reads.  From the last pool on it is the single-frame net on B clips.
   // The conv list and the parameter table are the single-frame net's; only planes and their fm differ
   int hier_n = 0;  // pools, 1..4; 0: not a hierarchical net
+  // vy_net_create_hier_join: how the triples are joined, VY_HJOIN_MAX or VY_HJOIN_CONV (h_join_type 'conv': `_conv1d`,
+  // layers.py:50-60 — a depthwise 3-tap filter over the frames, BatchNorm, LeakyReLU).  The conv join has parameters of its
+  // own, "hjoin.<i>.0.weight" (C, 3) and the four BatchNorm tensors "hjoin.<i>.1.*", appended BEHIND the single-frame net's
+  // table, which stays a prefix of this one; the conv list is still the single-frame net's: a join is not a ConvT
+  int hier_join = VY_HJOIN_MAX;
   struct HierPool {
     int src, dst, dst_co, C;  // pre-pool plane (its C channels at 0) -> channels [dst_co, dst_co + C) of the pooled plane
     int conv;                 // the stride-2 conv that reads the pooled plane: the pool runs in front of it
+    int join = VY_HJOIN_MAX;  // the net's hier_join
+    // VY_HJOIN_CONV: parameter indices and the folded-BatchNorm scratch (element offsets), as a ConvT's
+    int p_weight = -1, p_gamma = -1, p_beta = -1, p_mean = -1, p_var = -1;
+    int64_t scale_off = -1, shift_off = -1;
   };
   std::vector<HierPool> hpools;
   int hier_frames() const {
@@ -260,6 +269,17 @@ struct vy_net {
     a.d_cs = dp.C;
     a.d_co = hp.dst_co;
     return a;
+  }
+  // one launch of a conv join: inference (grads == nullptr; z and partials stay null) or a training launch, whose z plane and
+  // partial rows train.hip adds
+  HierJoinArgs join_args(const HierPool& hp, float* grads) const {
+    HierJoinArgs j;
+    memset(&j, 0, sizeof j);
+    j.g = hier_args(hp, grads);
+    j.w = dev_params + params[hp.p_weight].info.offset;
+    j.scale = dev_params + hp.scale_off;
+    j.shift = dev_params + hp.shift_off;
+    return j;
   }
 
   // frames a stem / stage plane of a window net holds for `b` clips: b*k of the clip plan, `frames` of a video plan
@@ -422,6 +442,7 @@ struct vy_net {
         hp.src = cur;
         hp.C = chans[st];
         hp.conv = (int)convs.size();
+        hp.join = hier_join;
         if (st == 3) {  // the fourth pooled plane is route 0: straight into the place a single-frame backbone writes it
           hp.dst = cat2;
           hp.dst_co = 128;
@@ -501,6 +522,19 @@ struct vy_net {
       x_c = planes[cat].C;
     }
     while (n_backbone < (int)convs.size() && params[convs[n_backbone].p_weight].info.backbone) ++n_backbone;
+    // the conv joins' tensors, behind the last single-frame parameter: a `_conv2d` cell's five, part of the backbone
+    // (wrappers.py:50-52 freezes d_model whole).  Library shape (C, 3): the reference's (C, 1, 3, 1, 1)
+    for (size_t i = 0; i < hpools.size(); ++i) {
+      HierPool& hp = hpools[i];
+      if (hp.join != VY_HJOIN_CONV) continue;
+      const std::string pre = "hjoin." + std::to_string(i);
+      const int wshape[2] = {hp.C, 3}, cshape[1] = {hp.C};
+      hp.p_weight = add_param(pre + ".0.weight", VY_P_WEIGHT, 2, wshape, 1, 1);
+      hp.p_gamma = add_param(pre + ".1.gamma", VY_P_GAMMA, 1, cshape, 1, 1);
+      hp.p_beta = add_param(pre + ".1.beta", VY_P_BETA, 1, cshape, 1, 1);
+      hp.p_mean = add_param(pre + ".1.running_mean", VY_P_RUNNING_MEAN, 1, cshape, 0, 1);
+      hp.p_var = add_param(pre + ".1.running_var", VY_P_RUNNING_VAR, 1, cshape, 0, 1);
+    }
     tensor_elems = param_elems;
     // folded-BN scratch behind the tensors
     for (auto& c : convs) {
@@ -517,6 +551,23 @@ struct vy_net {
       f.scale = c.scale_off;
       f.shift = c.shift_off;
       f.C = c.cout;
+      f.pad = 0;
+      folds.push_back(f);
+    }
+    for (HierPool& hp : hpools) {  // ... and the joins' BatchNorms behind the cells' (folds[0] stays the stem's)
+      if (hp.join != VY_HJOIN_CONV) continue;
+      hp.scale_off = param_elems;
+      param_elems += (hp.C + 63) & ~63;
+      hp.shift_off = param_elems;
+      param_elems += (hp.C + 63) & ~63;
+      FoldDesc f;
+      f.gamma = params[hp.p_gamma].info.offset;
+      f.beta = params[hp.p_beta].info.offset;
+      f.mean = params[hp.p_mean].info.offset;
+      f.var = params[hp.p_var].info.offset;
+      f.scale = hp.scale_off;
+      f.shift = hp.shift_off;
+      f.C = hp.C;
       f.pad = 0;
       folds.push_back(f);
     }
@@ -589,13 +640,16 @@ struct vy_net {
     return slot;
   }
 
+  // what join `i` of a hierarchical net is called: as a tap, a launch label and in the region table
+  std::string join_name(int i) const { return (hier_join == VY_HJOIN_CONV ? "hjoin." : "hpool.") + std::to_string(i); }
+
   // what a plane is called in the region table: the first cell that writes it, else the pool of a hierarchical net that
   // does, else the route that is imported / pooled into it
   std::string plane_name(int p) const {
     for (const ConvT& c : convs)
       if (c.out_plane == p) return c.name;
     for (size_t i = 0; i < hpools.size(); ++i)
-      if (hpools[i].dst == p) return "hpool." + std::to_string(i);
+      if (hpools[i].dst == p) return join_name((int)i);
     for (int i = 0; i < 3; ++i)
       if (routes[i].plane == p) return "route." + std::to_string(i);
     return "plane." + std::to_string(p);
@@ -997,13 +1051,20 @@ struct vy_net {
     HOOKED(hook, "window_pool", 0.0, 0.0, vy_launch_window_pool(pool_args(nullptr), s));
     return 0;
   }
-  // hierarchical nets: pool `i`, in front of the conv that reads the pooled plane
+  // hierarchical nets: join `i` — the max, or the conv join with its folded BatchNorm — in front of the conv that reads the
+  // pooled plane
   template <typename Hook>
   int hier_pool(int i, hipStream_t s, Hook& hook) {
     const HierPoolArgs a = hier_args(hpools[i], nullptr);
+    const double by = 16.0 * a.frames * a.H * a.W * a.C;  // three reads, one write, either join
     char nm[16];
+    if (hpools[i].join == VY_HJOIN_CONV) {
+      snprintf(nm, sizeof nm, "hjoin.%d", i);
+      HOOKED(hook, nm, 6.0 * a.frames * a.H * a.W * a.C, by, vy_launch_hier_join(join_args(hpools[i], nullptr), s));
+      return 0;
+    }
     snprintf(nm, sizeof nm, "hpool.%d", i);
-    HOOKED(hook, nm, 0.0, 16.0 * a.frames * a.H * a.W * a.C, vy_launch_hier_pool(a, s));
+    HOOKED(hook, nm, 0.0, by, vy_launch_hier_pool(a, s));
     return 0;
   }
   // the backbone: the stem and stage cells, with the pools of a hierarchical net between the groups they separate
@@ -1124,12 +1185,12 @@ inline int vy_check_bank(const vy_net* net, const char* entry, const BankRef& ba
 
 // ---- what a tap name means, for every entry that takes one (vy_net_tap_frames, vy_net_read_activation; train.hip:
 // vy_net_read_grad_activation, vy_net_read_train_tap): channels [co, co + C) of `plane`.  A cell's name is its output
-// (conv: its index); "hpool.<i>" the plane pool i of a hierarchical net writes (hpool: i); "pool.<i>" pooled route i of
-// either window kind.  The frames the tap holds are the plane's, whatever it names: planes[plane].fm per batch entry,
+// (conv: its index); "hpool.<i>" the plane pool i of a hierarchical net writes (hpool: i) — "hjoin.<i>" on a net with the
+// conv join, which has no "hpool.*" as a max net has no "hjoin.*"; "pool.<i>" pooled route i of either window kind.  The frames the tap holds are the plane's, whatever it names: planes[plane].fm per batch entry,
 // plane_batch(plane) in the bound plan
 struct TapRef {
   int plane, co, C;
-  int conv, hpool;  // -1: not a cell / not a pooled plane of a hierarchical net
+  int conv, hpool;  // -1: not a cell / not a pooled plane of a hierarchical net (either join: vy_net::hier_join says which)
 };
 // VY_ERR_INVALID if the net has no such tap
 inline int vy_resolve_tap(const vy_net* net, const char* name, TapRef* t) {
@@ -1137,7 +1198,7 @@ inline int vy_resolve_tap(const vy_net* net, const char* name, TapRef* t) {
     const size_t len = strlen(prefix);
     return strncmp(name, prefix, len) == 0 && name[len] >= '0' && name[len] < '0' + n && !name[len + 1] ? name[len] - '0' : -1;
   };
-  if (const int i = index("hpool.", net->hier_n); i >= 0) {
+  if (const int i = index(net->hier_join == VY_HJOIN_CONV ? "hjoin." : "hpool.", net->hier_n); i >= 0) {
     const vy_net::HierPool& hp = net->hpools[i];
     *t = {hp.dst, hp.dst_co, hp.C, -1, i};
     return 0;

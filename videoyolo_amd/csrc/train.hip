@@ -38,6 +38,16 @@ struct TrainCell {
   int bucket = 0;             // gradient bucket: 0 heads, 1 stages.2, 2 stages.1, 3 stages.0
 };
 
+// One conv join of a hierarchical net at the planned shape (vy_net::HierPool with VY_HJOIN_CONV): the geometry of its pooled
+// plane, and its z plane, saved statistics and partial rows — regions like a cell's
+struct TrainJoin {
+  int B = 0, H = 0, W = 0;  // pooled frames (b * fm) and their size
+  long long M = 0;          // B * H * W pooled positions: the BatchNorm's count
+  size_t z_off = 0;         // float offset of its z plane (B, H + 2, W + 2, C) in the z region
+  size_t save_off = 0;      // float offset of its saved [mean | invstd] rows in the save region
+  int blocks = 0;           // blocks = partial rows of its training launches (vy_hier_join_blocks)
+};
+
 struct TrainPlan {
   int B = 0, H = 0, W = 0;
   // vy_net::commits when vy_net_bind_train committed the inference plan these regions lie behind — 0: none; any later
@@ -47,6 +57,7 @@ struct TrainPlan {
   size_t dsplit_off = 0, g_off = 0, z_off = 0, save_off = 0, coef_off = 0, sums_off = 0, slice_off = 0, part_off = 0;
   size_t slab_off = 0, loss_part_off = 0, loss_off = 0, zero_off = 0, sdesc_off = 0, seg_off = 0, chunk_off = 0, total = 0;
   std::vector<TrainCell> cells;  // per conv
+  std::vector<TrainJoin> joins;  // per conv join of a hierarchical net (none otherwise)
   // all image sets (forward + data gradient) for the one-launch rebuild
   std::vector<SplitDesc> sdesc;
   long long sdesc_total = 0;
@@ -54,6 +65,8 @@ struct TrainPlan {
   std::vector<int32_t> chunk_seg;
   // gradient buckets (contiguous parameter ranges, by TrainCell::bucket): first element, length (0: no such bucket)
   int64_t bucket_lo[4] = {0, 0, 0, 0}, bucket_len[4] = {0, 0, 0, 0};
+  // the conv joins' parameters lie behind the heads': a second range of the stages.0 bucket (0: no conv join)
+  int64_t join_lo = 0, join_len = 0;
 };
 
 struct BwdDgrad {
@@ -282,8 +295,32 @@ TrainPlan plan_train(const vy_net& net, const VyTrain& opt, const NetPlan& fwd, 
       slab = std::max(slab, (size_t)cell.splits * c.cout * Ntot);
     }
   }
+  // the conv joins of a hierarchical net, behind the cells: z of the pooled plane's geometry (border included), saved
+  // statistics, and the partial rows of their three passes — statistics [blocks][2][C] and weight gradient [blocks][C][3] in
+  // double, bn_bwd_reduce's [chunks][2][C] floats
+  std::vector<size_t> jz_used;
+  for (const vy_net::HierPool& hp : net.hpools) {
+    if (hp.join != VY_HJOIN_CONV) continue;
+    const PlaneT& dp = net.planes[hp.dst];
+    TrainJoin j;
+    j.B = b * dp.fm;
+    j.H = h / dp.div;
+    j.W = w / dp.div;
+    j.M = (long long)j.B * j.H * j.W;
+    j.blocks = (int)vy_hier_join_blocks(j.B, j.H, j.W, hp.C);
+    j.z_off = zfl;
+    jz_used.push_back((size_t)j.B * (j.H + 2) * (j.W + 2) * hp.C * sizeof(float));
+    zfl += vy_net::al(jz_used.back()) / sizeof(float) + gap_fl;
+    j.save_off = sfl;
+    sfl += 2 * (size_t)((hp.C + 63) & ~63);
+    const int rpc = vy_bn_bwd_rows_per_chunk(j.B, j.H, hp.C);
+    part = std::max(part, 2 * (size_t)j.blocks * 3 * hp.C);  // (doubles: 3 columns per channel cover the forward's 2)
+    part = std::max(part, (size_t)(((long long)j.B * j.H + rpc - 1) / rpc) * 2 * hp.C);
+    p.joins.push_back(j);
+  }
   p.z_off = ws.off;
   for (size_t i = 0; i < n; ++i) ws.take(z_used[i], "z", net.convs[i].name);  // (cell.z_off: the same walk, above)
+  for (size_t i = 0; i < jz_used.size(); ++i) ws.take(jz_used[i], "z", net.join_name((int)i));
   p.save_off = ws.take(sfl * sizeof(float), "train.save");
   p.coef_off = ws.take(3 * 1024 * sizeof(float), "train.coef");
   p.sums_off = ws.take(2 * 2 * 1024 * sizeof(double), "train.sums");  // [global | local] x [2][C]
@@ -338,6 +375,11 @@ TrainPlan plan_train(const vy_net& net, const VyTrain& opt, const NetPlan& fwd, 
       hi[cell.bucket] = std::max(hi[cell.bucket], pi.offset + ((pi.size + 63) & ~(int64_t)63));
     }
   }
+  if (!p.joins.empty()) {  // (appended in order: the first join's weight ... the last join's running_var)
+    const vy_param_info &first = net.params[net.hpools.front().p_weight].info, &last = net.params[net.hpools.back().p_var].info;
+    p.join_lo = first.offset;
+    p.join_len = last.offset + ((last.size + 63) & ~(int64_t)63) - first.offset;
+  }
   for (int k = 0; k < 4; ++k)
     if (hi[k] > lo[k]) {
       p.bucket_lo[k] = lo[k];
@@ -371,6 +413,15 @@ struct TrainCtx {
   float* slabs() const { return at<float>(p.slab_off); }
   float* param(int pidx) const { return net->dev_params + net->params[pidx].info.offset; }
   float* grad_of(int pidx) const { return t->grads + net->params[pidx].info.offset; }
+  // conv join i: its plan record, z plane and BatchNorm state
+  const TrainJoin& join(int i) const { return p.joins[i]; }
+  float* join_z(int i) const { return at<float>(p.z_off) + p.joins[i].z_off; }
+  BnViews join_bn(int i) const {
+    const vy_net::HierPool& hp = net->hpools[i];
+    float* save = at<float>(p.save_off) + p.joins[i].save_off;
+    return {param(hp.p_gamma), param(hp.p_beta), param(hp.p_mean), param(hp.p_var), net->dev_params + hp.scale_off,
+            net->dev_params + hp.shift_off, save, save + ((hp.C + 63) & ~63)};
+  }
   BnViews bn_views(int ci) const {
     const ConvT& cv = net->convs[ci];
     float* save = at<float>(p.save_off) + p.cells[ci].save_off;
@@ -479,18 +530,11 @@ int raw_conv(const TrainCtx& c, int ci, const float* x, int* n_part) {
   return 0;
 }
 
-// statistics -> scale / shift, running and saved statistics; then the apply pass from z into the cell's output view
-int bn_forward(const TrainCtx& c, int ci, int n_part) {
-  vy_net* net = c.net;
-  const ConvT& cv = net->convs[ci];
-  const TrainCell& cell = c.cell(ci);
-  const BnViews bn = c.bn_views(ci);
-  const int C = cv.cout;
-  const double* parts = reinterpret_cast<const double*>(c.partials());
+// the finalize of a train-mode BatchNorm over `count` samples, a cell's or a conv join's (sums: null — the partial rows)
+BnFinalizeArgs finalize_args(const vy_net* net, const BnViews& bn, int C, double count) {
   BnFinalizeArgs f;
-  f.count = (double)cell.M;
-  VY_TRY(combine_sums(c, cv, 2 * C, [&] { return vy_launch_reduce_partials_f64(parts, n_part, 2 * C, c.sums_local(), c.s); },
-                      &f.count, &f.sums));
+  f.sums = nullptr;
+  f.count = count;
   f.gamma = bn.gamma;
   f.beta = bn.beta;
   f.running_mean = bn.running_mean;
@@ -501,8 +545,22 @@ int bn_forward(const TrainCtx& c, int ci, int n_part) {
   f.save_invstd = bn.save_invstd;
   f.C = C;
   f.eps = 1e-5f;
-  f.momentum = 0.9f;  // layers.py:68
+  f.momentum = 0.9f;  // layers.py:68 (and :57, the join's)
   f.var_unbiased = net->sem.bn_running_var_unbiased;  // vy_net_set_semantics: read at every launch
+  return f;
+}
+
+// statistics -> scale / shift, running and saved statistics; then the apply pass from z into the cell's output view
+int bn_forward(const TrainCtx& c, int ci, int n_part) {
+  vy_net* net = c.net;
+  const ConvT& cv = net->convs[ci];
+  const TrainCell& cell = c.cell(ci);
+  const BnViews bn = c.bn_views(ci);
+  const int C = cv.cout;
+  const double* parts = reinterpret_cast<const double*>(c.partials());
+  BnFinalizeArgs f = finalize_args(net, bn, C, (double)cell.M);
+  VY_TRY(combine_sums(c, cv, 2 * C, [&] { return vy_launch_reduce_partials_f64(parts, n_part, 2 * C, c.sums_local(), c.s); },
+                      &f.count, &f.sums));
   if (f.sums)
     HIP_TRY(vy_launch_bn_finalize(f, c.s));
   else if (!(train_abl(net) & 128))  // (128: the finalize launch of the forward statistics skipped)
@@ -545,6 +603,40 @@ int train_cells(const TrainCtx& c, int first, int last, const float* x) {
   return 0;
 }
 
+// join `i` of a hierarchical net in recording mode.  The max is the inference launch.  The conv join: z and its per-block
+// statistics rows, then the finalize and the apply pass every cell uses, into the pooled plane's channels — its BatchNorm is
+// never a synchronised one (`_conv1d` is called without norm_layer), so the ranks exchange nothing here
+int train_join(const TrainCtx& c, int i) {
+  vy_net* net = c.net;
+  const vy_net::HierPool& hp = net->hpools[i];
+  if (hp.join != VY_HJOIN_CONV) return net->hier_pool(i, c.s, plain);
+  const TrainJoin& jn = c.join(i);
+  const BnViews bn = c.join_bn(i);
+  HierJoinArgs j = net->join_args(hp, nullptr);
+  j.z = c.join_z(i);
+  j.partials = reinterpret_cast<double*>(c.partials());
+  HIP_TRY(vy_launch_hier_join_raw(j, c.s));
+  const BnFinalizeArgs f = finalize_args(net, bn, hp.C, (double)jn.M);
+  HIP_TRY(vy_launch_bn_reduce_finalize(j.partials, jn.blocks, f, c.slice_sums(), c.s));
+  BnApplyArgs ap;
+  memset(&ap, 0, sizeof ap);
+  ap.z = j.z;
+  ap.scale = bn.scale;
+  ap.shift = bn.shift;
+  ap.out = net->plane_ptr(hp.dst);
+  ap.B = jn.B;
+  ap.H = jn.H;
+  ap.W = jn.W;
+  ap.C = hp.C;
+  ap.o_Hp = jn.H + 2;
+  ap.o_Wp = jn.W + 2;
+  ap.o_cs = net->planes[hp.dst].C;
+  ap.o_co = hp.dst_co;
+  ap.ups = 1;
+  HIP_TRY(vy_launch_bn_apply(ap, c.s));
+  return 0;
+}
+
 // routes (heads-only nets): the three route tensors, imported into their planes in front of the first conv; bank (windowed
 // heads-only nets): each clip's frames of the bank, pooled into the same planes
 int forward_train(const TrainCtx& c, const float* x, const float* const* routes, const BankRef* bank = nullptr) {
@@ -555,7 +647,7 @@ int forward_train(const TrainCtx& c, const float* x, const float* const* routes,
   int first = 0;
   for (int i = 0; i < (int)net->hpools.size(); ++i) {  // a hierarchical net: the pool in front of the conv that reads it
     VY_TRY(train_cells(c, first, net->hpools[i].conv, x));
-    VY_TRY(net->hier_pool(i, c.s, plain));
+    VY_TRY(train_join(c, i));
     first = net->hpools[i].conv;
   }
   VY_TRY(train_cells(c, first, net->n_backbone, x));
@@ -829,6 +921,57 @@ int data_grad(const TrainCtx& c, int ci, DzView dz, BwdState& st) {
   return 0;
 }
 
+// The backward of conv join `i`, from the complete gradient of its pooled plane (the caller has checked that): the
+// BatchNorm + leaky backward of every cell on the join's z plane (dz overwrites z; dgamma, dbeta), then hier_join_bwd — the
+// three frames' gradients WRITTEN into the pre-pool gradient plane, and dw through its per-block rows and the ordered
+// column sum, in double, rounded to fp32 once.  All on the main stream: partials() and sums_local() are its scratch
+int join_backward(const TrainCtx& c, int i) {
+  vy_net* net = c.net;
+  const vy_net::HierPool& hp = net->hpools[i];
+  const TrainJoin& jn = c.join(i);
+  const BnViews bn = c.join_bn(i);
+  BnBwdArgs bb;
+  memset(&bb, 0, sizeof bb);
+  bb.g = c.gplane(hp.dst);
+  bb.z = c.join_z(i);
+  bb.scale = bn.scale;
+  bb.shift = bn.shift;
+  bb.save_mean = bn.save_mean;
+  bb.save_invstd = bn.save_invstd;
+  bb.coef = c.coef();
+  bb.partials = c.partials();
+  bb.B = jn.B;
+  bb.H = jn.H;
+  bb.W = jn.W;
+  bb.C = hp.C;
+  bb.g_Hp = jn.H + 2;
+  bb.g_Wp = jn.W + 2;
+  bb.g_cs = net->planes[hp.dst].C;
+  bb.g_co = hp.dst_co;
+  bb.ups = 1;
+  bb.chunk = vy_bn_bwd_rows_per_chunk(jn.B, jn.H, hp.C);
+  HIP_TRY(vy_launch_bn_bwd_reduce(bb, c.s));
+  BnBwdFinalizeArgs f;
+  memset(&f, 0, sizeof f);
+  f.count = (double)jn.M;
+  f.local_sums = c.sums_local();
+  f.gamma = bn.gamma;
+  f.save_invstd = bn.save_invstd;
+  f.dgamma = c.grad_of(hp.p_gamma);
+  f.dbeta = c.grad_of(hp.p_beta);
+  f.coef = c.coef();
+  f.C = hp.C;
+  HIP_TRY(vy_launch_bn_bwd_reduce_finalize(c.partials(), vy_bn_bwd_chunks(bb), f, c.s));
+  HIP_TRY(vy_launch_bn_bwd_apply(bb, c.s));
+  HierJoinArgs j = net->join_args(hp, c.gplanes());
+  j.z = bb.z;
+  j.partials = reinterpret_cast<double*>(c.partials());
+  HIP_TRY(vy_launch_hier_join_bwd(j, c.s));
+  HIP_TRY(vy_launch_reduce_partials_f64(j.partials, jn.blocks, 3 * hp.C, c.sums_local(), c.s));
+  HIP_TRY(vy_launch_f64_to_f32(c.sums_local(), c.grad_of(hp.p_weight), 3 * hp.C, c.s));
+  return 0;
+}
+
 // the main stream waits for the weight gradients launched so far
 int join_side(const TrainCtx& c) {
   if (!c.t->side) return 0;
@@ -844,6 +987,9 @@ int emit_bucket(const TrainCtx& c, int bk) {
   if (c.p.bucket_len[bk] == 0) return 0;
   if (int rc = c.t->gb_cb(c.t->gb_user, c.p.bucket_lo[bk], c.p.bucket_len[bk]))
     return fail(VY_ERR_STATE, "gradient bucket callback failed (%d)", rc);
+  if (bk == 3 && c.p.join_len)  // the conv joins of a hierarchical net: stages.0's, in a range of their own behind the heads
+    if (int rc = c.t->gb_cb(c.t->gb_user, c.p.join_lo, c.p.join_len))
+      return fail(VY_ERR_STATE, "gradient bucket callback failed (%d)", rc);
   return 0;
 }
 
@@ -865,7 +1011,10 @@ int backward_cells(const TrainCtx& c, BwdState& st, int first, int last, const f
       // gradient, which the producer in front reads as its output gradient
       if (st.covered(hp.dst, hp.dst_co, hp.dst_co + hp.C) != 1)
         return fail(VY_ERR_STATE, "internal: gradient of the pooled plane in front of '%s' was never produced", cv.name.c_str());
-      HIP_TRY(vy_launch_hier_pool_bwd(c.net->hier_args(hp, c.gplanes()), c.s));
+      if (hp.join == VY_HJOIN_CONV)
+        VY_TRY(join_backward(c, (int)(&hp - c.net->hpools.data())));
+      else
+        HIP_TRY(vy_launch_hier_pool_bwd(c.net->hier_args(hp, c.gplanes()), c.s));
       st.touched[hp.src].push_back({0, hp.C});
     }
     if (ci == 0 || c.cell(ci - 1).bucket != c.cell(ci).bucket) VY_TRY(emit_bucket(c, c.cell(ci).bucket));
@@ -1244,6 +1393,22 @@ int vy_net_read_train_tap(vy_net* net, const char* name, int32_t which, float* d
   VY_TRY(vy_resolve_tap(net, name, &t));
   if (t.hpool >= 0) {  // a pooled plane: its gradient, or the pre-pool plane it was made of
     const vy_net::HierPool& hp = net->hpools[t.hpool];
+    if (hp.join == VY_HJOIN_CONV && (which == VY_TAP_Z || which == VY_TAP_BN)) {  // a conv join: z / dz and BatchNorm, as a cell's
+      const TrainJoin& jn = c.join(t.hpool);
+      const bool z = which == VY_TAP_Z;
+      const int32_t d[4] = {z ? jn.B : 4, hp.C, z ? jn.H + 2 : 1, z ? jn.W + 2 : 1};
+      if (dims) memcpy(dims, d, sizeof d);
+      if (!dst_dev) return 0;
+      if (z) {
+        HIP_TRY(vy_launch_padded_plane_to_nchw(c.join_z(t.hpool), d[0], d[2], d[3], hp.C, 0, hp.C, dst_dev, c.s));
+        return 0;
+      }
+      const BnViews v = c.join_bn(t.hpool);
+      const float* rows[4] = {v.save_mean, v.save_invstd, v.scale, v.shift};
+      for (int r = 0; r < 4; ++r)
+        HIP_TRY(hipMemcpyAsync(dst_dev + (size_t)r * hp.C, rows[r], sizeof(float) * hp.C, hipMemcpyDeviceToDevice, c.s));
+      return 0;
+    }
     if (which != VY_TAP_GRAD_PADDED && which != VY_TAP_INPUT_PADDED)
       return fail(VY_ERR_INVALID, "'%s' has the taps VY_TAP_GRAD_PADDED and VY_TAP_INPUT_PADDED only", name);
     const bool grad = which == VY_TAP_GRAD_PADDED;

@@ -1312,6 +1312,68 @@ class YOLOV3Hier(_ClipNet):
         "not available on a hierarchical net (yolo3_darknet53 with hierarchical=...): use a single-frame net")
 
 
+class YOLOV3HierConv(YOLOV3Hier):
+    """The hierarchical net with the reference's learned join, ``h_join_type='conv'`` (``_conv1d``, layers.py:50-60;
+    h_darknet.py:97-101, 116-119): where ``YOLOV3Hier`` takes the max of a triple of frames, this net applies, per channel,
+    a 3-tap filter over the triple, ``z = w[c,0] x_0 + w[c,1] x_1 + w[c,2] x_2`` (Conv3D (3,1,1), groups = C, no bias), then
+    BatchNorm (train mode: statistics over the ``B * frames * H * W`` pooled positions; never a synchronised one) and
+    LeakyReLU(0.1).  Constructed directly — ``YOLOV3HierConv(classes, hierarchical=[3,3,1,1,1])`` — because
+    ``yolo3_darknet53(..., h_join_type='conv')`` still raises.
+
+    Join ``i`` (C = 32, 64, 128, 256) has five tensors of its own behind the single-frame net's: ``hjoin.<i>.0.weight`` of
+    shape (C, 3) and ``hjoin.<i>.1.gamma / beta / running_mean / running_var``, part of the backbone (``freeze_base``
+    freezes them).  ``load_parameters`` / ``set_parameters`` also take the weight as the reference's (C, 1, 3, 1, 1) and the
+    keys as ``d_model.convs1d.<i>.<rest>`` [UPSTREAM-RECALLED: no such file was at hand to verify it]; a single-frame file
+    has no join keys and loads with ``allow_missing=True`` only, the joins keeping their values.
+
+    ``initialize()`` gives the joins the reference's values: the weight is ZEROS (``weight_initializer='zeros'``), gamma 1,
+    beta 0, running mean 0, running variance 1.  With zero weights every pooled plane is the constant ``leaky(beta)``
+    whatever the frames hold, and only the gradient of the join weights carries information through a join at first: that
+    is the reference's choice.  A mean start is ``set_data(np.full((C, 3), 1 / 3))`` on each ``hjoin.<i>.0.weight``.  The
+    'synthetic' initializer, a variance-preserving net for benchmarks and parity tests, starts them at 1/3."""
+
+    h_join_type = "conv"
+    _JOIN_RE = re.compile(r"^d_model\.convs1d\.(\d)\.")
+
+    def _create_handle(self, num_class, out):
+        return self._lib.vy_net_create_hier_join(num_class, self._pools, _lib.VY_HJOIN_CONV, out)
+
+    @classmethod
+    def _key(cls, name):
+        m = cls._JOIN_RE.match(name)
+        return "hjoin.%s.%s" % (m.group(1), name[m.end():]) if m else super()._key(name)
+
+    def initialize(self, init=None, ctx=None, force_reinit=False, seed=None, **kwargs):
+        """As ``YOLOV3.initialize`` for the single-frame tensors; the joins as the class says."""
+        if callable(init) or init not in (None, "uniform", "synthetic"):
+            return super().initialize(init, ctx=ctx, force_reinit=force_reinit, seed=seed, **kwargs)
+
+        def both(table):
+            cells = [(n, s) for n, s in table if not n.startswith("hjoin.")]
+            if init == "synthetic":
+                vals = _init.synthetic_params(cells, 233 if seed is None else seed, **kwargs)
+            else:
+                vals = _init.uniform_params(cells, seed)
+            for n, s in table:
+                if n.startswith("hjoin."):
+                    leaf = n.rsplit(".", 1)[1]
+                    start = {"weight": 1.0 / 3.0 if init == "synthetic" else 0.0, "gamma": 1.0, "running_var": 1.0}
+                    vals[n] = np.full(s, start.get(leaf, 0.0), np.float32)
+            return vals
+
+        return super().initialize(both, ctx=ctx, force_reinit=force_reinit)
+
+    def set_parameters(self, arrays, allow_missing=False, ignore_extra=False):
+        """As ``YOLOV3.set_parameters``; a join weight may come in the reference's shape (C, 1, 3, 1, 1)."""
+        fixed = OrderedDict()
+        for k, v in arrays.items():
+            p = self._params.get(self._key(k))
+            if p is not None and p.name.startswith("hjoin.") and p.kind == "weight" and np.shape(v) == (p.shape[0], 1, 3, 1, 1):
+                v = np.asarray(v, np.float32).reshape(p.shape)
+            fixed[k] = v
+        super().set_parameters(fixed, allow_missing=allow_missing, ignore_extra=ignore_extra)
+
+
 class YOLOV3NoBackboneWindow(_Windowed, YOLOV3NoBackbone):
     """``yolo3_no_backbone(classes, k=k, k_join_type=..., k_join_pos='early')``: the head half of ``YOLOV3Window``, for the
     reference's ``--features_dir --window k`` workflow (datasets/imgnetvid.py:146-174 stacks the k frames' saved routes
@@ -1460,7 +1522,8 @@ def yolo3_darknet53(classes, pretrained_base=True, norm_layer=BatchNorm, norm_kw
 
     Only the arguments that select those paths are honoured; any other temporal / two-stream / hierarchical option
     (``new_model`` alone, a hierarchical list without it, ``h_join_type`` None or 'conv', any other list) raises
-    NotImplementedError naming it (out of scope).
+    NotImplementedError naming it (out of scope).  ``h_join_type='conv'`` IS built, as the class
+    ``YOLOV3HierConv(classes, hierarchical=[3,3,1,1,1], ...)``: this factory does not return it yet.
     ``pretrained_base=True`` cannot be honoured offline (gluoncv model zoo download,
     three_darknet.py:262): it warns and leaves the backbone to ``initialize()`` / ``load_parameters``.
     """
