@@ -349,6 +349,37 @@ int vy_net_video_detect(vy_net* net, const int32_t* table, float* ids, float* sc
  * vy_net_forward_features exports for that frame (extract_base_features.py:120-160). */
 int vy_net_video_read_slot(vy_net* net, int32_t slot, float* f0, float* f1, float* f2, void* stream);
 
+/* Hier-video plans: a hierarchical net (vy_net_create_hier / _hier_join) run over a video, each level once per frame.
+ * detect_yolo3.py --window T,step gives a hierarchical net one T-frame clip per frame too (T = 3^n_pools; the table of the video plans above),
+ * and the clip entries then run the stem T times and pool i's group of cells T / 3^(i+1) times per emitted frame.  Extend
+ * every level to the frame positions u of the video: level 0 at u is the stem on frame clamp(u, 0, N - 1), level L at u the
+ * cells of that group on join(level L-1 at u - d, u, u + d) with d = step * 3^(L-1), operands in that order.  Level n at
+ * u = i is then bit for bit what the clip of frame i gives, clamps included — eval-mode BatchNorm is per frame and a conv's
+ * result does not depend on its batch.  A hier-video plan runs a chunk of `centres` consecutive frames i = a .. a + centres
+ * - 1: with h_L = step * (3^L - 1) / 2, level L is held at the centres + 2 (h_n - h_L) consecutive positions from
+ * a - (h_n - h_L) on, so every join is a dilated triple, dst[p] = join(src[p], src[p + d], src[p + 2d]).  Nothing is kept
+ * between calls: the caller hands every chunk its centres + 2 h_n level-0 frames, clamped where they leave the video.
+ * centres in [1, VY_VIDEO_TABLE_MAX], step in [1, VY_HIER_VIDEO_STEP_MAX].  Every entry: VY_ERR_STATE on a net that is not
+ * hierarchical, doing nothing. */
+#define VY_HIER_VIDEO_STEP_MAX 64
+/* frames_in = centres + 2 h_n = centres + step * (3^n_pools - 1): the frames a vy_net_hier_video_detect call takes. */
+int vy_net_hier_video_frames(const vy_net* net, int32_t centres, int32_t step, int32_t* frames_in);
+/* Bytes of the workspace of a hier-video plan; 0 plus vy_last_error on a request it refuses. */
+size_t vy_net_hier_video_workspace_bytes(const vy_net* net, int32_t centres, int32_t step, int32_t height, int32_t width);
+/* Binds (and zeroes, as vy_net_bind_workspace) a hier-video plan.  The net then serves vy_net_hier_video_detect and the
+ * taps only — vy_net_read_head at batch = centres, vy_net_read_activation each tap with the frames of its level, "hpool.i" /
+ * "hjoin.i" the joined planes as ever — and vy_net_profile_infer, which then times the launches of a
+ * vy_net_hier_video_detect call on its x (the joins under their labels "hpool.i" / "hjoin.i", bytes: the source plane and
+ * the destination once each): vy_net_forward_infer and the training entries return VY_ERR_STATE until
+ * vy_net_bind_workspace / vy_net_bind_train bind a clip plan again, which ends this one.  Like vy_net_bind_workspace it
+ * ends a training plan bound before it. */
+int vy_net_bind_hier_video(vy_net* net, void* dev_ws, size_t bytes, int32_t centres, int32_t step, int32_t height,
+                           int32_t width, void* stream);
+/* One chunk: x (frames_in, 3, height, width), frame j the video's frame clamp(a - h_n + j, 0, N - 1).  Outputs as
+ * vy_net_forward_infer at batch = centres, row-block c the detections of frame a + c.  x is only read.  Asynchronous. */
+int vy_net_hier_video_detect(vy_net* net, const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
+                             void* stream);
+
 /* The detection tail ALONE, on caller-supplied prediction-conv outputs: YOLOOutputV3.hybrid_forward's inference branch
  * (yolo3.py:158-197: decode, x C tile, class-major rows) for the three scales, their concat (yolo3.py:1195), box_nms and
  * the slice (yolo3.py:1197-1206) — what `net.yolo_outputs[i](pred)` + `F.contrib.box_nms` compute in the reference.
@@ -649,7 +680,8 @@ int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, in
 
 /* The regions a plan carves out of the workspace, one per call, in offset order: region `index` of the clip plan
  * (VY_PLAN_CLIP: what vy_net_workspace_bytes sizes; frames, ring ignored), the training plan (VY_PLAN_TRAIN: the clip plan
- * with every plane kept, then the training regions) or the video plan (VY_PLAN_VIDEO: batch counts clips) of the shape.
+ * with every plane kept, then the training regions), the video plan (VY_PLAN_VIDEO: batch counts clips) or the hier-video
+ * plan (VY_PLAN_HIER_VIDEO: batch counts the centres, frames is the step, ring ignored) of the shape.
  * name: the carve — "fold", "det.state" .. "det.score", "sk.flags", "sk.slabs", "ck", "wsplit:<cell>", "wino:<cell>",
  * "plane:<the first cell that writes the slot>", "ring"; "dgrad_image:<cell>", "grad:<plane>", "z:<cell>", "train.save" ..
  * "train.chunk", "wgrad_table:<cell>".  bytes: what the plan means the kernels to use, from offset on; span: the bytes up
@@ -659,7 +691,7 @@ int vy_net_bind_train(vy_net* net, void* dev_ws, size_t bytes, int32_t batch, in
  * binds count them in.  A host-side query like the sizing queries: it needs no device and no bound workspace, plans anew
  * and changes nothing on the handle.  VY_ERR_RANGE for an index past the last region, VY_ERR_INVALID for a shape the
  * matching sizing query refuses.  Tests only. */
-enum vy_plan_kind { VY_PLAN_CLIP = 0, VY_PLAN_TRAIN = 1, VY_PLAN_VIDEO = 2 };
+enum vy_plan_kind { VY_PLAN_CLIP = 0, VY_PLAN_TRAIN = 1, VY_PLAN_VIDEO = 2, VY_PLAN_HIER_VIDEO = 3 };
 typedef struct vy_plan_region {
   char name[96];
   size_t offset, bytes, span;

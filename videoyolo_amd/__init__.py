@@ -15,7 +15,7 @@ from .model import (YOLOV3, YOLOV3T, YOLOV3NoBackbone, YOLOV3_noback, YOLOV3Wind
 from .trainer import Trainer  # noqa: F401,E402
 from . import parallel  # noqa: F401,E402
 from . import video  # noqa: F401,E402
-from .video import VideoSession, window_indices  # noqa: F401,E402
+from .video import VideoSession, hier_detect_video, window_indices  # noqa: F401,E402
 from . import lr_scheduler  # noqa: F401,E402
 from .lr_scheduler import LRScheduler, LRSequential  # noqa: F401,E402
 from . import metrics  # noqa: F401,E402
@@ -25,5 +25,5 @@ from .metrics import FrameMApMetric  # noqa: F401,E402
 from .transforms import MixupDetection, MixedClip  # noqa: F401,E402
 
 __all__ = ["yolo3_darknet53", "yolo3_no_backbone", "YOLOV3", "YOLOV3T", "YOLOV3NoBackbone", "YOLOV3_noback", "YOLOV3Window", "YOLOV3Hier", "YOLOV3HierConv", "YOLOV3NoBackboneWindow",
-           "BatchNorm", "SyncBatchNorm", "autograd", "Trainer", "parallel", "lr_scheduler", "video", "VideoSession", "window_indices",
+           "BatchNorm", "SyncBatchNorm", "autograd", "Trainer", "parallel", "lr_scheduler", "video", "VideoSession", "window_indices", "hier_detect_video",
            "LRScheduler", "LRSequential", "metrics", "VIDDetectionMetric", "COCODetectionMetric", "FrameMApMetric", "MixupDetection", "MixedClip"]

@@ -12,6 +12,7 @@ VY_TAP_Z, VY_TAP_BN, VY_TAP_GRAD_PADDED, VY_TAP_INPUT_PADDED = 0, 1, 2, 3
 VY_JOIN_MAX, VY_JOIN_MEAN = 0, 1
 VY_HJOIN_MAX, VY_HJOIN_CONV = 0, 1
 VY_VIDEO_TABLE_MAX = 512
+VY_HIER_VIDEO_STEP_MAX = 64
 
 
 class VyError(RuntimeError):
@@ -52,7 +53,7 @@ class PlanRegion(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 96), ("offset", ctypes.c_size_t), ("bytes", ctypes.c_size_t), ("span", ctypes.c_size_t)]
 
 
-VY_PLAN_CLIP, VY_PLAN_TRAIN, VY_PLAN_VIDEO = 0, 1, 2
+VY_PLAN_CLIP, VY_PLAN_TRAIN, VY_PLAN_VIDEO, VY_PLAN_HIER_VIDEO = 0, 1, 2, 3
 VY_ERR_RANGE = -5
 
 _vp, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_size_t
@@ -143,6 +144,11 @@ SIGNATURES.update({
     "vy_net_video_push": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i32), _vp]),
     "vy_net_video_detect": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), _vp, _vp, _vp, _vp, _vp]),
     "vy_net_video_read_slot": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    # hier-video plans of a hierarchical net: each level once per frame, the joins dilated (video.hier_detect_video)
+    "vy_net_hier_video_frames": (ctypes.c_int, [_vp, _i32, _i32, ctypes.POINTER(_i32)]),
+    "vy_net_hier_video_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32]),
+    "vy_net_bind_hier_video": (ctypes.c_int, [_vp, _vp, _sz, _i32, _i32, _i32, _i32, _vp]),
+    "vy_net_hier_video_detect": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 })
 
 

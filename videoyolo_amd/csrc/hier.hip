@@ -21,6 +21,11 @@
 // filter over the frames of a triple, then BatchNorm and LeakyReLU.  Inference is one launch (hier_join_kernel: three reads,
 // one write); training writes z and per-block statistics rows (hier_join_raw_kernel) for the BatchNorm kernels every cell
 // uses, and the backward (hier_join_bwd_kernel) writes the three frames' gradients and per-block rows of the weight gradient.
+//
+// Over a whole video (a hier-video plan) consecutive clips share their triples, so both inference joins exist in a dilated
+// form as well — frames p, p + d, p + 2d of one plane — behind the five kernels above, which carry no dilation.
+#include <cstring>
+
 #include "kernels.h"
 #include "../../include/vy_math.h"
 
@@ -43,13 +48,8 @@ __device__ inline bool locate(const HierPoolArgs& a, long long* so, long long* p
   return true;
 }
 
-__global__ __launch_bounds__(256) void hier_pool_kernel(HierPoolArgs a) {
-  long long so, po;
-  if (!locate(a, &so, &po)) return;
-  const long long fstep = a.frame_pixels * a.s_cs;
-  const f32x4 v0 = *reinterpret_cast<const f32x4*>(a.src + so);
-  const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.src + so + fstep);
-  const f32x4 v2 = *reinterpret_cast<const f32x4*>(a.src + so + 2 * fstep);
+// the max of three operands in frame order: strict >, so on ties the earliest operand's bits are kept
+__device__ inline f32x4 max3(const f32x4 v0, const f32x4 v1, const f32x4 v2) {
   f32x4 m = v0;
   if (v1.x > m.x) m.x = v1.x;
   if (v1.y > m.y) m.y = v1.y;
@@ -59,7 +59,17 @@ __global__ __launch_bounds__(256) void hier_pool_kernel(HierPoolArgs a) {
   if (v2.y > m.y) m.y = v2.y;
   if (v2.z > m.z) m.z = v2.z;
   if (v2.w > m.w) m.w = v2.w;
-  *reinterpret_cast<f32x4*>(a.dst + po) = m;
+  return m;
+}
+
+__global__ __launch_bounds__(256) void hier_pool_kernel(HierPoolArgs a) {
+  long long so, po;
+  if (!locate(a, &so, &po)) return;
+  const long long fstep = a.frame_pixels * a.s_cs;
+  const f32x4 v0 = *reinterpret_cast<const f32x4*>(a.src + so);
+  const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.src + so + fstep);
+  const f32x4 v2 = *reinterpret_cast<const f32x4*>(a.src + so + 2 * fstep);
+  *reinterpret_cast<f32x4*>(a.dst + po) = max3(v0, v1, v2);
 }
 
 __device__ inline f32x4 where_equal(const f32x4 v, const f32x4 m, const f32x4 g) {
@@ -117,6 +127,15 @@ __device__ inline f32x4 join_z4(const JoinW& k, const f32x4 v0, const f32x4 v1, 
   z.w = join_z(k.w[0].w, k.w[1].w, k.w[2].w, v0.w, v1.w, v2.w);
   return z;
 }
+// the folded BatchNorm affine and LeakyReLU(0.1) of the inference join
+__device__ inline f32x4 join_apply4(const f32x4 z, const f32x4 sc, const f32x4 sh) {
+  f32x4 y;
+  y.x = vy_leaky(fmaf(z.x, sc.x, sh.x));
+  y.y = vy_leaky(fmaf(z.y, sc.y, sh.y));
+  y.z = vy_leaky(fmaf(z.z, sc.z, sh.z));
+  y.w = vy_leaky(fmaf(z.w, sc.w, sh.w));
+  return y;
+}
 // first channel of the lane's four
 __device__ inline unsigned lane_channel(const HierPoolArgs& a) {
   return 4u * ((blockIdx.x * 256u + threadIdx.x) & ((1u << a.c4_shift) - 1u));
@@ -135,13 +154,86 @@ __global__ __launch_bounds__(256) void hier_join_kernel(HierJoinArgs j) {
   const JoinW k = join_weights(j.w, c);
   const f32x4 sc = *reinterpret_cast<const f32x4*>(j.scale + c);
   const f32x4 sh = *reinterpret_cast<const f32x4*>(j.shift + c);
-  const f32x4 z = join_z4(k, v0, v1, v2);
-  f32x4 y;
-  y.x = vy_leaky(fmaf(z.x, sc.x, sh.x));
-  y.y = vy_leaky(fmaf(z.y, sc.y, sh.y));
-  y.z = vy_leaky(fmaf(z.z, sc.z, sh.z));
-  y.w = vy_leaky(fmaf(z.w, sc.w, sh.w));
-  *reinterpret_cast<f32x4*>(a.dst + po) = y;
+  *reinterpret_cast<f32x4*>(a.dst + po) = join_apply4(join_z4(k, v0, v1, v2), sc, sh);
+}
+
+// ---- the dilated joins of a hier-video plan (vy_net_bind_hier_video): the same two inference joins, but destination
+// frame p is made of source frames p, p + d, p + 2d (in that order) of a plane that holds frames + 2d frames, d = a.dil —
+// consecutive clips of a video share their triples, so every level is computed once per frame position.  Same lane map,
+// borders, channel strides and d_co as above; a locate of their own, so that the five kernels above carry no dilation.
+__device__ inline bool locate_dilated(const HierPoolArgs& a, unsigned z, long long* so, long long* po) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.row_items) return false;
+  const unsigned px = i >> a.c4_shift, q = i & ((1u << a.c4_shift) - 1u);
+  const unsigned in_frame = (blockIdx.y + 1u) * (unsigned)(a.W + 2) + px + 1u;
+  const long long n = z;
+  *so = (n * a.frame_pixels + in_frame) * a.s_cs + 4u * q;
+  *po = (n * a.frame_pixels + in_frame) * a.d_cs + a.d_co + 4u * q;
+  return true;
+}
+
+// the join's per-lane constants (the max: none)
+struct JoinK {
+  JoinW k;
+  f32x4 sc, sh;
+};
+template <bool CONV>
+__device__ inline JoinK join_constants(const HierJoinArgs& j) {
+  JoinK c = {};
+  if (CONV) {
+    const unsigned ch = lane_channel(j.g);
+    c.k = join_weights(j.w, ch);
+    c.sc = *reinterpret_cast<const f32x4*>(j.scale + ch);
+    c.sh = *reinterpret_cast<const f32x4*>(j.shift + ch);
+  }
+  return c;
+}
+template <bool CONV>
+__device__ inline f32x4 join3(const JoinK& c, const f32x4 v0, const f32x4 v1, const f32x4 v2) {
+  return CONV ? join_apply4(join_z4(c.k, v0, v1, v2), c.sc, c.sh) : max3(v0, v1, v2);
+}
+
+// three reads, one write: the grid's z is the destination frame.  The correctness baseline of the chain walk below, which
+// is what a net launches (VY_HIER_CHAIN=0 launches this one)
+template <bool CONV>
+__global__ __launch_bounds__(256) void hier_dilated_kernel(HierJoinArgs j) {
+  const HierPoolArgs& a = j.g;
+  long long so, po;
+  if (!locate_dilated(a, blockIdx.z, &so, &po)) return;
+  const long long fstep = (long long)a.dil * a.frame_pixels * a.s_cs;
+  const f32x4 v0 = *reinterpret_cast<const f32x4*>(a.src + so);
+  const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.src + so + fstep);
+  const f32x4 v2 = *reinterpret_cast<const f32x4*>(a.src + so + 2 * fstep);
+  *reinterpret_cast<f32x4*>(a.dst + po) = join3<CONV>(join_constants<CONV>(j), v0, v1, v2);
+}
+
+// The chain walk: destination frames p = r (mod d) form a chain whose consecutive members share two operands, so a lane
+// walks a chain and keeps the two previous operands in registers — every source frame of a chain is read once.  Chains are
+// cut into segments of kChainSeg destination frames (the grid's z is segment * d + r): the grid stays full when there
+// are few chains, and a segment re-reads only its first two operands, (kChainSeg + 2) / kChainSeg source reads per write.
+// Measured (profiles/hier_video_step.txt, 16 centres at 416x416): hpool.0 at 0.90 / 0.85 / 0.88 of the copy rate of its
+// algorithmic bytes at T = 9 / 27 / 81, where the three reads reach 0.72 / 0.66 / 0.70.
+constexpr int kChainSeg = 8;
+template <bool CONV>
+__global__ __launch_bounds__(256) void hier_dilated_chain_kernel(HierJoinArgs j) {
+  const HierPoolArgs& a = j.g;
+  const unsigned d = (unsigned)a.dil, seg = blockIdx.z / d, r = blockIdx.z - seg * d;
+  const unsigned first = seg * (unsigned)kChainSeg * d + r;  // this lane's first destination frame
+  if (first >= (unsigned)a.frames) return;
+  long long so, po;
+  if (!locate_dilated(a, first, &so, &po)) return;
+  const long long sstep = (long long)d * a.frame_pixels * a.s_cs, dstep = (long long)d * a.frame_pixels * a.d_cs;
+  const JoinK c = join_constants<CONV>(j);
+  f32x4 v0 = *reinterpret_cast<const f32x4*>(a.src + so);
+  f32x4 v1 = *reinterpret_cast<const f32x4*>(a.src + so + sstep);
+  const unsigned left = ((unsigned)a.frames - first + d - 1u) / d;  // members of the chain from `first` on
+  const int n = (int)(left < (unsigned)kChainSeg ? left : (unsigned)kChainSeg);
+  for (int k = 0; k < n; ++k) {
+    const f32x4 v2 = *reinterpret_cast<const f32x4*>(a.src + so + (k + 2) * sstep);
+    *reinterpret_cast<f32x4*>(a.dst + po + k * dstep) = join3<CONV>(c, v0, v1, v2);
+    v0 = v1;
+    v1 = v2;
+  }
 }
 
 // The per-block rows of the two training kernels.  Every lane leaves K doubles in LDS (lanes past the end of the row:
@@ -258,8 +350,41 @@ hipError_t launch_join(HierJoinArgs j, int mode, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the dilated inference joins: conv = the learned join (else the max, whose w / scale / shift stay null); chain: the chain walk
+hipError_t launch_dilated(HierJoinArgs j, bool conv, bool chain, hipStream_t s) {
+  dim3 grid;
+  HierPoolArgs& a = j.g;
+  const bool ptrs = a.src && a.dst && (!conv || (j.w && j.scale && j.shift));
+  // (the source plane holds frames + 2 dil frames: the caller's plan says so)
+  if (!ptrs || a.dil < 1 || a.dil > 65535 || (conv && a.C > 1024) || !geometry(a, &grid)) return hipErrorInvalidValue;
+  if (chain) {
+    const long long d = a.dil, members = (a.frames + d - 1) / d;  // of the longest chain
+    const long long z = d * ((members + kChainSeg - 1) / kChainSeg);
+    if (z > 65535) return hipErrorInvalidValue;
+    grid.z = (unsigned)z;
+    if (conv)
+      hipLaunchKernelGGL(hier_dilated_chain_kernel<true>, grid, dim3(256), 0, s, j);
+    else
+      hipLaunchKernelGGL(hier_dilated_chain_kernel<false>, grid, dim3(256), 0, s, j);
+  } else if (conv) {
+    hipLaunchKernelGGL(hier_dilated_kernel<true>, grid, dim3(256), 0, s, j);
+  } else {
+    hipLaunchKernelGGL(hier_dilated_kernel<false>, grid, dim3(256), 0, s, j);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 
+hipError_t vy_launch_hier_pool_dilated(const HierPoolArgs& a, int chain, hipStream_t s) {
+  HierJoinArgs j;
+  memset(&j, 0, sizeof j);
+  j.g = a;
+  return launch_dilated(j, false, chain != 0, s);
+}
+hipError_t vy_launch_hier_join_dilated(const HierJoinArgs& a, int chain, hipStream_t s) {
+  return launch_dilated(a, true, chain != 0, s);
+}
 hipError_t vy_launch_hier_pool(const HierPoolArgs& a, hipStream_t s) { return launch(a, false, s); }
 hipError_t vy_launch_hier_pool_bwd(const HierPoolArgs& a, hipStream_t s) { return launch(a, true, s); }
 hipError_t vy_launch_hier_join(const HierJoinArgs& a, hipStream_t s) { return launch_join(a, 0, s); }

@@ -252,6 +252,7 @@ struct HierPoolArgs {
   const float* gdst;   // backward: gradient plane of dst (read)
   int frames;          // pooled frames
   int H, W, C, s_cs, d_cs, d_co;
+  int dil;             // the dilated launches only (a hier-video plan): d >= 1, see below; every other launch ignores it
   // filled by the launcher
   int c4_shift;            // log2(C / 4)
   unsigned row_items;      // W * C / 4 lanes per row
@@ -286,6 +287,15 @@ hipError_t vy_launch_hier_join_raw(const HierJoinArgs& a, hipStream_t s);
 // backward: gsrc frame 3n + t = w[c][t] * dz (written, never accumulated, interior only) and the per-block rows of
 // dw[c][t] = sum x_t * dz in double, for vy_launch_reduce_partials_f64
 hipError_t vy_launch_hier_join_bwd(const HierJoinArgs& a, hipStream_t s);
+
+// ---- the two inference joins in dilated form (hier.hip; a hier-video plan, vy_net_bind_hier_video): dst frame p, p < frames,
+// is the join of src frames p, p + dil, p + 2 dil, in that order, of a plane that holds frames + 2 dil frames — the same
+// arithmetic, tie rule, borders, channel strides and d_co as vy_launch_hier_pool / vy_launch_hier_join.  chain != 0 (what a
+// net launches unless VY_HIER_CHAIN=0): the chain walk — a lane follows the frames p = r mod dil and reads each source frame
+// once per segment — instead of three reads per destination frame, the baseline it is checked against; the same bits either
+// way (profiles/hier_video_step.txt: 0.76 ... 1.6 of the copy rate over three runs against 0.60 ... 1.6).
+hipError_t vy_launch_hier_pool_dilated(const HierPoolArgs& a, int chain, hipStream_t s);
+hipError_t vy_launch_hier_join_dilated(const HierJoinArgs& a, int chain, hipStream_t s);
 
 // ---- per-frame route ring of a video plan (video.hip): the three routes of single frames, kept in R slots and pooled by
 // window.  A slot is the three routes back to back, tight NHWC without borders (only ring_pool and the test tap read it):

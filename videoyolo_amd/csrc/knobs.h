@@ -25,6 +25,8 @@ struct VyKnobs {
   // training step (train.hip)
   int train_side_stream = 1;  // VY_TRAIN_SIDE_STREAM=0: weight gradients on the main stream
   std::string train_labels;   // VY_TRAIN_LABELS=<path>: the first training step's launch labels go there (empty: none)
+  // hier-video plans (hier.hip)
+  int hier_chain = 1;  // VY_HIER_CHAIN=0 (A/B, tests): the dilated joins as three reads per frame, not as chain walks
   // planners (net_internal.h, train.hip, detect.hip)
   int plan_guard = 0;  // VY_PLAN_GUARD=<bytes> (tests): unused bytes behind every carve; 0 or a multiple of 256 up to 1 MiB
   // measurement builds only (read under -DVY_TRAIN_ABL_BUILD / -DVY_WINO_BM128; the defaults elsewhere)
@@ -76,6 +78,7 @@ inline VyKnobs vy_knobs_read() {
   }
   geti("VY_TRAIN_SIDE_STREAM", k.train_side_stream);
   if (const char* s = getenv("VY_TRAIN_LABELS")) k.train_labels = s;
+  geti("VY_HIER_CHAIN", k.hier_chain);
   geti("VY_PLAN_GUARD", k.plan_guard);
   if (k.plan_guard < 0 || k.plan_guard % 256 || k.plan_guard > (1 << 20)) k.plan_guard = 0;
 #ifdef VY_TRAIN_ABL_BUILD

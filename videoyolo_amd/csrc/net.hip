@@ -254,11 +254,11 @@ size_t vy_net_workspace_bytes(const vy_net* net, int32_t batch, int32_t height, 
   return net->plan(batch, height, width, net->keep_activations).total;
 }
 
-// plan, check the caller's workspace against the plan, commit it and take the workspace.  frames, ring: vy_net::plan
+// plan, check the caller's workspace against the plan, commit it and take the workspace.  frames, ring, hstep: vy_net::plan
 static int bind_plan(vy_net* net, void* dev_ws, size_t bytes, int b, int h, int w, int frames, int ring, const char* what,
-                     void* stream) {
+                     void* stream, int hstep = 0) {
   VY_TRY(net->bind_cus(dev_ws));
-  NetPlan plan = net->plan(b, h, w, net->keep_activations, frames, ring);
+  NetPlan plan = net->plan(b, h, w, net->keep_activations, frames, ring, nullptr, hstep);
   const size_t need = plan.total;
   if (bytes < need) return fail(VY_ERR_INVALID, "%sworkspace too small: %zu < %zu bytes", what, bytes, need);
   return net->commit_bind(std::move(plan), dev_ws, bytes, need, static_cast<hipStream_t>(stream));
@@ -430,6 +430,44 @@ int vy_net_video_read_slot(vy_net* net, int32_t slot, float* f0, float* f1, floa
   return 0;
 }
 
+// ---- hier-video plans
+static int check_hier_video_shape(int32_t centres, int32_t step, int32_t h, int32_t w) {
+  if (centres < 1 || centres > VY_VIDEO_TABLE_MAX || step < 1 || step > VY_HIER_VIDEO_STEP_MAX)
+    return fail(VY_ERR_INVALID, "hier-video plan: centres %d must lie in [1, %d] and step %d in [1, %d]", centres,
+                VY_VIDEO_TABLE_MAX, step, VY_HIER_VIDEO_STEP_MAX);
+  return vy_check_shape(centres, h, w);
+}
+
+int vy_net_hier_video_frames(const vy_net* net, int32_t centres, int32_t step, int32_t* frames_in) {
+  VY_TRY(vy_serves(net, "vy_net_hier_video_frames", VY_HIER));
+  if (!frames_in) return fail(VY_ERR_INVALID, "null argument");
+  VY_TRY(check_hier_video_shape(centres, step, 32, 32));
+  *frames_in = centres + step * (net->hier_frames() - 1);
+  return 0;
+}
+
+size_t vy_net_hier_video_workspace_bytes(const vy_net* net, int32_t centres, int32_t step, int32_t height, int32_t width) {
+  if (vy_serves(net, "vy_net_hier_video_workspace_bytes", VY_HIER) || check_hier_video_shape(centres, step, height, width)) return 0;
+  net->resolve_cus();
+  return net->plan(centres, height, width, net->keep_activations, 0, 0, nullptr, step).total;
+}
+
+int vy_net_bind_hier_video(vy_net* net, void* dev_ws, size_t bytes, int32_t centres, int32_t step, int32_t height,
+                           int32_t width, void* stream) {
+  VY_TRY(vy_serves(net, "vy_net_bind_hier_video", VY_HIER));
+  if (!dev_ws) return fail(VY_ERR_INVALID, "null argument");
+  VY_TRY(check_hier_video_shape(centres, step, height, width));
+  return bind_plan(net, dev_ws, bytes, centres, height, width, 0, 0, "hier-video ", stream, step);
+}
+
+int vy_net_hier_video_detect(vy_net* net, const float* x, float* ids, float* scores, float* bboxes, int32_t* keep_idx,
+                             void* stream) {
+  VY_TRY(vy_serves(net, "vy_net_hier_video_detect", VY_HIER));
+  return run_entry(net, x && ids && scores && bboxes, "vy_net_hier_video_detect", stream, [&](hipStream_t s) {
+    return infer_sequence(net, x, ids, scores, bboxes, keep_idx, s, plain);  // (the joins of this plan run dilated)
+  });
+}
+
 int vy_net_read_head(vy_net* net, int32_t i, float* dst_dev, void* stream) {
   if (!net || !dst_dev || i < 0 || i > 2) return fail(VY_ERR_INVALID, "bad argument");
   if (int rc = net->check_ready(true)) return rc;
@@ -497,7 +535,8 @@ int vy_net_profile_infer(vy_net* net, const float* x, float* ids, float* scores,
       ev1.push_back(e);
     }
   };
-  int rc = run_entry(net, true, nullptr, stream,
+  // (a hierarchical net bound for video: the launches of a vy_net_hier_video_detect call on x)
+  int rc = run_entry(net, true, net->cur.hier_step ? "vy_net_profile_infer" : nullptr, stream,
                      [&](hipStream_t) { return infer_sequence(net, x, ids, scores, bboxes, nullptr, s, hook); });
   if (rc == 0) {
     hipError_t e = hipStreamSynchronize(s);

@@ -94,6 +94,10 @@ struct NetPlan {
   // pooled routes on hold B clips, and behind the planes lies a ring of video_R slots of per-frame routes (video.hip).
   // 0: the clip plan — binding either way switches the net over
   int video_F = 0, video_R = 0;
+  // a hier-video plan (vy_net_bind_hier_video): B counts the centres of a chunk, hier_step is the step between
+  // the frames of a clip, and a backbone plane holds the frame positions its level needs for them (vy_net::frames_of) —
+  // the joins run dilated (hier.hip).  0: any other plan
+  int hier_step = 0;
   size_t fold_desc_off = 0, det_scratch_off = 0;  // byte offsets in the workspace
   size_t sk_off = 0, sk_slabs_off = 0;  // stream-K scratch of the conv launches (conv_igemm.hip): the flags, the slabs
   int guard = 0;  // unused bytes behind every carve (VY_PLAN_GUARD; 0 outside the tests)
@@ -262,6 +266,10 @@ struct vy_net {
       a.gdst = grads + dp.off;
     }
     a.frames = plane_batch(hp.dst);
+    if (cur.hier_step) {  // pool i joins positions d = step * 3^i apart: h_(i+1) - h_i
+      a.dil = cur.hier_step;
+      for (const HierPool* q = hpools.data(); q != &hp; ++q) a.dil *= 3;
+    }
     a.H = dp.H;
     a.W = dp.W;
     a.C = hp.C;
@@ -282,10 +290,15 @@ struct vy_net {
     return j;
   }
 
-  // frames a stem / stage plane of a window net holds for `b` clips: b*k of the clip plan, `frames` of a video plan
-  static int backbone_frames(const PlaneT& p, int b, int frames) { return frames && p.fm > 1 ? frames : b * p.fm; }
+  // frames a stem / stage plane holds for `b` clips: b * fm of the clip plan; `frames` of a window net's video plan; of a
+  // hier-video plan with step `hstep` (b centres) the positions of the plane's level L, T / fm = 3^L:
+  // b + 2 (h_n - h_L) = b + hstep (T - T / fm) with h_L = hstep (3^L - 1) / 2 — b from the last pool on
+  int frames_of(const PlaneT& p, int b, int frames, int hstep) const {
+    if (hstep) return b + hstep * (hier_frames() - hier_frames() / p.fm);
+    return frames && p.fm > 1 ? frames : b * p.fm;
+  }
   // frames of the batch a plane holds / a conv runs on (its output plane's: a window net's backbone cells B*k)
-  int plane_batch(int p) const { return backbone_frames(planes[p], cur.B, cur.video_F); }
+  int plane_batch(int p) const { return frames_of(planes[p], cur.B, cur.video_F, cur.hier_step); }
   int conv_batch(const ConvT& c) const { return plane_batch(c.out_plane); }
   PlaneAt plane(int i) const { return {planes[i].C, cur.planes[i].H, cur.planes[i].W, cur.planes[i].off}; }
   // the pooling launch of a window net, forward (grads == nullptr) or backward (grads: the training gradient planes,
@@ -657,10 +670,13 @@ struct vy_net {
 
   // frames / ring: a video plan (vy_net_bind_video) — `frames` single frames in the stem and stage planes instead of b*k,
   // b clips from the pooled routes on, and `ring` route slots behind the planes; 0, 0: the clip plan.
+  // hstep: a hier-video plan (vy_net_bind_hier_video) — b centres, every backbone plane at its level's count (frames_of).
   // regions (tests: vy_net_plan_region): every carve is appended to it, in offset order
-  NetPlan plan(int b, int h, int w, bool keep_all, int frames = 0, int ring = 0, std::vector<PlanRegion>* regions = nullptr) const {
+  NetPlan plan(int b, int h, int w, bool keep_all, int frames = 0, int ring = 0, std::vector<PlanRegion>* regions = nullptr,
+               int hstep = 0) const {
     NetPlan p;
     p.B = b;
+    p.hier_step = hstep;
     p.H = h;
     p.W = w;
     p.planes_shared = !keep_all;
@@ -697,7 +713,7 @@ struct vy_net {
       const int runs = c.is_stem ? 1 : vy_conv_runs(c.k * c.k, (c.cin + 31) >> 5);
       if (runs < 2) continue;
       const PlaneT& op = planes[c.out_plane];
-      const long long Mo = (long long)backbone_frames(op, b, frames) * cdiv(h, op.div) * cdiv(w, op.div);
+      const long long Mo = (long long)frames_of(op, b, frames, hstep) * cdiv(h, op.div) * cdiv(w, op.div);
       p.ck_bytes = std::max(p.ck_bytes, vy_conv_chunk_scratch_bytes(Mo, c.cout, runs));
     }
     p.ck_off = take(p.ck_bytes, "ck");
@@ -719,7 +735,7 @@ struct vy_net {
       q.H = cdiv(h, g.div);
       q.W = cdiv(w, g.div);
       if ((size_t)slot[i] == i)  // owns its storage
-        q.off = (take((size_t)backbone_frames(g, b, frames) * (q.H + 2) * (q.W + 2) * g.C * sizeof(float), "plane",
+        q.off = (take((size_t)frames_of(g, b, frames, hstep) * (q.H + 2) * (q.W + 2) * g.C * sizeof(float), "plane",
                       regions ? plane_name((int)i) : std::string()) - p.planes_off) / sizeof(float);
     }
     for (size_t i = 0; i < planes.size(); ++i) p.planes[i].off = p.planes[slot[i]].off;  // (an owner may come later)
@@ -740,9 +756,9 @@ struct vy_net {
   int check_ready(bool video_ok = false) const {
     if (!dev_params) return fail(VY_ERR_STATE, "parameters not bound (vy_net_bind_params)");
     if (!dev_ws) return fail(VY_ERR_STATE, "workspace not bound (vy_net_bind_workspace)");
-    if (cur.video_F && !video_ok)
-      return fail(VY_ERR_STATE, "the net is bound for video (vy_net_bind_video): bind a clip plan again with "
-                  "vy_net_bind_workspace / vy_net_bind_train");
+    if ((cur.video_F || cur.hier_step) && !video_ok)
+      return fail(VY_ERR_STATE, "the net is bound for video (%s): bind a clip plan again with "
+                  "vy_net_bind_workspace / vy_net_bind_train", cur.hier_step ? "vy_net_bind_hier_video" : "vy_net_bind_video");
     return 0;
   }
 
@@ -1056,15 +1072,19 @@ struct vy_net {
   template <typename Hook>
   int hier_pool(int i, hipStream_t s, Hook& hook) {
     const HierPoolArgs a = hier_args(hpools[i], nullptr);
-    const double by = 16.0 * a.frames * a.H * a.W * a.C;  // three reads, one write, either join
+    // three reads, one write, either join; a dilated join (a hier-video plan): its algorithmic bytes — the source plane's
+    // frames + 2 dil frames once, the destination once
+    const double by = 4.0 * (a.dil ? 2.0 * (a.frames + a.dil) : 4.0 * a.frames) * a.H * a.W * a.C;
     char nm[16];
     if (hpools[i].join == VY_HJOIN_CONV) {
       snprintf(nm, sizeof nm, "hjoin.%d", i);
-      HOOKED(hook, nm, 6.0 * a.frames * a.H * a.W * a.C, by, vy_launch_hier_join(join_args(hpools[i], nullptr), s));
+      const HierJoinArgs j = join_args(hpools[i], nullptr);
+      HOOKED(hook, nm, 6.0 * a.frames * a.H * a.W * a.C, by,
+             a.dil ? vy_launch_hier_join_dilated(j, knobs.hier_chain, s) : vy_launch_hier_join(j, s));
       return 0;
     }
     snprintf(nm, sizeof nm, "hpool.%d", i);
-    HOOKED(hook, nm, 0.0, by, vy_launch_hier_pool(a, s));
+    HOOKED(hook, nm, 0.0, by, a.dil ? vy_launch_hier_pool_dilated(a, knobs.hier_chain, s) : vy_launch_hier_pool(a, s));
     return 0;
   }
   // the backbone: the stem and stage cells, with the pools of a hierarchical net between the groups they separate
@@ -1134,8 +1154,8 @@ inline int vy_serves(const vy_net* net, const char* entry, unsigned kinds) {
                        "vy_net_video_* serve"},
             {"windowed heads-only", "a windowed heads-only net (vy_net_create_heads_window), which the *_bank entry points and "
                                     "vy_net_train_backward_routes serve"},
-            {"hierarchical", "a hierarchical net (vy_net_create_hier), which vy_net_forward_infer, vy_net_profile_infer and "
-                             "vy_net_train_*forward / _backward serve"}};
+            {"hierarchical", "a hierarchical net (vy_net_create_hier), which vy_net_forward_infer, vy_net_profile_infer, "
+                             "vy_net_train_*forward / _backward and vy_net_hier_video_* serve"}};
   if (!net) return fail(VY_ERR_INVALID, "%s: net is null", entry);
   const unsigned kind = net->kind();
   if (kind & kinds) return 0;
@@ -1154,8 +1174,9 @@ inline int entry_ready(vy_net* net, bool args_ok, const char* video_entry) {
   int rc = 0;
   if (!net || !args_ok) rc = fail(VY_ERR_INVALID, "null argument");
   if (rc == 0) rc = net->check_ready(video_entry != nullptr);
-  if (rc == 0 && video_entry && !net->cur.video_F)
-    rc = fail(VY_ERR_STATE, "%s: the net is not bound for video (vy_net_bind_video)", video_entry);
+  if (rc == 0 && video_entry && !(net->hier_n ? net->cur.hier_step : net->cur.video_F))
+    rc = fail(VY_ERR_STATE, "%s: the net is not bound for video (%s)", video_entry,
+              net->hier_n ? "vy_net_bind_hier_video" : "vy_net_bind_video");
   if (rc && net) net->sk_dirty = true;  // (any error return: see vy_net::sk_dirty)
   return rc;
 }

@@ -1185,6 +1185,9 @@ int vy_net_plan_region(const vy_net* net, int32_t plan, int32_t batch, int32_t h
   } else if (plan == VY_PLAN_VIDEO) {
     if (!vy_net_video_workspace_bytes(net, frames, batch, ring, height, width)) return VY_ERR_INVALID;
     total = net->plan(batch, height, width, net->keep_activations, frames, ring, &regions).total;
+  } else if (plan == VY_PLAN_HIER_VIDEO) {  // batch: the centres, frames: the step
+    if (!vy_net_hier_video_workspace_bytes(net, batch, frames, height, width)) return VY_ERR_INVALID;
+    total = net->plan(batch, height, width, net->keep_activations, 0, 0, &regions, frames).total;
   } else if (plan == VY_PLAN_TRAIN) {
     if (!vy_net_train_workspace_bytes(net, batch, height, width)) return VY_ERR_INVALID;
     const NetPlan fwd = net->plan(batch, height, width, /*keep_all=*/true, 0, 0, &regions);

@@ -1066,12 +1066,15 @@ class YOLOV3(object):
         (x,), (b, h, w), _ = self._inputs(x)
         with torch.cuda.device(self._device):
             self._ensure_plan(b, h, w)
-            outs = self._detect_outputs(b, self._out_rows(), keep=False)
-            cap = 256
-            stats = (_lib.LaunchStat * cap)()
-            n = ctypes.c_int32(cap)
-            _lib.check(self._lib.vy_net_profile_infer(self._h, *_ptrs((x,) + outs[:3]), stats, ctypes.byref(n),
-                                                      self._stream()))
+            return self._profile_call(x, b)
+
+    def _profile_call(self, x, b):
+        """``vy_net_profile_infer`` on the bound plan, outputs at batch b"""
+        outs = self._detect_outputs(b, self._out_rows(), keep=False)
+        cap = 256
+        stats = (_lib.LaunchStat * cap)()
+        n = ctypes.c_int32(cap)
+        _lib.check(self._lib.vy_net_profile_infer(self._h, *_ptrs((x,) + outs[:3]), stats, ctypes.byref(n), self._stream()))
         return [(stats[i].name.decode(), float(stats[i].ms), float(stats[i].flops), float(stats[i].bytes))
                 for i in range(n.value)]
 
@@ -1307,6 +1310,48 @@ class YOLOV3Hier(_ClipNet):
         if mode != "exact":
             raise NotImplementedError("conv mode %r: a hierarchical net runs the exact fp32 kernels only" % (mode,))
         super().set_conv_mode(mode)
+
+    # ---- over a whole video: every level once per frame position.  The public door is the function
+    # videoyolo_amd.hier_detect_video(net, frames, ...) (video.py), not a method: the public surface of this
+    # class is pinned (tests/test_model_surface_host.py); what follows is the binding it takes on the net
+    _hier_video = None  # (step,) while the workspace is bound to a hier-video plan; _plan is then (centres, H, W, False)
+
+    def _drop_plan(self):
+        self._hier_video = None
+        super()._drop_plan()
+
+    def _ensure_plan(self, b, h, w, train=False):
+        if self._hier_video is not None:  # hier_detect_video took the binding: this call binds its own plan again
+            self._drop_plan()
+        super()._ensure_plan(b, h, w, train=train)
+
+    def _ensure_hier_video(self, centres, step, h, w):
+        if self._hier_video == (step,) and self._plan == (centres, h, w, False):
+            return
+        self._need_device()
+        self._drop_plan()
+        need = self._lib.vy_net_hier_video_workspace_bytes(self._h, centres, step, h, w)
+        if need and self._ws is not None and self._ws.numel() < need:
+            self._ws = None  # released before its successor is allocated
+        self._ws = self._size_and_bind(self._ws, need, lambda ws, nbytes: self._lib.vy_net_bind_hier_video(
+            self._h, ws, nbytes, centres, step, h, w, self._stream()))
+        self._plan, self._hier_video = (centres, h, w, False), (step,)
+
+    def _tap_batch(self, name):
+        if self._hier_video is None:
+            return super()._tap_batch(name)
+        fm = ctypes.c_int32(0)  # a tap of a hier-video plan holds the positions of its level: video.hier_video_chunks' counts
+        _lib.check(self._lib.vy_net_tap_frames(self._h, name.encode(), ctypes.byref(fm)))
+        return self._plan[0] + self._hier_video[0] * (self.frames - self.frames // fm.value)
+
+    def _profile_video_chunk(self, x, step=1):
+        """``profile`` of one library call of ``hier_detect_video``: x ``(F + step * (T - 1), 3, H, W)`` on the device, the level-0 frames of
+        a chunk of F centres (tools/hier_video_step.py; the joins are the launches ``hpool.<i>`` / ``hjoin.<i>``)."""
+        torch = _torch()
+        centres = int(x.shape[0]) - int(step) * (self.frames - 1)
+        with torch.cuda.device(self._device):
+            self._ensure_hier_video(centres, int(step), int(x.shape[2]), int(x.shape[3]))
+            return self._profile_call(x.contiguous(), centres)
 
     extract_features = detect_two_streams = _refusal(
         "not available on a hierarchical net (yolo3_darknet53 with hierarchical=...): use a single-frame net")

@@ -9,6 +9,10 @@ and the stages once per frame, keeps the routes in a ring of slots inside its wo
 
 ``window_indices`` and ``RingSchedule`` are plain Python (no device): the table of the reference's loop, and the
 frame -> slot bookkeeping a session follows.
+
+A hierarchical net (``hier_detect_video(net, frames)``) needs no ring: ``hier_video_chunks`` (plain Python too) cuts the video into
+stateless chunks of centres, each with the level-0 frames its levels reach, and ``hier_detect_video`` runs them on a
+hier-video plan (``vy_net_bind_hier_video`` / ``vy_net_hier_video_detect``), every level once per frame position.
 """
 import ctypes
 
@@ -35,6 +39,78 @@ def min_ring(k, step, frames_per_step):
     from its centre, which itself lies ``(k - 1 - k // 2) * step`` frames (the window's look-ahead) behind the first new
     frame.  Frame j lives in slot ``j % ring``, so all of these must be distinct slots."""
     return int(frames_per_step) + (int(k) - 1) * int(step)
+
+
+def hier_reach(pools, step, level):
+    """``h_L = step * (3^L - 1) / 2``: how far level L of a hierarchical net reaches on either side of its position."""
+    return int(step) * (3 ** int(level) - 1) // 2
+
+
+def hier_video_chunks(n_frames, pools, step=1, frames_per_step=16):
+    """The chunks of ``hier_detect_video`` over a video of ``n_frames`` frames, for a net of ``pools`` pools (clips of
+    ``T = 3 ** pools`` frames, ``step`` apart) run ``frames_per_step`` centres at a time -> ``(chunks, counts)``.
+
+    ``chunks``: one ``(centres, frame_index)`` per call.  ``centres`` lists the frames the call emits, at most
+    ``frames_per_step`` consecutive ones (fewer in the last chunk: the plan still runs ``frames_per_step`` centres, and the
+    outputs behind ``len(centres)`` are dropped).  ``frame_index`` (int64, ``frames_per_step + 2 h_n`` entries) is the
+    level-0 input: entry j is frame ``clamp(a - h_n + j, 0, n_frames - 1)``, a the first centre — all the clamping of
+    ``window_indices(n_frames, T, step)`` lives here.
+    ``counts``: per level L = 0 .. pools the positions a call holds of it, ``frames_per_step + 2 (h_n - h_L)``, level L
+    starting at position ``a - (h_n - h_L)``; join L -> L + 1 is ``dst[p] = join(src[p], src[p + d], src[p + 2d])`` with
+    ``d = step * 3 ** L``."""
+    n_frames, pools, step, f = int(n_frames), int(pools), int(step), int(frames_per_step)
+    if n_frames < 1 or not 1 <= pools <= 4 or f < 1 or f > _lib.VY_VIDEO_TABLE_MAX or not 1 <= step <= _lib.VY_HIER_VIDEO_STEP_MAX:
+        raise ValueError("hier_video_chunks: n_frames >= 1, pools in 1..4, step in 1..%d, frames_per_step in 1..%d (got %d, %d, "
+                         "%d, %d)" % (_lib.VY_HIER_VIDEO_STEP_MAX, _lib.VY_VIDEO_TABLE_MAX, n_frames, pools, step, f))
+    reach = hier_reach(pools, step, pools)
+    counts = [f + 2 * (reach - hier_reach(pools, step, level)) for level in range(pools + 1)]
+    chunks = []
+    for a in range(0, n_frames, f):
+        index = np.clip(np.arange(a - reach, a + f + reach, dtype=np.int64), 0, n_frames - 1)
+        chunks.append((list(range(a, min(a + f, n_frames))), index))
+    return chunks, counts
+
+
+def hier_detect_video(net, frames, step=1, frames_per_step=16, return_index=False):
+    """``(ids, scores, bboxes)`` for the ``(N, 3, H, W)`` video ``frames`` (host array or device tensor, any N >= 1) on the
+    hierarchical net ``net`` (``YOLOV3Hier`` or ``YOLOV3HierConv``), one row-block per frame: bit for bit
+    ``net(frames[window_indices(N, T, step)])``, the clips of the reference's ``detect_yolo3.py --window T,step``, but with
+    the stem and every group of cells run once per frame position instead of once per clip.  ``frames_per_step`` frames are
+    emitted per library call, which recomputes the ``step * (T - 1) / 2`` frames of context on either side: nothing is kept
+    between calls, the last chunk is padded and the padding dropped.  ``frames`` is only read; a host video is uploaded once
+    per chunk's frame range.  The call takes the net's workspace binding; a later clip or training call binds its own plan
+    again.  One rank only.  (A function, not a method: the public surface of the model classes is pinned.)"""
+    from .model import YOLOV3Hier
+    if not isinstance(net, YOLOV3Hier):
+        raise TypeError("hier_detect_video takes a hierarchical net (YOLOV3Hier / YOLOV3HierConv), got %s" % type(net).__name__)
+    import torch
+    from . import parallel
+    if parallel.world_size() > 1:
+        raise NotImplementedError("video detection of a hierarchical net is not supported on more than one rank")
+    shape = tuple(frames.shape) if hasattr(frames, "shape") else tuple(np.shape(frames))
+    if len(shape) != 4 or shape[1] != 3 or shape[0] < 1:
+        raise ValueError("expected (n, 3, H, W) frames with n >= 1, got %s" % (shape,))
+    chunks, counts = hier_video_chunks(shape[0], net._pools, step, frames_per_step)
+    net._need_device()
+    on_device = isinstance(frames, torch.Tensor) and frames.device == torch.device(net._device)
+    if not on_device and not isinstance(frames, torch.Tensor):
+        frames = torch.as_tensor(np.asarray(frames, np.float32))
+    f = int(frames_per_step)
+    outs = []
+    with torch.cuda.device(net._device):
+        net._ensure_hier_video(f, int(step), shape[2], shape[3])
+        for centres, index in chunks:
+            lo, hi = int(index[0]), int(index[-1])
+            # the frame range of the chunk: a view of a device video, one upload of a host one — never once per clip
+            span = frames[lo:hi + 1].to(device=net._device, dtype=torch.float32)
+            if len(index) == hi + 1 - lo and span.is_contiguous():
+                x = span  # an interior chunk reads its frames in place
+            else:  # clamped at an end of the video (or a strided input): the level-0 frames gathered, counts[0] of them
+                x = span.index_select(0, torch.as_tensor(index - lo, device=span.device)).contiguous()
+            assert x.shape[0] == counts[0]
+            got = net._detect_call("vy_net_hier_video_detect", f, _ptrs([x]), return_index)
+            outs.append(tuple(t[:len(centres)] for t in got))
+    return tuple(torch.cat(ts, 0) for ts in zip(*outs))
 
 
 class RingSchedule:
